@@ -10,8 +10,13 @@ N GPUs (torchrun, one process per GPU): the SAME ceremony is sharded by dealer; 
 generates and verifies its dealers' rows for all receivers, then RCCL all-gathers (over xGMI) the
 decision rows, the A_i0 commitments and the final-share partial sums (strong scaling).
 
-Also printed in the same JSON line: the roofline of the dominant kernel (VALU issue slots, with the
-PMC-measured HBM bytes per launch) and the CPU baseline: the
+A plain run sets up, warms up, times the steps and prints the line.  --dump-outputs DIR also writes
+what the last timed step returned to its caller as DIR/<name>.npy (dump_outputs).
+
+With --full the same JSON line also carries what takes runs of its own: the shader clock before and
+after the timed region, the roofline of the dominant kernel from one extra serialised pass (VALU
+issue slots, with the PMC-measured HBM bytes per launch), the opt-in
+interpolation mode on the same inputs, and the CPU baseline: the
 dalek-algorithm-matched C oracle timed on a bounded sample of the same ceremony (share generation
 and round-2 and round-4 checks of a subset of dealers against all receivers) on every host thread
 this process may use, extrapolated to the whole ceremony.
@@ -651,7 +656,7 @@ def bench_batch(args, ws, rank, local):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    clk0 = be.clock_probe()
+    clk0 = be.clock_probe() if args.full else None
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -664,23 +669,28 @@ def bench_batch(args, ws, rank, local):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    clk1 = be.clock_probe()
+    clk1 = be.clock_probe() if args.full else None
     if dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert all(q == n for q in res.n_qualified), "an honest ceremony disqualified a dealer"
-    # per-kernel device times: one extra serialised batch (one chunk stream)
-    be.set_streams(1)
-    step()
-    torch.cuda.synchronize()
-    be.set_streams(args.streams)
-    ph = be.phase_times("r24")
-    U, Ls = be.last_split(), be.last_split_len()
-    mults = dkg_amd.split_multipliers(n, Ls, U) if be.last_combine() == 2 else None
-    work = {k: v * B for k, v in fused_valu(n, t, U, plen=Ls, mults=mults).items()}
-    work_i = {k: v * B for k, v in fused_valu(n, t, U, INSTR, Ls, mults).items()}
-    rl = kernel_rooflines(ph, work, work_i)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res)
+    U = be.last_split()
+    rl = None
+    if args.full:
+        # per-kernel device times: one extra serialised batch (one chunk stream)
+        be.set_streams(1)
+        step()
+        torch.cuda.synchronize()
+        be.set_streams(args.streams)
+        ph = be.phase_times("r24")
+        Ls = be.last_split_len()
+        mults = dkg_amd.split_multipliers(n, Ls, U) if be.last_combine() == 2 else None
+        work = {k: v * B for k, v in fused_valu(n, t, U, plen=Ls, mults=mults).items()}
+        work_i = {k: v * B for k, v in fused_valu(n, t, U, INSTR, Ls, mults).items()}
+        rl = kernel_rooflines(ph, work, work_i)
     pairs = B * n * (n - 1) * ws  # whole node: every rank runs its own B ceremonies
     out = {"metric": f"verified shares/sec (whole node) of {B} independent n={n},t={t} ceremonies per GPU "
                      f"x {ws} GPU(s) (BASELINE config 5)",
@@ -695,7 +705,8 @@ def bench_batch(args, ws, rank, local):
            "phases_ms": {k: round(v, 3) for k, v in res.ms.items()}}
     out["config"]["degree_split"] = U
     out["ref_equiv"] = ref_equiv(n, t, out["value"])
-    out.update(clock_fields(clk0, clk1))
+    if args.full:
+        out.update(clock_fields(clk0, clk1))
     out["config"]["binomial"] = "per-wave loops" if be.last_binomial() else "one launch per step"
     if rl:
         dom = max(rl, key=lambda k: rl[k]["ms_per_pass"])
@@ -703,7 +714,7 @@ def bench_batch(args, ws, rank, local):
                                                  f"per batch: {B} x the closed form of one ceremony's fused "
                                                  f"round-2/4 pipeline; device time in a serialised batch")
         add_traffic(out, dom, rl[dom]["ms_per_pass"], n, t, U, Ls, bool(be.last_binomial()), B)
-    if rank == 0 and not args.no_cpu:
+    if rank == 0 and args.full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(n, t, 20.0, ceremonies=B)
         out["gpu_vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     if rank == 0:
@@ -762,6 +773,53 @@ def sharded_self_check(args, dist, be, res, ta, D, N, dev):
                             "reconstruction, finalise)"}
 
 
+DUMP_MAX_ELEMS = 1 << 20  # per array: 4 MB of float32; a result has at most 15 arrays (< 64 MB in all)
+
+
+def result_arrays(res):
+    """The outputs a caller of the timed path receives from one step, by field name, as float32 arrays
+    (every value is a byte, a flag or a count of at most n: exact in float32).  CeremonyResult and
+    BatchResult (dataclasses) field by field; a ShardResult as its mpk, final and public shares and the
+    fields of its common decisions.  Timings (`ms`) are not outputs.  An array of more than
+    DUMP_MAX_ELEMS elements is cut to a fixed seeded sample of its elements, in index order."""
+    import dataclasses
+
+    import numpy as np
+
+    if dataclasses.is_dataclass(res):
+        src = {f.name: getattr(res, f.name) for f in dataclasses.fields(res)}
+    else:
+        src = {"mpk": res.mpk, "final_share": res.final_share, "public_share": res.public_share}
+        src.update({f.name: getattr(res.decisions, f.name) for f in dataclasses.fields(res.decisions)})
+    out = {}
+    for name, v in src.items():
+        if v is None or isinstance(v, dict):
+            continue
+        if isinstance(v, (list, tuple)) and v and isinstance(v[0], (bytes, bytearray)):
+            v = b"".join(v)
+        if isinstance(v, (bytes, bytearray)):
+            a = np.frombuffer(bytes(v), dtype=np.uint8)
+        elif hasattr(v, "cpu"):
+            a = v.cpu().numpy()
+        else:
+            a = np.asarray(v.tolist() if hasattr(v, "tolist") else v)
+        a = a.astype(np.float32).reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0x0d6b).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        out[name] = a
+    return out
+
+
+def dump_outputs(path, res):
+    """--dump-outputs DIR: DIR/<name>.npy for every array of result_arrays(res), the last timed step's
+    result.  The inputs are seeded, so two builds run with the same arguments compare file for file."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, a in result_arrays(res).items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 _RESULT_OUT = None
 
 
@@ -787,9 +845,15 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", default="D", choices=sorted(CONFIGS) + sorted(BATCH))
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the shader clock around the timed region, "
+                         "the per-kernel roofline (one extra serialised pass), the interpolation mode and the CPU "
+                         "baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's result as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-interp", action="store_true",
-                    help="skip the side measurement of the opt-in interpolation verify mode")
+                    help="with --full: skip the side measurement of the opt-in interpolation verify mode")
     ap.add_argument("--streams", type=int, default=2, help="dealer-chunk streams of the round-2/4 checks")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (one GPU per rank); gloo = rehearsal with ranks sharing GPUs")
@@ -883,7 +947,7 @@ def main():
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    clk0 = be.clock_probe()
+    clk0 = be.clock_probe() if args.full else None
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -896,7 +960,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    clk1 = be.clock_probe()
+    clk1 = be.clock_probe() if args.full else None
     if dist:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -907,6 +971,8 @@ def main():
     shard_stats = None
     if ws > 1:
         shard_stats = sharded_self_check(args, dist, be, res, ta, D, N, dev)
+    if args.dump_outputs and rank == 0 and res is not None:
+        dump_outputs(args.dump_outputs, res)
     pairs = n * (n - 1)
     value = pairs * args.steps / elapsed
     metric = f"verified shares/sec (whole node) at n={n},t={t}; full-ceremony wall time"
@@ -923,11 +989,13 @@ def main():
                    "parallelism": f"dealer-sharded x{ws}" if ws > 1 else "single GPU"},
     }
     out["ref_equiv"] = ref_equiv(n, t, value)
-    out.update(clock_fields(clk0, clk1))
+    if args.full:
+        out.update(clock_fields(clk0, clk1))
     if args.mode == "full":
         out["config"]["mode"] = "full: shares hybrid-encrypted (elgamal.rs) and decrypted by each receiver"
     if rank == 0 and ws == 1 and res is not None and args.mode == "full":
         out["phases_ms"] = {k: round(v, 3) for k, v in res.ms.items()}
+    if rank == 0 and ws == 1 and res is not None and args.mode == "full" and args.full:
         # per-kernel roofline of the whole full-mode ceremony: one serialised extra ceremony
         be.set_streams(1)
         step()
@@ -977,7 +1045,6 @@ def main():
         out["config"]["rounds_2_4_fused"] = not args.no_overlap
         ov = not args.no_overlap
         U, Ls = be.last_split(), be.last_split_len()
-        mults = dkg_amd.split_multipliers(n, Ls, U) if be.last_combine() == 2 else None
         out["config"]["degree_split"] = U
         out["config"]["split_pieces"] = split_pieces(t, U, Ls)[0]
         out["config"]["recombination"] = {0: "none", 1: "powers of j^L", 2: "short lattice multipliers"}[be.last_combine()]
@@ -985,6 +1052,9 @@ def main():
         out["config"]["recombination_addends"] = "affine Niels" if aff else "cached projective"
         out["config"]["stepping_additions"] = "dedicated (complete redo where exceptional)" if ded else "complete"
         out["stepping_redos"] = be.stepping_redos()
+    if rank == 0 and ws == 1 and res is not None and args.mode != "full" and args.verify != "interp" and args.full:
+        # --full: the side measurements of the headline configuration, each in runs of its own
+        mults = dkg_amd.split_multipliers(n, Ls, U) if be.last_combine() == 2 else None
         w2 = algorithmic_valu(n, t, 2, U, plen=Ls, mults=mults, affine=aff, ded=ded)
         w4 = algorithmic_valu(n, t, 4, U, plen=Ls, mults=mults, affine=aff, ded=ded)
         work = fused_valu(n, t, U, plen=Ls, mults=mults, affine=aff, ded=ded) if ov else w2
@@ -1041,7 +1111,7 @@ def main():
                            "bytes_per_rank_byte_rows": 2 * sc.R * n + sc.A0.numel() + sc.part.numel(),
                            "n4096_ws8_bytes_per_rank": 2 * R4 * 4 * W4 + 32 * R4 + 32 * 4096,
                            "n4096_ws8_bytes_per_rank_byte_rows": 2 * R4 * 4096 + 32 * R4 + 32 * 4096}
-    if ws > 1 and args.mode != "full" and args.verify == "group":
+    if ws > 1 and args.mode != "full" and args.verify == "group" and args.full:
         # per-GPU roofline of this rank's shard: one extra serialised pass (every rank joins its
         # collectives); the rank's work is its D dealers' share of the closed form
         be.set_streams(1)

@@ -162,6 +162,37 @@ def test_cpu_baseline_small_batch():
     assert r["batch_s_extrapolated"] == pytest.approx(10 * r["ceremony_s_extrapolated"])
 
 
+def test_dump_outputs_arrays(tmp_path):
+    """--dump-outputs: one float32 .npy per output field of the step's result (timings left out),
+    bytes as their values, a list of 32-byte keys joined, an oversized array cut to the same
+    seeded sample on every call."""
+    import numpy as np
+
+    from dkg_amd.api import BatchResult, CeremonyResult, Int32s
+
+    r = CeremonyResult(n=3, t=1, mpk=bytes(range(32)), qualified=[1, 1, 0], r2_error=[0, 0, 0], r4_error=[0, 1, 0],
+                       complaints2=[0, 2, 1], reconstruct=[0, 0, 1], n_qualified=2, phase4_error=0,
+                       ms={"total": 1.5})
+    bench.dump_outputs(str(tmp_path / "d"), r)
+    got = {p.name[:-4]: np.load(p) for p in (tmp_path / "d").iterdir()}
+    assert set(got) == {"n", "t", "mpk", "qualified", "r2_error", "r4_error", "complaints2", "reconstruct",
+                        "n_qualified", "phase4_error"}  # no `ms`, no absent big outputs
+    assert all(a.dtype == np.float32 and a.ndim == 1 for a in got.values())
+    assert got["mpk"].tolist() == list(range(32)) and got["complaints2"].tolist() == [0, 2, 1]
+    assert got["n_qualified"].tolist() == [2]
+    big = bytes(i % 251 for i in range(bench.DUMP_MAX_ELEMS + 1000))
+    b = BatchResult(B=2, n=1, t=0, mpk=[b"\x01" * 32, b"\x02" * 32], n_qualified=[1, 1], phase4_error=b"\0\0",
+                    qualified=b"\1\1", r2_error=b"\0\0", r4_error=b"\0\0",
+                    complaints2=Int32s((7).to_bytes(4, "little") * 2), reconstruct=b"\0\0", final_share=None,
+                    public_share=None, dec2=big, dec4=None, ms={})
+    a1, a2 = bench.result_arrays(b), bench.result_arrays(b)
+    assert a1["mpk"].tolist() == [1.0] * 32 + [2.0] * 32 and a1["complaints2"].tolist() == [7.0, 7.0]
+    assert "final_share" not in a1 and "dec4" not in a1
+    assert a1["dec2"].size == bench.DUMP_MAX_ELEMS and np.array_equal(a1["dec2"], a2["dec2"])
+    assert set(a1["dec2"].tolist()) <= set(range(251))
+    assert sum(a.nbytes for a in a1.values()) <= 64e6
+
+
 def test_ref_equiv_w2_matches_survey():
     """SURVEY.md 8(d)'s tabulated reference-equivalent work per verified share (dalek-3 cost model):
     W2 = A 8,647 (t=4); B 19,663; C 58,831; D 200,961; E 625,085 Fp-mults; W4 = D 198,549, E 622,673."""

@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("gpus", [2, 3])
 def test_bench_multi_rank_gloo_on_one_gpu(gpus):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dist-backend", "gloo",
-           "--steps", "2", "--warmup", "1", "--no-cpu", "--no-interp", "--dist-timeout", "120"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-interp", "--dist-timeout", "120"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
