@@ -146,6 +146,13 @@ def lib():
     L.dkg_decrypt_shares.argtypes = [p, sz, sz, u8p, u8p, u8p, p, p, p]
     L.dkg_ceremony_run_full_device.argtypes = [p, sz, sz, p, p, p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_full.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
+    L.dkg_member_keys_batch.argtypes = [p, u8p, ctypes.c_uint32, sz, sz, p, p]
+    L.dkg_encrypt_shares_batch.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, p, p]
+    L.dkg_decrypt_shares_batch.argtypes = [p, sz, sz, u8p, u8p, u8p, p, p, p]
+    L.dkg_ceremony_batch_full_device.argtypes = [p, sz, sz, sz, p, p, p, u8p, u8p, ctypes.POINTER(BatchOut)]
+    L.dkg_ceremony_batch_verify_full.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(BatchOut),
+                                                 p, p]
+    L.dkg_ctx_set_batch_full_chunk.argtypes = [p, sz]
     L.dkg_misbehaviour_prove.argtypes = [p, sz, u8p, u8p, u8p, p]
     L.dkg_complaint1_verify.argtypes = [p, sz, sz, p, u8p, u8p, u8p, u8p, p]
     L.dkg_complaint3_verify.argtypes = [p, sz, sz, p, u8p, u8p, u8p, u8p, p]
@@ -206,4 +213,6 @@ EXPORTED = [
     "dkg_shard_finalise_device", "dkg_multi_create", "dkg_multi_destroy", "dkg_multi_size", "dkg_multi_ctx",
     "dkg_multi_last_error", "dkg_multi_phase_ms", "dkg_multi_env_init", "dkg_multi_ceremony_run",
     "dkg_multi_ceremony_run_device", "dkg_multi_ceremony_verify",
+    "dkg_member_keys_batch", "dkg_encrypt_shares_batch", "dkg_decrypt_shares_batch", "dkg_ceremony_batch_full_device",
+    "dkg_ceremony_batch_verify_full", "dkg_ctx_set_batch_full_chunk",
 ]

@@ -400,6 +400,43 @@ class Backend:
         r.E, r.A = E, A
         return r
 
+    # ---- full mode for batches of ceremonies (key arrays [B][n][32], rows c*n + i = dealer i of ceremony c)
+    def member_keys_batch(self, master: bytes, ceremony0: int, B: int, n: int):
+        """member_keys of ceremonies ceremony0 .. ceremony0 + B-1 in one launch: (sk, pk), each [B][n][32]."""
+        sk, pk = ctypes.create_string_buffer(max(32 * B * n, 1)), ctypes.create_string_buffer(max(32 * B * n, 1))
+        _check(self._ctx, _lib.lib().dkg_member_keys_batch(self._ctx, master, ceremony0, B, n, sk, pk))
+        return sk.raw[:32 * B * n], pk.raw[:32 * B * n]
+
+    def encrypt_shares_batch(self, pk: bytes, s: bytes, s_prime: bytes, r: bytes, B: int, n: int):
+        """encrypt_shares per ceremony (recipient q of ceremony c under pk[c][q]): (e1, ct)."""
+        size = 64 * B * n * n
+        e1, ct = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
+        _check(self._ctx, _lib.lib().dkg_encrypt_shares_batch(self._ctx, B, n, pk, s, s_prime, r, e1, ct))
+        return e1.raw[:size], ct.raw[:size]
+
+    def decrypt_shares_batch(self, sk: bytes, e1: bytes, ct: bytes, B: int, n: int):
+        """decrypt_shares per ceremony with sk [B][n][32]: (s, s_prime, ok)."""
+        V = B * n
+        s, sp, ok = (ctypes.create_string_buffer(max(32 * V * n, 1)), ctypes.create_string_buffer(max(32 * V * n, 1)),
+                     ctypes.create_string_buffer(max(2 * V * n, 1)))
+        _check(self._ctx, _lib.lib().dkg_decrypt_shares_batch(self._ctx, B, n, sk, e1, ct, s, sp, ok))
+        return s.raw[:32 * V * n], sp.raw[:32 * V * n], ok.raw[:2 * V * n]
+
+    def set_batch_full_chunk(self, ceremonies: int):
+        """Ceremonies per chunk of the batched hybrid stage (0: automatic).  Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_batch_full_chunk(self._ctx, ceremonies))
+
+    def batch_full_phase_times(self) -> dict:
+        """Device ms of the last batched full-mode call's hybrid kernels, summed over its chunks."""
+        names = ("enc_decode", "enc_tab", "enc_e1", "enc_mul", "enc_encode", "enc_sym",
+                 "dec_decode", "dec_mul", "dec_encode", "dec_sym")
+        out = {}
+        for nm in names:
+            v = _lib.lib().dkg_ctx_phase_ms(self._ctx, f"bfull.{nm}".encode())
+            if v >= 0:
+                out[nm] = v
+        return out
+
     # ---- complaint proofs (broadcast.rs)
     def misbehaviour_prove(self, sk: bytes, enc: bytes, w: bytes) -> bytes:
         """ProofOfMisbehaviour::generate for B = len(sk) // 32 complaints: proofs [B][192]."""
@@ -685,6 +722,8 @@ class BatchResult:
     dec2: Optional[bytes]
     dec4: Optional[bytes]
     ms: dict
+    s: Optional[bytes] = None        # ceremony_batch_verify_full: the decrypted shares [B*n][n][32]
+    s_prime: Optional[bytes] = None
 
     def ceremony(self, c: int) -> dict:
         """The outputs of ceremony c in the layout of a single CeremonyResult."""
@@ -795,6 +834,37 @@ def ceremony_batch_verify(be: "Backend", B: int, n: int, t: int, E: bytes, A: by
     o, bufs = _batch_out(B, n, True)
     _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify(be.ctx, B, n, t, E, A, s, s_prime, ctypes.byref(o)))
     return _batch_result(B, n, t, o, bufs)
+
+
+def ceremony_batch_full_device(be: "Backend", B: int, n: int, t: int, d_a: int, d_b: int, d_r: int, sk: bytes,
+                               pk: bytes, big: bool = False) -> BatchResult:
+    """B honest full-mode ceremonies (dkg_ceremony_batch_full_device): device coefficients d_a, d_b
+    [B*n][t+1][32], encryption randomness d_r [B*n][n][2][32] (enc_randomness_device(master, c0, B, 0, n, n,
+    t, d_r)), sk / pk = member_keys_batch output.  Output buffers are kept on the backend as in
+    ceremony_batch_device."""
+    key = (B, n, big)
+    cache = getattr(be, "_batch_bufs", None)
+    if cache is None or cache[0] != key:
+        cache = (key,) + _batch_out(B, n, big)
+        be._batch_bufs = cache
+    o, bufs = cache[1], cache[2]
+    vp = ctypes.c_void_p
+    _check(be.ctx, _lib.lib().dkg_ceremony_batch_full_device(be.ctx, B, n, t, vp(d_a), vp(d_b), vp(d_r), sk, pk,
+                                                               ctypes.byref(o)))
+    return _batch_result(B, n, t, o, bufs)
+
+
+def ceremony_batch_verify_full(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, e1: bytes, ct: bytes,
+                               sk: bytes) -> BatchResult:
+    """Receiver side of B full-mode ceremonies from (possibly tampered) broadcast values
+    (dkg_ceremony_batch_verify_full); the result also carries the decrypted s / s_prime."""
+    o, bufs = _batch_out(B, n, True)
+    size = 32 * B * n * n
+    s, sp = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
+    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_full(be.ctx, B, n, t, E, A, e1, ct, sk, ctypes.byref(o), s, sp))
+    r = _batch_result(B, n, t, o, bufs)
+    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
+    return r
 
 
 class Environment:

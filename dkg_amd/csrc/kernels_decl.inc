@@ -267,6 +267,22 @@ void dealer_seeds(size_t rows, size_t D, size_t d0, uint32_t c0, const uint32_t*
 // encryption randomness rows (seedgen.hip): r [rows][n][2][8] = wide(block 2N + 2q + w) of each dealer stream
 void enc_randomness(size_t rows, size_t n, size_t N, const uint32_t* seeds, uint32_t* r, hipStream_t stream);
 
+// ---- full mode for batches of ceremonies, hybrid_batch.hip: key c*n + q belongs to recipient q of
+// ceremony c, item (c, i, q, w) sits at ((c*n + i)*n + q)*2 + w
+// signed radix-16 combs (benc_tab_words() words each: 64 windows x 8 multiples, cached form) of the
+// decoded keys pk_ext[.., key], key < keys
+size_t benc_tab_words();
+void benc_tab(size_t keys, const uint32_t* pk_ext, size_t stride, uint32_t* tab, hipStream_t stream);
+// K = pk_key * r for every item of the keys' ceremonies (r [items][8] canonical), K_ext SoA [40][count]
+void benc_mul(size_t keys, size_t n, const uint32_t* r, const uint32_t* tab, uint32_t* K_ext, size_t count,
+              hipStream_t stream);
+// K = sk_key * R for every item (sk [keys][8], wave-uniform; R decoded SoA [40][count]); table:
+// bdec_mul_table_words(keys, n) words for the width-4 window's odd multiples
+size_t bdec_mul_table_words(size_t keys, size_t n);
+size_t bdec_launch_waves();  // waves per launch (the table's slots): larger calls run as slices
+void bdec_mul(size_t keys, size_t n, const uint32_t* sk, const uint32_t* R_ext, uint32_t* K_ext, size_t count,
+              uint32_t* table, hipStream_t stream);
+
 // ---- committee verification by interpolation (interp.hip)
 // F[d][k] = sum_j W[k][j] s[d][j] (and F' from s'; sp may be null), WT[j][k] = W[k][j] in Montgomery form
 void interp(size_t D, size_t N, size_t nrecv, const uint32_t* WT, const uint32_t* s, const uint32_t* sp, uint32_t* F,

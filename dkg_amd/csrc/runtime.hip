@@ -105,6 +105,13 @@ struct dkg_ctx {
   // (arena-owned; dkg_ceremony_shard_recon_device reads them after the exchange)
   const uint32_t* shard_s = nullptr;
   size_t shard_n = 0, shard_d0 = 0, shard_D = 0;
+  // full mode of the batches (dkg_ceremony_batch_full_device and its primitives): ceremonies per
+  // chunk of the hybrid stage (0: automatic, bfull_chunk_size), and the phase marks of the last call --
+  // (phase, event) in stream order, a segment between two marks belonging to the later one's phase
+  // (-1: a start mark); events come from a grow-only pool
+  size_t bfull_chunk = 0;
+  std::vector<hipEvent_t> bf_pool;
+  std::vector<std::pair<int, hipEvent_t>> bf_marks;
   std::string timed_tag;                // set while pev[] hold a serialised verify_device's phases
   std::map<std::string, double> phase_ms;  // last value per "r<round>.<phase>"
 };
@@ -1450,7 +1457,7 @@ struct BatchRound1 {
 // (qualification, complaints, round-3 sums, mpk) are grouped kernels.  Every output equals what B
 // separate ceremonies produce.
 void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
-                     const uint32_t* s, const uint32_t* sp, dkg_batch_out* out) {
+                     const uint32_t* s, const uint32_t* sp, dkg_batch_out* out, const uint8_t* e_ok = nullptr) {
   const size_t N = t + 1, V = B * n;
   uint8_t* dec2 = buf<uint8_t>(ctx, "b.dec2", V * n);
   uint8_t* dec4 = buf<uint8_t>(ctx, "b.dec4", V * n);
@@ -1477,7 +1484,9 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
     dkgk::encode_points(pub, V, V, pubc, ctx->stream);
     HCK(hipEventRecord(ctx->ev[3], ctx->stream));
   };
-  verify_rounds(ctx, n, t, V, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, nullptr, nullptr, false);
+  // e_ok (may be null; [V] on the device): full mode's decode mask of each dealer's ciphertexts -- a row
+  // that did not decode is missing data (DKG_MISSING in round 2), as in receivers_rounds
+  verify_rounds(ctx, n, t, V, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, e_ok, nullptr, false);
   // round 4 (committee.rs:515-522, 567-569, 660-670): rows of disqualified dealers SKIPPED
   round4_device(ctx, B, n, t, dec4, qmask, rej4, r4d);
   dkgk::mask_not_and(V, rej4, qmask, hmask, ctx->stream);
@@ -1684,6 +1693,121 @@ void collect_hybrid_phases(dkg_ctx* ctx) {
   }
 }
 
+// ---- full mode for batches (hybrid_batch.hip): ceremony c's recipients own keys c*n .. c*n + n-1.
+// The hybrid stage runs in chunks of ceremonies so that its scratch -- the extended-form R and K, the
+// K encodings, the decoded keys and their radix-16 combs, the decryption's odd-multiple table -- does
+// not grow with B (10,000 x 64 unchunked: 26 GB of R / K / Kc and 52 GB of combs).
+constexpr size_t BFULL_SCRATCH_BYTES = (size_t)2 << 30;  // automatic chunk: R + K + Kc + keys + combs within 2 GiB
+enum {
+  BF_ENC_DECODE, BF_ENC_TAB, BF_ENC_E1, BF_ENC_MUL, BF_ENC_ENCODE, BF_ENC_SYM,
+  BF_DEC_DECODE, BF_DEC_MUL, BF_DEC_ENCODE, BF_DEC_SYM, BF_PHASES
+};
+const char* const BF_NAMES[BF_PHASES] = {"enc_decode", "enc_tab", "enc_e1", "enc_mul", "enc_encode", "enc_sym",
+                                         "dec_decode", "dec_mul", "dec_encode", "dec_sym"};
+
+size_t bfull_chunk_size(const dkg_ctx* ctx, size_t B, size_t n) {
+  const size_t items = 2 * n * n;
+  const size_t per = items * (2 * PTB + 32) + n * (PTB + 4 * dkgk::benc_tab_words());
+  // automatic: within the scratch budget, and the chunk's decryption one launch under the table cap
+  const size_t fit = std::min(BFULL_SCRATCH_BYTES / per, dkgk::bdec_launch_waves() / (2 * n * ((n + 63) / 64)));
+  const size_t c = ctx->bfull_chunk ? ctx->bfull_chunk : std::max<size_t>(1, fit);
+  return std::min(c, B);
+}
+
+void bf_reset(dkg_ctx* ctx) { ctx->bf_marks.clear(); }
+void bf_mark(dkg_ctx* ctx, hipStream_t st, int phase) {
+  const size_t k = ctx->bf_marks.size();
+  if (k == ctx->bf_pool.size()) {
+    hipEvent_t e;
+    HCK(hipEventCreate(&e));
+    ctx->bf_pool.push_back(e);
+  }
+  HCK(hipEventRecord(ctx->bf_pool[k], st));
+  ctx->bf_marks.emplace_back(phase, ctx->bf_pool[k]);
+}
+// After a sync: the summed device times of the last call's hybrid kernels over all chunks
+// (dkg_ctx_phase_ms "bfull.enc_decode", ".enc_tab", ".enc_e1", ".enc_mul", ".enc_encode", ".enc_sym",
+// ".dec_decode", ".dec_mul", ".dec_encode", ".dec_sym"); a phase the call did not run reads -1.
+void collect_bfull_phases(dkg_ctx* ctx) {
+  double ms[BF_PHASES] = {};
+  bool seen[BF_PHASES] = {};
+  for (size_t k = 1; k < ctx->bf_marks.size(); k++) {
+    const int ph = ctx->bf_marks[k].first;
+    if (ph < 0) continue;
+    float v = 0;
+    HCK(hipEventElapsedTime(&v, ctx->bf_marks[k - 1].second, ctx->bf_marks[k].second));
+    ms[ph] += v;
+    seen[ph] = true;
+  }
+  for (int i = 0; i < BF_PHASES; i++) {
+    const std::string name = std::string("bfull.") + BF_NAMES[i];
+    if (seen[i]) ctx->phase_ms[name] = ms[i];
+    else ctx->phase_ms.erase(name);
+  }
+  ctx->bf_marks.clear();
+}
+
+// Dealers' side: pkc [B*n][8] key encodings, s / sp [B*n][n][8], r [B*n][n][2][8] -> e1, ct
+// [B*n][n][2][8]; pk_ok [B*n] = the key decodes.  All on ctx->stream.
+void encrypt_batch_device(dkg_ctx* ctx, size_t B, size_t n, const uint32_t* pkc, const uint32_t* s, const uint32_t* sp,
+                          const uint32_t* r, uint32_t* e1, uint32_t* ct, uint8_t* pk_ok) {
+  hipStream_t st = ctx->stream;
+  const size_t chunk = bfull_chunk_size(ctx, B, n);
+  const size_t mk = chunk * n, mi = 2 * mk * n;
+  uint32_t* pk_ext = buf<uint32_t>(ctx, "bf.pk_ext", PTB * mk);
+  uint32_t* tab = buf<uint32_t>(ctx, "bf.tab", 4 * dkgk::benc_tab_words() * mk);
+  uint32_t* R = buf<uint32_t>(ctx, "bf.R", PTB * mi);
+  uint32_t* K = buf<uint32_t>(ctx, "bf.K", PTB * mi);
+  uint32_t* Kc = buf<uint32_t>(ctx, "bf.Kc", 32 * mi);
+  bf_mark(ctx, st, -1);
+  for (size_t c0 = 0; c0 < B; c0 += chunk) {
+    const size_t Bc = std::min(chunk, B - c0), keys = Bc * n, items = 2 * keys * n;
+    const size_t k0 = c0 * n, p0 = k0 * n, i0 = 2 * p0;  // first key / (dealer, recipient) pair / item
+    dkgk::decode_points(pkc + 8 * k0, keys, pk_ext, keys, pk_ok + k0, st);
+    bf_mark(ctx, st, BF_ENC_DECODE);
+    dkgk::benc_tab(keys, pk_ext, keys, tab, st);
+    bf_mark(ctx, st, BF_ENC_TAB);
+    dkgk::fixed_base(items, r + 8 * i0, ctx->tab_gw, R, st);  // e1 = G::generator() * r  (elgamal.rs:141)
+    bf_mark(ctx, st, BF_ENC_E1);
+    dkgk::benc_mul(keys, n, r + 8 * i0, tab, K, items, st);   // key = pk * r  (elgamal.rs:138-140)
+    bf_mark(ctx, st, BF_ENC_MUL);
+    dkgk::encode_points(R, items, items, e1 + 8 * i0, st);
+    dkgk::encode_points(K, items, items, Kc, st);
+    bf_mark(ctx, st, BF_ENC_ENCODE);
+    dkgk::sym_xor(keys, n, Kc, false, ct + 8 * i0, const_cast<uint32_t*>(s) + 8 * p0,
+                  const_cast<uint32_t*>(sp) + 8 * p0, st);
+    bf_mark(ctx, st, BF_ENC_SYM);
+  }
+  check_launch(ctx);
+}
+
+// Receivers' side: sk [B*n][8]; item_ok [B*n][n][2] = e1 decodes; dealer_ok_out (may be null) [B*n].
+void decrypt_batch_device(dkg_ctx* ctx, size_t B, size_t n, const uint32_t* sk, const uint32_t* e1, const uint32_t* ct,
+                          uint32_t* s, uint32_t* sp, uint8_t* item_ok, uint8_t* dealer_ok_out) {
+  hipStream_t st = ctx->stream;
+  const size_t chunk = bfull_chunk_size(ctx, B, n);
+  const size_t mk = chunk * n, mi = 2 * mk * n;
+  uint32_t* R = buf<uint32_t>(ctx, "bf.R", PTB * mi);
+  uint32_t* K = buf<uint32_t>(ctx, "bf.K", PTB * mi);
+  uint32_t* Kc = buf<uint32_t>(ctx, "bf.Kc", 32 * mi);
+  uint32_t* T = buf<uint32_t>(ctx, "bf.dec_tab", 4 * dkgk::bdec_mul_table_words(mk, n));
+  bf_mark(ctx, st, -1);
+  for (size_t c0 = 0; c0 < B; c0 += chunk) {
+    const size_t Bc = std::min(chunk, B - c0), keys = Bc * n, items = 2 * keys * n;
+    const size_t k0 = c0 * n, p0 = k0 * n, i0 = 2 * p0;
+    dkgk::decode_points(e1 + 8 * i0, items, R, items, item_ok + i0, st);
+    bf_mark(ctx, st, BF_DEC_DECODE);
+    dkgk::bdec_mul(keys, n, sk + 8 * k0, R, K, items, T, st);  // committee.rs:282-286
+    bf_mark(ctx, st, BF_DEC_MUL);
+    dkgk::encode_points(K, items, items, Kc, st);
+    bf_mark(ctx, st, BF_DEC_ENCODE);
+    dkgk::sym_xor(keys, n, Kc, true, const_cast<uint32_t*>(ct) + 8 * i0, s + 8 * p0, sp + 8 * p0, st);
+    bf_mark(ctx, st, BF_DEC_SYM);
+  }
+  if (dealer_ok_out) dkgk::dealer_ok(B * n, 2 * n, item_ok, dealer_ok_out, st);
+  check_launch(ctx);
+}
+
 // ---- complaint proofs (dl_equality/zkp.rs, broadcast.rs:50-135, 181-283)
 // Cold path (one proof per complaint): the group work goes to the GPU as batched MSMs (k_msm), the
 // Fiat-Shamir hashes, ChaCha20 and scalar arithmetic run on the host.
@@ -1876,6 +2000,8 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   for (auto& e : ctx->hev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->join)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : ctx->bf_pool)
     if (e) (void)hipEventDestroy(e);
   if (ctx->fork) (void)hipEventDestroy(ctx->fork);
   for (auto& st : ctx->sub)
@@ -3167,6 +3293,204 @@ int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E,
     out->ms_round4 = ev_ms(ctx, 3, 4);
     out->ms_finalise = ev_ms(ctx, 4, 5);
     out->ms_total = ev_ms(ctx, 0, 5);
+    return DKG_OK;
+  });
+}
+
+// ---- full mode for batches of ceremonies (hybrid_batch.hip)
+int dkg_ctx_set_batch_full_chunk(dkg_ctx* ctx, size_t ceremonies) {
+  if (!ctx) return DKG_E_ARG;
+  ctx->bfull_chunk = ceremonies;
+  return DKG_OK;
+}
+
+int dkg_member_keys_batch(dkg_ctx* ctx, const uint8_t master[32], uint32_t ceremony0, size_t B, size_t n,
+                          uint8_t* sk_out, uint8_t* pk_out) {
+  return guarded(ctx, [&] {
+    if (!master || !sk_out || !pk_out) return DKG_E_ARG;
+    const size_t V = B * n;
+    if (!V) return DKG_OK;
+    static const char tag[] = "dkg-amd/v1/member";
+    std::vector<uint8_t> sk(32 * V), pk(32 * V);
+    for (size_t c = 0; c < B; c++) {
+      const uint32_t ceremony = ceremony0 + (uint32_t)c;
+      for (size_t j = 0; j < n; j++) {  // MemberCommunicationKey::new (procedure_keys.rs:72-76), as dkg_member_keys
+        uint8_t msg[sizeof tag - 1 + 40], seed[32], st[64];
+        memcpy(msg, tag, sizeof tag - 1);
+        memcpy(msg + sizeof tag - 1, master, 32);
+        for (int k = 0; k < 4; k++) {
+          msg[sizeof tag - 1 + 32 + k] = (uint8_t)(ceremony >> (8 * k));
+          msg[sizeof tag - 1 + 36 + k] = (uint8_t)((uint32_t)j >> (8 * k));
+        }
+        dkgh::blake2b(seed, 32, msg, sizeof msg);
+        dkgh::chacha20(seed, 0, st, 64);
+        dkgh::zl_to_bytes(&sk[32 * (c * n + j)], dkgh::zl_from_bytes_wide(st, 64));
+      }
+    }
+    uint32_t* dsk = buf<uint32_t>(ctx, "mk_sk", 32 * V);
+    uint32_t* dpe = buf<uint32_t>(ctx, "mk_pk_ext", PTB * V);
+    uint32_t* dpc = buf<uint32_t>(ctx, "mk_pk", 32 * V);
+    h2d(ctx, dsk, sk.data(), 32 * V);
+    dkgk::fixed_base(V, dsk, ctx->tab_gw, dpe, ctx->stream);  // to_public of all B*n keys, one launch
+    dkgk::encode_points(dpe, V, V, dpc, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, pk.data(), dpc, 32 * V);
+    sync(ctx);
+    // committee.rs:134-135: each ceremony's keys sorted by public-key bytes
+    std::vector<size_t> order(n);
+    for (size_t c = 0; c < B; c++) {
+      const uint8_t* cpk = &pk[32 * c * n];
+      for (size_t j = 0; j < n; j++) order[j] = j;
+      std::sort(order.begin(), order.end(),
+                [&](size_t a, size_t b) { return memcmp(cpk + 32 * a, cpk + 32 * b, 32) < 0; });
+      for (size_t q = 0; q < n; q++) {
+        memcpy(sk_out + 32 * (c * n + q), &sk[32 * (c * n + order[q])], 32);
+        memcpy(pk_out + 32 * (c * n + q), cpk + 32 * order[q], 32);
+      }
+    }
+    return DKG_OK;
+  });
+}
+
+namespace {
+// DKG_E_DECODE when a recipient key of the last encrypt_batch_device did not decode (after a sync)
+int batch_keys_status(dkg_ctx* ctx, const uint8_t* ok, size_t V) {
+  for (size_t k = 0; k < V; k++)
+    if (!ok[k]) {
+      ctx->err = "encrypt_shares_batch: a recipient public key does not decode";
+      return DKG_E_DECODE;
+    }
+  return DKG_OK;
+}
+}  // namespace
+
+int dkg_encrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* pk, const uint8_t* s,
+                             const uint8_t* s_prime, const uint8_t* r, uint8_t* e1, uint8_t* ct) {
+  return guarded(ctx, [&] {
+    if (!pk || !s || !s_prime || !r || !e1 || !ct) return DKG_E_ARG;
+    if (!B || !n) return DKG_OK;
+    const size_t V = B * n, items = 2 * V * n;
+    uint32_t* dpk = buf<uint32_t>(ctx, "bx_pk", 32 * V);
+    h2d(ctx, dpk, pk, 32 * V);
+    uint32_t* ds = upload_scalars(ctx, "bx_s", s, V * n);
+    uint32_t* dsp = upload_scalars(ctx, "bx_sp", s_prime, V * n);
+    uint32_t* dr = upload_scalars(ctx, "bx_r", r, items);
+    uint32_t* de1 = buf<uint32_t>(ctx, "bx_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "bx_ct", 32 * items);
+    uint8_t* pok = buf<uint8_t>(ctx, "bx_pkok", V);
+    uint8_t* ok = hbuf<uint8_t>(ctx, "hb.bf_pkok", V);
+    bf_reset(ctx);
+    encrypt_batch_device(ctx, B, n, dpk, ds, dsp, dr, de1, dct, pok);
+    d2h(ctx, ok, pok, V);
+    d2h(ctx, e1, de1, 32 * items);
+    d2h(ctx, ct, dct, 32 * items);
+    sync(ctx);
+    collect_bfull_phases(ctx);
+    return batch_keys_status(ctx, ok, V);
+  });
+}
+
+int dkg_decrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* sk, const uint8_t* e1, const uint8_t* ct,
+                             uint8_t* s, uint8_t* s_prime, uint8_t* ok) {
+  return guarded(ctx, [&] {
+    if (!sk || !e1 || !ct || !s || !s_prime) return DKG_E_ARG;
+    if (!B || !n) return DKG_OK;
+    const size_t V = B * n, items = 2 * V * n;
+    uint32_t* dsk = upload_scalars(ctx, "bx_sk", sk, V);
+    uint32_t* de1 = buf<uint32_t>(ctx, "bx_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "bx_ct", 32 * items);
+    h2d(ctx, de1, e1, 32 * items);
+    h2d(ctx, dct, ct, 32 * items);
+    uint32_t* ds = buf<uint32_t>(ctx, "bx_s", 32 * V * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "bx_sp", 32 * V * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "bx_ok", items);
+    bf_reset(ctx);
+    decrypt_batch_device(ctx, B, n, dsk, de1, dct, ds, dsp, iok, nullptr);
+    d2h(ctx, s, ds, 32 * V * n);
+    d2h(ctx, s_prime, dsp, 32 * V * n);
+    if (ok) d2h(ctx, ok, iok, items);
+    sync(ctx);
+    collect_bfull_phases(ctx);
+    return DKG_OK;
+  });
+}
+
+// Full-mode batch: round 1 of every ceremony with its shares hybrid-encrypted to that ceremony's sorted
+// member keys, the receivers' decryption, then rounds 2-5 on the decrypted shares as the plaintext
+// batch runs them.  The hybrid stage is serialised on the ctx stream: the encryption in ms_round1, the
+// decryption in ms_checks.
+int dkg_ceremony_batch_full_device(dkg_ctx* ctx, size_t B, size_t n, size_t t, const void* d_a, const void* d_b,
+                                   const void* d_r, const uint8_t* sk, const uint8_t* pk, dkg_batch_out* out) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !sk || !pk) return DKG_E_ARG;
+    if (B == 0) return DKG_OK;
+    if (!d_a || !d_b || !d_r) return DKG_E_ARG;
+    const size_t N = t + 1, V = B * n, items = 2 * V * n;
+    uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
+    uint32_t* dpk = buf<uint32_t>(ctx, "bfm_pk", 32 * V);
+    h2d(ctx, dpk, pk, 32 * V);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
+    uint32_t* ds = buf<uint32_t>(ctx, "bat_s", 32 * V * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "bat_sp", 32 * V * n);
+    uint32_t* e1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
+    uint32_t* ct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
+    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
+    uint8_t* pok = buf<uint8_t>(ctx, "bfm_pkok", V);
+    uint8_t* ok = hbuf<uint8_t>(ctx, "hb.bf_pkok", V);  // pinned: the copy below must not stall the queue
+    BatchRound1 r1(ctx, V, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, ds, dsp);
+    wait_shares(ctx, ctx->stream);  // the encryption reads the shares the side stream evaluates
+    bf_reset(ctx);
+    encrypt_batch_device(ctx, B, n, dpk, ds, dsp, (const uint32_t*)d_r, e1, ct, pok);  // committee.rs:169-172
+    d2h(ctx, ok, pok, V);
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    decrypt_batch_device(ctx, B, n, dsk, e1, ct, rs, rsp, iok, eok);                    // committee.rs:282-286
+    std::unique_ptr<ExtScope> ext(r1.deferred() ? nullptr : new ExtScope(ctx, V, N));
+    batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok);
+    collect_bfull_phases(ctx);
+    batch_times(ctx, out, true);
+    return batch_keys_status(ctx, ok, V);
+  });
+}
+
+int dkg_ceremony_batch_verify_full(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                   const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, dkg_batch_out* out,
+                                   uint8_t* s_out, uint8_t* s_prime_out) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk) return DKG_E_ARG;
+    if (B == 0) return DKG_OK;
+    const size_t N = t + 1, V = B * n, items = 2 * V * n;
+    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
+    h2d(ctx, Ec, E, 32 * V * N);
+    h2d(ctx, Ac, A, 32 * V * N);
+    uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
+    uint32_t* de1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
+    h2d(ctx, de1, e1, 32 * items);
+    h2d(ctx, dct, ct, 32 * items);
+    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    bf_reset(ctx);
+    decrypt_batch_device(ctx, B, n, dsk, de1, dct, rs, rsp, iok, eok);
+    batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok);
+    collect_bfull_phases(ctx);
+    if (s_out) d2h(ctx, s_out, rs, 32 * V * n);
+    if (s_prime_out) d2h(ctx, s_prime_out, rsp, 32 * V * n);
+    sync(ctx);
+    batch_times(ctx, out, false);
     return DKG_OK;
   });
 }

@@ -508,6 +508,54 @@ int dkg_ceremony_run_full_device(dkg_ctx *ctx, size_t n, size_t t, const void *d
 int dkg_ceremony_verify_full(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *E, const uint8_t *A, const uint8_t *e1,
                              const uint8_t *ct, const uint8_t *sk, dkg_ceremony_out *out);
 
+/* ---- full mode for batches of independent ceremonies ----
+ * B ceremonies of n parties, each with its OWN member keys, run as dkg_ceremony_run_full_device /
+ * dkg_ceremony_verify_full run one.  Row c*n + i of every [B*n]-row array is dealer i of ceremony c
+ * (as in dkg_ceremony_batch_device); key arrays sk, pk are [B][n][32], recipient q of ceremony c
+ * owning sk[c][q] / pk[c][q]; ciphertext arrays are [B*n dealer rows][n recipients][2][32] with
+ * [..][0] = the randomness s' and [..][1] = the share s.  Every output equals what B separate
+ * single-ceremony calls return.  Per-kernel device times of the last call, summed over its chunks:
+ * dkg_ctx_phase_ms "bfull.enc_decode", "bfull.enc_tab" (the keys' radix-16 combs), "bfull.enc_e1"
+ * (g*r), "bfull.enc_mul" (K = pk*r), "bfull.enc_encode", "bfull.enc_sym", "bfull.dec_decode",
+ * "bfull.dec_mul" (K = sk*e1), "bfull.dec_encode", "bfull.dec_sym"; -1 for a phase the call did not
+ * run. */
+/* dkg_member_keys for ceremonies ceremony0 .. ceremony0 + B-1 (one fixed-base launch for all B*n
+ * keys): ceremony c's rows equal dkg_member_keys(master, ceremony0 + c, n), sorted by public-key
+ * bytes within the ceremony. */
+int dkg_member_keys_batch(dkg_ctx *ctx, const uint8_t master[32], uint32_t ceremony0, size_t B, size_t n, uint8_t *sk,
+                          uint8_t *pk);
+/* dkg_encrypt_shares per ceremony: s, s_prime [B*n][n][32], r [B*n][n][2][32] (canonical scalars)
+ * -> e1, ct [B*n][n][2][32]; recipient q of ceremony c is encrypted to pk[c][q] (only public keys
+ * enter).  DKG_E_DECODE if a key does not decode. */
+int dkg_encrypt_shares_batch(dkg_ctx *ctx, size_t B, size_t n, const uint8_t *pk, const uint8_t *s,
+                             const uint8_t *s_prime, const uint8_t *r, uint8_t *e1, uint8_t *ct);
+/* dkg_decrypt_shares per ceremony with sk [B][n][32]: s, s_prime [B*n][n][32]; ok [B*n][n][2] (may be
+ * NULL) = e1 decoded. */
+int dkg_decrypt_shares_batch(dkg_ctx *ctx, size_t B, size_t n, const uint8_t *sk, const uint8_t *e1, const uint8_t *ct,
+                             uint8_t *s, uint8_t *s_prime, uint8_t *ok);
+/* Honest full-mode batch from device coefficients d_a, d_b [B*n][t+1][32] and encryption randomness
+ * d_r [B*n][n][2][32] (the layout dkg_enc_randomness_device(.., B, 0, n, n, t, ..) writes); sk, pk =
+ * dkg_member_keys_batch output (host).  Share evaluation, encryption, the receivers' decryption, then
+ * rounds 2-5 on the decrypted shares.  The hybrid stage runs on the context's stream: the encryption
+ * is timed in ms_round1, the decryption in ms_checks. */
+int dkg_ceremony_batch_full_device(dkg_ctx *ctx, size_t B, size_t n, size_t t, const void *d_a, const void *d_b,
+                                   const void *d_r, const uint8_t *sk, const uint8_t *pk, dkg_batch_out *out);
+/* Receiver side of a full-mode batch from (possibly tampered) host broadcast values: E, A
+ * [B*n][t+1][32], e1, ct [B*n][n][2][32], sk [B][n][32].  A dealer with a ciphertext whose e1 does not
+ * decode is missing data: DKG_MISSING for every receiver of its ceremony in round 2.  s_out,
+ * s_prime_out ([B*n][n][32], may be NULL) receive the decrypted shares. */
+int dkg_ceremony_batch_verify_full(dkg_ctx *ctx, size_t B, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                   const uint8_t *e1, const uint8_t *ct, const uint8_t *sk, dkg_batch_out *out,
+                                   uint8_t *s_out, uint8_t *s_prime_out);
+/* The hybrid stage of the batch calls above runs in chunks of `ceremonies` ceremonies, so that its
+ * scratch does not grow with B: per ceremony 2n^2 items x 352 B (the extended-form R and K, K's
+ * encoding) and n keys x (160 B decoded + 80 KiB radix-16 comb) -- 8.1 MB at n = 64 -- plus the
+ * decryption's odd-multiple table (40 KB per wave of a launch, at most 1.3 GB).  0 (default):
+ * automatic, the largest count whose per-ceremony scratch fits 2 GiB (263 ceremonies at n = 64) and
+ * whose decryption is one launch under the table's cap of 32,768 waves (256 at n = 64), at least 1.
+ * Outputs do not depend on it. */
+int dkg_ctx_set_batch_full_chunk(dkg_ctx *ctx, size_t ceremonies);
+
 /* ---- complaint proofs: dl_equality/zkp.rs, broadcast.rs ----
  * enc [B][128] = one dealer->accuser ciphertext pair: e1_rand || ct_rand || e1_share || ct_share.
  * proof [192] = ProofOfMisbehaviour (broadcast.rs:181-186): share_key || randomness_key || c1 || r1
