@@ -156,6 +156,11 @@ def lib():
     L.dkg_misbehaviour_prove.argtypes = [p, sz, u8p, u8p, u8p, p]
     L.dkg_complaint1_verify.argtypes = [p, sz, sz, p, u8p, u8p, u8p, u8p, p]
     L.dkg_complaint3_verify.argtypes = [p, sz, sz, p, u8p, u8p, u8p, u8p, p]
+    L.dkg_complaints_prove.argtypes = [p, sz, u8p, u8p, u8p, p]
+    L.dkg_complaints_verify.argtypes = [p, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, u8p, p, p]
+    L.dkg_ctx_set_complaint_eval.argtypes = [p, ctypes.c_int]
+    L.dkg_ceremony_verify_full_complaints.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p,
+                                                      ctypes.POINTER(CeremonyOut), p, p]
     L.dkg_dealer_coeffs.argtypes = [u8p, ctypes.c_uint32, sz, sz, sz, p, p]
     L.dkg_scalar_sum_device.argtypes = [p, sz, sz, p, p, p]
     L.dkg_point_sum_device.argtypes = [p, sz, p, p, p]
@@ -215,4 +220,5 @@ EXPORTED = [
     "dkg_multi_ceremony_run_device", "dkg_multi_ceremony_verify",
     "dkg_member_keys_batch", "dkg_encrypt_shares_batch", "dkg_decrypt_shares_batch", "dkg_ceremony_batch_full_device",
     "dkg_ceremony_batch_verify_full", "dkg_ctx_set_batch_full_chunk",
+    "dkg_complaints_prove", "dkg_complaints_verify", "dkg_ctx_set_complaint_eval", "dkg_ceremony_verify_full_complaints",
 ]

@@ -459,6 +459,52 @@ class Backend:
         _check(self._ctx, _lib.lib().dkg_complaint3_verify(self._ctx, B, t, acc, share, randomness, E, A, res))
         return list(res)[:B]
 
+    # ---- round-2 complaints as device batches, and the qualified set they prove (committee.rs:370-398)
+    def set_complaint_eval(self, mode: int):
+        """How complaints_verify evaluates P_i(j): 0 automatic, 1 per-pair Horner, 2 difference tables.
+        Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_complaint_eval(self._ctx, mode))
+
+    def complaints_prove(self, sk: bytes, enc: bytes, w: bytes) -> bytes:
+        """ProofOfMisbehaviour::generate for C = len(sk) // 32 complaints on the device: proofs [C][192],
+        byte-identical to misbehaviour_prove."""
+        C = len(sk) // 32
+        out = ctypes.create_string_buffer(max(192 * C, 1))
+        _check(self._ctx, _lib.lib().dkg_complaints_prove(self._ctx, C, sk, enc, w, out))
+        return out.raw[:192 * C]
+
+    def complaints_verify(self, n: int, t: int, accusers: Sequence[int], accused: Sequence[int], pk: bytes, E: bytes,
+                          enc: bytes, proofs: bytes, fetched1: Optional[bytes] = None):
+        """compute_qualified_set over the broadcast complaints of one ceremony: (verdicts, qualified).
+        accusers / accused 1-based; enc [C][128] = what the ACCUSED broadcast to the accuser."""
+        C = len(accusers)
+        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
+        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
+        res = (ctypes.c_int32 * max(C, 1))()
+        q = ctypes.create_string_buffer(max(n, 1))
+        _check(self._ctx, _lib.lib().dkg_complaints_verify(self._ctx, n, t, C, acc, acd, pk, E, fetched1, enc, proofs,
+                                                            res, q))
+        return list(res)[:C], list(q.raw[:n])
+
+    def ceremony_verify_full_complaints(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, pk: bytes,
+                                        accusers: Sequence[int], accused: Sequence[int], proofs: bytes, n: int,
+                                        t: int):
+        """ceremony_verify_full with the reference's rule for the qualified set: a dealer is cleared only
+        by a complaint that verifies.  Returns (CeremonyResult, verdicts, dissent)."""
+        C = len(accusers)
+        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
+        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
+        res = (ctypes.c_int32 * max(C, 1))()
+        dis = (ctypes.c_int32 * max(n, 1))()
+        o, bufs = self._ceremony_out(n, t, True)
+        for k in ("E", "A"):
+            setattr(o, k, None)
+        _check(self._ctx, _lib.lib().dkg_ceremony_verify_full_complaints(
+            self._ctx, n, t, E, A, e1, ct, sk, pk, C, acc, acd, proofs, ctypes.byref(o), res, dis))
+        r = self._result(n, t, o, bufs, True)
+        r.E, r.A = E, A
+        return r, list(res)[:C], list(dis)[:n]
+
     def dealer_coefficients_device(self, master: bytes, ceremony0: int, B: int, d0: int, D: int, t: int,
                                    d_a: int, d_b: int):
         """dkg_dealer_coeffs on the GPU for B ceremonies: rows [B*D][t+1][32] at device pointers."""

@@ -242,6 +242,34 @@ def intake_phase3(n: int, t: int, msgs: Sequence[Optional[BroadcastPhase3]]) -> 
     return bytes(A), bytes(ok)
 
 
+def intake_phase2(n: int, msgs: Sequence[Optional[BroadcastPhase2]]) -> Tuple[List[int], List[int], bytes]:
+    """Every party's phase-2 broadcast (msgs[j] from party j+1, None if it did not broadcast) as
+    MembersFetchedState2::from_broadcast (committee.rs:878-910) hands it to compute_qualified_set
+    (:370-398): the sender index is the position + 1, an absent broadcast is dropped (the only thing
+    from_broadcast drops), and the complaints come out flattened in broadcast order as
+    (accuser, accused, proofs [C][192]) for Backend.complaints_verify /
+    ceremony_verify_full_complaints.  The ciphertext copy a complaint carries is ignored: verify reads
+    the accused's own phase-1 broadcast (broadcast.rs:57).  An accused index outside 1..n, where the
+    reference's indexing panics (:379), raises ValueError."""
+    if len(msgs) != n:
+        raise ValueError("one entry per party expected")
+    accuser: List[int] = []
+    accused: List[int] = []
+    proofs: List[bytes] = []
+    for j, m in enumerate(msgs):
+        if m is None:
+            continue
+        for mp in m.misbehaving_parties:
+            if not 1 <= mp.accused_index <= n:
+                raise ValueError("accused index out of range")
+            if len(mp.proof) != 192:
+                raise ValueError("a ProofOfMisbehaviour is 192 bytes")
+            accuser.append(j + 1)
+            accused.append(mp.accused_index)
+            proofs.append(mp.proof)
+    return accuser, accused, b"".join(proofs)
+
+
 def verify_broadcasts(be, n: int, t: int, phase1: Sequence[Optional[BroadcastPhase1]],
                       phase3: Sequence[Optional[BroadcastPhase3]]):
     """Rounds 2-5 of a plaintext-mode committee on its broadcasts (one dkg_ceremony_verify_fetched)."""

@@ -1,0 +1,478 @@
+// Round-2 complaints on gfx950: ProofOfMisbehaviour::generate (broadcast.rs:189-226) and
+// MisbehavingPartiesRound1::verify (broadcast.rs:50-99 with ProofOfMisbehaviour::verify, :227-283) as
+// batches, one work item per complaint.  A proof is (share_key, randomness_key, c1, r1, c2, r2): the
+// two recovered symmetric keys K = sk * e1 and a DLEQ(g, e1, pk, K; sk) proof for each
+// (correct_hybrid_decryption_key/zkp.rs:27-47, dl_equality/zkp.rs:29-74).  The work is staged as in
+// hybrid.hip, so that no kernel carries both a scalar-multiplication loop and the ARX state:
+//   prep    : scalars (reductions, negations), the points to decode, SymmetricKey::process (ARX);
+//   ladder  : the variable-base products (k_cmp_ladder), one item per product;
+//   combs   : the g / h terms through the shared fixed-base kernels (fixed_base);
+//   horner  : P_i(j) per (accused, accuser) pair (k_cmp_horner), or the difference tables (runtime);
+//   check   : the two check elements h p1 + g p2, h p2 + g p1 against P_i(j) (k_cv_check, combs);
+//   final   : the Fiat-Shamir challenges (two-block Blake2b) and the verdict (ARX).
+#include "kernels.h"
+#include "points.h"
+#include "hybrid_dev.h"
+#include "sym.h"
+
+namespace dkgk {
+
+namespace {
+
+// the Ristretto basepoint's encoding as little-endian words (ChallengeContext's first base)
+__device__ const uint32_t CMP_G[8] = {0x0aaef2e2u, 0x714ebc6au, 0x61a984a8u, 0x5f5100c5u,
+                                      0x6a0be358u, 0x8ddd82a5u, 0x4559a6b6u, 0x762d8de0u};
+
+// r = -a mod l (a canonical)
+DKG_DEV void sc_neg(sc& r, const sc& a) {
+  uint32_t nz = 0;
+  int64_t b = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    nz |= a.v[i];
+    const int64_t d = (int64_t)sc_const::L[i] - (int64_t)a.v[i] + b;
+    r.v[i] = (uint32_t)d;
+    b = d >> 32;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) r.v[i] = nz ? r.v[i] : 0u;
+}
+
+// Scalar::from_bytes_mod_order_wide of a 64-byte hash: lo + hi 2^256 mod l
+DKG_DEV void sc_wide(sc& r, const uint64_t (&h)[8]) {
+  uint32_t lo[8], hi[8];
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    lo[2 * i] = (uint32_t)h[i];
+    lo[2 * i + 1] = (uint32_t)(h[i] >> 32);
+    hi[2 * i] = (uint32_t)h[4 + i];
+    hi[2 * i + 1] = (uint32_t)(h[4 + i] >> 32);
+  }
+  sc a, b, rr;
+  sc_reduce256(a, lo);
+  sc_reduce256(b, hi);
+#pragma unroll
+  for (int i = 0; i < 8; i++) rr.v[i] = sc_const::RR[i];
+  sc_mont_mul(b, b, rr);  // hi * 2^256
+  sc_add(r, a, b);
+}
+
+// Scalar::hash_from_bytes::<Blake2b> (groups.rs:50-52) of ChallengeContext g || e1 || pk || K || a1 || a2
+// (challenge_context.rs:14-41); every part 8 words
+DKG_DEV void dleq_challenge(sc& c, const uint32_t* e1, const uint32_t* pk, const uint32_t* K, const uint32_t* a1,
+                            const uint32_t* a2) {
+  uint64_t m[32];
+  const uint32_t* parts[6] = {CMP_G, e1, pk, K, a1, a2};
+#pragma unroll
+  for (int p = 0; p < 6; p++)
+#pragma unroll
+    for (int j = 0; j < 4; j++) m[4 * p + j] = (uint64_t)parts[p][2 * j] | ((uint64_t)parts[p][2 * j + 1] << 32);
+#pragma unroll
+  for (int j = 24; j < 32; j++) m[j] = 0;
+  uint64_t h[8];
+  sym::blake2b_2block(h, m, 192, 64);
+  sc_wide(c, h);
+}
+
+// SymmetricKey::process + Scalar::from_bytes (from_bits, reduced) of a 32-byte ciphertext
+// (elgamal.rs:172-193; as k_sym_xor's decrypt branch)
+DKG_DEV void sym_scalar(sc& r, const uint32_t* K, const uint32_t* ct) {
+  uint64_t m[16];
+#pragma unroll
+  for (int j = 0; j < 4; j++) m[j] = (uint64_t)K[2 * j] | ((uint64_t)K[2 * j + 1] << 32);
+#pragma unroll
+  for (int j = 4; j < 16; j++) m[j] = 0;
+  uint64_t h[8];
+  sym::blake2b_1block(h, m, 32, 64);
+  uint32_t key[8], nonce[3];
+#pragma unroll
+  for (int j = 0; j < 4; j++) {
+    key[2 * j] = (uint32_t)h[j];
+    key[2 * j + 1] = (uint32_t)(h[j] >> 32);
+  }
+  nonce[0] = (uint32_t)h[4];
+  nonce[1] = (uint32_t)(h[4] >> 32);
+  nonce[2] = (uint32_t)h[5];
+  uint32_t ks[16];
+  sym::chacha20_ietf_block(ks, key, 0u, nonce);
+  uint32_t v[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) v[j] = ct[j] ^ ks[j];
+  v[7] &= 0x7fffffffu;
+  sc_reduce256(r, v);
+}
+
+DKG_DEV void copy8(uint32_t* dst, const uint32_t* src) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) dst[j] = src[j];
+}
+DKG_DEV void sc_load_reduced(sc& r, const uint32_t* p) {
+  uint32_t w[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) w[j] = p[j];
+  sc_reduce256(r, w);
+}
+DKG_DEV void sc_store(uint32_t* p, const sc& s) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) p[j] = s.v[j];
+}
+DKG_DEV bool eq8(const uint32_t* a, const uint32_t* b) {
+  uint32_t d = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) d |= a[j] ^ b[j];
+  return d == 0;
+}
+
+// bits [bit, bit + 2) of s; `bit` is wave-uniform (select chain, no indexed register file access)
+DKG_DEV uint32_t sc_bits2(const sc& s, int bit) {
+  const int wi = bit >> 5;
+  uint32_t word = s.v[0];
+#pragma unroll
+  for (int k = 1; k < 8; k++) word = (wi == k) ? s.v[k] : word;
+  return (word >> (bit & 31)) & 3u;  // bit is even in the window walk, so a window never straddles words
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ variable-base products
+// One item per product.  joint: out = a P + b Q by Straus' interleaving, one doubling per bit and the
+// addend (a_bit + 2 b_bit) in {P, Q, P + Q}.  Single base (joint = 0): out = a P with width-2
+// windows, which is the same walk over the bases (P, 2P): two doublings per step and the addend in
+// {P, 2P, 3P} -- 127 additions for 253 doublings.  (Two products of one base that shared their
+// doublings right-to-left would pay an addition slot per bit and scalar -- 253 doublings + 506
+// slots -- which is more field products than two windowed walks, 506 + 254.)  Scalars canonical.
+// Lanes carry independent scalars, so the walk is branch-free: every lane adds at every step, the
+// zero digit adding the identity.  The three addends (cached form) sit in a global table T laid out
+// [3][40 words][items, padded to 64]; the step's addend goes through the wave's LDS slot so that the
+// chain keeps one point in VGPRs, as k_dec_mul_w4 (whose launch bounds these are).
+__global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_cmp_ladder(size_t cnt, int joint, const uint32_t* __restrict__ bp,
+                                                      const uint32_t* __restrict__ bq,
+                                                      const uint32_t* __restrict__ sa,
+                                                      const uint32_t* __restrict__ sb,
+                                                      const uint32_t* __restrict__ Pext, size_t pstride,
+                                                      uint32_t* __restrict__ T, uint32_t* __restrict__ out) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* qcol = qs + threadIdx.x;
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = k < cnt;
+  const size_t kk = live ? k : 0;
+  const size_t stride = (size_t)gridDim.x * 64;
+  uint32_t* tb = T + k;  // padded: every lane of the grid owns a column
+  ge_p3 x;
+  {
+    ge_p3 q;
+    ge_cached c;
+    pt_load(x, Pext, pstride, bp[kk]);
+    ge_to_cached(c, x);
+    lds_put_cached(tb, c, (int)stride);
+    if (joint) pt_load(q, Pext, pstride, bq[kk]);
+    else ge_dbl<true>(q, x);
+    ge_to_cached(c, q);
+    lds_put_cached(tb + PT_WORDS * stride, c, (int)stride);
+    ge_add(x, x, c);
+    ge_to_cached(c, x);
+    lds_put_cached(tb + 2 * PT_WORDS * stride, c, (int)stride);
+  }
+  sc a, b;
+  sc_load(a, sa + 8 * kk);
+  if (joint) sc_load(b, sb + 8 * kk);
+  else sc_zero(b);
+  ge_identity(x);
+  const int steps = joint ? 253 : 127;
+#pragma unroll 1
+  for (int s = steps - 1; s >= 0; s--) {
+    uint32_t d;
+    if (joint) {
+      d = (sc_bits2(a, s) & 1u) | ((sc_bits2(b, s) & 1u) << 1);
+    } else {
+      d = sc_bits2(a, 2 * s);
+      ge_dbl_lean<DKG_DEC_IL != 0>(x, x, false);
+    }
+    ge_dbl_lean<DKG_DEC_IL != 0>(x, x, true);
+    if (__builtin_amdgcn_ballot_w64(d != 0) == 0) continue;  // no lane of the wave adds
+    const uint32_t* src = tb + (size_t)(d ? d - 1 : 0) * PT_WORDS * stride;
+#pragma unroll
+    for (int w = 0; w < PT_WORDS; w++) {
+      const uint32_t idw = (w == 0 || w == 10) ? 1u : (w == 20 ? 2u : 0u);  // cached identity (1, 1, 2, 0)
+      const uint32_t v = src[(size_t)w * stride];
+      qcol[w * 64] = d ? v : idw;
+    }
+    ge_add_lds<DKG_DEC_IL != 0>(x, x, qcol, false, 64, s == 0);
+  }
+  if (live) pt_store(out, cnt, k, x);
+}
+
+size_t cmp_ladder_table_words(size_t cnt) { return 3 * (size_t)PT_WORDS * ((cnt + 63) / 64 * 64); }
+
+void cmp_ladder(size_t cnt, bool joint, const uint32_t* bp, const uint32_t* bq, const uint32_t* sa, const uint32_t* sb,
+                const uint32_t* Pext, size_t pstride, uint32_t* T, uint32_t* out, hipStream_t stream) {
+  if (!cnt) return;
+  hipLaunchKernelGGL(k_cmp_ladder, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, stream, cnt, joint ? 1 : 0, bp, bq,
+                     sa, sb, Pext, pstride, T, out);
+}
+
+// ------------------------------------------------------------------ P_i(j) per pair
+// Horner in the exponent, k_horner generalised to a list of (row, index) pairs: lane = pair
+// list[k] = complaint c, row = accused[c] - 1 of the decoded commitments Eext (element row * N + k),
+// index x = accuser[c] (< 2^nb).  The indices differ between lanes, so x * acc is a branch-free
+// double-and-add over nb bits (a bit no lane of the wave has set skips its addition).  R: point-major
+// [c][40].
+__global__ __launch_bounds__(64, 2) void k_cmp_horner(size_t cnt, const uint32_t* __restrict__ list,
+                                                      const uint32_t* __restrict__ accuser,
+                                                      const uint32_t* __restrict__ accused,
+                                                      const uint32_t* __restrict__ Eext, size_t stride, size_t N, int nb,
+                                                      uint32_t* __restrict__ R) {
+  const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = k < cnt;
+  const size_t c = list[live ? k : 0];
+  const uint32_t x = accuser[c];
+  const size_t row = (size_t)(accused[c] - 1) * N;
+  ge_p3 acc;
+  pt_load(acc, Eext, stride, row + N - 1);
+#pragma unroll 1
+  for (size_t kk = N - 1; kk-- > 0;) {
+    ge_cached bc;
+    ge_to_cached(bc, acc);
+    ge_identity(acc);
+#pragma unroll 1
+    for (int b = nb - 1; b >= 0; b--) {
+      ge_dbl_lean(acc, acc, true);
+      const bool bit = (x >> b) & 1u;
+      if (__builtin_amdgcn_ballot_w64(bit) == 0) continue;
+      ge_p3 sum;
+      ge_add(sum, acc, bc);
+#pragma unroll
+      for (int w = 0; w < PT_WORDS; w++) pt_word(acc, w) = bit ? pt_word(sum, w) : pt_word(acc, w);
+    }
+    ge_p3 e;
+    pt_load(e, Eext, stride, row + kk);
+    ge_to_cached(bc, e);
+    ge_add(acc, acc, bc);
+  }
+  if (live) pt_store_aos(R, c, acc);
+}
+
+void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* accuser, const uint32_t* accused, const uint32_t* Eext,
+                size_t stride, size_t N, int nb, uint32_t* R, hipStream_t stream) {
+  if (!cnt) return;
+  hipLaunchKernelGGL(k_cmp_horner, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, stream, cnt, list, accuser, accused,
+                     Eext, stride, N, nb, R);
+}
+
+// ------------------------------------------------------------------ verify: prep / check / final
+// Thread (c, m): proof m of complaint c (m = 0 the share's, m = 1 the randomness's).  enc [C][32 words]
+// = e1_rand | ct_rand | e1_share | ct_share, proofs [C][48 words] = K_share | K_rand | c1 | r1 | c2 | r2.
+// Out: the points to decode Pc [5C][8] (pk_accuser, e1_share, K_share, e1_rand, K_rand), the
+// responses rs [2C][8] and negated challenges nc [2C][8] (canonical), the decrypted scalars p12
+// [2C][8] (p1 = share, p2 = randomness), and the ladders' base indices.
+__global__ __launch_bounds__(256) void k_cv_prep(size_t C, const uint32_t* __restrict__ accuser,
+                                                 const uint32_t* __restrict__ pk, const uint32_t* __restrict__ enc,
+                                                 const uint32_t* __restrict__ proofs, uint32_t* __restrict__ Pc,
+                                                 uint32_t* __restrict__ rs, uint32_t* __restrict__ nc,
+                                                 uint32_t* __restrict__ p12, uint32_t* __restrict__ bp1,
+                                                 uint32_t* __restrict__ bp2, uint32_t* __restrict__ bq2) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 2 * C) return;
+  const size_t c = idx >> 1, m = idx & 1;
+  const uint32_t* e = enc + 32 * c;
+  const uint32_t* P = proofs + 48 * c;
+  const uint32_t* e1 = e + (m ? 0 : 16);
+  const uint32_t* ct = e + (m ? 8 : 24);
+  const uint32_t* K = P + 8 * m;
+  if (m == 0) copy8(Pc + 8 * (5 * c), pk + 8 * (size_t)(accuser[c] - 1));
+  copy8(Pc + 8 * (5 * c + 1 + 2 * m), e1);
+  copy8(Pc + 8 * (5 * c + 2 + 2 * m), K);
+  sc x, y;
+  sc_load_reduced(x, P + 16 + 16 * m);  // challenge
+  sc_neg(y, x);
+  sc_store(nc + 8 * idx, y);
+  sc_load_reduced(x, P + 24 + 16 * m);  // response
+  sc_store(rs + 8 * idx, x);
+  sym_scalar(x, K, ct);
+  sc_store(p12 + 8 * idx, x);
+  bp1[idx] = (uint32_t)(5 * c);
+  bp2[idx] = (uint32_t)(5 * c + 1 + 2 * m);
+  bq2[idx] = (uint32_t)(5 * c + 2 + 2 * m);
+}
+
+void cv_prep(size_t C, const uint32_t* accuser, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
+             uint32_t* Pc, uint32_t* rs, uint32_t* nc, uint32_t* p12, uint32_t* bp1, uint32_t* bp2, uint32_t* bq2,
+             hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_cv_prep, dim3((unsigned)((2 * C + 255) / 256)), dim3(256), 0, stream, C, accuser, pk, enc, proofs,
+                     Pc, rs, nc, p12, bp1, bp2, bq2);
+}
+
+// The two check elements of complaint c against P = P_accused(accuser): eq[2c] = (h p1 + g p2 == P),
+// the quirk of ProofOfMisbehaviour::verify (broadcast.rs:271-283), eq[2c + 1] = (h p2 + g p1 == P), the
+// accusation (:87-96).  ridx[c]: bit 31 clear = element of Rh (k_cmp_horner, P itself); set = element
+// of Rt, the difference tables' evaluations, which hold b_j P(j) when `scale` is given (b_j 2^256 mod
+// l at scale + 8 (j - 1)): the scalars are then taken to b_j p first, as k_check does.
+__global__ __launch_bounds__(256, DKG_COMB_WAVES) void k_cv_check(size_t C, const uint32_t* __restrict__ accuser,
+                                                  const uint32_t* __restrict__ p12, const uint32_t* __restrict__ ridx,
+                                                  const uint32_t* __restrict__ Rh, const uint32_t* __restrict__ Rt,
+                                                  const uint32_t* __restrict__ scale,
+                                                  const uint32_t* __restrict__ tab_g,
+                                                  const uint32_t* __restrict__ tab_h, uint8_t* __restrict__ eq) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 2 * C) return;
+  const size_t c = idx >> 1, m = idx & 1;  // m = 0 the quirk, 1 the accusation
+  const uint32_t ri = ridx[c];
+  const bool tab = ri >> 31;
+  sc x, f;
+  const bool scaled = tab && scale;
+  if (scaled) sc_load(f, scale + 8 * (size_t)(accuser[c] - 1));
+  ge_p3 acc, r;
+  ge_identity(acc);
+  sc_load(x, p12 + 8 * (2 * c + m));  // h * (p1 | p2)
+  if (scaled) sc_mont_mul(x, x, f);
+  combw_mul_add(acc, x, tab_h);
+  sc_load(x, p12 + 8 * (2 * c + 1 - m));  // g * (p2 | p1)
+  if (scaled) sc_mont_mul(x, x, f);
+  combw_mul_add(acc, x, tab_g);
+  pt_load_aos(r, tab ? Rt : Rh, ri & 0x7fffffffu);
+  eq[idx] = ristretto_eq(acc, r) ? 1 : 0;
+}
+
+void cv_check(size_t C, const uint32_t* accuser, const uint32_t* p12, const uint32_t* ridx, const uint32_t* Rh,
+              const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
+              hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_cv_check, dim3((unsigned)((2 * C + 255) / 256)), dim3(256), 0, stream, C, accuser, p12, ridx, Rh,
+                     Rt, scale, tab_g, tab_h, eq);
+}
+
+// Verdict of complaint c (the codes of dkg_complaint1_verify, and 4 when the accused published no
+// phase-1 broadcast, committee.rs:377-380).  a1c / a2c [2C][8]: the encoded announcements g r - pk c,
+// e1 r - K c; pok [5C] decode flags of k_cv_prep's points; rowok [n] = the accused row decodes;
+// fetched (may be null) [n].
+__global__ __launch_bounds__(256) void k_cv_final(size_t C, const uint32_t* __restrict__ accuser,
+                                                  const uint32_t* __restrict__ accused,
+                                                  const uint32_t* __restrict__ pk, const uint32_t* __restrict__ enc,
+                                                  const uint32_t* __restrict__ proofs,
+                                                  const uint32_t* __restrict__ a1c, const uint32_t* __restrict__ a2c,
+                                                  const uint8_t* __restrict__ pok, const uint8_t* __restrict__ rowok,
+                                                  const uint8_t* __restrict__ fetched, const uint8_t* __restrict__ eq,
+                                                  int32_t* __restrict__ verdict) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const size_t i = accused[c] - 1;
+  const uint32_t* pkj = pk + 8 * (size_t)(accuser[c] - 1);
+  bool valid = true;
+#pragma unroll 1
+  for (int m = 0; m < 2; m++) {
+    sc ch;
+    dleq_challenge(ch, enc + 32 * c + (m ? 0 : 16), pkj, proofs + 48 * c + 8 * m, a1c + 8 * (2 * c + m),
+                   a2c + 8 * (2 * c + m));
+    valid = valid && eq8(ch.v, proofs + 48 * c + 16 + 16 * m);  // the proof's challenge bytes as sent
+  }
+  bool dec = rowok[i] != 0;
+#pragma unroll
+  for (int p = 0; p < 5; p++) dec = dec && pok[5 * c + p];
+  int32_t v;
+  if (fetched && !fetched[i]) v = 4;
+  else if (!dec) v = -1;
+  else if (!valid) v = 1;        // InvalidProofOfMisbehaviour
+  else if (eq[2 * c]) v = 1;     // ProofOfMisbehaviour::verify's check (:271-283)
+  else if (eq[2 * c + 1]) v = 2; // FalseClaimedInequality (:94-96)
+  else v = 0;
+  verdict[c] = v;
+}
+
+void cv_final(size_t C, const uint32_t* accuser, const uint32_t* accused, const uint32_t* pk, const uint32_t* enc,
+              const uint32_t* proofs, const uint32_t* a1c, const uint32_t* a2c, const uint8_t* pok, const uint8_t* rowok,
+              const uint8_t* fetched, const uint8_t* eq, int32_t* verdict, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_cv_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, accuser, accused, pk, enc,
+                     proofs, a1c, a2c, pok, rowok, fetched, eq, verdict);
+}
+
+// ------------------------------------------------------------------ prove: prep / finish
+// sk [C][8], enc [C][32], w [C][16] raw words.  Out: Pc [2C][8] = (e1_share, e1_rand); the ladders'
+// scalars ls [4C][8] = (sk, sk, w1, w2) on bases lb [4C] = (e1_share, e1_rand, e1_share, e1_rand);
+// the comb's scalars gs [3C][8] = (sk, w1, w2).
+__global__ __launch_bounds__(256) void k_cp_prep(size_t C, const uint32_t* __restrict__ sk, const uint32_t* __restrict__ enc,
+                                                 const uint32_t* __restrict__ w, uint32_t* __restrict__ Pc,
+                                                 uint32_t* __restrict__ ls, uint32_t* __restrict__ lb,
+                                                 uint32_t* __restrict__ gs) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  copy8(Pc + 8 * (2 * c), enc + 32 * c + 16);
+  copy8(Pc + 8 * (2 * c + 1), enc + 32 * c);
+  sc x;
+  sc_load_reduced(x, sk + 8 * c);
+  sc_store(ls + 8 * (4 * c), x);
+  sc_store(ls + 8 * (4 * c + 1), x);
+  sc_store(gs + 8 * (3 * c), x);
+  sc_load_reduced(x, w + 16 * c);
+  sc_store(ls + 8 * (4 * c + 2), x);
+  sc_store(gs + 8 * (3 * c + 1), x);
+  sc_load_reduced(x, w + 16 * c + 8);
+  sc_store(ls + 8 * (4 * c + 3), x);
+  sc_store(gs + 8 * (3 * c + 2), x);
+#pragma unroll
+  for (int k = 0; k < 4; k++) lb[4 * c + k] = (uint32_t)(2 * c + (k & 1));
+}
+
+void cp_prep(size_t C, const uint32_t* sk, const uint32_t* enc, const uint32_t* w, uint32_t* Pc, uint32_t* ls,
+             uint32_t* lb, uint32_t* gs, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_cp_prep, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, sk, enc, w, Pc, ls, lb, gs);
+}
+
+// lc [4C][8] = encodings of (K_share, K_rand, e1_share w1, e1_rand w2), gc [3C][8] of (pk, g w1, g w2),
+// ls / gs as k_cp_prep: challenge c = H(g, e1, pk, K, g w, e1 w), response r = c sk + w
+// (dl_equality/zkp.rs:29-49) -> proofs [C][48 words].
+__global__ __launch_bounds__(256) void k_cp_finish(size_t C, const uint32_t* __restrict__ enc,
+                                                   const uint32_t* __restrict__ lc, const uint32_t* __restrict__ gc,
+                                                   const uint32_t* __restrict__ gs, uint32_t* __restrict__ proofs) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  uint32_t* P = proofs + 48 * c;
+  copy8(P, lc + 8 * (4 * c));
+  copy8(P + 8, lc + 8 * (4 * c + 1));
+  sc x;
+  sc_load(x, gs + 8 * (3 * c));
+#pragma unroll 1
+  for (int m = 0; m < 2; m++) {
+    sc ch, wn, r;
+    dleq_challenge(ch, enc + 32 * c + (m ? 0 : 16), gc + 8 * (3 * c), lc + 8 * (4 * c + m), gc + 8 * (3 * c + 1 + m),
+                   lc + 8 * (4 * c + 2 + m));
+    sc_load(wn, gs + 8 * (3 * c + 1 + m));
+    sc_mul(r, ch, x);
+    sc_add(r, r, wn);
+    sc_store(P + 16 + 16 * m, ch);
+    sc_store(P + 24 + 16 * m, r);
+  }
+}
+
+void cp_finish(size_t C, const uint32_t* enc, const uint32_t* lc, const uint32_t* gc, const uint32_t* gs,
+               uint32_t* proofs, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_cp_finish, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, enc, lc, gc, gs, proofs);
+}
+
+// ------------------------------------------------------------------ the qualified set from proven complaints
+// One wave per dealer row i of dec [rows][n]: qmask[i] = row i holds no MISSING and cmask[i] (no
+// verified complaint against i, committee.rs:370-398); rej[i] = !qmask[i] for the host half.
+__global__ __launch_bounds__(64) void k_qualified_complaints(size_t n, const uint8_t* __restrict__ dec,
+                                                             const uint8_t* __restrict__ cmask,
+                                                             uint8_t* __restrict__ rej, uint8_t* __restrict__ qmask) {
+  const size_t i = blockIdx.x;
+  bool missing = false;
+  for (size_t j = threadIdx.x; j < n; j += 64) missing = missing || dec[i * n + j] == 4;
+  const bool any = __builtin_amdgcn_ballot_w64(missing) != 0;
+  if (threadIdx.x == 0) {
+    const uint8_t q = (!any && cmask[i]) ? 1 : 0;
+    qmask[i] = q;
+    rej[i] = !q;
+  }
+}
+
+void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8_t* cmask, uint8_t* rej, uint8_t* qmask,
+                          hipStream_t stream) {
+  if (!rows) return;
+  hipLaunchKernelGGL(k_qualified_complaints, dim3((unsigned)rows), dim3(64), 0, stream, n, dec, cmask, rej, qmask);
+}
+
+}  // namespace dkgk

@@ -283,6 +283,33 @@ size_t bdec_launch_waves();  // waves per launch (the table's slots): larger cal
 void bdec_mul(size_t keys, size_t n, const uint32_t* sk, const uint32_t* R_ext, uint32_t* K_ext, size_t count,
               uint32_t* table, hipStream_t stream);
 
+// ---- round-2 complaints, complaints.hip (broadcast.rs:50-99, 189-283)
+// out[k] = sa[k] P (joint = false, width-2 windows) or sa[k] P + sb[k] Q (Straus), P / Q = elements
+// bp[k] / bq[k] of the decoded SoA Pext; scalars canonical [cnt][8]; out SoA [40][cnt];
+// T: cmp_ladder_table_words(cnt) words of scratch
+size_t cmp_ladder_table_words(size_t cnt);
+void cmp_ladder(size_t cnt, bool joint, const uint32_t* bp, const uint32_t* bq, const uint32_t* sa, const uint32_t* sb,
+                const uint32_t* Pext, size_t pstride, uint32_t* T, uint32_t* out, hipStream_t stream);
+// R[c] (point-major) = sum_k accuser[c]^k Eext[(accused[c] - 1) * N + k] for the complaints c in list[0..cnt)
+void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* accuser, const uint32_t* accused, const uint32_t* Eext,
+                size_t stride, size_t N, int nb, uint32_t* R, hipStream_t stream);
+void cv_prep(size_t C, const uint32_t* accuser, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
+             uint32_t* Pc, uint32_t* rs, uint32_t* nc, uint32_t* p12, uint32_t* bp1, uint32_t* bp2, uint32_t* bq2,
+             hipStream_t stream);
+void cv_check(size_t C, const uint32_t* accuser, const uint32_t* p12, const uint32_t* ridx, const uint32_t* Rh,
+              const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
+              hipStream_t stream);
+void cv_final(size_t C, const uint32_t* accuser, const uint32_t* accused, const uint32_t* pk, const uint32_t* enc,
+              const uint32_t* proofs, const uint32_t* a1c, const uint32_t* a2c, const uint8_t* pok, const uint8_t* rowok,
+              const uint8_t* fetched, const uint8_t* eq, int32_t* verdict, hipStream_t stream);
+void cp_prep(size_t C, const uint32_t* sk, const uint32_t* enc, const uint32_t* w, uint32_t* Pc, uint32_t* ls,
+             uint32_t* lb, uint32_t* gs, hipStream_t stream);
+void cp_finish(size_t C, const uint32_t* enc, const uint32_t* lc, const uint32_t* gc, const uint32_t* gs,
+               uint32_t* proofs, hipStream_t stream);
+// qmask[i] = row i of dec [rows][n] holds no MISSING and cmask[i]; rej[i] = !qmask[i]
+void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8_t* cmask, uint8_t* rej, uint8_t* qmask,
+                          hipStream_t stream);
+
 // ---- committee verification by interpolation (interp.hip)
 // F[d][k] = sum_j W[k][j] s[d][j] (and F' from s'; sp may be null), WT[j][k] = W[k][j] in Montgomery form
 void interp(size_t D, size_t N, size_t nrecv, const uint32_t* WT, const uint32_t* s, const uint32_t* sp, uint32_t* F,

@@ -88,6 +88,14 @@ struct dkg_ctx {
   int addend_mode = 0;                  // short vectors' addends: 0 affine Niels (affine_pieces, mixed
                                         // additions), 1 cached projective (read from R)
   size_t sdig_n = 0, sdig_L = 0, sdig_K = 0;  // key of the cached short multipliers (v.sdig)
+  // the last verify_device's evaluations R[c][j] (point-major, column c = dealer for one segment),
+  // their scale b_j 2^256 mod l (null: R holds P(j) itself) and the columns' decode mask: read by the
+  // complaint verification, which runs the pipeline without its checks (VerifySeg::dec == null)
+  const uint32_t* last_R = nullptr;
+  const uint32_t* last_scale = nullptr;
+  const uint8_t* last_dok = nullptr;
+  int complaint_eval = 0;               // P_i(j) of the complaints: 0 by the dealer's complaint count,
+                                        // 1 per-pair Horner, 2 difference tables
   // round-1 commitments of the ceremony being verified, in extended form on this device (set by
   // the drivers that generate them, ExtScope): verify_device places them instead of decoding the
   // encodings, finalise reads A_i0 from them.  E/A [D][t+1] points, word stride ext_stride.
@@ -281,7 +289,7 @@ struct VerifySeg {
   const uint32_t* Ccomp;
   const uint32_t* s;
   const uint32_t* sp;
-  uint8_t* dec;
+  uint8_t* dec;                       // null: no checks, the evaluations only (ctx->last_R)
   const uint8_t* extra_ok = nullptr;  // [D] device: 0 = the dealer's other broadcast data is missing
   size_t self_mod = 0;                // self = (dealer + dealer_base) mod self_mod == j; 0: n
 };
@@ -663,6 +671,9 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   if (short_mult) split_short(ctx, n, L, U, &sdig, &stop, &sscale);
   else if (U > 1) split_digits(ctx, n, L, &ydig, &ytop);
   ctx->last_combine = U > 1 ? (short_mult ? 2 : 1) : 0;
+  ctx->last_R = R;
+  ctx->last_scale = sscale;
+  ctx->last_dok = dok;
   // padding columns, and the positions past t of the last piece, are the identity
   if (npad != D * nseg || U * L != N) dkgk::fill_identity(L * W, Cpm, home);
   HCK(hipMemsetAsync(pok, 1, npad * N, home));
@@ -683,7 +694,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
     if (segs[k].extra_ok && !defer_masks) dkgk::and_dealer_mask(D, nseg, k, segs[k].extra_ok, dok, home);
   // checks of dealers [d0, d1) on stream st
   auto checks = [&](size_t d0, size_t d1, hipStream_t st, size_t j0 = 0, size_t jn = 0) {
-    if (d1 <= d0) return;
+    if (d1 <= d0 || !segs[0].dec) return;
     wait_shares(ctx, st);
     if (defer_masks)  // dealers [d0, d1) start a column group (d0 = 64 g0): relative indexing
       for (int k = 0; k < nseg; k++)
@@ -1190,10 +1201,14 @@ std::vector<uint8_t> recon_secrets(size_t n, const std::vector<uint8_t>& fin, co
 // copies after a sync), so that a caller queues both rounds' device halves and copies everything back
 // in one round trip.  The single-GPU drivers, the batches and the sharded combine all decide through
 // these four functions.
+// cmask (device [groups*n], may be null): the qualified set by PROVEN complaints instead -- cmask[i] = no
+// verified complaint against i (compute_qualified_set, :370-398, run on the broadcast complaints by
+// the caller): a row is then disqualified by MISSING or by cmask only, a REJECT alone keeps it.
 void round2_device(dkg_ctx* ctx, size_t groups, size_t n, const uint8_t* dec2, uint8_t* qmask, uint8_t* rej,
-                   int32_t* cnt) {
+                   int32_t* cnt, const uint8_t* cmask = nullptr) {
   dkgk::decision_summary(groups, n, dec2, rej, cnt, ctx->stream);
-  dkgk::mask_not_and(groups * n, rej, nullptr, qmask, ctx->stream);  // qualified = no rejecting row
+  if (cmask) dkgk::qualified_complaints(groups * n, n, dec2, cmask, rej, qmask, ctx->stream);
+  else dkgk::mask_not_and(groups * n, rej, nullptr, qmask, ctx->stream);  // qualified = no rejecting row
 }
 // host half: `qualified` holds the copied rej flags on entry
 void round2_host(size_t V, size_t t, uint8_t* qualified, const int32_t* complaints, uint8_t* r2err) {
@@ -1225,7 +1240,7 @@ void round4_host(size_t V, const uint8_t* qualified, uint8_t* recon) {
 // failed recovery) or, when a dealer is reconstructed, adds g * its recovered secret (a second trip).
 void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
                            const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                           const uint8_t* e_ok, const uint8_t* a_ok) {
+                           const uint8_t* e_ok, const uint8_t* a_ok, const uint8_t* cmask) {
   const size_t N = t + 1;
   uint8_t* dec2 = buf<uint8_t>(ctx, "dec2", n * n);
   uint8_t* dec4 = buf<uint8_t>(ctx, "dec4", n * n);
@@ -1237,7 +1252,7 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   // ---- rounds 2 and 4 (committee.rs:260-366, :508-580), fused or in protocol order (verify_rounds)
   auto round3 = [&] {
     wait_shares(ctx, ctx->stream);
-    round2_device(ctx, 1, n, dec2, qmask, rej2, cnt);
+    round2_device(ctx, 1, n, dec2, qmask, rej2, cnt, cmask);
     // ---- round 3 (committee.rs:433-476): final share s_j = sum_{i in Q} s_ij, public g s_j
     dkgk::sum_shares(n, n, s, qmask, fs, ctx->stream);
     // the public shares g s_j are an output only: computed on the side stream, off the path to
@@ -1350,8 +1365,8 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
 // formula when they marked a group (with_binom_ded)
 void receivers_rounds(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
                       const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                      const uint8_t* e_ok = nullptr, const uint8_t* a_ok = nullptr) {
-  with_binom_ded(ctx, [&] { receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, e_ok, a_ok); });
+                      const uint8_t* e_ok = nullptr, const uint8_t* a_ok = nullptr, const uint8_t* cmask = nullptr) {
+  with_binom_ded(ctx, [&] { receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, e_ok, a_ok, cmask); });
 }
 
 // Round 1 for D dealers on device: a, b canonical [D][N][8] -> Ecomp, Acomp [D][N][8], s, sp [D][n][8].
@@ -3249,12 +3264,15 @@ int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d
   });
 }
 
-int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
-                             const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk) return DKG_E_ARG;
+}  // extern "C"
+
+namespace {
+
+// dkg_ceremony_verify_full's body.  cmask (device [n], may be null): the qualified set follows the
+// proven complaints (round2_device) instead of the receivers' own rejections.
+int ceremony_verify_full_impl(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
+                              const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out, const uint8_t* cmask) {
+  {
     const size_t N = t + 1, items = 2 * n * n;
     uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
     uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
@@ -3282,7 +3300,7 @@ int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E,
       HCK(hipEventRecord(ctx->shares_done, ctx->side));
       ctx->shares_pending = true;
     }
-    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, true, eok);  // waits for the shares before it returns
+    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, true, eok, nullptr, cmask);  // waits for the shares before it returns
     collect_hybrid_phases(ctx);  // decryption phases only (no encryption here: full.enc_* read -1)
     if (out->s) d2h(ctx, out->s, rs, 32 * n * n);
     if (out->s_prime) d2h(ctx, out->s_prime, rsp, 32 * n * n);
@@ -3294,8 +3312,297 @@ int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E,
     out->ms_finalise = ev_ms(ctx, 4, 5);
     out->ms_total = ev_ms(ctx, 0, 5);
     return DKG_OK;
+  }
+}
+
+// ---- round-2 complaints as device batches (complaints.hip)
+// Does an accused dealer with `count` complaints get the difference tables of its row (every P_i(j),
+// verify_device without checks) instead of one Horner walk per complaint?  Both are one dependent
+// chain however many complaints there are (the walks of all complaints run side by side, and so do
+// the tables of all accused rows), so what decides is the chains' lengths, not the work:
+//   Horner: N steps of nb doublings, one addition per index bit some lane of the wave has set
+//           (about the bit length of `count` + 1 for a dealer accused by receivers 1..count), + 1;
+//   tables: N binomial steps and n stepping steps.
+// The per-step latencies are fitted to profiles/complaints_eval_ab.txt (n = 1024, t = 511: the tables
+// win at every count, 11.3-11.6 ms against 23.0-39.6 ms per call at 1-1,023 complaints; n = 1024, t = 3:
+// Horner wins at every count, 3.2-3.5 against 7.0-7.2 ms; n = 64 and 256 with t = (n-1)/2 in between).
+bool complaint_tables_pay(size_t n, size_t N, size_t count) {
+  if (N < 2) return false;  // a constant polynomial: P_i(j) = E_i0
+  int nb = 1, cb = 1;
+  while ((n >> nb) != 0) nb++;
+  while ((count >> cb) != 0) cb++;
+  const double horner_us = 3.6 * (double)N * (nb + std::min(nb, cb + 1) + 1);
+  const double tables_us = 13.0 * (double)N + 3.7 * (double)n;
+  return tables_us < horner_us;
+}
+
+// MisbehavingPartiesRound1::verify (broadcast.rs:50-99) for C complaints of one ceremony.  Device: dpk
+// [n][8] member keys, Ec [n][N][8] commitments; host: accuser / accused (1-based, validated by the
+// caller), fetched1 (may be null), enc [C][128], proofs [C][192].  verdict [C] on the host; rowok_host
+// (may be null) [n] = E row i decodes.  Ends synchronised.
+void complaints_verify_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser,
+                            const uint32_t* accused, const uint32_t* dpk, const uint32_t* Ec, const uint8_t* fetched1,
+                            const uint8_t* enc, const uint8_t* proofs, int32_t* verdict, uint8_t* rowok_host) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  // every row decoded once: the rows' validity for the qualified set, and the Horner walks' input
+  uint32_t* Eext = buf<uint32_t>(ctx, "cv_Eext", PTB * n * N);
+  uint8_t* epok = buf<uint8_t>(ctx, "cv_Epok", n * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "cv_rowok", n);
+  dkgk::decode_points(Ec, n * N, Eext, n * N, epok, st);
+  dkgk::dealer_ok(n, N, epok, rowok, st);
+  if (rowok_host) d2h(ctx, rowok_host, rowok, n);
+  if (!C) {
+    check_launch(ctx);
+    sync(ctx);
+    return;
+  }
+  uint32_t* dacc = buf<uint32_t>(ctx, "cv_accuser", 4 * C);
+  uint32_t* dacd = buf<uint32_t>(ctx, "cv_accused", 4 * C);
+  uint32_t* denc = buf<uint32_t>(ctx, "cv_enc", 128 * C);
+  uint32_t* dprf = buf<uint32_t>(ctx, "cv_proofs", 192 * C);
+  uint8_t* dfet = nullptr;
+  h2d(ctx, dacc, accuser, 4 * C);
+  h2d(ctx, dacd, accused, 4 * C);
+  h2d(ctx, denc, enc, 128 * C);
+  h2d(ctx, dprf, proofs, 192 * C);
+  if (fetched1) {
+    dfet = buf<uint8_t>(ctx, "cv_fetched", n);
+    h2d(ctx, dfet, fetched1, n);
+  }
+  // scalars, the points to decode, SymmetricKey::process of both ciphertexts
+  uint32_t* Pc = buf<uint32_t>(ctx, "cv_Pc", 32 * 5 * C);
+  uint32_t* rs = buf<uint32_t>(ctx, "cv_rs", 32 * 2 * C);
+  uint32_t* nc = buf<uint32_t>(ctx, "cv_nc", 32 * 2 * C);
+  uint32_t* p12 = buf<uint32_t>(ctx, "cv_p12", 32 * 2 * C);
+  uint32_t* bp1 = buf<uint32_t>(ctx, "cv_bp1", 4 * 2 * C);
+  uint32_t* bp2 = buf<uint32_t>(ctx, "cv_bp2", 4 * 2 * C);
+  uint32_t* bq2 = buf<uint32_t>(ctx, "cv_bq2", 4 * 2 * C);
+  dkgk::cv_prep(C, dacc, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
+  uint32_t* Pext = buf<uint32_t>(ctx, "cv_Pext", PTB * 5 * C);
+  uint8_t* ppok = buf<uint8_t>(ctx, "cv_Ppok", 5 * C);
+  dkgk::decode_points(Pc, 5 * C, Pext, 5 * C, ppok, st);
+  // announcements (dl_equality/zkp.rs:60-63): a1 = g r - pk c (comb + one-base walk), a2 = e1 r - K c (Straus)
+  uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(2 * C));
+  uint32_t* S1 = buf<uint32_t>(ctx, "cv_S1", PTB * 2 * C);
+  uint32_t* S2 = buf<uint32_t>(ctx, "cv_S2", PTB * 2 * C);
+  uint32_t* G = buf<uint32_t>(ctx, "cv_G", PTB * 2 * C);
+  dkgk::cmp_ladder(2 * C, false, bp1, nullptr, nc, nullptr, Pext, 5 * C, T, S1, st);
+  dkgk::cmp_ladder(2 * C, true, bp2, bq2, rs, nc, Pext, 5 * C, T, S2, st);
+  dkgk::fixed_base(2 * C, rs, ctx->tab_gw, G, st);
+  dkgk::add_points(2 * C, S1, G, 2 * C, S1, st);
+  uint32_t* a1c = buf<uint32_t>(ctx, "cv_a1c", 32 * 2 * C);
+  uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
+  dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
+  dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
+  // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint.
+  // A pair complained about again takes a further table row of its own, so that the table path
+  // serves every complaint of a dealer it is chosen for.
+  std::vector<size_t> count(n, 0);
+  for (size_t c = 0; c < C; c++) count[accused[c] - 1]++;
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;   // (accused, accuser) -> occurrences so far
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> rowof;  // (accused, occurrence) -> table row
+  std::vector<uint32_t> rows, hl, ridx(C);
+  for (size_t c = 0; c < C; c++) {
+    const uint32_t i = accused[c], j = accuser[c];
+    const bool tables = N >= 2 && (ctx->complaint_eval == 2 ||
+                                   (ctx->complaint_eval == 0 && complaint_tables_pay(n, N, count[i - 1])));
+    if (!tables) {
+      hl.push_back((uint32_t)c);
+      ridx[c] = (uint32_t)c;
+      continue;
+    }
+    const uint32_t m = seen[{i, j}]++;
+    auto it = rowof.find({i, m});
+    if (it == rowof.end()) {
+      it = rowof.emplace(std::make_pair(i, m), (uint32_t)rows.size()).first;
+      rows.push_back(i);
+    }
+    if (((size_t)it->second + 1) * n >= ((size_t)1 << 31)) {
+      ctx->err = "complaints_verify: too many table rows";
+      throw Fail{DKG_E_ARG};
+    }
+    ridx[c] = 0x80000000u | (uint32_t)((size_t)it->second * n + (j - 1));
+  }
+  uint32_t* dridx = buf<uint32_t>(ctx, "cv_ridx", 4 * C);
+  h2d(ctx, dridx, ridx.data(), 4 * C);
+  uint32_t* Rh = buf<uint32_t>(ctx, "cv_Rh", PTB * C);
+  if (!hl.empty()) {
+    uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
+    h2d(ctx, dhl, hl.data(), 4 * hl.size());
+    int nb = 1;
+    while ((n >> nb) != 0) nb++;
+    dkgk::cmp_horner(hl.size(), dhl, dacc, dacd, Eext, n * N, N, nb, Rh, st);
+  }
+  const uint32_t *Rt = nullptr, *scale = nullptr;
+  if (!rows.empty()) {
+    const size_t D = rows.size();
+    uint32_t* Trows = buf<uint32_t>(ctx, "cv_Trows", 32 * D * N);
+    for (size_t r = 0; r < D; r++)
+      HCK(hipMemcpyAsync(Trows + 8 * N * r, Ec + 8 * N * (size_t)(rows[r] - 1), 32 * N, hipMemcpyDeviceToDevice, st));
+    VerifySeg g{2, D, 0, Trows, nullptr, nullptr, nullptr};
+    verify_device(ctx, n, t, &g, 1, false, "cv");
+    Rt = ctx->last_R;
+    scale = ctx->last_scale;
+  }
+  uint8_t* eq = buf<uint8_t>(ctx, "cv_eq", 2 * C);
+  dkgk::cv_check(C, dacc, p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+  int32_t* dver = buf<int32_t>(ctx, "cv_verdict", 4 * C);
+  dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, a1c, a2c, ppok, rowok, dfet, eq, dver, st);
+  check_launch(ctx);
+  d2h(ctx, verdict, dver, 4 * C);
+  sync(ctx);  // the staging vectors (ridx, hl) live until here
+}
+
+// 1-based party indices within 1..n
+bool complaint_indices_ok(size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused) {
+  for (size_t c = 0; c < C; c++)
+    if (accuser[c] < 1 || accuser[c] > n || accused[c] < 1 || accused[c] > n) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
+                             const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk) return DKG_E_ARG;
+    return ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, out, nullptr);
   });
 }
+
+int dkg_ctx_set_complaint_eval(dkg_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  ctx->complaint_eval = mode;
+  return DKG_OK;
+}
+
+int dkg_complaints_prove(dkg_ctx* ctx, size_t C, const uint8_t* sk, const uint8_t* enc, const uint8_t* w,
+                         uint8_t* proofs) {
+  return guarded(ctx, [&] {
+    if (!sk || !enc || !w || !proofs) return DKG_E_ARG;
+    if (!C) return DKG_OK;
+    hipStream_t st = ctx->stream;
+    uint32_t* dsk = buf<uint32_t>(ctx, "cp_sk", 32 * C);
+    uint32_t* denc = buf<uint32_t>(ctx, "cp_enc", 128 * C);
+    uint32_t* dw = buf<uint32_t>(ctx, "cp_w", 64 * C);
+    h2d(ctx, dsk, sk, 32 * C);
+    h2d(ctx, denc, enc, 128 * C);
+    h2d(ctx, dw, w, 64 * C);
+    uint32_t* Pc = buf<uint32_t>(ctx, "cp_Pc", 32 * 2 * C);
+    uint32_t* ls = buf<uint32_t>(ctx, "cp_ls", 32 * 4 * C);
+    uint32_t* lb = buf<uint32_t>(ctx, "cp_lb", 4 * 4 * C);
+    uint32_t* gs = buf<uint32_t>(ctx, "cp_gs", 32 * 3 * C);
+    dkgk::cp_prep(C, dsk, denc, dw, Pc, ls, lb, gs, st);
+    uint32_t* Pext = buf<uint32_t>(ctx, "cp_Pext", PTB * 2 * C);
+    uint8_t* pok = buf<uint8_t>(ctx, "cp_pok", 2 * C);
+    dkgk::decode_points(Pc, 2 * C, Pext, 2 * C, pok, st);
+    // K = sk e1 (recover_symmetric_key, broadcast.rs:197-202) and the announcements e1 w; pk = g sk, g w
+    uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(4 * C));
+    uint32_t* Lx = buf<uint32_t>(ctx, "cp_L", PTB * 4 * C);
+    uint32_t* Gx = buf<uint32_t>(ctx, "cp_G", PTB * 3 * C);
+    dkgk::cmp_ladder(4 * C, false, lb, nullptr, ls, nullptr, Pext, 2 * C, T, Lx, st);
+    dkgk::fixed_base(3 * C, gs, ctx->tab_gw, Gx, st);
+    uint32_t* lc = buf<uint32_t>(ctx, "cp_lc", 32 * 4 * C);
+    uint32_t* gc = buf<uint32_t>(ctx, "cp_gc", 32 * 3 * C);
+    dkgk::encode_points(Lx, 4 * C, 4 * C, lc, st);
+    dkgk::encode_points(Gx, 3 * C, 3 * C, gc, st);
+    uint32_t* dprf = buf<uint32_t>(ctx, "cp_proofs", 192 * C);
+    dkgk::cp_finish(C, denc, lc, gc, gs, dprf, st);
+    check_launch(ctx);
+    std::vector<uint8_t> ok(2 * C);
+    d2h(ctx, ok.data(), pok, 2 * C);
+    d2h(ctx, proofs, dprf, 192 * C);
+    sync(ctx);
+    for (auto v : ok)
+      if (!v) {
+        ctx->err = "complaints_prove: a ciphertext point does not decode";
+        return DKG_E_DECODE;
+      }
+    return DKG_OK;
+  });
+}
+
+int dkg_complaints_verify(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                          const uint8_t* pk, const uint8_t* E, const uint8_t* fetched1, const uint8_t* enc,
+                          const uint8_t* proofs, int32_t* verdict, uint8_t* qualified) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !pk || !E) return DKG_E_ARG;
+    if (C && (!accuser || !accused || !enc || !proofs || !verdict)) return DKG_E_ARG;
+    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
+    const size_t N = t + 1;
+    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
+    uint32_t* Ec = buf<uint32_t>(ctx, "cv_E", 32 * n * N);
+    h2d(ctx, dpk, pk, 32 * n);
+    h2d(ctx, Ec, E, 32 * n * N);
+    std::vector<uint8_t> rowok(n);
+    complaints_verify_core(ctx, n, t, C, accuser, accused, dpk, Ec, fetched1, enc, proofs, verdict, rowok.data());
+    if (qualified) {
+      for (size_t i = 0; i < n; i++) qualified[i] = rowok[i] && (!fetched1 || fetched1[i]);
+      for (size_t c = 0; c < C; c++)
+        if (verdict[c] == 0) qualified[accused[c] - 1] = 0;  // committee.rs:381-394: cleared only on Ok
+    }
+    return DKG_OK;
+  });
+}
+
+int dkg_ceremony_verify_full_complaints(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                        const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, const uint8_t* pk,
+                                        size_t C, const uint32_t* accuser, const uint32_t* accused,
+                                        const uint8_t* proofs, dkg_ceremony_out* out, int32_t* verdict,
+                                        int32_t* dissent) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
+    if (C && (!accuser || !accused || !proofs || !verdict)) return DKG_E_ARG;
+    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
+    const size_t N = t + 1;
+    // the complaints against this ceremony's own broadcasts: the pair the accused sent the accuser
+    // (broadcast.rs:57), items (i, q, w) at (i n + q) 2 + w, w = 0 the randomness
+    std::vector<uint8_t> enc(128 * C);
+    for (size_t c = 0; c < C; c++) {
+      const size_t item = ((size_t)(accused[c] - 1) * n + (accuser[c] - 1)) * 2;
+      memcpy(&enc[128 * c], e1 + 32 * item, 32);
+      memcpy(&enc[128 * c + 32], ct + 32 * item, 32);
+      memcpy(&enc[128 * c + 64], e1 + 32 * (item + 1), 32);
+      memcpy(&enc[128 * c + 96], ct + 32 * (item + 1), 32);
+    }
+    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
+    uint32_t* Ec = buf<uint32_t>(ctx, "cv_E", 32 * n * N);
+    h2d(ctx, dpk, pk, 32 * n);
+    h2d(ctx, Ec, E, 32 * n * N);
+    complaints_verify_core(ctx, n, t, C, accuser, accused, dpk, Ec, nullptr, enc.data(), proofs, verdict, nullptr);
+    std::vector<uint8_t> cmask(n, 1);
+    for (size_t c = 0; c < C; c++)
+      if (verdict[c] == 0) cmask[accused[c] - 1] = 0;
+    uint8_t* dcm = buf<uint8_t>(ctx, "cv_cmask", n);
+    h2d(ctx, dcm, cmask.data(), n);
+    sync(ctx);
+    rc = ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, out, dcm);
+    if (rc || !dissent) return rc;
+    // a receiver that rejected a dealer without a proven complaint of its own against it
+    std::vector<uint8_t> d2(n * n);
+    d2h(ctx, d2.data(), buf<uint8_t>(ctx, "dec2", n * n), n * n);
+    sync(ctx);
+    std::vector<uint8_t> proven(n * n, 0);  // [accused][accuser]
+    for (size_t c = 0; c < C; c++)
+      if (verdict[c] == 0) proven[(size_t)(accused[c] - 1) * n + (accuser[c] - 1)] = 1;
+    for (size_t j = 0; j < n; j++) {
+      int32_t v = 0;
+      for (size_t i = 0; i < n; i++) v += d2[i * n + j] == DKG_REJECT && !proven[i * n + j];
+      dissent[j] = v;
+    }
+    return DKG_OK;
+  });
+}
+
 
 // ---- full mode for batches of ceremonies (hybrid_batch.hip)
 int dkg_ctx_set_batch_full_chunk(dkg_ctx* ctx, size_t ceremonies) {

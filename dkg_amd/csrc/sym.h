@@ -2,6 +2,7 @@
 // RNG (seedgen.hip) and the hybrid share encryption (hybrid.hip).
 //   blake2b_1block  : BLAKE2b of a message of at most 128 bytes (blake2 0.9.1 `Blake2b` = 512-bit
 //                     output; 256-bit for the seed derivation), unkeyed.
+//   blake2b_2block  : the same for 129..256 bytes (the complaint proofs' 192-byte transcripts).
 //   chacha20_block  : original ChaCha20 block, 64-bit counter, zero nonce (rand_chacha ChaCha20Rng).
 //   chacha20_ietf_block : RFC 8439 block, 32-bit counter + 96-bit nonce (chacha20 0.7 `ChaCha20`,
 //                     used by SymmetricKey::process, elgamal.rs:172-193).
@@ -60,6 +61,50 @@ __device__ inline void blake2b_1block(uint64_t (&h)[8], const uint64_t (&m)[16],
   }
 #pragma unroll
   for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+}
+
+// BLAKE2b of a message of 129..256 bytes given as 32 little-endian words (zero padded): two
+// compressions, the first with counter 128, the second final with counter len.  (The 192-byte
+// Fiat-Shamir transcript of the complaint proofs, challenge_context.rs:14-41.)
+__device__ inline void blake2b_2block(uint64_t (&h)[8], const uint64_t (&m)[32], uint32_t len, uint32_t outlen) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) h[i] = B2_IV[i];
+  h[0] ^= 0x01010000ULL ^ outlen;
+#pragma unroll 1
+  for (int blk = 0; blk < 2; blk++) {
+    const uint64_t* mb = m + 16 * blk;
+    uint64_t v[16];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      v[i] = h[i];
+      v[8 + i] = B2_IV[i];
+    }
+    v[12] ^= blk ? len : 128u;
+    if (blk) v[14] = ~v[14];
+    for (int r = 0; r < 12; r++) {
+      const uint8_t* s = B2_SIGMA[r % 10];
+#define G(a, b, c, d, x, y)          \
+  v[a] += v[b] + (x);                \
+  v[d] = rotr64(v[d] ^ v[a], 32);    \
+  v[c] += v[d];                      \
+  v[b] = rotr64(v[b] ^ v[c], 24);    \
+  v[a] += v[b] + (y);                \
+  v[d] = rotr64(v[d] ^ v[a], 16);    \
+  v[c] += v[d];                      \
+  v[b] = rotr64(v[b] ^ v[c], 63);
+      G(0, 4, 8, 12, mb[s[0]], mb[s[1]]);
+      G(1, 5, 9, 13, mb[s[2]], mb[s[3]]);
+      G(2, 6, 10, 14, mb[s[4]], mb[s[5]]);
+      G(3, 7, 11, 15, mb[s[6]], mb[s[7]]);
+      G(0, 5, 10, 15, mb[s[8]], mb[s[9]]);
+      G(1, 6, 11, 12, mb[s[10]], mb[s[11]]);
+      G(2, 7, 8, 13, mb[s[12]], mb[s[13]]);
+      G(3, 4, 9, 14, mb[s[14]], mb[s[15]]);
+#undef G
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[8 + i];
+  }
 }
 
 // One ChaCha20 block (original layout: 64-bit block counter in words 12-13, zero nonce).

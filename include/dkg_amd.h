@@ -578,6 +578,48 @@ int dkg_complaint1_verify(dkg_ctx *ctx, size_t B, size_t t, const uint32_t *accu
 int dkg_complaint3_verify(dkg_ctx *ctx, size_t B, size_t t, const uint32_t *accuser, const uint8_t *share,
                           const uint8_t *randomness, const uint8_t *E, const uint8_t *A, int32_t *result);
 
+/* ---- round-2 complaints as device batches (complaints.hip) and the qualified set they prove ----
+ * In the reference a dealer leaves the qualified set only through a complaint that VERIFIES:
+ * Phases<Phase2>::compute_qualified_set (committee.rs:370-398) runs MisbehavingPartiesRound1::verify
+ * (broadcast.rs:50-99) on every broadcast complaint and clears the accused only on Ok. */
+#define DKG_COMPLAINT_IGNORED 4 /* the accused published no phase-1 broadcast: skipped (committee.rs:377-380) */
+/* ProofOfMisbehaviour::generate (broadcast.rs:189-226) for C complaints on the device.  Layouts as
+ * dkg_misbehaviour_prove: sk [C][32] accuser keys, enc [C][128], w [C][2][32], proofs [C][192].
+ * Byte-identical to it. */
+int dkg_complaints_prove(dkg_ctx *ctx, size_t C, const uint8_t *sk, const uint8_t *enc, const uint8_t *w,
+                         uint8_t *proofs);
+/* Phases<Phase2>::compute_qualified_set (committee.rs:370-398) over C broadcast complaints of ONE
+ * ceremony.  accuser[c], accused[c]: 1-based, DKG_E_ARG outside 1..n.  pk [n][32] sorted member keys.
+ * E [n][t+1][32] phase-1 commitments.  fetched1 [n] (NULL = all present).
+ * enc [C][128] = the ciphertext pair the ACCUSED broadcast to the accuser (not what the complaint
+ * carries, broadcast.rs:57).  proofs [C][192].
+ * verdict [C]: the codes of dkg_complaint1_verify (0 Ok, 1, 2, -1 a point does not decode), plus
+ * DKG_COMPLAINT_IGNORED when the accused published no phase-1 broadcast (:377-380).
+ * qualified [n] (may be NULL): 1 unless fetched1[i] == 0, E row i does not decode, or some complaint
+ * against i has verdict 0.  Requires dkg_env_init (h). */
+int dkg_complaints_verify(dkg_ctx *ctx, size_t n, size_t t, size_t C, const uint32_t *accuser,
+                          const uint32_t *accused, const uint8_t *pk, const uint8_t *E, const uint8_t *fetched1,
+                          const uint8_t *enc, const uint8_t *proofs, int32_t *verdict, uint8_t *qualified);
+/* How dkg_complaints_verify evaluates P_i(j) = sum_k j^k E_i[k] (broadcast.rs:75-86): 0 automatic (per
+ * accused dealer by its number of complaints), 1 always per-pair Horner in the exponent, 2 always the
+ * difference tables of the accused rows.  Outputs do not depend on it. */
+int dkg_ctx_set_complaint_eval(dkg_ctx *ctx, int mode);
+/* dkg_ceremony_verify_full with the reference's rule for the qualified set (committee.rs:370-398):
+ * decryption and the round-2/4 decisions run exactly as there (dec2, complaints2, r2_error keep their
+ * meaning); then the C complaints (accuser, accused 1-based, proofs [C][192]; pk [n][32]) are verified
+ * against this ceremony's own E, e1 and ct, and qualified[i] = row i is not MISSING and no complaint
+ * against i has verdict 0.  SKIPPED in round 4, the round-3 sums, reconstruct, r4_error, phase4_error,
+ * the public shares and mpk follow from that set.  verdict [C] as dkg_complaints_verify.
+ * dissent [n] (may be NULL): dissent[j] = number of dealers i that receiver j rejected
+ * (dec2[i][j] == DKG_REJECT) without a verdict-0 complaint by j against i among the C: such a party
+ * has cleared i locally (committee.rs:311) while everyone else keeps it.  The outputs are the view
+ * of the parties that are neither accuser nor accused. */
+int dkg_ceremony_verify_full_complaints(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                        const uint8_t *e1, const uint8_t *ct, const uint8_t *sk, const uint8_t *pk,
+                                        size_t C, const uint32_t *accuser, const uint32_t *accused,
+                                        const uint8_t *proofs, dkg_ceremony_out *out, int32_t *verdict,
+                                        int32_t *dissent);
+
 /* ---- synthetic inputs: the seeded RNG convention ----
  * dealer seed = BLAKE2b-256("dkg-amd/v1/dealer" || master[32] || u32le ceremony || u32le dealer);
  * coefficients = ChaCha20Rng(seed): hiding b_0..b_t first, then sharing a_0..a_t (committee.rs:143-146),
