@@ -18,6 +18,8 @@ DKG_E_NOMEM = -4
 REJECT, ACCEPT, SELF, SKIPPED, MISSING = 0, 1, 2, 3, 4
 # per-party finalise status (dkg_finalise_parties)
 FIN_OK, FIN_R2_ERROR, FIN_R4_ERROR, FIN_PHASE4_ERROR, FIN_INSUFFICIENT, FIN_PANIC = 0, 1, 2, 3, 4, 5
+# complaint verdicts beyond the primitives' 0..3 and -1 (dkg_complaints_verify, dkg_complaints3_verify)
+COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3 = 4, 5
 
 _lib = None
 
@@ -161,6 +163,11 @@ def lib():
     L.dkg_ctx_set_complaint_eval.argtypes = [p, ctypes.c_int]
     L.dkg_ceremony_verify_full_complaints.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p,
                                                       ctypes.POINTER(CeremonyOut), p, p]
+    L.dkg_complaints3_verify.argtypes = [p, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, u8p, u8p, p, p]
+    L.dkg_ceremony_verify_fetched_proven.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p, u8p,
+                                                     ctypes.POINTER(CeremonyOut), p, p, p]
+    L.dkg_ceremony_verify_full_proven.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p, u8p, sz, p, p,
+                                                  u8p, u8p, ctypes.POINTER(CeremonyOut), p, p, p, p, p]
     L.dkg_dealer_coeffs.argtypes = [u8p, ctypes.c_uint32, sz, sz, sz, p, p]
     L.dkg_scalar_sum_device.argtypes = [p, sz, sz, p, p, p]
     L.dkg_point_sum_device.argtypes = [p, sz, p, p, p]
@@ -221,4 +228,5 @@ EXPORTED = [
     "dkg_member_keys_batch", "dkg_encrypt_shares_batch", "dkg_decrypt_shares_batch", "dkg_ceremony_batch_full_device",
     "dkg_ceremony_batch_verify_full", "dkg_ctx_set_batch_full_chunk",
     "dkg_complaints_prove", "dkg_complaints_verify", "dkg_ctx_set_complaint_eval", "dkg_ceremony_verify_full_complaints",
+    "dkg_complaints3_verify", "dkg_ceremony_verify_fetched_proven", "dkg_ceremony_verify_full_proven",
 ]

@@ -94,6 +94,22 @@ class CeremonyResult:
 
 
 @dataclass
+class ProvenResult:
+    """A ceremony whose reconstructable set follows the proven round-4 complaints
+    (Phases<Phase4>::proceed, committee.rs:625-688).  verdict4[c]: 0 valid, 2 / 3 false claims, -1 the E
+    row does not decode, COMPLAINT_IGNORED (accused disqualified), COMPLAINT_NO_PHASE3 (valid
+    unverified).  finalise_status: dkg_amd._lib.FIN_*, the finalising parties' common outcome;
+    recovery_index the 0-based dealer of FIN_INSUFFICIENT / FIN_PANIC, else -1.  Full mode adds the
+    round-1 complaints' verdict and dissent (ceremony_verify_full_complaints)."""
+    result: CeremonyResult
+    verdict4: List[int]
+    finalise_status: int
+    recovery_index: int
+    verdict: Optional[List[int]] = None
+    dissent: Optional[List[int]] = None
+
+
+@dataclass
 class PartyFinalise:
     """Per-party outcome of Phases<Phase5>::finalise (dkg_finalise_parties): status[p] is one of
     dkg_amd._lib.FIN_* and recovery_index[p] the dealer of InsufficientSharesForRecovery (else -1)."""
@@ -504,6 +520,66 @@ class Backend:
         r = self._result(n, t, o, bufs, True)
         r.E, r.A = E, A
         return r, list(res)[:C], list(dis)[:n]
+
+    # ---- round-4 complaints as a device batch, and the reconstructable set they prove (committee.rs:625-688)
+    def complaints3_verify(self, n: int, t: int, accusers: Sequence[int], accused: Sequence[int], share: bytes,
+                           randomness: bytes, E: bytes, A: bytes, qualified: Optional[bytes] = None,
+                           fetched3: Optional[bytes] = None):
+        """Phases<Phase4>::proceed's loop over the broadcast round-4 complaints of one ceremony:
+        (verdicts, reconstruct).  accusers / accused 1-based; share / randomness [C][32] as disclosed."""
+        C = len(accusers)
+        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
+        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
+        res = (ctypes.c_int32 * max(C, 1))()
+        rec = ctypes.create_string_buffer(max(n, 1))
+        _check(self._ctx, _lib.lib().dkg_complaints3_verify(
+            self._ctx, n, t, C, acc, acd, share, randomness, E, A,
+            None if qualified is None else bytes(qualified), None if fetched3 is None else bytes(fetched3), res, rec))
+        return list(res)[:C], list(rec.raw[:n])
+
+    def ceremony_verify_fetched_proven(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, fetched1: bytes,
+                                       fetched3: bytes, accusers4: Sequence[int], accused4: Sequence[int],
+                                       share4: bytes, randomness4: bytes, n: int, t: int) -> ProvenResult:
+        """ceremony_verify_fetched whose reconstruct follows the proven round-4 complaints."""
+        C4 = len(accusers4)
+        acc = (ctypes.c_uint32 * max(C4, 1))(*accusers4)
+        acd = (ctypes.c_uint32 * max(C4, 1))(*accused4)
+        res = (ctypes.c_int32 * max(C4, 1))()
+        st, ri = ctypes.c_int32(), ctypes.c_int32()
+        o, bufs = self._ceremony_out(n, t, True)
+        for k in ("E", "A", "s", "s_prime"):
+            setattr(o, k, None)
+        _check(self._ctx, _lib.lib().dkg_ceremony_verify_fetched_proven(
+            self._ctx, n, t, E, A, s, s_prime, bytes(fetched1), bytes(fetched3), C4, acc, acd, share4, randomness4,
+            ctypes.byref(o), res, ctypes.byref(st), ctypes.byref(ri)))
+        r = self._result(n, t, o, bufs, True)
+        r.E, r.A, r.s, r.s_prime = E, A, s, s_prime
+        return ProvenResult(r, list(res)[:C4], st.value, ri.value)
+
+    def ceremony_verify_full_proven(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, pk: bytes,
+                                    accusers: Sequence[int], accused: Sequence[int], proofs: bytes,
+                                    accusers4: Sequence[int], accused4: Sequence[int], share4: bytes,
+                                    randomness4: bytes, n: int, t: int,
+                                    fetched3: Optional[bytes] = None) -> ProvenResult:
+        """ceremony_verify_full_complaints whose reconstruct follows the proven round-4 complaints."""
+        C, C4 = len(accusers), len(accusers4)
+        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
+        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
+        acc4 = (ctypes.c_uint32 * max(C4, 1))(*accusers4)
+        acd4 = (ctypes.c_uint32 * max(C4, 1))(*accused4)
+        res = (ctypes.c_int32 * max(C, 1))()
+        res4 = (ctypes.c_int32 * max(C4, 1))()
+        dis = (ctypes.c_int32 * max(n, 1))()
+        st, ri = ctypes.c_int32(), ctypes.c_int32()
+        o, bufs = self._ceremony_out(n, t, True)
+        for k in ("E", "A"):
+            setattr(o, k, None)
+        _check(self._ctx, _lib.lib().dkg_ceremony_verify_full_proven(
+            self._ctx, n, t, E, A, e1, ct, sk, pk, C, acc, acd, proofs, None if fetched3 is None else bytes(fetched3),
+            C4, acc4, acd4, share4, randomness4, ctypes.byref(o), res, dis, res4, ctypes.byref(st), ctypes.byref(ri)))
+        r = self._result(n, t, o, bufs, True)
+        r.E, r.A = E, A
+        return ProvenResult(r, list(res4)[:C4], st.value, ri.value, list(res)[:C], list(dis)[:n])
 
     def dealer_coefficients_device(self, master: bytes, ceremony0: int, B: int, d0: int, D: int, t: int,
                                    d_a: int, d_b: int):

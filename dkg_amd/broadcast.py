@@ -278,3 +278,67 @@ def verify_broadcasts(be, n: int, t: int, phase1: Sequence[Optional[BroadcastPha
     r = be.ceremony_verify_fetched(p1.E, A, p1.share, p1.randomness, p1.fetched1, f3, n, t)
     r.fetch_invalid = list(p1.fetch_invalid)  # receivers whose round 2 aborts (committee.rs:277-280)
     return r
+
+
+def intake_phase4(n: int, msgs: Sequence[Optional[BroadcastPhase4]]) -> Tuple[List[int], List[int], bytes, bytes]:
+    """Every party's phase-4 broadcast (msgs[j] from party j+1, None if it did not broadcast) as
+    MembersFetchedState4::from_broadcast and FetchedMisbehaviourComplaints::from_broadcasts_4
+    (committee.rs:964-993, 1027-1070) hand it to Phases<Phase4>::proceed (:625-688): the sender index is
+    the position + 1, an absent broadcast is dropped, and the complaints come out flattened in
+    broadcast order as (accuser, accused, share [C][32], randomness [C][32]) for
+    Backend.complaints3_verify / ceremony_verify_*_proven.  An accused index outside 1..n, where the
+    reference's indexing panics (:639), raises ValueError."""
+    if len(msgs) != n:
+        raise ValueError("one entry per party expected")
+    accuser: List[int] = []
+    accused: List[int] = []
+    share: List[bytes] = []
+    randomness: List[bytes] = []
+    for j, m in enumerate(msgs):
+        if m is None:
+            continue
+        for mp in m.misbehaving_parties:
+            if not 1 <= mp.accused_index <= n:
+                raise ValueError("accused index out of range")
+            if len(mp.decrypted_share) != 32 or len(mp.decrypted_randomness) != 32:
+                raise ValueError("a disclosed scalar is 32 bytes")
+            accuser.append(j + 1)
+            accused.append(mp.accused_index)
+            share.append(mp.decrypted_share)
+            randomness.append(mp.decrypted_randomness)
+    return accuser, accused, b"".join(share), b"".join(randomness)
+
+
+def verify_broadcasts_proven(be, n: int, t: int, phase1: Sequence[Optional[BroadcastPhase1]],
+                             phase3: Sequence[Optional[BroadcastPhase3]],
+                             phase4: Sequence[Optional[BroadcastPhase4]],
+                             phase2: Optional[Sequence[Optional[BroadcastPhase2]]] = None,
+                             sk: Optional[bytes] = None, pk: Optional[bytes] = None):
+    """Rounds 2-5 of a committee on its broadcasts with the reconstructable set by the proven phase-4
+    complaints (a ProvenResult).  Plaintext mode (sk is None): one
+    dkg_ceremony_verify_fetched_proven.  Full mode (sk, pk and the phase-2 broadcasts given): one
+    dkg_ceremony_verify_full_proven on the hybrid ciphertexts, which has no phase-1 intake mask, so
+    every phase-1 broadcast must be well-formed (ValueError otherwise)."""
+    acc4, acd4, sh4, rn4 = intake_phase4(n, phase4)
+    A, f3 = intake_phase3(n, t, phase3)
+    if sk is None:
+        p1 = intake_phase1(n, t, phase1, mode=0)
+        r = be.ceremony_verify_fetched_proven(p1.E, A, p1.share, p1.randomness, p1.fetched1, f3, acc4, acd4, sh4, rn4,
+                                              n, t)
+    else:
+        if pk is None or phase2 is None:
+            raise ValueError("full mode needs the member keys and the phase-2 broadcasts")
+        p1 = intake_phase1(n, t, phase1, mode=1)
+        if not all(p1.fetched1):
+            raise ValueError("full mode needs every phase-1 broadcast")
+        # items (dealer i, recipient q, w) at (i n + q) 2 + w, w = 0 the randomness: e1 and e2 apart
+        e1, ct = bytearray(64 * n * n), bytearray(64 * n * n)
+        for k in range(n * n):
+            for w, src in enumerate((p1.randomness, p1.share)):
+                e1[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k:64 * k + 32]
+                ct[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k + 32:64 * k + 64]
+        acc2, acd2, proofs = intake_phase2(n, phase2)
+        r = be.ceremony_verify_full_proven(p1.E, A, bytes(e1), bytes(ct), sk, pk, acc2, acd2, proofs, acc4, acd4, sh4,
+                                           rn4, n, t, fetched3=f3)
+    r.result.fetch_invalid = list(p1.fetch_invalid)  # receivers whose round 2 aborts (committee.rs:277-280)
+    return r

@@ -1,4 +1,4 @@
-// Round-2 complaints on gfx950: ProofOfMisbehaviour::generate (broadcast.rs:189-226) and
+// Complaints on gfx950.  Round 2: ProofOfMisbehaviour::generate (broadcast.rs:189-226) and
 // MisbehavingPartiesRound1::verify (broadcast.rs:50-99 with ProofOfMisbehaviour::verify, :227-283) as
 // batches, one work item per complaint.  A proof is (share_key, randomness_key, c1, r1, c2, r2): the
 // two recovered symmetric keys K = sk * e1 and a DLEQ(g, e1, pk, K; sk) proof for each
@@ -10,6 +10,9 @@
 //   horner  : P_i(j) per (accused, accuser) pair (k_cmp_horner), or the difference tables (runtime);
 //   check   : the two check elements h p1 + g p2, h p2 + g p1 against P_i(j) (k_cv_check, combs);
 //   final   : the Fiat-Shamir challenges (two-block Blake2b) and the verdict (ARX).
+// Round 4: MisbehavingPartiesRound3::verify (broadcast.rs:104-144) as a batch, one lane per complaint
+// (k_c3_prep / k_c3_check / k_c3_final at the end of this file): no proofs, so only the horner / tables
+// stage and a check of both sides from one walk of the g comb.
 #include "kernels.h"
 #include "points.h"
 #include "hybrid_dev.h"
@@ -473,6 +476,106 @@ void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8
                           hipStream_t stream) {
   if (!rows) return;
   hipLaunchKernelGGL(k_qualified_complaints, dim3((unsigned)rows), dim3(64), 0, stream, n, dec, cmask, rej, qmask);
+}
+
+// ------------------------------------------------------------------ round-4 complaints: prep / check / final
+// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) for C complaints of one ceremony, lane =
+// complaint.  A complaint discloses the accuser's decrypted pair; it holds when the pair passes against
+// the accused's E row and fails against its A row.  Both rows live in ONE decoded array of 2n rows (E
+// rows 0..n-1, A rows n..2n-1), so complaint c is the two evaluation items 2c = (row i, index j) and
+// 2c + 1 = (row n + i, index j) of k_cmp_horner / the difference tables.
+// prep: share / randomness [C][8] raw -> sr [2C][8] canonical (k_reduce_scalars' reduction, what the
+// host-driven primitive's upload applies), and the items' index lists acc2 / acd2 [2C].
+__global__ __launch_bounds__(256) void k_c3_prep(size_t C, uint32_t n, const uint32_t* __restrict__ accuser,
+                                                 const uint32_t* __restrict__ accused,
+                                                 const uint32_t* __restrict__ share,
+                                                 const uint32_t* __restrict__ randomness, uint32_t* __restrict__ sr,
+                                                 uint32_t* __restrict__ acc2, uint32_t* __restrict__ acd2) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  sc x;
+  sc_load_reduced(x, share + 8 * c);
+  sc_store(sr + 8 * (2 * c), x);
+  sc_load_reduced(x, randomness + 8 * c);
+  sc_store(sr + 8 * (2 * c + 1), x);
+  acc2[2 * c] = acc2[2 * c + 1] = accuser[c];
+  acd2[2 * c] = accused[c];
+  acd2[2 * c + 1] = n + accused[c];
+}
+
+void c3_prep(size_t C, size_t n, const uint32_t* accuser, const uint32_t* accused, const uint32_t* share,
+             const uint32_t* randomness, uint32_t* sr, uint32_t* acc2, uint32_t* acd2, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_c3_prep, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, (uint32_t)n, accuser,
+                     accused, share, randomness, sr, acc2, acd2);
+}
+
+// eq[2c] = (g share + h randomness == P^E_i(j)), eq[2c + 1] = (g share == P^A_i(j)): one walk of the g
+// comb serves both sides, the h comb's terms are added to it.  ridx [2C] per item as k_cv_check's
+// (bit 31: Rt, the tables' b_j P(j) when `scale` is given); both items of a complaint take the same
+// source, so the scalars are scaled once.
+__global__ __launch_bounds__(256, DKG_COMB_WAVES) void k_c3_check(size_t C, const uint32_t* __restrict__ accuser,
+                                                  const uint32_t* __restrict__ sr, const uint32_t* __restrict__ ridx,
+                                                  const uint32_t* __restrict__ Rh, const uint32_t* __restrict__ Rt,
+                                                  const uint32_t* __restrict__ scale,
+                                                  const uint32_t* __restrict__ tab_g,
+                                                  const uint32_t* __restrict__ tab_h, uint8_t* __restrict__ eq) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const uint32_t re = ridx[2 * c], ra = ridx[2 * c + 1];
+  const bool tab = re >> 31;
+  sc x, f;
+  const bool scaled = tab && scale;
+  if (scaled) sc_load(f, scale + 8 * (size_t)(accuser[c] - 1));
+  ge_p3 acc, r;
+  ge_identity(acc);
+  sc_load(x, sr + 8 * (2 * c));  // g * share
+  if (scaled) sc_mont_mul(x, x, f);
+  combw_mul_add(acc, x, tab_g);
+  pt_load_aos(r, tab ? Rt : Rh, ra & 0x7fffffffu);
+  eq[2 * c + 1] = ristretto_eq(acc, r) ? 1 : 0;
+  sc_load(x, sr + 8 * (2 * c + 1));  // + h * randomness
+  if (scaled) sc_mont_mul(x, x, f);
+  combw_mul_add(acc, x, tab_h);
+  pt_load_aos(r, tab ? Rt : Rh, re & 0x7fffffffu);
+  eq[2 * c] = ristretto_eq(acc, r) ? 1 : 0;
+}
+
+void c3_check(size_t C, const uint32_t* accuser, const uint32_t* sr, const uint32_t* ridx, const uint32_t* Rh,
+              const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
+              hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_c3_check, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, accuser, sr, ridx, Rh, Rt,
+                     scale, tab_g, tab_h, eq);
+}
+
+// Verdict of complaint c as Phases<Phase4>::proceed treats it (committee.rs:636-670): 4 the accused is
+// disqualified (:639), 5 it has no phase-3 broadcast -- absent, or its A row does not decode -- so the
+// complaint holds unverified (:643), else the codes of dkg_complaint3_verify.  rowok [2n] decode flags
+// of the E rows then the A rows; qualified / fetched3 [n] may be null (all 1).
+__global__ __launch_bounds__(256) void k_c3_final(size_t C, size_t n, const uint32_t* __restrict__ accused,
+                                                  const uint8_t* __restrict__ rowok,
+                                                  const uint8_t* __restrict__ qualified,
+                                                  const uint8_t* __restrict__ fetched3, const uint8_t* __restrict__ eq,
+                                                  int32_t* __restrict__ verdict) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const size_t i = accused[c] - 1;
+  int32_t v;
+  if (qualified && !qualified[i]) v = 4;
+  else if ((fetched3 && !fetched3[i]) || !rowok[n + i]) v = 5;
+  else if (!rowok[i]) v = -1;
+  else if (!eq[2 * c]) v = 3;     // FalseClaimedEquality (broadcast.rs:129-130)
+  else if (eq[2 * c + 1]) v = 2;  // FalseClaimedInequality (:131-132)
+  else v = 0;
+  verdict[c] = v;
+}
+
+void c3_final(size_t C, size_t n, const uint32_t* accused, const uint8_t* rowok, const uint8_t* qualified,
+              const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_c3_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, n, accused, rowok,
+                     qualified, fetched3, eq, verdict);
 }
 
 }  // namespace dkgk

@@ -309,6 +309,18 @@ void cp_finish(size_t C, const uint32_t* enc, const uint32_t* lc, const uint32_t
 // qmask[i] = row i of dec [rows][n] holds no MISSING and cmask[i]; rej[i] = !qmask[i]
 void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8_t* cmask, uint8_t* rej, uint8_t* qmask,
                           hipStream_t stream);
+// round-4 complaints (MisbehavingPartiesRound3::verify, broadcast.rs:104-144), lane = complaint: the
+// reduced scalars sr [2C][8] = (share, randomness) and the evaluation items' lists acc2 / acd2 [2C]
+// (item 2c: E row accused - 1, item 2c + 1: A row n + accused - 1 of the decoded 2n rows);
+void c3_prep(size_t C, size_t n, const uint32_t* accuser, const uint32_t* accused, const uint32_t* share,
+             const uint32_t* randomness, uint32_t* sr, uint32_t* acc2, uint32_t* acd2, hipStream_t stream);
+// eq[2c] = (g share + h randomness == P^E), eq[2c + 1] = (g share == P^A); ridx [2C], Rh, Rt, scale as cv_check;
+void c3_check(size_t C, const uint32_t* accuser, const uint32_t* sr, const uint32_t* ridx, const uint32_t* Rh,
+              const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
+              hipStream_t stream);
+// the verdicts (rowok [2n]; qualified, fetched3 [n] may be null)
+void c3_final(size_t C, size_t n, const uint32_t* accused, const uint8_t* rowok, const uint8_t* qualified,
+              const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict, hipStream_t stream);
 
 // ---- committee verification by interpolation (interp.hip)
 // F[d][k] = sum_j W[k][j] s[d][j] (and F' from s'; sp may be null), WT[j][k] = W[k][j] in Montgomery form

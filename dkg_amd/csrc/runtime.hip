@@ -1240,7 +1240,7 @@ void round4_host(size_t V, const uint8_t* qualified, uint8_t* recon) {
 // failed recovery) or, when a dealer is reconstructed, adds g * its recovered secret (a second trip).
 void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
                            const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                           const uint8_t* e_ok, const uint8_t* a_ok, const uint8_t* cmask) {
+                           const uint8_t* e_ok, const uint8_t* a_ok, const uint8_t* cmask, const uint8_t* proven4) {
   const size_t N = t + 1;
   uint8_t* dec2 = buf<uint8_t>(ctx, "dec2", n * n);
   uint8_t* dec4 = buf<uint8_t>(ctx, "dec4", n * n);
@@ -1274,6 +1274,11 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   uint8_t* rej4 = buf<uint8_t>(ctx, "o.rej4", n);
   uint8_t* r4d = buf<uint8_t>(ctx, "o.r4err", n);
   round4_device(ctx, 1, n, t, dec4, qmask, rej4, r4d);
+  // proven4 (device [n], may be null): the reconstructable set by PROVEN round-4 complaints instead --
+  // proven4[i] = some broadcast complaint against i holds (Phases<Phase4>::proceed, committee.rs:636-670,
+  // run on the complaints by the caller); a receiver's own rejection alone reconstructs nobody.  The
+  // qualified mask is applied below as for the rejections (:639).
+  const uint8_t* acc4 = proven4 ? proven4 : rej4;
   HCK(hipEventRecord(ctx->ev[4], ctx->stream));
   // ---- finalise (committee.rs:726-805): mpk = sum_{i in Q \ recon} A_i0 (+ sum_{recon} g * L_i(0))
   uint32_t* A0 = buf<uint32_t>(ctx, "A0ext", PTB * n);
@@ -1286,7 +1291,7 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
     dkgk::decode_points(A0c, n, A0, n, a0ok, ctx->stream);
   }
   uint8_t* hmask = buf<uint8_t>(ctx, "hmask", n);
-  dkgk::mask_not_and(n, rej4, qmask, hmask, ctx->stream);  // the final parties: qualified, not accused
+  dkgk::mask_not_and(n, acc4, qmask, hmask, ctx->stream);  // the final parties: qualified, not accused
   uint32_t* mpk_ext = buf<uint32_t>(ctx, "mpk_ext", PTB);
   dkgk::sum_points(n, A0, n, hmask, mpk_ext, 1, 0, ctx->stream);
   uint32_t* mpk_c = buf<uint32_t>(ctx, "mpk_comp", 32);
@@ -1294,7 +1299,7 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   check_launch(ctx);
   uint8_t* h = hbuf<uint8_t>(ctx, "rr.out", 8 * n + 32);  // rej2 | rej4 | r4err | cnt | mpk
   d2h(ctx, h, rej2, n);
-  d2h(ctx, h + n, rej4, n);
+  d2h(ctx, h + n, acc4, n);
   d2h(ctx, h + 2 * n, r4d, n);
   d2h(ctx, h + 3 * n, cnt, 4 * n);
   d2h(ctx, h + 7 * n, mpk_c, 32);
@@ -1365,8 +1370,11 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
 // formula when they marked a group (with_binom_ded)
 void receivers_rounds(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
                       const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                      const uint8_t* e_ok = nullptr, const uint8_t* a_ok = nullptr, const uint8_t* cmask = nullptr) {
-  with_binom_ded(ctx, [&] { receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, e_ok, a_ok, cmask); });
+                      const uint8_t* e_ok = nullptr, const uint8_t* a_ok = nullptr, const uint8_t* cmask = nullptr,
+                      const uint8_t* proven4 = nullptr) {
+  with_binom_ded(ctx, [&] {
+    receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, e_ok, a_ok, cmask, proven4);
+  });
 }
 
 // Round 1 for D dealers on device: a, b canonical [D][N][8] -> Ecomp, Acomp [D][N][8], s, sp [D][n][8].
@@ -3269,15 +3277,25 @@ int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d
 namespace {
 
 // dkg_ceremony_verify_full's body.  cmask (device [n], may be null): the qualified set follows the
-// proven complaints (round2_device) instead of the receivers' own rejections.
+// proven complaints (round2_device) instead of the receivers' own rejections.  EA (device [2n][N][8], may
+// be null): the commitments are on the device already, E rows then A rows.  a_ok, proven4 (device [n],
+// may be null): as receivers_rounds_once.
 int ceremony_verify_full_impl(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
-                              const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out, const uint8_t* cmask) {
+                              const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out, const uint8_t* cmask,
+                              const uint32_t* EA = nullptr, const uint8_t* a_ok = nullptr,
+                              const uint8_t* proven4 = nullptr) {
   {
     const size_t N = t + 1, items = 2 * n * n;
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
-    h2d(ctx, Ec, E, 32 * n * N);
-    h2d(ctx, Ac, A, 32 * n * N);
+    const uint32_t *Ec, *Ac;
+    if (EA) {
+      Ec = EA, Ac = EA + 8 * n * N;
+    } else {
+      uint32_t* e = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
+      uint32_t* a = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
+      h2d(ctx, e, E, 32 * n * N);
+      h2d(ctx, a, A, 32 * n * N);
+      Ec = e, Ac = a;
+    }
     uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
     uint32_t* de1 = buf<uint32_t>(ctx, "fm_e1", 32 * items);
     uint32_t* dct = buf<uint32_t>(ctx, "fm_ct", 32 * items);
@@ -3300,7 +3318,7 @@ int ceremony_verify_full_impl(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E
       HCK(hipEventRecord(ctx->shares_done, ctx->side));
       ctx->shares_pending = true;
     }
-    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, true, eok, nullptr, cmask);  // waits for the shares before it returns
+    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, true, eok, a_ok, cmask, proven4);  // waits for the shares before it returns
     collect_hybrid_phases(ctx);  // decryption phases only (no encryption here: full.enc_* read -1)
     if (out->s) d2h(ctx, out->s, rs, 32 * n * n);
     if (out->s_prime) d2h(ctx, out->s_prime, rsp, 32 * n * n);
@@ -3334,6 +3352,74 @@ bool complaint_tables_pay(size_t n, size_t N, size_t count) {
   const double horner_us = 3.6 * (double)N * (nb + std::min(nb, cb + 1) + 1);
   const double tables_us = 13.0 * (double)N + 3.7 * (double)n;
   return tables_us < horner_us;
+}
+
+// P_row(x) = sum_k x^k C_row[k] for C (row, index) items: per row, the difference tables of that row
+// or one Horner walk per item (ctx->complaint_eval; automatic: complaint_tables_pay by the row's item
+// count).  index / row (host) and dindex / drow (device) [C]: 1-based, index within 1..n, row within
+// 1..nrows; Cc [nrows][N][8] compressed and Cext (stride nrows * N) decoded commitments on the device.
+// An (row, index) pair listed again takes a further table row of its own, so that the table path
+// serves every item of a row it is chosen for.  Out: dridx [C] (bit 31: element of Rt, else of Rh),
+// Rh, Rt, scale as k_cv_check reads them.  Work is queued on ctx->stream; the staging vectors live
+// in `ev`, which the caller keeps until it has synchronised.
+struct ComplaintEvals {
+  std::vector<uint32_t> rows, hl, ridx;
+  const uint32_t *dridx = nullptr, *Rh = nullptr, *Rt = nullptr, *scale = nullptr;
+};
+void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, const uint32_t* index,
+                     const uint32_t* row, const uint32_t* dindex, const uint32_t* drow, const uint32_t* Cc,
+                     const uint32_t* Cext, ComplaintEvals& ev) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  std::vector<size_t> count(nrows, 0);
+  for (size_t c = 0; c < C; c++) count[row[c] - 1]++;
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;   // (row, index) -> occurrences so far
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> rowof;  // (row, occurrence) -> table row
+  std::vector<uint32_t>&rows = ev.rows, &hl = ev.hl, &ridx = ev.ridx;
+  ridx.resize(C);
+  for (size_t c = 0; c < C; c++) {
+    const uint32_t i = row[c], j = index[c];
+    const bool tables = N >= 2 && (ctx->complaint_eval == 2 ||
+                                   (ctx->complaint_eval == 0 && complaint_tables_pay(n, N, count[i - 1])));
+    if (!tables) {
+      hl.push_back((uint32_t)c);
+      ridx[c] = (uint32_t)c;
+      continue;
+    }
+    const uint32_t m = seen[{i, j}]++;
+    auto it = rowof.find({i, m});
+    if (it == rowof.end()) {
+      it = rowof.emplace(std::make_pair(i, m), (uint32_t)rows.size()).first;
+      rows.push_back(i);
+    }
+    if (((size_t)it->second + 1) * n >= ((size_t)1 << 31)) {
+      ctx->err = "complaints_verify: too many table rows";
+      throw Fail{DKG_E_ARG};
+    }
+    ridx[c] = 0x80000000u | (uint32_t)((size_t)it->second * n + (j - 1));
+  }
+  uint32_t* dridx = buf<uint32_t>(ctx, "cv_ridx", 4 * C);
+  h2d(ctx, dridx, ridx.data(), 4 * C);
+  uint32_t* Rh = buf<uint32_t>(ctx, "cv_Rh", PTB * C);
+  if (!hl.empty()) {
+    uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
+    h2d(ctx, dhl, hl.data(), 4 * hl.size());
+    int nb = 1;
+    while ((n >> nb) != 0) nb++;
+    dkgk::cmp_horner(hl.size(), dhl, dindex, drow, Cext, nrows * N, N, nb, Rh, st);
+  }
+  if (!rows.empty()) {
+    const size_t D = rows.size();
+    uint32_t* Trows = buf<uint32_t>(ctx, "cv_Trows", 32 * D * N);
+    for (size_t r = 0; r < D; r++)
+      HCK(hipMemcpyAsync(Trows + 8 * N * r, Cc + 8 * N * (size_t)(rows[r] - 1), 32 * N, hipMemcpyDeviceToDevice, st));
+    VerifySeg g{2, D, 0, Trows, nullptr, nullptr, nullptr};
+    verify_device(ctx, n, t, &g, 1, false, "cv");
+    ev.Rt = ctx->last_R;
+    ev.scale = ctx->last_scale;
+  }
+  ev.dridx = dridx;
+  ev.Rh = Rh;
 }
 
 // MisbehavingPartiesRound1::verify (broadcast.rs:50-99) for C complaints of one ceremony.  Device: dpk
@@ -3395,63 +3481,17 @@ void complaints_verify_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const ui
   uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
   dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
   dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
-  // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint.
-  // A pair complained about again takes a further table row of its own, so that the table path
-  // serves every complaint of a dealer it is chosen for.
-  std::vector<size_t> count(n, 0);
-  for (size_t c = 0; c < C; c++) count[accused[c] - 1]++;
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;   // (accused, accuser) -> occurrences so far
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> rowof;  // (accused, occurrence) -> table row
-  std::vector<uint32_t> rows, hl, ridx(C);
-  for (size_t c = 0; c < C; c++) {
-    const uint32_t i = accused[c], j = accuser[c];
-    const bool tables = N >= 2 && (ctx->complaint_eval == 2 ||
-                                   (ctx->complaint_eval == 0 && complaint_tables_pay(n, N, count[i - 1])));
-    if (!tables) {
-      hl.push_back((uint32_t)c);
-      ridx[c] = (uint32_t)c;
-      continue;
-    }
-    const uint32_t m = seen[{i, j}]++;
-    auto it = rowof.find({i, m});
-    if (it == rowof.end()) {
-      it = rowof.emplace(std::make_pair(i, m), (uint32_t)rows.size()).first;
-      rows.push_back(i);
-    }
-    if (((size_t)it->second + 1) * n >= ((size_t)1 << 31)) {
-      ctx->err = "complaints_verify: too many table rows";
-      throw Fail{DKG_E_ARG};
-    }
-    ridx[c] = 0x80000000u | (uint32_t)((size_t)it->second * n + (j - 1));
-  }
-  uint32_t* dridx = buf<uint32_t>(ctx, "cv_ridx", 4 * C);
-  h2d(ctx, dridx, ridx.data(), 4 * C);
-  uint32_t* Rh = buf<uint32_t>(ctx, "cv_Rh", PTB * C);
-  if (!hl.empty()) {
-    uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
-    h2d(ctx, dhl, hl.data(), 4 * hl.size());
-    int nb = 1;
-    while ((n >> nb) != 0) nb++;
-    dkgk::cmp_horner(hl.size(), dhl, dacc, dacd, Eext, n * N, N, nb, Rh, st);
-  }
-  const uint32_t *Rt = nullptr, *scale = nullptr;
-  if (!rows.empty()) {
-    const size_t D = rows.size();
-    uint32_t* Trows = buf<uint32_t>(ctx, "cv_Trows", 32 * D * N);
-    for (size_t r = 0; r < D; r++)
-      HCK(hipMemcpyAsync(Trows + 8 * N * r, Ec + 8 * N * (size_t)(rows[r] - 1), 32 * N, hipMemcpyDeviceToDevice, st));
-    VerifySeg g{2, D, 0, Trows, nullptr, nullptr, nullptr};
-    verify_device(ctx, n, t, &g, 1, false, "cv");
-    Rt = ctx->last_R;
-    scale = ctx->last_scale;
-  }
+  // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint
+  ComplaintEvals ev;
+  complaint_evals(ctx, n, t, n, C, accuser, accused, dacc, dacd, Ec, Eext, ev);
+  const uint32_t *dridx = ev.dridx, *Rh = ev.Rh, *Rt = ev.Rt, *scale = ev.scale;
   uint8_t* eq = buf<uint8_t>(ctx, "cv_eq", 2 * C);
   dkgk::cv_check(C, dacc, p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
   int32_t* dver = buf<int32_t>(ctx, "cv_verdict", 4 * C);
   dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, a1c, a2c, ppok, rowok, dfet, eq, dver, st);
   check_launch(ctx);
   d2h(ctx, verdict, dver, 4 * C);
-  sync(ctx);  // the staging vectors (ridx, hl) live until here
+  sync(ctx);  // the staging vectors (ev) live until here
 }
 
 // 1-based party indices within 1..n
@@ -3460,6 +3500,141 @@ bool complaint_indices_ok(size_t n, size_t C, const uint32_t* accuser, const uin
     if (accuser[c] < 1 || accuser[c] > n || accused[c] < 1 || accused[c] > n) return false;
   return true;
 }
+
+// dissent[j] = the dealers receiver j rejected in the ceremony just run (dec2 on the device) without a
+// proven complaint of its own against them among the C
+void complaint_dissent(dkg_ctx* ctx, size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                       const int32_t* verdict, int32_t* dissent) {
+  std::vector<uint8_t> d2(n * n);
+  d2h(ctx, d2.data(), buf<uint8_t>(ctx, "dec2", n * n), n * n);
+  sync(ctx);
+  std::vector<uint8_t> proven(n * n, 0);  // [accused][accuser]
+  for (size_t c = 0; c < C; c++)
+    if (verdict[c] == 0) proven[(size_t)(accused[c] - 1) * n + (accuser[c] - 1)] = 1;
+  for (size_t j = 0; j < n; j++) {
+    int32_t v = 0;
+    for (size_t i = 0; i < n; i++) v += d2[i * n + j] == DKG_REJECT && !proven[i * n + j];
+    dissent[j] = v;
+  }
+}
+
+// ---- round-4 complaints as a device batch (complaints.hip, k_c3_*)
+// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) as Phases<Phase4>::proceed applies it
+// (committee.rs:636-670) for C complaints of one ceremony.  Device: EA [2n][N][8], the E rows then the A
+// rows; host: accuser / accused (1-based, validated by the caller), share / randomness [C][32],
+// qualified / fetched3 [n] (may be null = all 1).  verdict [C] on the host; rowok_host (may be null)
+// [2n] = the row decodes.  Ends synchronised.
+void complaints3_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                      const uint8_t* share, const uint8_t* randomness, const uint32_t* EA, const uint8_t* qualified,
+                      const uint8_t* fetched3, int32_t* verdict, uint8_t* rowok_host) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  // both rows of every dealer decoded once: the rows' validity, and the Horner walks' input
+  uint32_t* EAext = buf<uint32_t>(ctx, "c3_EAext", PTB * 2 * n * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "c3_pok", 2 * n * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "c3_rowok", 2 * n);
+  dkgk::decode_points(EA, 2 * n * N, EAext, 2 * n * N, pok, st);
+  dkgk::dealer_ok(2 * n, N, pok, rowok, st);
+  if (rowok_host) d2h(ctx, rowok_host, rowok, 2 * n);
+  if (!C) {
+    check_launch(ctx);
+    sync(ctx);
+    return;
+  }
+  uint32_t* dacc = buf<uint32_t>(ctx, "c3_accuser", 4 * C);
+  uint32_t* dacd = buf<uint32_t>(ctx, "c3_accused", 4 * C);
+  uint32_t* dsh = buf<uint32_t>(ctx, "c3_share", 32 * C);
+  uint32_t* drn = buf<uint32_t>(ctx, "c3_rand", 32 * C);
+  h2d(ctx, dacc, accuser, 4 * C);
+  h2d(ctx, dacd, accused, 4 * C);
+  h2d(ctx, dsh, share, 32 * C);
+  h2d(ctx, drn, randomness, 32 * C);
+  uint8_t *dq = nullptr, *df3 = nullptr;
+  if (qualified) {
+    dq = buf<uint8_t>(ctx, "c3_qualified", n);
+    h2d(ctx, dq, qualified, n);
+  }
+  if (fetched3) {
+    df3 = buf<uint8_t>(ctx, "c3_fetched3", n);
+    h2d(ctx, df3, fetched3, n);
+  }
+  uint32_t* sr = buf<uint32_t>(ctx, "c3_sr", 32 * 2 * C);
+  uint32_t* acc2 = buf<uint32_t>(ctx, "c3_acc2", 4 * 2 * C);
+  uint32_t* acd2 = buf<uint32_t>(ctx, "c3_acd2", 4 * 2 * C);
+  dkgk::c3_prep(C, n, dacc, dacd, dsh, drn, sr, acc2, acd2, st);
+  // P^E_i(j), P^A_i(j): items 2c, 2c + 1 on rows i, n + i.  Both rows of a dealer carry the same item
+  // count, so the automatic switch sends them the same way
+  std::vector<uint32_t> index(2 * C), row(2 * C);
+  for (size_t c = 0; c < C; c++) {
+    index[2 * c] = index[2 * c + 1] = accuser[c];
+    row[2 * c] = accused[c];
+    row[2 * c + 1] = (uint32_t)n + accused[c];
+  }
+  ComplaintEvals ev;
+  complaint_evals(ctx, n, t, 2 * n, 2 * C, index.data(), row.data(), acc2, acd2, EA, EAext, ev);
+  uint8_t* eq = buf<uint8_t>(ctx, "c3_eq", 2 * C);
+  dkgk::c3_check(C, dacc, sr, ev.dridx, ev.Rh, ev.Rt, ev.scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+  int32_t* dver = buf<int32_t>(ctx, "c3_verdict", 4 * C);
+  dkgk::c3_final(C, n, dacd, rowok, dq, df3, eq, dver, st);
+  check_launch(ctx);
+  d2h(ctx, verdict, dver, 4 * C);
+  sync(ctx);  // the staging vectors (ev) live until here
+}
+
+// proven[i] = some complaint against i holds: verdict 0, or the accused has no phase-3 broadcast
+// (committee.rs:643, :664-669)
+std::vector<uint8_t> proven_round4(size_t n, size_t C, const uint32_t* accused, const int32_t* verdict) {
+  std::vector<uint8_t> p(n, 0);
+  for (size_t c = 0; c < C; c++)
+    if (verdict[c] == 0 || verdict[c] == DKG_COMPLAINT_NO_PHASE3) p[accused[c] - 1] = 1;
+  return p;
+}
+
+// What follows a ceremony that took `reconstruct` from the proven round-4 complaints: the verdicts
+// against dealers that round 2 disqualified become IGNORED (committee.rs:639), and the finalising
+// parties' common outcome.  a_ok[i] = dealer i has a usable phase-3 broadcast.  A qualified dealer
+// without one that nobody complained about is in no set: every party's finalise reaches the expect
+// at committee.rs:791-795 with indexed_committed_shares[i] never stored (:527-530).  Dealers are
+// visited in index order and the first failure wins (:745-797); mpk is zeroed on a panic.
+void proven_outcome(size_t n, size_t t, size_t C4, const uint32_t* accused4, int32_t* verdict4,
+                    const uint8_t* a_ok, dkg_ceremony_out* out, int32_t* finalise_status, int32_t* recovery_index) {
+  const uint8_t *qualified = out->qualified, *recon = out->reconstruct;
+  for (size_t c = 0; c < C4; c++)
+    if (!qualified[accused4[c] - 1]) verdict4[c] = DKG_COMPLAINT_IGNORED;
+  int32_t status = DKG_FIN_OK, index = -1;
+  if (out->phase4_error) {
+    status = DKG_FIN_PHASE4_ERROR;
+  } else {
+    const bool insufficient = recovery_fails(disclosing_parties(n, qualified, recon, out->r2_error, out->r4_error), t);
+    for (size_t i = 0; i < n && status == DKG_FIN_OK; i++) {
+      if (recon[i] && insufficient) status = DKG_FIN_INSUFFICIENT;
+      else if (!recon[i] && qualified[i] && !a_ok[i]) status = DKG_FIN_PANIC;
+      if (status != DKG_FIN_OK) index = (int32_t)i;
+    }
+  }
+  if (status == DKG_FIN_PANIC) memset(out->mpk, 0, 32);
+  if (finalise_status) *finalise_status = status;
+  if (recovery_index) *recovery_index = index;
+}
+
+// A copy of *out in which the four per-party flag arrays the proven ceremonies read afterwards are
+// present: the caller's own, or scratch.  finish() hands the scalar results back to the caller's struct.
+struct OutFlags {
+  std::vector<uint8_t> scratch;
+  dkg_ceremony_out o;
+  OutFlags(const dkg_ceremony_out* out, size_t n) : scratch(4 * n), o(*out) {
+    if (!o.qualified) o.qualified = scratch.data();
+    if (!o.reconstruct) o.reconstruct = scratch.data() + n;
+    if (!o.r2_error) o.r2_error = scratch.data() + 2 * n;
+    if (!o.r4_error) o.r4_error = scratch.data() + 3 * n;
+  }
+  void finish(dkg_ceremony_out* out) const {
+    dkg_ceremony_out r = o;
+    r.qualified = out->qualified, r.reconstruct = out->reconstruct;
+    r.r2_error = out->r2_error, r.r4_error = out->r4_error;
+    *out = r;
+  }
+};
 
 }  // namespace
 
@@ -3587,18 +3762,137 @@ int dkg_ceremony_verify_full_complaints(dkg_ctx* ctx, size_t n, size_t t, const 
     sync(ctx);
     rc = ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, out, dcm);
     if (rc || !dissent) return rc;
-    // a receiver that rejected a dealer without a proven complaint of its own against it
-    std::vector<uint8_t> d2(n * n);
-    d2h(ctx, d2.data(), buf<uint8_t>(ctx, "dec2", n * n), n * n);
-    sync(ctx);
-    std::vector<uint8_t> proven(n * n, 0);  // [accused][accuser]
-    for (size_t c = 0; c < C; c++)
-      if (verdict[c] == 0) proven[(size_t)(accused[c] - 1) * n + (accuser[c] - 1)] = 1;
-    for (size_t j = 0; j < n; j++) {
-      int32_t v = 0;
-      for (size_t i = 0; i < n; i++) v += d2[i * n + j] == DKG_REJECT && !proven[i * n + j];
-      dissent[j] = v;
+    complaint_dissent(ctx, n, C, accuser, accused, verdict, dissent);
+    return DKG_OK;
+  });
+}
+
+// ---- round-4 complaints as a device batch, and the ceremonies that reconstruct by them
+int dkg_complaints3_verify(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                           const uint8_t* share, const uint8_t* randomness, const uint8_t* E, const uint8_t* A,
+                           const uint8_t* qualified, const uint8_t* fetched3, int32_t* verdict, uint8_t* reconstruct) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !E || !A) return DKG_E_ARG;
+    if (C && (!accuser || !accused || !share || !randomness || !verdict)) return DKG_E_ARG;
+    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
+    const size_t N = t + 1;
+    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
+    h2d(ctx, EA, E, 32 * n * N);
+    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
+    complaints3_core(ctx, n, t, C, accuser, accused, share, randomness, EA, qualified, fetched3, verdict, nullptr);
+    if (reconstruct) {
+      const std::vector<uint8_t> p = proven_round4(n, C, accused, verdict);
+      memcpy(reconstruct, p.data(), n);
     }
+    return DKG_OK;
+  });
+}
+
+int dkg_ceremony_verify_fetched_proven(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                       const uint8_t* s, const uint8_t* s_prime, const uint8_t* fetched1,
+                                       const uint8_t* fetched3, size_t C4, const uint32_t* accuser4,
+                                       const uint32_t* accused4, const uint8_t* share4, const uint8_t* randomness4,
+                                       dkg_ceremony_out* out, int32_t* verdict4, int32_t* finalise_status,
+                                       int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !s || !s_prime || !fetched1 || !fetched3) return DKG_E_ARG;
+    if (C4 && (!accuser4 || !accused4 || !share4 || !randomness4 || !verdict4)) return DKG_E_ARG;
+    if (!complaint_indices_ok(n, C4, accuser4, accused4)) return DKG_E_ARG;
+    const size_t N = t + 1;
+    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
+    h2d(ctx, EA, E, 32 * n * N);
+    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
+    // the complaints first: their verdicts do not depend on the qualified set, only whether they count
+    std::vector<uint8_t> rowok(2 * n);
+    complaints3_core(ctx, n, t, C4, accuser4, accused4, share4, randomness4, EA, nullptr, fetched3, verdict4,
+                     rowok.data());
+    const std::vector<uint8_t> proven = proven_round4(n, C4, accused4, verdict4);
+    uint8_t* dp4 = buf<uint8_t>(ctx, "c3_proven", n);
+    h2d(ctx, dp4, proven.data(), n);
+    uint32_t* ds = upload_scalars(ctx, "cer_s", s, n * n);
+    uint32_t* dsp = upload_scalars(ctx, "cer_sp", s_prime, n * n);
+    uint8_t* f1 = buf<uint8_t>(ctx, "cer_f1", n);
+    uint8_t* f3 = buf<uint8_t>(ctx, "cer_f3", n);
+    h2d(ctx, f1, fetched1, n);
+    h2d(ctx, f3, fetched3, n);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    OutFlags fl(out, n);
+    receivers_rounds(ctx, n, t, EA, EA + 8 * n * N, ds, dsp, &fl.o, true, f1, f3, nullptr, dp4);
+    fl.o.ms_round1 = 0;
+    fl.o.ms_round2 = ev_ms(ctx, 1, 2);
+    fl.o.ms_round3 = ev_ms(ctx, 2, 3);
+    fl.o.ms_round4 = ev_ms(ctx, 3, 4);
+    fl.o.ms_finalise = ev_ms(ctx, 4, 5);
+    fl.o.ms_total = ev_ms(ctx, 0, 5);
+    std::vector<uint8_t> a_ok(n);
+    for (size_t i = 0; i < n; i++) a_ok[i] = fetched3[i] && rowok[n + i];
+    proven_outcome(n, t, C4, accused4, verdict4, a_ok.data(), &fl.o, finalise_status, recovery_index);
+    fl.finish(out);
+    return DKG_OK;
+  });
+}
+
+int dkg_ceremony_verify_full_proven(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                    const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, const uint8_t* pk,
+                                    size_t C, const uint32_t* accuser, const uint32_t* accused, const uint8_t* proofs,
+                                    const uint8_t* fetched3, size_t C4, const uint32_t* accuser4,
+                                    const uint32_t* accused4, const uint8_t* share4, const uint8_t* randomness4,
+                                    dkg_ceremony_out* out, int32_t* verdict, int32_t* dissent, int32_t* verdict4,
+                                    int32_t* finalise_status, int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
+    if (C && (!accuser || !accused || !proofs || !verdict)) return DKG_E_ARG;
+    if (C4 && (!accuser4 || !accused4 || !share4 || !randomness4 || !verdict4)) return DKG_E_ARG;
+    if (!complaint_indices_ok(n, C, accuser, accused) || !complaint_indices_ok(n, C4, accuser4, accused4))
+      return DKG_E_ARG;
+    const size_t N = t + 1;
+    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
+    h2d(ctx, EA, E, 32 * n * N);
+    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
+    // round-4 complaints, then round-2 complaints (as dkg_ceremony_verify_full_complaints), then the rounds
+    std::vector<uint8_t> rowok(2 * n);
+    complaints3_core(ctx, n, t, C4, accuser4, accused4, share4, randomness4, EA, nullptr, fetched3, verdict4,
+                     rowok.data());
+    const std::vector<uint8_t> proven = proven_round4(n, C4, accused4, verdict4);
+    uint8_t* dp4 = buf<uint8_t>(ctx, "c3_proven", n);
+    h2d(ctx, dp4, proven.data(), n);
+    uint8_t* f3 = nullptr;
+    if (fetched3) {
+      f3 = buf<uint8_t>(ctx, "cer_f3", n);
+      h2d(ctx, f3, fetched3, n);
+    }
+    std::vector<uint8_t> enc(128 * C);
+    for (size_t c = 0; c < C; c++) {
+      const size_t item = ((size_t)(accused[c] - 1) * n + (accuser[c] - 1)) * 2;
+      memcpy(&enc[128 * c], e1 + 32 * item, 32);
+      memcpy(&enc[128 * c + 32], ct + 32 * item, 32);
+      memcpy(&enc[128 * c + 64], e1 + 32 * (item + 1), 32);
+      memcpy(&enc[128 * c + 96], ct + 32 * (item + 1), 32);
+    }
+    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
+    h2d(ctx, dpk, pk, 32 * n);
+    complaints_verify_core(ctx, n, t, C, accuser, accused, dpk, EA, nullptr, enc.data(), proofs, verdict, nullptr);
+    std::vector<uint8_t> cmask(n, 1);
+    for (size_t c = 0; c < C; c++)
+      if (verdict[c] == 0) cmask[accused[c] - 1] = 0;
+    uint8_t* dcm = buf<uint8_t>(ctx, "cv_cmask", n);
+    h2d(ctx, dcm, cmask.data(), n);
+    sync(ctx);
+    OutFlags fl(out, n);
+    rc = ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, &fl.o, dcm, EA, f3, dp4);
+    if (rc) return rc;
+    std::vector<uint8_t> a_ok(n);
+    for (size_t i = 0; i < n; i++) a_ok[i] = (!fetched3 || fetched3[i]) && rowok[n + i];
+    proven_outcome(n, t, C4, accused4, verdict4, a_ok.data(), &fl.o, finalise_status, recovery_index);
+    fl.finish(out);
+    if (dissent) complaint_dissent(ctx, n, C, accuser, accused, verdict, dissent);
     return DKG_OK;
   });
 }

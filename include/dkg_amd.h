@@ -620,6 +620,68 @@ int dkg_ceremony_verify_full_complaints(dkg_ctx *ctx, size_t n, size_t t, const 
                                         const uint8_t *proofs, dkg_ceremony_out *out, int32_t *verdict,
                                         int32_t *dissent);
 
+/* ---- round-4 complaints as a device batch (complaints.hip) and the reconstructable set they prove ----
+ * In the reference a dealer enters reconstructable_set only in Phases<Phase4>::proceed
+ * (committee.rs:625-688), through a broadcast MisbehavingPartiesRound3 complaint (broadcast.rs:104-144)
+ * that VERIFIES, or whose accused published no phase-3 broadcast (:643).  Complaints against
+ * disqualified dealers are ignored (:639), complaints that fail verify() too (:654-658). */
+#define DKG_COMPLAINT_NO_PHASE3 5 /* the accused published no usable phase-3 broadcast: the complaint holds
+                                     without verification (committee.rs:643) */
+/* Phases<Phase4>::proceed's loop (committee.rs:636-670) over C broadcast complaints of ONE ceremony.
+ * accuser[c], accused[c]: 1-based, DKG_E_ARG outside 1..n.  share, randomness [C][32]: the accuser's
+ * decrypted pair as the complaint discloses it, read as dkg_complaint3_verify reads it (reduced mod
+ * l).  E, A [n][t+1][32] the phase-1 / phase-3 commitments.  qualified [n] (NULL = all 1): the
+ * round-2 qualified set.  fetched3 [n] (NULL = all 1): 0 = no phase-3 broadcast.
+ * verdict [C], in this order of precedence:
+ *   DKG_COMPLAINT_IGNORED (4)   qualified[accused] == 0 (:639);
+ *   DKG_COMPLAINT_NO_PHASE3 (5) fetched3[accused] == 0, or the accused's A row does not decode (it
+ *                               could not be deserialized: no broadcast) -- valid unverified (:643);
+ *   -1                          the accused's E row does not decode;
+ *   3 FalseClaimedEquality      g share + h randomness != sum_k j^k E_i[k] (broadcast.rs:129-130);
+ *   2 FalseClaimedInequality    g share == sum_k j^k A_i[k] (:131-132);
+ *   0                           a valid complaint.
+ * 0, 2, 3 and -1 are dkg_complaint3_verify's codes.  reconstruct [n] (may be NULL): 1 when some
+ * complaint against i has verdict 0 or 5 (:664-669); all zero for C == 0.  The evaluations follow
+ * dkg_ctx_set_complaint_eval; outputs do not depend on it.  Requires dkg_env_init (h). */
+int dkg_complaints3_verify(dkg_ctx *ctx, size_t n, size_t t, size_t C, const uint32_t *accuser,
+                           const uint32_t *accused, const uint8_t *share, const uint8_t *randomness,
+                           const uint8_t *E, const uint8_t *A, const uint8_t *qualified, const uint8_t *fetched3,
+                           int32_t *verdict, uint8_t *reconstruct);
+/* dkg_ceremony_verify_fetched with the reference's rule for the reconstructable set: round 2 keeps
+ * the rejection rule (plaintext shares carry no ciphertexts to prove a round-1 complaint against),
+ * the receivers' round-4 checks run as there (dec4, r4_error, the SKIPPED rows keep their meaning,
+ * committee.rs:515-569), but reconstruct[i] = qualified[i] and some of the C4 broadcast complaints
+ * (accuser4, accused4 1-based; share4, randomness4 [C4][32]) against i has verdict 0 or 5.
+ * phase4_error, the disclosing parties, the recovered secrets and mpk follow from that set.
+ * verdict4 [C4] as dkg_complaints3_verify with the ceremony's own qualified set.
+ * finalise_status, recovery_index (may be NULL): the common outcome of the finalising parties in the
+ * DKG_FIN_* codes -- OK; PHASE4_ERROR (phase4_error == 1); INSUFFICIENT with the first
+ * reconstructed dealer (0-based) when fewer than t final parties disclose (:779-781); and
+ * DKG_FIN_PANIC with recovery_index = i and mpk ALL ZERO when a qualified dealer i has no usable
+ * phase-3 broadcast (fetched3[i] == 0 or an undecodable A row), is not in reconstruct, and so was
+ * complained about by nobody: indexed_committed_shares[i] was never stored (:527-530) and every
+ * party's finalise hits the expect at :791-795.  Dealers are visited in index order and the first
+ * failure wins (:745-797).  The rejection-rule drivers cannot reach the PANIC state: there every
+ * receiver's own rejection of such a dealer reconstructs it. */
+int dkg_ceremony_verify_fetched_proven(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                       const uint8_t *s, const uint8_t *s_prime, const uint8_t *fetched1,
+                                       const uint8_t *fetched3, size_t C4, const uint32_t *accuser4,
+                                       const uint32_t *accused4, const uint8_t *share4, const uint8_t *randomness4,
+                                       dkg_ceremony_out *out, int32_t *verdict4, int32_t *finalise_status,
+                                       int32_t *recovery_index);
+/* dkg_ceremony_verify_full_complaints (qualified set by the proven round-1 complaints,
+ * committee.rs:370-398) whose reconstructable set follows the proven round-4 complaints as in
+ * dkg_ceremony_verify_fetched_proven (:625-688).  fetched3 [n] may be NULL (all present); the other
+ * added arguments as there. */
+int dkg_ceremony_verify_full_proven(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                    const uint8_t *e1, const uint8_t *ct, const uint8_t *sk, const uint8_t *pk,
+                                    size_t C, const uint32_t *accuser, const uint32_t *accused,
+                                    const uint8_t *proofs, const uint8_t *fetched3, size_t C4,
+                                    const uint32_t *accuser4, const uint32_t *accused4, const uint8_t *share4,
+                                    const uint8_t *randomness4, dkg_ceremony_out *out, int32_t *verdict,
+                                    int32_t *dissent, int32_t *verdict4, int32_t *finalise_status,
+                                    int32_t *recovery_index);
+
 /* ---- synthetic inputs: the seeded RNG convention ----
  * dealer seed = BLAKE2b-256("dkg-amd/v1/dealer" || master[32] || u32le ceremony || u32le dealer);
  * coefficients = ChaCha20Rng(seed): hiding b_0..b_t first, then sharing a_0..a_t (committee.rs:143-146),
