@@ -70,6 +70,11 @@ def split_multipliers(n: int, L: int, pieces: int):
              for u in range(pieces)] for j in range(n)]
 
 
+def _carray(ctype, count: int, values=()):
+    """A ctypes array of `count` entries (at least one, so that it is never a null pointer)."""
+    return (ctype * max(count, 1))(*values)
+
+
 @dataclass
 class CeremonyResult:
     n: int
@@ -275,7 +280,7 @@ class Backend:
 
     def poly_eval_batch(self, coeffs: bytes, D: int, N: int, xs: List[int]) -> bytes:
         M = len(xs)
-        arr = (ctypes.c_uint32 * max(M, 1))(*xs)
+        arr = _carray(ctypes.c_uint32, M, xs)
         out = ctypes.create_string_buffer(32 * max(D * M, 1))
         _check(self._ctx, _lib.lib().dkg_poly_eval_batch(self._ctx, D, N, coeffs, M, arr, out))
         return out.raw[: 32 * D * M]
@@ -343,40 +348,40 @@ class Backend:
                 setattr(r, k, bufs[k].raw)
         return r
 
+    def _ceremony_call(self, fn, n, t, args, tail=(), big=True, given=None):
+        """One ceremony entry point, fn(ctx, n, t, *args, out, *tail), as a CeremonyResult.  given: the
+        big fields that the caller supplied, {name: bytes}: null in the out struct, so not copied back,
+        and put on the result as they came."""
+        given = given or {}
+        o, bufs = self._ceremony_out(n, t, big)
+        for k in given:
+            setattr(o, k, None)
+        _check(self._ctx, fn(self._ctx, n, t, *args, ctypes.byref(o), *tail))
+        r = self._result(n, t, o, bufs, big)
+        for k, v in given.items():
+            setattr(r, k, v)
+        return r
+
     def ceremony(self, a: bytes, b: bytes, n: int, t: int) -> CeremonyResult:
-        o, bufs = self._ceremony_out(n, t, True)
-        _check(self._ctx, _lib.lib().dkg_ceremony_run(self._ctx, n, t, a, b, ctypes.byref(o)))
-        return self._result(n, t, o, bufs, True)
+        return self._ceremony_call(_lib.lib().dkg_ceremony_run, n, t, (a, b))
 
     def ceremony_verify(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, n: int, t: int) -> CeremonyResult:
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A", "s", "s_prime"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify(self._ctx, n, t, E, A, s, s_prime, ctypes.byref(o)))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A, r.s, r.s_prime = E, A, s, s_prime
-        return r
+        return self._ceremony_call(_lib.lib().dkg_ceremony_verify, n, t, (E, A, s, s_prime),
+                                   given={"E": E, "A": A, "s": s, "s_prime": s_prime})
 
     def ceremony_verify_fetched(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, fetched1: bytes,
                                 fetched3: bytes, n: int, t: int) -> CeremonyResult:
         """ceremony_verify after the broadcast intake (MembersFetchedState1/3::from_broadcast):
         fetched1[i] / fetched3[i] = 0 for a dealer whose phase-1 / phase-3 broadcast is absent or
         malformed (see dkg_amd.broadcast)."""
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A", "s", "s_prime"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify_fetched(self._ctx, n, t, E, A, s, s_prime, fetched1,
-                                                                 fetched3, ctypes.byref(o)))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A, r.s, r.s_prime = E, A, s, s_prime
-        return r
+        return self._ceremony_call(_lib.lib().dkg_ceremony_verify_fetched, n, t,
+                                   (E, A, s, s_prime, fetched1, fetched3),
+                                   given={"E": E, "A": A, "s": s, "s_prime": s_prime})
 
     def ceremony_device(self, d_a: int, d_b: int, n: int, t: int) -> CeremonyResult:
         """d_a, d_b: device pointers (e.g. torch tensor .data_ptr()) to [n][t+1][32] scalars."""
-        o, bufs = self._ceremony_out(n, t, False)
-        _check(self._ctx, _lib.lib().dkg_ceremony_run_device(self._ctx, n, t, ctypes.c_void_p(d_a),
-                                                              ctypes.c_void_p(d_b), ctypes.byref(o)))
-        return self._result(n, t, o, bufs, False)
+        vp = ctypes.c_void_p
+        return self._ceremony_call(_lib.lib().dkg_ceremony_run_device, n, t, (vp(d_a), vp(d_b)), big=False)
 
     # ---- full (encrypted-share) mode
     def member_keys(self, master: bytes, ceremony: int, n: int):
@@ -401,20 +406,13 @@ class Backend:
                                                                 ctypes.c_void_p(d_r)))
 
     def ceremony_full_device(self, d_a: int, d_b: int, d_r: int, sk: bytes, pk: bytes, n: int, t: int):
-        o, bufs = self._ceremony_out(n, t, False)
         vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_run_full_device(self._ctx, n, t, vp(d_a), vp(d_b), vp(d_r), sk, pk,
-                                                                   ctypes.byref(o)))
-        return self._result(n, t, o, bufs, False)
+        return self._ceremony_call(_lib.lib().dkg_ceremony_run_full_device, n, t, (vp(d_a), vp(d_b), vp(d_r), sk, pk),
+                                   big=False)
 
     def ceremony_verify_full(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, n: int, t: int):
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify_full(self._ctx, n, t, E, A, e1, ct, sk, ctypes.byref(o)))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A = E, A
-        return r
+        return self._ceremony_call(_lib.lib().dkg_ceremony_verify_full, n, t, (E, A, e1, ct, sk),
+                                   given={"E": E, "A": A})
 
     # ---- full mode for batches of ceremonies (key arrays [B][n][32], rows c*n + i = dealer i of ceremony c)
     def member_keys_batch(self, master: bytes, ceremony0: int, B: int, n: int):
@@ -463,15 +461,15 @@ class Backend:
 
     def complaint1_verify(self, t: int, accusers: List[int], pk: bytes, enc: bytes, E: bytes, proofs: bytes):
         B = len(accusers)
-        acc = (ctypes.c_uint32 * max(B, 1))(*accusers)
-        res = (ctypes.c_int32 * max(B, 1))()
+        acc = _carray(ctypes.c_uint32, B, accusers)
+        res = _carray(ctypes.c_int32, B)
         _check(self._ctx, _lib.lib().dkg_complaint1_verify(self._ctx, B, t, acc, pk, enc, E, proofs, res))
         return list(res)[:B]
 
     def complaint3_verify(self, t: int, accusers: List[int], share: bytes, randomness: bytes, E: bytes, A: bytes):
         B = len(accusers)
-        acc = (ctypes.c_uint32 * max(B, 1))(*accusers)
-        res = (ctypes.c_int32 * max(B, 1))()
+        acc = _carray(ctypes.c_uint32, B, accusers)
+        res = _carray(ctypes.c_int32, B)
         _check(self._ctx, _lib.lib().dkg_complaint3_verify(self._ctx, B, t, acc, share, randomness, E, A, res))
         return list(res)[:B]
 
@@ -494,9 +492,9 @@ class Backend:
         """compute_qualified_set over the broadcast complaints of one ceremony: (verdicts, qualified).
         accusers / accused 1-based; enc [C][128] = what the ACCUSED broadcast to the accuser."""
         C = len(accusers)
-        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
-        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
-        res = (ctypes.c_int32 * max(C, 1))()
+        acc = _carray(ctypes.c_uint32, C, accusers)
+        acd = _carray(ctypes.c_uint32, C, accused)
+        res = _carray(ctypes.c_int32, C)
         q = ctypes.create_string_buffer(max(n, 1))
         _check(self._ctx, _lib.lib().dkg_complaints_verify(self._ctx, n, t, C, acc, acd, pk, E, fetched1, enc, proofs,
                                                             res, q))
@@ -508,17 +506,11 @@ class Backend:
         """ceremony_verify_full with the reference's rule for the qualified set: a dealer is cleared only
         by a complaint that verifies.  Returns (CeremonyResult, verdicts, dissent)."""
         C = len(accusers)
-        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
-        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
-        res = (ctypes.c_int32 * max(C, 1))()
-        dis = (ctypes.c_int32 * max(n, 1))()
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify_full_complaints(
-            self._ctx, n, t, E, A, e1, ct, sk, pk, C, acc, acd, proofs, ctypes.byref(o), res, dis))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A = E, A
+        res, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, n)
+        r = self._ceremony_call(
+            _lib.lib().dkg_ceremony_verify_full_complaints, n, t,
+            (E, A, e1, ct, sk, pk, C, _carray(ctypes.c_uint32, C, accusers), _carray(ctypes.c_uint32, C, accused), proofs),
+            (res, dis), given={"E": E, "A": A})
         return r, list(res)[:C], list(dis)[:n]
 
     # ---- round-4 complaints as a device batch, and the reconstructable set they prove (committee.rs:625-688)
@@ -528,9 +520,9 @@ class Backend:
         """Phases<Phase4>::proceed's loop over the broadcast round-4 complaints of one ceremony:
         (verdicts, reconstruct).  accusers / accused 1-based; share / randomness [C][32] as disclosed."""
         C = len(accusers)
-        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
-        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
-        res = (ctypes.c_int32 * max(C, 1))()
+        acc = _carray(ctypes.c_uint32, C, accusers)
+        acd = _carray(ctypes.c_uint32, C, accused)
+        res = _carray(ctypes.c_int32, C)
         rec = ctypes.create_string_buffer(max(n, 1))
         _check(self._ctx, _lib.lib().dkg_complaints3_verify(
             self._ctx, n, t, C, acc, acd, share, randomness, E, A,
@@ -542,18 +534,13 @@ class Backend:
                                        share4: bytes, randomness4: bytes, n: int, t: int) -> ProvenResult:
         """ceremony_verify_fetched whose reconstruct follows the proven round-4 complaints."""
         C4 = len(accusers4)
-        acc = (ctypes.c_uint32 * max(C4, 1))(*accusers4)
-        acd = (ctypes.c_uint32 * max(C4, 1))(*accused4)
-        res = (ctypes.c_int32 * max(C4, 1))()
+        res = _carray(ctypes.c_int32, C4)
         st, ri = ctypes.c_int32(), ctypes.c_int32()
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A", "s", "s_prime"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify_fetched_proven(
-            self._ctx, n, t, E, A, s, s_prime, bytes(fetched1), bytes(fetched3), C4, acc, acd, share4, randomness4,
-            ctypes.byref(o), res, ctypes.byref(st), ctypes.byref(ri)))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A, r.s, r.s_prime = E, A, s, s_prime
+        r = self._ceremony_call(
+            _lib.lib().dkg_ceremony_verify_fetched_proven, n, t,
+            (E, A, s, s_prime, bytes(fetched1), bytes(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+             _carray(ctypes.c_uint32, C4, accused4), share4, randomness4),
+            (res, ctypes.byref(st), ctypes.byref(ri)), given={"E": E, "A": A, "s": s, "s_prime": s_prime})
         return ProvenResult(r, list(res)[:C4], st.value, ri.value)
 
     def ceremony_verify_full_proven(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, pk: bytes,
@@ -563,22 +550,14 @@ class Backend:
                                     fetched3: Optional[bytes] = None) -> ProvenResult:
         """ceremony_verify_full_complaints whose reconstruct follows the proven round-4 complaints."""
         C, C4 = len(accusers), len(accusers4)
-        acc = (ctypes.c_uint32 * max(C, 1))(*accusers)
-        acd = (ctypes.c_uint32 * max(C, 1))(*accused)
-        acc4 = (ctypes.c_uint32 * max(C4, 1))(*accusers4)
-        acd4 = (ctypes.c_uint32 * max(C4, 1))(*accused4)
-        res = (ctypes.c_int32 * max(C, 1))()
-        res4 = (ctypes.c_int32 * max(C4, 1))()
-        dis = (ctypes.c_int32 * max(n, 1))()
+        res, res4, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4), _carray(ctypes.c_int32, n)
         st, ri = ctypes.c_int32(), ctypes.c_int32()
-        o, bufs = self._ceremony_out(n, t, True)
-        for k in ("E", "A"):
-            setattr(o, k, None)
-        _check(self._ctx, _lib.lib().dkg_ceremony_verify_full_proven(
-            self._ctx, n, t, E, A, e1, ct, sk, pk, C, acc, acd, proofs, None if fetched3 is None else bytes(fetched3),
-            C4, acc4, acd4, share4, randomness4, ctypes.byref(o), res, dis, res4, ctypes.byref(st), ctypes.byref(ri)))
-        r = self._result(n, t, o, bufs, True)
-        r.E, r.A = E, A
+        r = self._ceremony_call(
+            _lib.lib().dkg_ceremony_verify_full_proven, n, t,
+            (E, A, e1, ct, sk, pk, C, _carray(ctypes.c_uint32, C, accusers), _carray(ctypes.c_uint32, C, accused), proofs,
+             None if fetched3 is None else bytes(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+             _carray(ctypes.c_uint32, C4, accused4), share4, randomness4),
+            (res, dis, res4, ctypes.byref(st), ctypes.byref(ri)), given={"E": E, "A": A})
         return ProvenResult(r, list(res4)[:C4], st.value, ri.value, list(res)[:C], list(dis)[:n])
 
     def dealer_coefficients_device(self, master: bytes, ceremony0: int, B: int, d0: int, D: int, t: int,
@@ -625,8 +604,8 @@ class Backend:
         """Phases<Phase5>::finalise as every party runs it (committee.rs:726-805), with optional
         per-party earlier failures and missing phase-5 disclosures (dkg_finalise_parties)."""
         mpk = ctypes.create_string_buffer(32 * max(n, 1))
-        st = (ctypes.c_int32 * max(n, 1))()
-        ri = (ctypes.c_int32 * max(n, 1))()
+        st = _carray(ctypes.c_int32, n)
+        ri = _carray(ctypes.c_int32, n)
         mask = lambda x: None if x is None else bytes(bytearray(x))  # noqa: E731
         _check(self._ctx, _lib.lib().dkg_finalise_parties(
             self._ctx, n, t, mask(qualified), mask(reconstruct), mask(r2_error), mask(r4_error), mask(disclosed),
@@ -644,7 +623,7 @@ class Backend:
         per-party outcomes as numpy arrays (uint8 / int32) instead of lists -- no per-element
         conversion on the multi-GPU driver's path."""
         q, r2e, rc, r4e = (ctypes.create_string_buffer(max(n, 1)) for _ in range(4))
-        c = (ctypes.c_int32 * max(n, 1))()
+        c = _carray(ctypes.c_int32, n)
         o = _lib.ShardOutcome(ctypes.cast(q, ctypes.c_void_p), ctypes.cast(c, ctypes.c_void_p),
                               ctypes.cast(r2e, ctypes.c_void_p), ctypes.cast(rc, ctypes.c_void_p),
                               ctypes.cast(r4e, ctypes.c_void_p), 0, 0)

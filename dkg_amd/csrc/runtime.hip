@@ -1238,9 +1238,24 @@ void round4_host(size_t V, const uint8_t* qualified, uint8_t* recon) {
 // round-4 half the reconstruction flags, and the master key is summed over the honest set (qualified,
 // not reconstructed: committee.rs:726-805) speculatively; the host then only zeroes it (Phase4 failure,
 // failed recovery) or, when a dealer is reconstructed, adds g * its recovered secret (a second trip).
-void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
-                           const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                           const uint8_t* e_ok, const uint8_t* a_ok, const uint8_t* cmask, const uint8_t* proven4) {
+// Per-dealer masks on the device ([n], null = absent).  e_ok / a_ok: the e_ok / a_ok of verify_rounds
+// (an intake mask, or the decode mask of the dealer's ciphertexts).  cmask: the qualified set follows
+// the PROVEN round-2 complaints (round2_device) instead of the receivers' own rejections.  proven4: the
+// reconstructable set follows the PROVEN round-4 complaints -- proven4[i] = some broadcast complaint
+// against i holds (Phases<Phase4>::proceed, committee.rs:636-670, run on the complaints by the
+// caller); a receiver's own rejection alone reconstructs nobody.
+struct RoundMasks {
+  const uint8_t *e_ok = nullptr, *a_ok = nullptr, *cmask = nullptr, *proven4 = nullptr;
+};
+// The parties' common outcome, as written to dkg_ceremony_out where the caller gave arrays.
+struct RoundsResult {
+  std::vector<uint8_t> qualified, reconstruct, r2_error, r4_error;
+  int32_t n_qualified = 0;
+  bool phase4_error = false;
+};
+RoundsResult receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
+                                   const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
+                                   const RoundMasks& m) {
   const size_t N = t + 1;
   uint8_t* dec2 = buf<uint8_t>(ctx, "dec2", n * n);
   uint8_t* dec4 = buf<uint8_t>(ctx, "dec4", n * n);
@@ -1252,7 +1267,7 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   // ---- rounds 2 and 4 (committee.rs:260-366, :508-580), fused or in protocol order (verify_rounds)
   auto round3 = [&] {
     wait_shares(ctx, ctx->stream);
-    round2_device(ctx, 1, n, dec2, qmask, rej2, cnt, cmask);
+    round2_device(ctx, 1, n, dec2, qmask, rej2, cnt, m.cmask);
     // ---- round 3 (committee.rs:433-476): final share s_j = sum_{i in Q} s_ij, public g s_j
     dkgk::sum_shares(n, n, s, qmask, fs, ctx->stream);
     // the public shares g s_j are an output only: computed on the side stream, off the path to
@@ -1265,7 +1280,7 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
     HCK(hipEventRecord(ctx->pub_done, ctx->side));
     HCK(hipEventRecord(ctx->ev[3], ctx->stream));
   };
-  verify_rounds(ctx, n, t, n, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, e_ok, a_ok, false);
+  verify_rounds(ctx, n, t, n, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, m.e_ok, m.a_ok, false);
   wait_shares(ctx, ctx->stream);
   ctx->shares_pending = false;
   // round-4 outcome on the device: a qualified dealer some receiver rejects is reconstructed
@@ -1274,11 +1289,9 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   uint8_t* rej4 = buf<uint8_t>(ctx, "o.rej4", n);
   uint8_t* r4d = buf<uint8_t>(ctx, "o.r4err", n);
   round4_device(ctx, 1, n, t, dec4, qmask, rej4, r4d);
-  // proven4 (device [n], may be null): the reconstructable set by PROVEN round-4 complaints instead --
-  // proven4[i] = some broadcast complaint against i holds (Phases<Phase4>::proceed, committee.rs:636-670,
-  // run on the complaints by the caller); a receiver's own rejection alone reconstructs nobody.  The
-  // qualified mask is applied below as for the rejections (:639).
-  const uint8_t* acc4 = proven4 ? proven4 : rej4;
+  // the proven complaints' mask stands in for the rejections; the qualified mask is applied below
+  // to either (:639)
+  const uint8_t* acc4 = m.proven4 ? m.proven4 : rej4;
   HCK(hipEventRecord(ctx->ev[4], ctx->stream));
   // ---- finalise (committee.rs:726-805): mpk = sum_{i in Q \ recon} A_i0 (+ sum_{recon} g * L_i(0))
   uint32_t* A0 = buf<uint32_t>(ctx, "A0ext", PTB * n);
@@ -1364,17 +1377,42 @@ void receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Eco
   if (out->reconstruct) memcpy(out->reconstruct, recon.data(), n);
   out->n_qualified = nq;
   out->phase4_error = phase4_error;  // committee.rs:673-677
+  return {std::move(qualified), std::move(recon), std::move(r2err), std::move(r4e), nq, phase4_error};
 }
 
 // receivers_rounds_once with the per-step binomial's dedicated additions, rerun with the complete
 // formula when they marked a group (with_binom_ded)
-void receivers_rounds(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
-                      const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
-                      const uint8_t* e_ok = nullptr, const uint8_t* a_ok = nullptr, const uint8_t* cmask = nullptr,
-                      const uint8_t* proven4 = nullptr) {
-  with_binom_ded(ctx, [&] {
-    receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, e_ok, a_ok, cmask, proven4);
-  });
+RoundsResult receivers_rounds(dkg_ctx* ctx, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
+                              const uint32_t* s, const uint32_t* sp, dkg_ceremony_out* out, bool copy_big,
+                              const RoundMasks& m = {}) {
+  RoundsResult r;
+  with_binom_ded(ctx, [&] { r = receivers_rounds_once(ctx, n, t, Ecomp, Acomp, s, sp, out, copy_big, m); });
+  return r;
+}
+
+// The commitments of one ceremony on the device, one array [2n][N][8]: the E rows, then the A rows
+// (E is also the whole array, as complaints3_core reads it).
+struct Commitments {
+  uint32_t *E, *A;
+};
+Commitments commitment_rows(dkg_ctx* ctx, size_t n, size_t N) {
+  uint32_t* EA = buf<uint32_t>(ctx, "cer_EA", 32 * 2 * n * N);
+  return {EA, EA + 8 * n * N};
+}
+Commitments upload_commitments(dkg_ctx* ctx, size_t n, size_t N, const uint8_t* E, const uint8_t* A) {
+  const Commitments c = commitment_rows(ctx, n, N);
+  h2d(ctx, c.E, E, 32 * n * N);
+  h2d(ctx, c.A, A, 32 * n * N);
+  return c;
+}
+
+void ceremony_times(dkg_ctx* ctx, dkg_ceremony_out* out, bool round1) {
+  out->ms_round1 = round1 ? ev_ms(ctx, 0, 1) : 0.0;
+  out->ms_round2 = ev_ms(ctx, 1, 2);
+  out->ms_round3 = ev_ms(ctx, 2, 3);
+  out->ms_round4 = ev_ms(ctx, 3, 4);
+  out->ms_finalise = ev_ms(ctx, 4, 5);
+  out->ms_total = ev_ms(ctx, 0, 5);
 }
 
 // Round 1 for D dealers on device: a, b canonical [D][N][8] -> Ecomp, Acomp [D][N][8], s, sp [D][n][8].
@@ -1905,6 +1943,452 @@ int need_env(dkg_ctx* ctx) {
   return DKG_OK;
 }
 
+// The argument prologue of the entry points that need the commitment key: the environment is set,
+// (t, n) are admissible and none of `required` is null.
+int ceremony_args(dkg_ctx* ctx, size_t n, size_t t, std::initializer_list<const void*> required) {
+  const int rc = need_env(ctx);
+  if (rc) return rc;
+  if (dkg_env_check(t, n) != DKG_OK) return DKG_E_ARG;
+  for (const void* p : required)
+    if (!p) return DKG_E_ARG;
+  return DKG_OK;
+}
+
+// ---- round-2 complaints as device batches (complaints.hip)
+// Does an accused dealer with `count` complaints get the difference tables of its row (every P_i(j),
+// verify_device without checks) instead of one Horner walk per complaint?  Both are one dependent
+// chain however many complaints there are (the walks of all complaints run side by side, and so do
+// the tables of all accused rows), so what decides is the chains' lengths, not the work:
+//   Horner: N steps of nb doublings, one addition per index bit some lane of the wave has set
+//           (about the bit length of `count` + 1 for a dealer accused by receivers 1..count), + 1;
+//   tables: N binomial steps and n stepping steps.
+// The per-step latencies are fitted to profiles/complaints_eval_ab.txt (n = 1024, t = 511: the tables
+// win at every count, 11.3-11.6 ms against 23.0-39.6 ms per call at 1-1,023 complaints; n = 1024, t = 3:
+// Horner wins at every count, 3.2-3.5 against 7.0-7.2 ms; n = 64 and 256 with t = (n-1)/2 in between).
+bool complaint_tables_pay(size_t n, size_t N, size_t count) {
+  if (N < 2) return false;  // a constant polynomial: P_i(j) = E_i0
+  int nb = 1, cb = 1;
+  while ((n >> nb) != 0) nb++;
+  while ((count >> cb) != 0) cb++;
+  const double horner_us = 3.6 * (double)N * (nb + std::min(nb, cb + 1) + 1);
+  const double tables_us = 13.0 * (double)N + 3.7 * (double)n;
+  return tables_us < horner_us;
+}
+
+// P_row(x) = sum_k x^k C_row[k] for C (row, index) items: per row, the difference tables of that row
+// or one Horner walk per item (ctx->complaint_eval; automatic: complaint_tables_pay by the row's item
+// count).  index / row (host) and dindex / drow (device) [C]: 1-based, index within 1..n, row within
+// 1..nrows; Cc [nrows][N][8] compressed and Cext (stride nrows * N) decoded commitments on the device.
+// An (row, index) pair listed again takes a further table row of its own, so that the table path
+// serves every item of a row it is chosen for.  Out: dridx [C] (bit 31: element of Rt, else of Rh),
+// Rh, Rt, scale as k_cv_check reads them.  Work is queued on ctx->stream; the staging vectors live
+// in `ev`, which the caller keeps until it has synchronised.
+struct ComplaintEvals {
+  std::vector<uint32_t> rows, hl, ridx;
+  const uint32_t *dridx = nullptr, *Rh = nullptr, *Rt = nullptr, *scale = nullptr;
+};
+void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, const uint32_t* index,
+                     const uint32_t* row, const uint32_t* dindex, const uint32_t* drow, const uint32_t* Cc,
+                     const uint32_t* Cext, ComplaintEvals& ev) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  std::vector<size_t> count(nrows, 0);
+  for (size_t c = 0; c < C; c++) count[row[c] - 1]++;
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;   // (row, index) -> occurrences so far
+  std::map<std::pair<uint32_t, uint32_t>, uint32_t> rowof;  // (row, occurrence) -> table row
+  std::vector<uint32_t>&rows = ev.rows, &hl = ev.hl, &ridx = ev.ridx;
+  ridx.resize(C);
+  for (size_t c = 0; c < C; c++) {
+    const uint32_t i = row[c], j = index[c];
+    const bool tables = N >= 2 && (ctx->complaint_eval == 2 ||
+                                   (ctx->complaint_eval == 0 && complaint_tables_pay(n, N, count[i - 1])));
+    if (!tables) {
+      hl.push_back((uint32_t)c);
+      ridx[c] = (uint32_t)c;
+      continue;
+    }
+    const uint32_t m = seen[{i, j}]++;
+    auto it = rowof.find({i, m});
+    if (it == rowof.end()) {
+      it = rowof.emplace(std::make_pair(i, m), (uint32_t)rows.size()).first;
+      rows.push_back(i);
+    }
+    if (((size_t)it->second + 1) * n >= ((size_t)1 << 31)) {
+      ctx->err = "complaints_verify: too many table rows";
+      throw Fail{DKG_E_ARG};
+    }
+    ridx[c] = 0x80000000u | (uint32_t)((size_t)it->second * n + (j - 1));
+  }
+  uint32_t* dridx = buf<uint32_t>(ctx, "cv_ridx", 4 * C);
+  h2d(ctx, dridx, ridx.data(), 4 * C);
+  uint32_t* Rh = buf<uint32_t>(ctx, "cv_Rh", PTB * C);
+  if (!hl.empty()) {
+    uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
+    h2d(ctx, dhl, hl.data(), 4 * hl.size());
+    int nb = 1;
+    while ((n >> nb) != 0) nb++;
+    dkgk::cmp_horner(hl.size(), dhl, dindex, drow, Cext, nrows * N, N, nb, Rh, st);
+  }
+  if (!rows.empty()) {
+    const size_t D = rows.size();
+    uint32_t* Trows = buf<uint32_t>(ctx, "cv_Trows", 32 * D * N);
+    for (size_t r = 0; r < D; r++)
+      HCK(hipMemcpyAsync(Trows + 8 * N * r, Cc + 8 * N * (size_t)(rows[r] - 1), 32 * N, hipMemcpyDeviceToDevice, st));
+    VerifySeg g{2, D, 0, Trows, nullptr, nullptr, nullptr};
+    verify_device(ctx, n, t, &g, 1, false, "cv");
+    ev.Rt = ctx->last_R;
+    ev.scale = ctx->last_scale;
+  }
+  ev.dridx = dridx;
+  ev.Rh = Rh;
+}
+
+// MisbehavingPartiesRound1::verify (broadcast.rs:50-99) for C complaints of one ceremony.  Device: dpk
+// [n][8] member keys, Ec [n][N][8] commitments; host: accuser / accused (1-based, validated by the
+// caller), fetched1 (may be null), enc [C][128], proofs [C][192].  verdict [C] on the host; rowok_host
+// (may be null) [n] = E row i decodes.  Ends synchronised.
+void complaints_verify_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser,
+                            const uint32_t* accused, const uint32_t* dpk, const uint32_t* Ec, const uint8_t* fetched1,
+                            const uint8_t* enc, const uint8_t* proofs, int32_t* verdict, uint8_t* rowok_host) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  // every row decoded once: the rows' validity for the qualified set, and the Horner walks' input
+  uint32_t* Eext = buf<uint32_t>(ctx, "cv_Eext", PTB * n * N);
+  uint8_t* epok = buf<uint8_t>(ctx, "cv_Epok", n * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "cv_rowok", n);
+  dkgk::decode_points(Ec, n * N, Eext, n * N, epok, st);
+  dkgk::dealer_ok(n, N, epok, rowok, st);
+  if (rowok_host) d2h(ctx, rowok_host, rowok, n);
+  if (!C) {
+    check_launch(ctx);
+    sync(ctx);
+    return;
+  }
+  uint32_t* dacc = buf<uint32_t>(ctx, "cv_accuser", 4 * C);
+  uint32_t* dacd = buf<uint32_t>(ctx, "cv_accused", 4 * C);
+  uint32_t* denc = buf<uint32_t>(ctx, "cv_enc", 128 * C);
+  uint32_t* dprf = buf<uint32_t>(ctx, "cv_proofs", 192 * C);
+  uint8_t* dfet = nullptr;
+  h2d(ctx, dacc, accuser, 4 * C);
+  h2d(ctx, dacd, accused, 4 * C);
+  h2d(ctx, denc, enc, 128 * C);
+  h2d(ctx, dprf, proofs, 192 * C);
+  if (fetched1) {
+    dfet = buf<uint8_t>(ctx, "cv_fetched", n);
+    h2d(ctx, dfet, fetched1, n);
+  }
+  // scalars, the points to decode, SymmetricKey::process of both ciphertexts
+  uint32_t* Pc = buf<uint32_t>(ctx, "cv_Pc", 32 * 5 * C);
+  uint32_t* rs = buf<uint32_t>(ctx, "cv_rs", 32 * 2 * C);
+  uint32_t* nc = buf<uint32_t>(ctx, "cv_nc", 32 * 2 * C);
+  uint32_t* p12 = buf<uint32_t>(ctx, "cv_p12", 32 * 2 * C);
+  uint32_t* bp1 = buf<uint32_t>(ctx, "cv_bp1", 4 * 2 * C);
+  uint32_t* bp2 = buf<uint32_t>(ctx, "cv_bp2", 4 * 2 * C);
+  uint32_t* bq2 = buf<uint32_t>(ctx, "cv_bq2", 4 * 2 * C);
+  dkgk::cv_prep(C, dacc, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
+  uint32_t* Pext = buf<uint32_t>(ctx, "cv_Pext", PTB * 5 * C);
+  uint8_t* ppok = buf<uint8_t>(ctx, "cv_Ppok", 5 * C);
+  dkgk::decode_points(Pc, 5 * C, Pext, 5 * C, ppok, st);
+  // announcements (dl_equality/zkp.rs:60-63): a1 = g r - pk c (comb + one-base walk), a2 = e1 r - K c (Straus)
+  uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(2 * C));
+  uint32_t* S1 = buf<uint32_t>(ctx, "cv_S1", PTB * 2 * C);
+  uint32_t* S2 = buf<uint32_t>(ctx, "cv_S2", PTB * 2 * C);
+  uint32_t* G = buf<uint32_t>(ctx, "cv_G", PTB * 2 * C);
+  dkgk::cmp_ladder(2 * C, false, bp1, nullptr, nc, nullptr, Pext, 5 * C, T, S1, st);
+  dkgk::cmp_ladder(2 * C, true, bp2, bq2, rs, nc, Pext, 5 * C, T, S2, st);
+  dkgk::fixed_base(2 * C, rs, ctx->tab_gw, G, st);
+  dkgk::add_points(2 * C, S1, G, 2 * C, S1, st);
+  uint32_t* a1c = buf<uint32_t>(ctx, "cv_a1c", 32 * 2 * C);
+  uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
+  dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
+  dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
+  // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint
+  ComplaintEvals ev;
+  complaint_evals(ctx, n, t, n, C, accuser, accused, dacc, dacd, Ec, Eext, ev);
+  const uint32_t *dridx = ev.dridx, *Rh = ev.Rh, *Rt = ev.Rt, *scale = ev.scale;
+  uint8_t* eq = buf<uint8_t>(ctx, "cv_eq", 2 * C);
+  dkgk::cv_check(C, dacc, p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+  int32_t* dver = buf<int32_t>(ctx, "cv_verdict", 4 * C);
+  dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, a1c, a2c, ppok, rowok, dfet, eq, dver, st);
+  check_launch(ctx);
+  d2h(ctx, verdict, dver, 4 * C);
+  sync(ctx);  // the staging vectors (ev) live until here
+}
+
+// C complaints' arguments: with C > 0 the index arrays and `payload` (what the complaints carry, and
+// where their verdicts go) are present, and the 1-based party indices lie within 1..n
+bool complaint_args_ok(size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                       std::initializer_list<const void*> payload) {
+  if (!C) return true;
+  if (!accuser || !accused) return false;
+  for (const void* p : payload)
+    if (!p) return false;
+  for (size_t c = 0; c < C; c++)
+    if (accuser[c] < 1 || accuser[c] > n || accused[c] < 1 || accused[c] > n) return false;
+  return true;
+}
+
+// dissent[j] = the dealers receiver j rejected in the ceremony just run (dec2 on the device) without a
+// proven complaint of its own against them among the C
+void complaint_dissent(dkg_ctx* ctx, size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                       const int32_t* verdict, int32_t* dissent) {
+  std::vector<uint8_t> d2(n * n);
+  d2h(ctx, d2.data(), buf<uint8_t>(ctx, "dec2", n * n), n * n);
+  sync(ctx);
+  std::vector<uint8_t> proven(n * n, 0);  // [accused][accuser]
+  for (size_t c = 0; c < C; c++)
+    if (verdict[c] == 0) proven[(size_t)(accused[c] - 1) * n + (accuser[c] - 1)] = 1;
+  for (size_t j = 0; j < n; j++) {
+    int32_t v = 0;
+    for (size_t i = 0; i < n; i++) v += d2[i * n + j] == DKG_REJECT && !proven[i * n + j];
+    dissent[j] = v;
+  }
+}
+
+// ---- round-4 complaints as a device batch (complaints.hip, k_c3_*)
+// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) as Phases<Phase4>::proceed applies it
+// (committee.rs:636-670) for C complaints of one ceremony.  Device: EA [2n][N][8], the E rows then the A
+// rows; host: accuser / accused (1-based, validated by the caller), share / randomness [C][32],
+// qualified / fetched3 [n] (may be null = all 1).  verdict [C] on the host; rowok_host (may be null)
+// [2n] = the row decodes.  Ends synchronised.
+void complaints3_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
+                      const uint8_t* share, const uint8_t* randomness, const uint32_t* EA, const uint8_t* qualified,
+                      const uint8_t* fetched3, int32_t* verdict, uint8_t* rowok_host) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  // both rows of every dealer decoded once: the rows' validity, and the Horner walks' input
+  uint32_t* EAext = buf<uint32_t>(ctx, "c3_EAext", PTB * 2 * n * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "c3_pok", 2 * n * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "c3_rowok", 2 * n);
+  dkgk::decode_points(EA, 2 * n * N, EAext, 2 * n * N, pok, st);
+  dkgk::dealer_ok(2 * n, N, pok, rowok, st);
+  if (rowok_host) d2h(ctx, rowok_host, rowok, 2 * n);
+  if (!C) {
+    check_launch(ctx);
+    sync(ctx);
+    return;
+  }
+  uint32_t* dacc = buf<uint32_t>(ctx, "c3_accuser", 4 * C);
+  uint32_t* dacd = buf<uint32_t>(ctx, "c3_accused", 4 * C);
+  uint32_t* dsh = buf<uint32_t>(ctx, "c3_share", 32 * C);
+  uint32_t* drn = buf<uint32_t>(ctx, "c3_rand", 32 * C);
+  h2d(ctx, dacc, accuser, 4 * C);
+  h2d(ctx, dacd, accused, 4 * C);
+  h2d(ctx, dsh, share, 32 * C);
+  h2d(ctx, drn, randomness, 32 * C);
+  uint8_t *dq = nullptr, *df3 = nullptr;
+  if (qualified) {
+    dq = buf<uint8_t>(ctx, "c3_qualified", n);
+    h2d(ctx, dq, qualified, n);
+  }
+  if (fetched3) {
+    df3 = buf<uint8_t>(ctx, "c3_fetched3", n);
+    h2d(ctx, df3, fetched3, n);
+  }
+  uint32_t* sr = buf<uint32_t>(ctx, "c3_sr", 32 * 2 * C);
+  uint32_t* acc2 = buf<uint32_t>(ctx, "c3_acc2", 4 * 2 * C);
+  uint32_t* acd2 = buf<uint32_t>(ctx, "c3_acd2", 4 * 2 * C);
+  dkgk::c3_prep(C, n, dacc, dacd, dsh, drn, sr, acc2, acd2, st);
+  // P^E_i(j), P^A_i(j): items 2c, 2c + 1 on rows i, n + i.  Both rows of a dealer carry the same item
+  // count, so the automatic switch sends them the same way
+  std::vector<uint32_t> index(2 * C), row(2 * C);
+  for (size_t c = 0; c < C; c++) {
+    index[2 * c] = index[2 * c + 1] = accuser[c];
+    row[2 * c] = accused[c];
+    row[2 * c + 1] = (uint32_t)n + accused[c];
+  }
+  ComplaintEvals ev;
+  complaint_evals(ctx, n, t, 2 * n, 2 * C, index.data(), row.data(), acc2, acd2, EA, EAext, ev);
+  uint8_t* eq = buf<uint8_t>(ctx, "c3_eq", 2 * C);
+  dkgk::c3_check(C, dacc, sr, ev.dridx, ev.Rh, ev.Rt, ev.scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+  int32_t* dver = buf<int32_t>(ctx, "c3_verdict", 4 * C);
+  dkgk::c3_final(C, n, dacd, rowok, dq, df3, eq, dver, st);
+  check_launch(ctx);
+  d2h(ctx, verdict, dver, 4 * C);
+  sync(ctx);  // the staging vectors (ev) live until here
+}
+
+// proven[i] = some complaint against i holds: verdict 0, or the accused has no phase-3 broadcast
+// (committee.rs:643, :664-669)
+std::vector<uint8_t> proven_round4(size_t n, size_t C, const uint32_t* accused, const int32_t* verdict) {
+  std::vector<uint8_t> p(n, 0);
+  for (size_t c = 0; c < C; c++)
+    if (verdict[c] == 0 || verdict[c] == DKG_COMPLAINT_NO_PHASE3) p[accused[c] - 1] = 1;
+  return p;
+}
+
+// The broadcast complaints of a ceremony to verify, as the host arrays of the C ABI (with C = 0 the
+// arrays may be null).  Round 2 (dkg_complaints_verify, on the ceremony's own ciphertexts): pk the
+// members' keys; verdict [C] out, dissent [n] out (may be null).  Round 4 (dkg_complaints3_verify):
+// verdict [C] out, finalise_status / recovery_index out (may be null).
+struct Complaints2 {
+  const uint8_t* pk;
+  size_t C;
+  const uint32_t *accuser, *accused;
+  const uint8_t* proofs;
+  int32_t *verdict, *dissent;
+};
+struct Complaints4 {
+  size_t C;
+  const uint32_t *accuser, *accused;
+  const uint8_t *share, *randomness;
+  int32_t *verdict, *finalise_status, *recovery_index;
+};
+
+// What follows a ceremony that took `reconstruct` from the proven round-4 complaints: the verdicts
+// against dealers that round 2 disqualified become IGNORED (committee.rs:639), and the finalising
+// parties' common outcome.  a_ok[i] = dealer i has a usable phase-3 broadcast.  A qualified dealer
+// without one that nobody complained about is in no set: every party's finalise reaches the expect
+// at committee.rs:791-795 with indexed_committed_shares[i] never stored (:527-530).  Dealers are
+// visited in index order and the first failure wins (:745-797); mpk is zeroed on a panic.
+void proven_outcome(size_t n, size_t t, const Complaints4& c4, const uint8_t* a_ok, const RoundsResult& r,
+                    uint8_t* mpk) {
+  const uint8_t *qualified = r.qualified.data(), *recon = r.reconstruct.data();
+  for (size_t c = 0; c < c4.C; c++)
+    if (!qualified[c4.accused[c] - 1]) c4.verdict[c] = DKG_COMPLAINT_IGNORED;
+  int32_t status = DKG_FIN_OK, index = -1;
+  if (r.phase4_error) {
+    status = DKG_FIN_PHASE4_ERROR;
+  } else {
+    const bool insufficient =
+        recovery_fails(disclosing_parties(n, qualified, recon, r.r2_error.data(), r.r4_error.data()), t);
+    for (size_t i = 0; i < n && status == DKG_FIN_OK; i++) {
+      if (recon[i] && insufficient) status = DKG_FIN_INSUFFICIENT;
+      else if (!recon[i] && qualified[i] && !a_ok[i]) status = DKG_FIN_PANIC;
+      if (status != DKG_FIN_OK) index = (int32_t)i;
+    }
+  }
+  if (status == DKG_FIN_PANIC) memset(mpk, 0, 32);
+  if (c4.finalise_status) *c4.finalise_status = status;
+  if (c4.recovery_index) *c4.recovery_index = index;
+}
+
+// One ceremony to verify, as the host pointers of the C ABI (null = absent).  The shares come either
+// in plaintext (s, s_prime) or encrypted with the members' keys (e1, ct, sk: full mode).  c2 / c4
+// decide whether a round's outcome follows the PROVEN complaints instead of the receivers' own
+// rejections -- their presence does, not C > 0: no complaints under the proven rule disqualify nobody.
+struct CeremonyInput {
+  const uint8_t *E = nullptr, *A = nullptr;                         // required
+  const uint8_t *s = nullptr, *s_prime = nullptr;                   // plaintext shares, or
+  const uint8_t *e1 = nullptr, *ct = nullptr, *sk = nullptr;        //   encrypted shares and the members' keys
+  const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;           // intake masks
+  const Complaints2* c2 = nullptr;
+  const Complaints4* c4 = nullptr;
+};
+
+// Rounds 2-5 of a ceremony from its broadcast values: every dkg_ceremony_verify* entry point.  The
+// commitments go to the device once, for both complaint cores and the rounds; the complaints are
+// verified before the timed region (ev[0]), which covers the decryption and the rounds as ms_* report.
+int verify_ceremony(dkg_ctx* ctx, size_t n, size_t t, const CeremonyInput& in, dkg_ceremony_out* out) {
+  const size_t N = t + 1, items = 2 * n * n;
+  const bool full = in.e1 != nullptr;
+  const Commitments cm = upload_commitments(ctx, n, N, in.E, in.A);
+  RoundMasks m;
+  // the round-4 complaints first: their verdicts do not depend on the qualified set, only whether
+  // they count (proven_outcome).  a_ok[i] = dealer i has a usable phase-3 broadcast
+  std::vector<uint8_t> proven, a_ok(n);
+  if (in.c4) {
+    const Complaints4& c = *in.c4;
+    std::vector<uint8_t> rowok(2 * n);
+    complaints3_core(ctx, n, t, c.C, c.accuser, c.accused, c.share, c.randomness, cm.E, nullptr, in.fetched3,
+                     c.verdict, rowok.data());
+    proven = proven_round4(n, c.C, c.accused, c.verdict);
+    uint8_t* dp4 = buf<uint8_t>(ctx, "c3_proven", n);
+    h2d(ctx, dp4, proven.data(), n);
+    m.proven4 = dp4;
+    for (size_t i = 0; i < n; i++) a_ok[i] = (!in.fetched3 || in.fetched3[i]) && rowok[n + i];
+  }
+  if (in.fetched1) {
+    uint8_t* f1 = buf<uint8_t>(ctx, "cer_f1", n);
+    h2d(ctx, f1, in.fetched1, n);
+    m.e_ok = f1;
+  }
+  if (in.fetched3) {
+    uint8_t* f3 = buf<uint8_t>(ctx, "cer_f3", n);
+    h2d(ctx, f3, in.fetched3, n);
+    m.a_ok = f3;
+  }
+  std::vector<uint8_t> enc, cmask;
+  if (in.c2) {
+    const Complaints2& c = *in.c2;
+    // the complaints against this ceremony's own broadcasts: the pair the accused sent the accuser
+    // (broadcast.rs:57), items (i, q, w) at (i n + q) 2 + w, w = 0 the randomness
+    enc.resize(128 * c.C);
+    for (size_t k = 0; k < c.C; k++) {
+      const size_t item = ((size_t)(c.accused[k] - 1) * n + (c.accuser[k] - 1)) * 2;
+      const uint8_t* part[4] = {in.e1 + 32 * item, in.ct + 32 * item, in.e1 + 32 * (item + 1),
+                                in.ct + 32 * (item + 1)};
+      for (size_t p = 0; p < 4; p++) memcpy(&enc[128 * k + 32 * p], part[p], 32);
+    }
+    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
+    h2d(ctx, dpk, c.pk, 32 * n);
+    complaints_verify_core(ctx, n, t, c.C, c.accuser, c.accused, dpk, cm.E, nullptr, enc.data(), c.proofs, c.verdict,
+                           nullptr);
+    cmask.assign(n, 1);  // the dealers without a proven complaint (committee.rs:381-394: cleared only on Ok)
+    for (size_t k = 0; k < c.C; k++)
+      if (c.verdict[k] == 0) cmask[c.accused[k] - 1] = 0;
+    uint8_t* dcm = buf<uint8_t>(ctx, "cv_cmask", n);
+    h2d(ctx, dcm, cmask.data(), n);
+    m.cmask = dcm;
+    sync(ctx);
+  }
+  const uint32_t *ds = nullptr, *dsp = nullptr, *dsk = nullptr;
+  uint32_t *de1 = nullptr, *dct = nullptr;
+  if (full) {
+    dsk = upload_scalars(ctx, "fm_sk", in.sk, n);
+    de1 = buf<uint32_t>(ctx, "fm_e1", 32 * items);
+    dct = buf<uint32_t>(ctx, "fm_ct", 32 * items);
+    h2d(ctx, de1, in.e1, 32 * items);
+    h2d(ctx, dct, in.ct, 32 * items);
+  } else {
+    ds = upload_scalars(ctx, "cer_s", in.s, n * n);
+    dsp = upload_scalars(ctx, "cer_sp", in.s_prime, n * n);
+  }
+  HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+  if (full) {
+    uint32_t* rs = buf<uint32_t>(ctx, "fm_s", 32 * n * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "fm_sp", 32 * n * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "fm_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "fm_eok", n);
+    // the decryption on the side stream beside the check pipeline, as in dkg_ceremony_run_full_device
+    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
+    if (side) {
+      HCK(hipEventRecord(ctx->side_fork, ctx->stream));
+      HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+    }
+    decrypt_device(ctx, n, n, dsk, de1, dct, rs, rsp, iok, eok, side ? ctx->side : ctx->stream);
+    if (side) {
+      HCK(hipEventRecord(ctx->shares_done, ctx->side));
+      ctx->shares_pending = true;
+    }
+    ds = rs, dsp = rsp;
+    m.e_ok = eok;  // the decode mask of the dealer's ciphertexts
+  }
+  const RoundsResult r = receivers_rounds(ctx, n, t, cm.E, cm.A, ds, dsp, out, true, m);  // waits for the shares
+  if (full) {
+    collect_hybrid_phases(ctx);  // decryption phases only (no encryption here: full.enc_* read -1)
+    if (out->s) d2h(ctx, out->s, ds, 32 * n * n);
+    if (out->s_prime) d2h(ctx, out->s_prime, dsp, 32 * n * n);
+    sync(ctx);
+  }
+  ceremony_times(ctx, out, false);
+  if (in.c4) proven_outcome(n, t, *in.c4, a_ok.data(), r, out->mpk);
+  if (in.c2 && in.c2->dissent)
+    complaint_dissent(ctx, n, in.c2->C, in.c2->accuser, in.c2->accused, in.c2->verdict, in.c2->dissent);
+  return DKG_OK;
+}
+
+// DKG_E_DECODE when a recipient key of the last encrypt_batch_device did not decode (after a sync)
+int batch_keys_status(dkg_ctx* ctx, const uint8_t* ok, size_t V) {
+  for (size_t k = 0; k < V; k++)
+    if (!ok[k]) {
+      ctx->err = "encrypt_shares_batch: a recipient public key does not decode";
+      return DKG_E_DECODE;
+    }
+  return DKG_OK;
+}
+
 }  // namespace
 
 // dkg_ctx_clock_probe: a dependent integer chain per lane between two reads of each clock; lane 0
@@ -2394,61 +2878,47 @@ int dkg_verify_receiver(dkg_ctx* ctx, size_t n, size_t t, int round, size_t j, c
 int dkg_ceremony_run_device(dkg_ctx* ctx, size_t n, size_t t, const void* d_a, const void* d_b,
                             dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out) return DKG_E_ARG;
     const size_t N = t + 1;
     HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
+    const Commitments cm = commitment_rows(ctx, n, N);
     uint32_t* ds = buf<uint32_t>(ctx, "cer_s", 32 * n * n);
     uint32_t* dsp = buf<uint32_t>(ctx, "cer_sp", 32 * n * n);
 #ifdef DKG_NO_R1_OVERLAP
-    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false);
+    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, cm.E, cm.A, ds, dsp, false);
 #else
     // with one stream (the bench's serialised roofline pass) the phases stay back to back
-    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false, ctx->nsub > 1);
+    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, cm.E, cm.A, ds, dsp, false, ctx->nsub > 1);
 #endif
     HCK(hipEventRecord(ctx->ev[1], ctx->stream));
     ExtScope ext(ctx, n, N);
-    receivers_rounds(ctx, n, t, Ec, Ac, ds, dsp, out, false);  // small outputs only
-    out->ms_round1 = ev_ms(ctx, 0, 1);
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
+    receivers_rounds(ctx, n, t, cm.E, cm.A, ds, dsp, out, false);  // small outputs only
+    ceremony_times(ctx, out, true);
     return DKG_OK;
   });
 }
 
 int dkg_ceremony_run(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* a, const uint8_t* b, dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out) return DKG_E_ARG;
     const size_t N = t + 1;
     uint32_t* da = upload_scalars(ctx, "cer_a", a, n * N);
     uint32_t* db = upload_scalars(ctx, "cer_b", b, n * N);
     HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
+    const Commitments cm = commitment_rows(ctx, n, N);
     uint32_t* ds = buf<uint32_t>(ctx, "cer_s", 32 * n * n);
     uint32_t* dsp = buf<uint32_t>(ctx, "cer_sp", 32 * n * n);
-    round1_device(ctx, n, n, t, da, db, Ec, Ac, ds, dsp);
+    round1_device(ctx, n, n, t, da, db, cm.E, cm.A, ds, dsp);
     HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    if (out->E) d2h(ctx, out->E, Ec, 32 * n * N);
-    if (out->A) d2h(ctx, out->A, Ac, 32 * n * N);
+    if (out->E) d2h(ctx, out->E, cm.E, 32 * n * N);
+    if (out->A) d2h(ctx, out->A, cm.A, 32 * n * N);
     if (out->s) d2h(ctx, out->s, ds, 32 * n * n);
     if (out->s_prime) d2h(ctx, out->s_prime, dsp, 32 * n * n);
     ExtScope ext(ctx, n, N);
-    receivers_rounds(ctx, n, t, Ec, Ac, ds, dsp, out, true);
-    out->ms_round1 = ev_ms(ctx, 0, 1);
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
+    receivers_rounds(ctx, n, t, cm.E, cm.A, ds, dsp, out, true);
+    ceremony_times(ctx, out, true);
     return DKG_OK;
   });
 }
@@ -2456,26 +2926,11 @@ int dkg_ceremony_run(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* a, const u
 int dkg_ceremony_verify(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* s,
                         const uint8_t* s_prime, dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, s, s_prime});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out) return DKG_E_ARG;
-    const size_t N = t + 1;
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
-    h2d(ctx, Ec, E, 32 * n * N);
-    h2d(ctx, Ac, A, 32 * n * N);
-    uint32_t* ds = upload_scalars(ctx, "cer_s", s, n * n);
-    uint32_t* dsp = upload_scalars(ctx, "cer_sp", s_prime, n * n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    receivers_rounds(ctx, n, t, Ec, Ac, ds, dsp, out, true);
-    out->ms_round1 = 0;
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
-    return DKG_OK;
+    CeremonyInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -2483,30 +2938,11 @@ int dkg_ceremony_verify_fetched(dkg_ctx* ctx, size_t n, size_t t, const uint8_t*
                                 const uint8_t* s, const uint8_t* s_prime, const uint8_t* fetched1,
                                 const uint8_t* fetched3, dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, s, s_prime, fetched1, fetched3});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !fetched1 || !fetched3) return DKG_E_ARG;
-    const size_t N = t + 1;
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
-    h2d(ctx, Ec, E, 32 * n * N);
-    h2d(ctx, Ac, A, 32 * n * N);
-    uint32_t* ds = upload_scalars(ctx, "cer_s", s, n * n);
-    uint32_t* dsp = upload_scalars(ctx, "cer_sp", s_prime, n * n);
-    uint8_t* f1 = buf<uint8_t>(ctx, "cer_f1", n);
-    uint8_t* f3 = buf<uint8_t>(ctx, "cer_f3", n);
-    h2d(ctx, f1, fetched1, n);
-    h2d(ctx, f3, fetched3, n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    receivers_rounds(ctx, n, t, Ec, Ac, ds, dsp, out, true, f1, f3);
-    out->ms_round1 = 0;
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
-    return DKG_OK;
+    CeremonyInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime, in.fetched1 = fetched1, in.fetched3 = fetched3;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -3226,16 +3662,14 @@ int dkg_decrypt_shares(dkg_ctx* ctx, size_t D, size_t n, const uint8_t* sk, cons
 int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d_a, const void* d_b, const void* d_r,
                                  const uint8_t* sk, const uint8_t* pk, dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, sk, pk, d_r});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !sk || !pk || !d_r) return DKG_E_ARG;
     const size_t N = t + 1, items = 2 * n * n;
     uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
     uint32_t* dpk = buf<uint32_t>(ctx, "fm_pk", 32 * n);
     h2d(ctx, dpk, pk, 32 * n);
     HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* Ec = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
+    const Commitments cm = commitment_rows(ctx, n, N);
     uint32_t* ds = buf<uint32_t>(ctx, "cer_s", 32 * n * n);
     uint32_t* dsp = buf<uint32_t>(ctx, "cer_sp", 32 * n * n);
     // With chunk streams (not the serialised roofline pass) the share evaluation, the encryption and
@@ -3245,7 +3679,7 @@ int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d
     // decrypted shares (wait_shares); the decode mask of the ciphertexts joins the dealer mask there.
     const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
     hipStream_t hy = side ? ctx->side : ctx->stream;
-    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false, side);
+    round1_device(ctx, n, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, cm.E, cm.A, ds, dsp, false, side);
     uint32_t* e1 = buf<uint32_t>(ctx, "fm_e1", 32 * items);
     uint32_t* ct = buf<uint32_t>(ctx, "fm_ct", 32 * items);
     encrypt_device(ctx, n, n, dpk, ds, dsp, (const uint32_t*)d_r, e1, ct, hy, pk);  // committee.rs:169-172
@@ -3260,393 +3694,23 @@ int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d
       ctx->shares_pending = true;
     }
     ExtScope ext(ctx, n, N);
-    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, false, eok);
+    RoundMasks m;
+    m.e_ok = eok;
+    receivers_rounds(ctx, n, t, cm.E, cm.A, rs, rsp, out, false, m);
     collect_hybrid_phases(ctx);
-    out->ms_round1 = ev_ms(ctx, 0, 1);
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
+    ceremony_times(ctx, out, true);
     return DKG_OK;
   });
 }
 
-}  // extern "C"
-
-namespace {
-
-// dkg_ceremony_verify_full's body.  cmask (device [n], may be null): the qualified set follows the
-// proven complaints (round2_device) instead of the receivers' own rejections.  EA (device [2n][N][8], may
-// be null): the commitments are on the device already, E rows then A rows.  a_ok, proven4 (device [n],
-// may be null): as receivers_rounds_once.
-int ceremony_verify_full_impl(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
-                              const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out, const uint8_t* cmask,
-                              const uint32_t* EA = nullptr, const uint8_t* a_ok = nullptr,
-                              const uint8_t* proven4 = nullptr) {
-  {
-    const size_t N = t + 1, items = 2 * n * n;
-    const uint32_t *Ec, *Ac;
-    if (EA) {
-      Ec = EA, Ac = EA + 8 * n * N;
-    } else {
-      uint32_t* e = buf<uint32_t>(ctx, "cer_E", 32 * n * N);
-      uint32_t* a = buf<uint32_t>(ctx, "cer_A", 32 * n * N);
-      h2d(ctx, e, E, 32 * n * N);
-      h2d(ctx, a, A, 32 * n * N);
-      Ec = e, Ac = a;
-    }
-    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
-    uint32_t* de1 = buf<uint32_t>(ctx, "fm_e1", 32 * items);
-    uint32_t* dct = buf<uint32_t>(ctx, "fm_ct", 32 * items);
-    h2d(ctx, de1, e1, 32 * items);
-    h2d(ctx, dct, ct, 32 * items);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    uint32_t* rs = buf<uint32_t>(ctx, "fm_s", 32 * n * n);
-    uint32_t* rsp = buf<uint32_t>(ctx, "fm_sp", 32 * n * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "fm_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "fm_eok", n);
-    // the decryption on the side stream beside the check pipeline, as in dkg_ceremony_run_full_device
-    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
-    if (side) {
-      HCK(hipEventRecord(ctx->side_fork, ctx->stream));
-      HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
-    }
-    decrypt_device(ctx, n, n, dsk, de1, dct, rs, rsp, iok, eok, side ? ctx->side : ctx->stream);
-    if (side) {
-      HCK(hipEventRecord(ctx->shares_done, ctx->side));
-      ctx->shares_pending = true;
-    }
-    receivers_rounds(ctx, n, t, Ec, Ac, rs, rsp, out, true, eok, a_ok, cmask, proven4);  // waits for the shares before it returns
-    collect_hybrid_phases(ctx);  // decryption phases only (no encryption here: full.enc_* read -1)
-    if (out->s) d2h(ctx, out->s, rs, 32 * n * n);
-    if (out->s_prime) d2h(ctx, out->s_prime, rsp, 32 * n * n);
-    sync(ctx);
-    out->ms_round1 = 0;
-    out->ms_round2 = ev_ms(ctx, 1, 2);
-    out->ms_round3 = ev_ms(ctx, 2, 3);
-    out->ms_round4 = ev_ms(ctx, 3, 4);
-    out->ms_finalise = ev_ms(ctx, 4, 5);
-    out->ms_total = ev_ms(ctx, 0, 5);
-    return DKG_OK;
-  }
-}
-
-// ---- round-2 complaints as device batches (complaints.hip)
-// Does an accused dealer with `count` complaints get the difference tables of its row (every P_i(j),
-// verify_device without checks) instead of one Horner walk per complaint?  Both are one dependent
-// chain however many complaints there are (the walks of all complaints run side by side, and so do
-// the tables of all accused rows), so what decides is the chains' lengths, not the work:
-//   Horner: N steps of nb doublings, one addition per index bit some lane of the wave has set
-//           (about the bit length of `count` + 1 for a dealer accused by receivers 1..count), + 1;
-//   tables: N binomial steps and n stepping steps.
-// The per-step latencies are fitted to profiles/complaints_eval_ab.txt (n = 1024, t = 511: the tables
-// win at every count, 11.3-11.6 ms against 23.0-39.6 ms per call at 1-1,023 complaints; n = 1024, t = 3:
-// Horner wins at every count, 3.2-3.5 against 7.0-7.2 ms; n = 64 and 256 with t = (n-1)/2 in between).
-bool complaint_tables_pay(size_t n, size_t N, size_t count) {
-  if (N < 2) return false;  // a constant polynomial: P_i(j) = E_i0
-  int nb = 1, cb = 1;
-  while ((n >> nb) != 0) nb++;
-  while ((count >> cb) != 0) cb++;
-  const double horner_us = 3.6 * (double)N * (nb + std::min(nb, cb + 1) + 1);
-  const double tables_us = 13.0 * (double)N + 3.7 * (double)n;
-  return tables_us < horner_us;
-}
-
-// P_row(x) = sum_k x^k C_row[k] for C (row, index) items: per row, the difference tables of that row
-// or one Horner walk per item (ctx->complaint_eval; automatic: complaint_tables_pay by the row's item
-// count).  index / row (host) and dindex / drow (device) [C]: 1-based, index within 1..n, row within
-// 1..nrows; Cc [nrows][N][8] compressed and Cext (stride nrows * N) decoded commitments on the device.
-// An (row, index) pair listed again takes a further table row of its own, so that the table path
-// serves every item of a row it is chosen for.  Out: dridx [C] (bit 31: element of Rt, else of Rh),
-// Rh, Rt, scale as k_cv_check reads them.  Work is queued on ctx->stream; the staging vectors live
-// in `ev`, which the caller keeps until it has synchronised.
-struct ComplaintEvals {
-  std::vector<uint32_t> rows, hl, ridx;
-  const uint32_t *dridx = nullptr, *Rh = nullptr, *Rt = nullptr, *scale = nullptr;
-};
-void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, const uint32_t* index,
-                     const uint32_t* row, const uint32_t* dindex, const uint32_t* drow, const uint32_t* Cc,
-                     const uint32_t* Cext, ComplaintEvals& ev) {
-  const size_t N = t + 1;
-  hipStream_t st = ctx->stream;
-  std::vector<size_t> count(nrows, 0);
-  for (size_t c = 0; c < C; c++) count[row[c] - 1]++;
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> seen;   // (row, index) -> occurrences so far
-  std::map<std::pair<uint32_t, uint32_t>, uint32_t> rowof;  // (row, occurrence) -> table row
-  std::vector<uint32_t>&rows = ev.rows, &hl = ev.hl, &ridx = ev.ridx;
-  ridx.resize(C);
-  for (size_t c = 0; c < C; c++) {
-    const uint32_t i = row[c], j = index[c];
-    const bool tables = N >= 2 && (ctx->complaint_eval == 2 ||
-                                   (ctx->complaint_eval == 0 && complaint_tables_pay(n, N, count[i - 1])));
-    if (!tables) {
-      hl.push_back((uint32_t)c);
-      ridx[c] = (uint32_t)c;
-      continue;
-    }
-    const uint32_t m = seen[{i, j}]++;
-    auto it = rowof.find({i, m});
-    if (it == rowof.end()) {
-      it = rowof.emplace(std::make_pair(i, m), (uint32_t)rows.size()).first;
-      rows.push_back(i);
-    }
-    if (((size_t)it->second + 1) * n >= ((size_t)1 << 31)) {
-      ctx->err = "complaints_verify: too many table rows";
-      throw Fail{DKG_E_ARG};
-    }
-    ridx[c] = 0x80000000u | (uint32_t)((size_t)it->second * n + (j - 1));
-  }
-  uint32_t* dridx = buf<uint32_t>(ctx, "cv_ridx", 4 * C);
-  h2d(ctx, dridx, ridx.data(), 4 * C);
-  uint32_t* Rh = buf<uint32_t>(ctx, "cv_Rh", PTB * C);
-  if (!hl.empty()) {
-    uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
-    h2d(ctx, dhl, hl.data(), 4 * hl.size());
-    int nb = 1;
-    while ((n >> nb) != 0) nb++;
-    dkgk::cmp_horner(hl.size(), dhl, dindex, drow, Cext, nrows * N, N, nb, Rh, st);
-  }
-  if (!rows.empty()) {
-    const size_t D = rows.size();
-    uint32_t* Trows = buf<uint32_t>(ctx, "cv_Trows", 32 * D * N);
-    for (size_t r = 0; r < D; r++)
-      HCK(hipMemcpyAsync(Trows + 8 * N * r, Cc + 8 * N * (size_t)(rows[r] - 1), 32 * N, hipMemcpyDeviceToDevice, st));
-    VerifySeg g{2, D, 0, Trows, nullptr, nullptr, nullptr};
-    verify_device(ctx, n, t, &g, 1, false, "cv");
-    ev.Rt = ctx->last_R;
-    ev.scale = ctx->last_scale;
-  }
-  ev.dridx = dridx;
-  ev.Rh = Rh;
-}
-
-// MisbehavingPartiesRound1::verify (broadcast.rs:50-99) for C complaints of one ceremony.  Device: dpk
-// [n][8] member keys, Ec [n][N][8] commitments; host: accuser / accused (1-based, validated by the
-// caller), fetched1 (may be null), enc [C][128], proofs [C][192].  verdict [C] on the host; rowok_host
-// (may be null) [n] = E row i decodes.  Ends synchronised.
-void complaints_verify_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser,
-                            const uint32_t* accused, const uint32_t* dpk, const uint32_t* Ec, const uint8_t* fetched1,
-                            const uint8_t* enc, const uint8_t* proofs, int32_t* verdict, uint8_t* rowok_host) {
-  const size_t N = t + 1;
-  hipStream_t st = ctx->stream;
-  // every row decoded once: the rows' validity for the qualified set, and the Horner walks' input
-  uint32_t* Eext = buf<uint32_t>(ctx, "cv_Eext", PTB * n * N);
-  uint8_t* epok = buf<uint8_t>(ctx, "cv_Epok", n * N);
-  uint8_t* rowok = buf<uint8_t>(ctx, "cv_rowok", n);
-  dkgk::decode_points(Ec, n * N, Eext, n * N, epok, st);
-  dkgk::dealer_ok(n, N, epok, rowok, st);
-  if (rowok_host) d2h(ctx, rowok_host, rowok, n);
-  if (!C) {
-    check_launch(ctx);
-    sync(ctx);
-    return;
-  }
-  uint32_t* dacc = buf<uint32_t>(ctx, "cv_accuser", 4 * C);
-  uint32_t* dacd = buf<uint32_t>(ctx, "cv_accused", 4 * C);
-  uint32_t* denc = buf<uint32_t>(ctx, "cv_enc", 128 * C);
-  uint32_t* dprf = buf<uint32_t>(ctx, "cv_proofs", 192 * C);
-  uint8_t* dfet = nullptr;
-  h2d(ctx, dacc, accuser, 4 * C);
-  h2d(ctx, dacd, accused, 4 * C);
-  h2d(ctx, denc, enc, 128 * C);
-  h2d(ctx, dprf, proofs, 192 * C);
-  if (fetched1) {
-    dfet = buf<uint8_t>(ctx, "cv_fetched", n);
-    h2d(ctx, dfet, fetched1, n);
-  }
-  // scalars, the points to decode, SymmetricKey::process of both ciphertexts
-  uint32_t* Pc = buf<uint32_t>(ctx, "cv_Pc", 32 * 5 * C);
-  uint32_t* rs = buf<uint32_t>(ctx, "cv_rs", 32 * 2 * C);
-  uint32_t* nc = buf<uint32_t>(ctx, "cv_nc", 32 * 2 * C);
-  uint32_t* p12 = buf<uint32_t>(ctx, "cv_p12", 32 * 2 * C);
-  uint32_t* bp1 = buf<uint32_t>(ctx, "cv_bp1", 4 * 2 * C);
-  uint32_t* bp2 = buf<uint32_t>(ctx, "cv_bp2", 4 * 2 * C);
-  uint32_t* bq2 = buf<uint32_t>(ctx, "cv_bq2", 4 * 2 * C);
-  dkgk::cv_prep(C, dacc, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
-  uint32_t* Pext = buf<uint32_t>(ctx, "cv_Pext", PTB * 5 * C);
-  uint8_t* ppok = buf<uint8_t>(ctx, "cv_Ppok", 5 * C);
-  dkgk::decode_points(Pc, 5 * C, Pext, 5 * C, ppok, st);
-  // announcements (dl_equality/zkp.rs:60-63): a1 = g r - pk c (comb + one-base walk), a2 = e1 r - K c (Straus)
-  uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(2 * C));
-  uint32_t* S1 = buf<uint32_t>(ctx, "cv_S1", PTB * 2 * C);
-  uint32_t* S2 = buf<uint32_t>(ctx, "cv_S2", PTB * 2 * C);
-  uint32_t* G = buf<uint32_t>(ctx, "cv_G", PTB * 2 * C);
-  dkgk::cmp_ladder(2 * C, false, bp1, nullptr, nc, nullptr, Pext, 5 * C, T, S1, st);
-  dkgk::cmp_ladder(2 * C, true, bp2, bq2, rs, nc, Pext, 5 * C, T, S2, st);
-  dkgk::fixed_base(2 * C, rs, ctx->tab_gw, G, st);
-  dkgk::add_points(2 * C, S1, G, 2 * C, S1, st);
-  uint32_t* a1c = buf<uint32_t>(ctx, "cv_a1c", 32 * 2 * C);
-  uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
-  dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
-  dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
-  // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint
-  ComplaintEvals ev;
-  complaint_evals(ctx, n, t, n, C, accuser, accused, dacc, dacd, Ec, Eext, ev);
-  const uint32_t *dridx = ev.dridx, *Rh = ev.Rh, *Rt = ev.Rt, *scale = ev.scale;
-  uint8_t* eq = buf<uint8_t>(ctx, "cv_eq", 2 * C);
-  dkgk::cv_check(C, dacc, p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
-  int32_t* dver = buf<int32_t>(ctx, "cv_verdict", 4 * C);
-  dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, a1c, a2c, ppok, rowok, dfet, eq, dver, st);
-  check_launch(ctx);
-  d2h(ctx, verdict, dver, 4 * C);
-  sync(ctx);  // the staging vectors (ev) live until here
-}
-
-// 1-based party indices within 1..n
-bool complaint_indices_ok(size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused) {
-  for (size_t c = 0; c < C; c++)
-    if (accuser[c] < 1 || accuser[c] > n || accused[c] < 1 || accused[c] > n) return false;
-  return true;
-}
-
-// dissent[j] = the dealers receiver j rejected in the ceremony just run (dec2 on the device) without a
-// proven complaint of its own against them among the C
-void complaint_dissent(dkg_ctx* ctx, size_t n, size_t C, const uint32_t* accuser, const uint32_t* accused,
-                       const int32_t* verdict, int32_t* dissent) {
-  std::vector<uint8_t> d2(n * n);
-  d2h(ctx, d2.data(), buf<uint8_t>(ctx, "dec2", n * n), n * n);
-  sync(ctx);
-  std::vector<uint8_t> proven(n * n, 0);  // [accused][accuser]
-  for (size_t c = 0; c < C; c++)
-    if (verdict[c] == 0) proven[(size_t)(accused[c] - 1) * n + (accuser[c] - 1)] = 1;
-  for (size_t j = 0; j < n; j++) {
-    int32_t v = 0;
-    for (size_t i = 0; i < n; i++) v += d2[i * n + j] == DKG_REJECT && !proven[i * n + j];
-    dissent[j] = v;
-  }
-}
-
-// ---- round-4 complaints as a device batch (complaints.hip, k_c3_*)
-// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) as Phases<Phase4>::proceed applies it
-// (committee.rs:636-670) for C complaints of one ceremony.  Device: EA [2n][N][8], the E rows then the A
-// rows; host: accuser / accused (1-based, validated by the caller), share / randomness [C][32],
-// qualified / fetched3 [n] (may be null = all 1).  verdict [C] on the host; rowok_host (may be null)
-// [2n] = the row decodes.  Ends synchronised.
-void complaints3_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
-                      const uint8_t* share, const uint8_t* randomness, const uint32_t* EA, const uint8_t* qualified,
-                      const uint8_t* fetched3, int32_t* verdict, uint8_t* rowok_host) {
-  const size_t N = t + 1;
-  hipStream_t st = ctx->stream;
-  // both rows of every dealer decoded once: the rows' validity, and the Horner walks' input
-  uint32_t* EAext = buf<uint32_t>(ctx, "c3_EAext", PTB * 2 * n * N);
-  uint8_t* pok = buf<uint8_t>(ctx, "c3_pok", 2 * n * N);
-  uint8_t* rowok = buf<uint8_t>(ctx, "c3_rowok", 2 * n);
-  dkgk::decode_points(EA, 2 * n * N, EAext, 2 * n * N, pok, st);
-  dkgk::dealer_ok(2 * n, N, pok, rowok, st);
-  if (rowok_host) d2h(ctx, rowok_host, rowok, 2 * n);
-  if (!C) {
-    check_launch(ctx);
-    sync(ctx);
-    return;
-  }
-  uint32_t* dacc = buf<uint32_t>(ctx, "c3_accuser", 4 * C);
-  uint32_t* dacd = buf<uint32_t>(ctx, "c3_accused", 4 * C);
-  uint32_t* dsh = buf<uint32_t>(ctx, "c3_share", 32 * C);
-  uint32_t* drn = buf<uint32_t>(ctx, "c3_rand", 32 * C);
-  h2d(ctx, dacc, accuser, 4 * C);
-  h2d(ctx, dacd, accused, 4 * C);
-  h2d(ctx, dsh, share, 32 * C);
-  h2d(ctx, drn, randomness, 32 * C);
-  uint8_t *dq = nullptr, *df3 = nullptr;
-  if (qualified) {
-    dq = buf<uint8_t>(ctx, "c3_qualified", n);
-    h2d(ctx, dq, qualified, n);
-  }
-  if (fetched3) {
-    df3 = buf<uint8_t>(ctx, "c3_fetched3", n);
-    h2d(ctx, df3, fetched3, n);
-  }
-  uint32_t* sr = buf<uint32_t>(ctx, "c3_sr", 32 * 2 * C);
-  uint32_t* acc2 = buf<uint32_t>(ctx, "c3_acc2", 4 * 2 * C);
-  uint32_t* acd2 = buf<uint32_t>(ctx, "c3_acd2", 4 * 2 * C);
-  dkgk::c3_prep(C, n, dacc, dacd, dsh, drn, sr, acc2, acd2, st);
-  // P^E_i(j), P^A_i(j): items 2c, 2c + 1 on rows i, n + i.  Both rows of a dealer carry the same item
-  // count, so the automatic switch sends them the same way
-  std::vector<uint32_t> index(2 * C), row(2 * C);
-  for (size_t c = 0; c < C; c++) {
-    index[2 * c] = index[2 * c + 1] = accuser[c];
-    row[2 * c] = accused[c];
-    row[2 * c + 1] = (uint32_t)n + accused[c];
-  }
-  ComplaintEvals ev;
-  complaint_evals(ctx, n, t, 2 * n, 2 * C, index.data(), row.data(), acc2, acd2, EA, EAext, ev);
-  uint8_t* eq = buf<uint8_t>(ctx, "c3_eq", 2 * C);
-  dkgk::c3_check(C, dacc, sr, ev.dridx, ev.Rh, ev.Rt, ev.scale, ctx->tab_gw, ctx->tab_hw, eq, st);
-  int32_t* dver = buf<int32_t>(ctx, "c3_verdict", 4 * C);
-  dkgk::c3_final(C, n, dacd, rowok, dq, df3, eq, dver, st);
-  check_launch(ctx);
-  d2h(ctx, verdict, dver, 4 * C);
-  sync(ctx);  // the staging vectors (ev) live until here
-}
-
-// proven[i] = some complaint against i holds: verdict 0, or the accused has no phase-3 broadcast
-// (committee.rs:643, :664-669)
-std::vector<uint8_t> proven_round4(size_t n, size_t C, const uint32_t* accused, const int32_t* verdict) {
-  std::vector<uint8_t> p(n, 0);
-  for (size_t c = 0; c < C; c++)
-    if (verdict[c] == 0 || verdict[c] == DKG_COMPLAINT_NO_PHASE3) p[accused[c] - 1] = 1;
-  return p;
-}
-
-// What follows a ceremony that took `reconstruct` from the proven round-4 complaints: the verdicts
-// against dealers that round 2 disqualified become IGNORED (committee.rs:639), and the finalising
-// parties' common outcome.  a_ok[i] = dealer i has a usable phase-3 broadcast.  A qualified dealer
-// without one that nobody complained about is in no set: every party's finalise reaches the expect
-// at committee.rs:791-795 with indexed_committed_shares[i] never stored (:527-530).  Dealers are
-// visited in index order and the first failure wins (:745-797); mpk is zeroed on a panic.
-void proven_outcome(size_t n, size_t t, size_t C4, const uint32_t* accused4, int32_t* verdict4,
-                    const uint8_t* a_ok, dkg_ceremony_out* out, int32_t* finalise_status, int32_t* recovery_index) {
-  const uint8_t *qualified = out->qualified, *recon = out->reconstruct;
-  for (size_t c = 0; c < C4; c++)
-    if (!qualified[accused4[c] - 1]) verdict4[c] = DKG_COMPLAINT_IGNORED;
-  int32_t status = DKG_FIN_OK, index = -1;
-  if (out->phase4_error) {
-    status = DKG_FIN_PHASE4_ERROR;
-  } else {
-    const bool insufficient = recovery_fails(disclosing_parties(n, qualified, recon, out->r2_error, out->r4_error), t);
-    for (size_t i = 0; i < n && status == DKG_FIN_OK; i++) {
-      if (recon[i] && insufficient) status = DKG_FIN_INSUFFICIENT;
-      else if (!recon[i] && qualified[i] && !a_ok[i]) status = DKG_FIN_PANIC;
-      if (status != DKG_FIN_OK) index = (int32_t)i;
-    }
-  }
-  if (status == DKG_FIN_PANIC) memset(out->mpk, 0, 32);
-  if (finalise_status) *finalise_status = status;
-  if (recovery_index) *recovery_index = index;
-}
-
-// A copy of *out in which the four per-party flag arrays the proven ceremonies read afterwards are
-// present: the caller's own, or scratch.  finish() hands the scalar results back to the caller's struct.
-struct OutFlags {
-  std::vector<uint8_t> scratch;
-  dkg_ceremony_out o;
-  OutFlags(const dkg_ceremony_out* out, size_t n) : scratch(4 * n), o(*out) {
-    if (!o.qualified) o.qualified = scratch.data();
-    if (!o.reconstruct) o.reconstruct = scratch.data() + n;
-    if (!o.r2_error) o.r2_error = scratch.data() + 2 * n;
-    if (!o.r4_error) o.r4_error = scratch.data() + 3 * n;
-  }
-  void finish(dkg_ceremony_out* out) const {
-    dkg_ceremony_out r = o;
-    r.qualified = out->qualified, r.reconstruct = out->reconstruct;
-    r.r2_error = out->r2_error, r.r4_error = out->r4_error;
-    *out = r;
-  }
-};
-
-}  // namespace
-
-extern "C" {
-
 int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* e1,
                              const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, e1, ct, sk});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk) return DKG_E_ARG;
-    return ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, out, nullptr);
+    CeremonyInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -3706,11 +3770,9 @@ int dkg_complaints_verify(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint
                           const uint8_t* pk, const uint8_t* E, const uint8_t* fetched1, const uint8_t* enc,
                           const uint8_t* proofs, int32_t* verdict, uint8_t* qualified) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {pk, E});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !pk || !E) return DKG_E_ARG;
-    if (C && (!accuser || !accused || !enc || !proofs || !verdict)) return DKG_E_ARG;
-    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
+    if (!complaint_args_ok(n, C, accuser, accused, {enc, proofs, verdict})) return DKG_E_ARG;
     const size_t N = t + 1;
     uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
     uint32_t* Ec = buf<uint32_t>(ctx, "cv_E", 32 * n * N);
@@ -3733,37 +3795,13 @@ int dkg_ceremony_verify_full_complaints(dkg_ctx* ctx, size_t n, size_t t, const 
                                         const uint8_t* proofs, dkg_ceremony_out* out, int32_t* verdict,
                                         int32_t* dissent) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, e1, ct, sk, pk});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
-    if (C && (!accuser || !accused || !proofs || !verdict)) return DKG_E_ARG;
-    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
-    const size_t N = t + 1;
-    // the complaints against this ceremony's own broadcasts: the pair the accused sent the accuser
-    // (broadcast.rs:57), items (i, q, w) at (i n + q) 2 + w, w = 0 the randomness
-    std::vector<uint8_t> enc(128 * C);
-    for (size_t c = 0; c < C; c++) {
-      const size_t item = ((size_t)(accused[c] - 1) * n + (accuser[c] - 1)) * 2;
-      memcpy(&enc[128 * c], e1 + 32 * item, 32);
-      memcpy(&enc[128 * c + 32], ct + 32 * item, 32);
-      memcpy(&enc[128 * c + 64], e1 + 32 * (item + 1), 32);
-      memcpy(&enc[128 * c + 96], ct + 32 * (item + 1), 32);
-    }
-    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
-    uint32_t* Ec = buf<uint32_t>(ctx, "cv_E", 32 * n * N);
-    h2d(ctx, dpk, pk, 32 * n);
-    h2d(ctx, Ec, E, 32 * n * N);
-    complaints_verify_core(ctx, n, t, C, accuser, accused, dpk, Ec, nullptr, enc.data(), proofs, verdict, nullptr);
-    std::vector<uint8_t> cmask(n, 1);
-    for (size_t c = 0; c < C; c++)
-      if (verdict[c] == 0) cmask[accused[c] - 1] = 0;
-    uint8_t* dcm = buf<uint8_t>(ctx, "cv_cmask", n);
-    h2d(ctx, dcm, cmask.data(), n);
-    sync(ctx);
-    rc = ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, out, dcm);
-    if (rc || !dissent) return rc;
-    complaint_dissent(ctx, n, C, accuser, accused, verdict, dissent);
-    return DKG_OK;
+    if (!complaint_args_ok(n, C, accuser, accused, {proofs, verdict})) return DKG_E_ARG;
+    const Complaints2 c2{pk, C, accuser, accused, proofs, verdict, dissent};
+    CeremonyInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk, in.c2 = &c2;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -3772,16 +3810,11 @@ int dkg_complaints3_verify(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uin
                            const uint8_t* share, const uint8_t* randomness, const uint8_t* E, const uint8_t* A,
                            const uint8_t* qualified, const uint8_t* fetched3, int32_t* verdict, uint8_t* reconstruct) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {E, A});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !E || !A) return DKG_E_ARG;
-    if (C && (!accuser || !accused || !share || !randomness || !verdict)) return DKG_E_ARG;
-    if (!complaint_indices_ok(n, C, accuser, accused)) return DKG_E_ARG;
-    const size_t N = t + 1;
-    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
-    h2d(ctx, EA, E, 32 * n * N);
-    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
-    complaints3_core(ctx, n, t, C, accuser, accused, share, randomness, EA, qualified, fetched3, verdict, nullptr);
+    if (!complaint_args_ok(n, C, accuser, accused, {share, randomness, verdict})) return DKG_E_ARG;
+    const Commitments cm = upload_commitments(ctx, n, t + 1, E, A);
+    complaints3_core(ctx, n, t, C, accuser, accused, share, randomness, cm.E, qualified, fetched3, verdict, nullptr);
     if (reconstruct) {
       const std::vector<uint8_t> p = proven_round4(n, C, accused, verdict);
       memcpy(reconstruct, p.data(), n);
@@ -3797,43 +3830,13 @@ int dkg_ceremony_verify_fetched_proven(dkg_ctx* ctx, size_t n, size_t t, const u
                                        dkg_ceremony_out* out, int32_t* verdict4, int32_t* finalise_status,
                                        int32_t* recovery_index) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, s, s_prime, fetched1, fetched3});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !s || !s_prime || !fetched1 || !fetched3) return DKG_E_ARG;
-    if (C4 && (!accuser4 || !accused4 || !share4 || !randomness4 || !verdict4)) return DKG_E_ARG;
-    if (!complaint_indices_ok(n, C4, accuser4, accused4)) return DKG_E_ARG;
-    const size_t N = t + 1;
-    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
-    h2d(ctx, EA, E, 32 * n * N);
-    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
-    // the complaints first: their verdicts do not depend on the qualified set, only whether they count
-    std::vector<uint8_t> rowok(2 * n);
-    complaints3_core(ctx, n, t, C4, accuser4, accused4, share4, randomness4, EA, nullptr, fetched3, verdict4,
-                     rowok.data());
-    const std::vector<uint8_t> proven = proven_round4(n, C4, accused4, verdict4);
-    uint8_t* dp4 = buf<uint8_t>(ctx, "c3_proven", n);
-    h2d(ctx, dp4, proven.data(), n);
-    uint32_t* ds = upload_scalars(ctx, "cer_s", s, n * n);
-    uint32_t* dsp = upload_scalars(ctx, "cer_sp", s_prime, n * n);
-    uint8_t* f1 = buf<uint8_t>(ctx, "cer_f1", n);
-    uint8_t* f3 = buf<uint8_t>(ctx, "cer_f3", n);
-    h2d(ctx, f1, fetched1, n);
-    h2d(ctx, f3, fetched3, n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    OutFlags fl(out, n);
-    receivers_rounds(ctx, n, t, EA, EA + 8 * n * N, ds, dsp, &fl.o, true, f1, f3, nullptr, dp4);
-    fl.o.ms_round1 = 0;
-    fl.o.ms_round2 = ev_ms(ctx, 1, 2);
-    fl.o.ms_round3 = ev_ms(ctx, 2, 3);
-    fl.o.ms_round4 = ev_ms(ctx, 3, 4);
-    fl.o.ms_finalise = ev_ms(ctx, 4, 5);
-    fl.o.ms_total = ev_ms(ctx, 0, 5);
-    std::vector<uint8_t> a_ok(n);
-    for (size_t i = 0; i < n; i++) a_ok[i] = fetched3[i] && rowok[n + i];
-    proven_outcome(n, t, C4, accused4, verdict4, a_ok.data(), &fl.o, finalise_status, recovery_index);
-    fl.finish(out);
-    return DKG_OK;
+    if (!complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4})) return DKG_E_ARG;
+    const Complaints4 c4{C4, accuser4, accused4, share4, randomness4, verdict4, finalise_status, recovery_index};
+    CeremonyInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime, in.fetched1 = fetched1, in.fetched3 = fetched3, in.c4 = &c4;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -3845,55 +3848,16 @@ int dkg_ceremony_verify_full_proven(dkg_ctx* ctx, size_t n, size_t t, const uint
                                     dkg_ceremony_out* out, int32_t* verdict, int32_t* dissent, int32_t* verdict4,
                                     int32_t* finalise_status, int32_t* recovery_index) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, e1, ct, sk, pk});
     if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
-    if (C && (!accuser || !accused || !proofs || !verdict)) return DKG_E_ARG;
-    if (C4 && (!accuser4 || !accused4 || !share4 || !randomness4 || !verdict4)) return DKG_E_ARG;
-    if (!complaint_indices_ok(n, C, accuser, accused) || !complaint_indices_ok(n, C4, accuser4, accused4))
+    if (!complaint_args_ok(n, C, accuser, accused, {proofs, verdict}) ||
+        !complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4}))
       return DKG_E_ARG;
-    const size_t N = t + 1;
-    uint32_t* EA = buf<uint32_t>(ctx, "c3_EA", 32 * 2 * n * N);
-    h2d(ctx, EA, E, 32 * n * N);
-    h2d(ctx, EA + 8 * n * N, A, 32 * n * N);
-    // round-4 complaints, then round-2 complaints (as dkg_ceremony_verify_full_complaints), then the rounds
-    std::vector<uint8_t> rowok(2 * n);
-    complaints3_core(ctx, n, t, C4, accuser4, accused4, share4, randomness4, EA, nullptr, fetched3, verdict4,
-                     rowok.data());
-    const std::vector<uint8_t> proven = proven_round4(n, C4, accused4, verdict4);
-    uint8_t* dp4 = buf<uint8_t>(ctx, "c3_proven", n);
-    h2d(ctx, dp4, proven.data(), n);
-    uint8_t* f3 = nullptr;
-    if (fetched3) {
-      f3 = buf<uint8_t>(ctx, "cer_f3", n);
-      h2d(ctx, f3, fetched3, n);
-    }
-    std::vector<uint8_t> enc(128 * C);
-    for (size_t c = 0; c < C; c++) {
-      const size_t item = ((size_t)(accused[c] - 1) * n + (accuser[c] - 1)) * 2;
-      memcpy(&enc[128 * c], e1 + 32 * item, 32);
-      memcpy(&enc[128 * c + 32], ct + 32 * item, 32);
-      memcpy(&enc[128 * c + 64], e1 + 32 * (item + 1), 32);
-      memcpy(&enc[128 * c + 96], ct + 32 * (item + 1), 32);
-    }
-    uint32_t* dpk = buf<uint32_t>(ctx, "cv_pk", 32 * n);
-    h2d(ctx, dpk, pk, 32 * n);
-    complaints_verify_core(ctx, n, t, C, accuser, accused, dpk, EA, nullptr, enc.data(), proofs, verdict, nullptr);
-    std::vector<uint8_t> cmask(n, 1);
-    for (size_t c = 0; c < C; c++)
-      if (verdict[c] == 0) cmask[accused[c] - 1] = 0;
-    uint8_t* dcm = buf<uint8_t>(ctx, "cv_cmask", n);
-    h2d(ctx, dcm, cmask.data(), n);
-    sync(ctx);
-    OutFlags fl(out, n);
-    rc = ceremony_verify_full_impl(ctx, n, t, E, A, e1, ct, sk, &fl.o, dcm, EA, f3, dp4);
-    if (rc) return rc;
-    std::vector<uint8_t> a_ok(n);
-    for (size_t i = 0; i < n; i++) a_ok[i] = (!fetched3 || fetched3[i]) && rowok[n + i];
-    proven_outcome(n, t, C4, accused4, verdict4, a_ok.data(), &fl.o, finalise_status, recovery_index);
-    fl.finish(out);
-    if (dissent) complaint_dissent(ctx, n, C, accuser, accused, verdict, dissent);
-    return DKG_OK;
+    const Complaints2 c2{pk, C, accuser, accused, proofs, verdict, dissent};
+    const Complaints4 c4{C4, accuser4, accused4, share4, randomness4, verdict4, finalise_status, recovery_index};
+    CeremonyInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk, in.fetched3 = fetched3, in.c2 = &c2, in.c4 = &c4;
+    return verify_ceremony(ctx, n, t, in, out);
   });
 }
 
@@ -3952,18 +3916,6 @@ int dkg_member_keys_batch(dkg_ctx* ctx, const uint8_t master[32], uint32_t cerem
     return DKG_OK;
   });
 }
-
-namespace {
-// DKG_E_DECODE when a recipient key of the last encrypt_batch_device did not decode (after a sync)
-int batch_keys_status(dkg_ctx* ctx, const uint8_t* ok, size_t V) {
-  for (size_t k = 0; k < V; k++)
-    if (!ok[k]) {
-      ctx->err = "encrypt_shares_batch: a recipient public key does not decode";
-      return DKG_E_DECODE;
-    }
-  return DKG_OK;
-}
-}  // namespace
 
 int dkg_encrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* pk, const uint8_t* s,
                              const uint8_t* s_prime, const uint8_t* r, uint8_t* e1, uint8_t* ct) {

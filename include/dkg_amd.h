@@ -242,7 +242,8 @@ typedef struct {
 /* Honest run from coefficients a, b ([n][t+1][32], host). */
 int dkg_ceremony_run(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *a, const uint8_t *b, dkg_ceremony_out *out);
 /* Receiver side (rounds 2-5) from broadcast values that may have been tampered with:
- * E, A [n][t+1][32]; s, s_prime [n][n][32]. */
+ * E, A [n][t+1][32]; s, s_prime [n][n][32]; all four required (DKG_E_ARG when NULL), here and in
+ * dkg_ceremony_verify_fetched. */
 int dkg_ceremony_verify(dkg_ctx *ctx, size_t n, size_t t, const uint8_t *E, const uint8_t *A, const uint8_t *s,
                         const uint8_t *s_prime, dkg_ceremony_out *out);
 /* dkg_ceremony_verify after the broadcast intake of MembersFetchedState1/3::from_broadcast

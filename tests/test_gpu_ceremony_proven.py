@@ -3,15 +3,21 @@ committee.rs:625-688): dkg_ceremony_verify_fetched_proven and dkg_ceremony_verif
 
 Where every receiver files its complaint the outcome is the rejection rule's, which passes its goldens;
 where the rules differ the expected sets, mpk and status are restated with tests/finalise_ref.py.
+The last section pins what all six verify entry points share through their one driver (verify_ceremony).
 """
+import ctypes
+import dataclasses
+
 import pytest
 
 import dkg_amd
-from dkg_amd import COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3, REJECT
+from dkg_amd import COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3, REJECT, _lib
 from dkg_amd import broadcast as B
-from dkg_amd._lib import FIN_INSUFFICIENT, FIN_OK, FIN_PANIC, FIN_PHASE4_ERROR
+from dkg_amd._lib import DKG_E_ARG, DKG_OK, FIN_INSUFFICIENT, FIN_OK, FIN_PANIC, FIN_PHASE4_ERROR
+from dkg_amd.api import CeremonyResult, ProvenResult
 from tests import finalise_ref as FR
 from tests import oracle_lib as O
+from tests.test_gpu import _check_ceremony
 from tests.test_gpu_complaints import _ceremony_fields, fixture_inputs
 
 pytestmark = pytest.mark.gpu
@@ -315,3 +321,129 @@ def test_full_from_wire_bytes(be, full):
     assert sorted(B.intake_phase4(n, p4)[0]) == sorted(x[0] for x in d["comp"])
     assert p.verdict4 == [0] * 9
     assert (p.finalise_status, p.recovery_index) == (FIN_OK, -1)
+
+
+# ---------------- 10. the one verify driver behind the entry points ----------------
+@pytest.fixture(scope="module")
+def amany(be, golden):
+    """fault_a_many_n10_t4 (six reconstructed dealers, phase4_error) with every receiver's round-4 complaint."""
+    c = golden("fault_a_many_n10_t4.json")
+    n, t = c["n"], c["t"]
+    be.env_init(t, n, CK)
+    ones = bytes([1] * n)
+    ref = be.ceremony_verify_fetched(H(c["E"]), H(c["A"]), H(c["s"]), H(c["s_prime"]), ones, ones, n, t)
+    comp = honest_complaints(ref, H(c["s"]), H(c["s_prime"]), n)
+    assert comp and ref.phase4_error
+    return c, comp
+
+
+def u32s(xs):
+    return (ctypes.c_uint32 * max(len(xs), 1))(*xs)
+
+
+def raw_proven(be, n, t, fn, args, verdicts, C4, null=()):
+    """fn(ctx, n, t, *args, out, *verdicts, status, index) through the C ABI, the out struct's `null`
+    arrays absent: what the call reports beside the per-party arrays (verdicts[-1] the round-4 ones)."""
+    o, _bufs = be._ceremony_out(n, t, True)
+    for k in null:
+        setattr(o, k, None)
+    st, ri = ctypes.c_int32(-9), ctypes.c_int32(-9)
+    rc = fn(be.ctx, n, t, *args, ctypes.byref(o), *verdicts, ctypes.byref(st), ctypes.byref(ri))
+    assert rc == DKG_OK
+    return bytes(o.mpk), o.n_qualified, o.phase4_error, list(verdicts[-1])[:C4], st.value, ri.value
+
+
+FLAG_ARRAYS = ("qualified", "reconstruct", "r2_error", "r4_error")
+
+
+def test_null_flag_arrays_fetched(be, amany):
+    """The proven outcome needs the four per-party flag vectors whether or not the caller asked for them."""
+    c, comp = amany
+    n, t = c["n"], c["t"]
+    be.env_init(t, n, CK)
+    acc, acd, sh, rn = lists(comp)
+    ones = bytes([1] * n)
+    args = (H(c["E"]), H(c["A"]), H(c["s"]), H(c["s_prime"]), ones, ones, len(comp), u32s(acc), u32s(acd), sh, rn)
+    fn = _lib.lib().dkg_ceremony_verify_fetched_proven
+    got = [raw_proven(be, n, t, fn, args, ((ctypes.c_int32 * len(comp))(),), len(comp), null)
+           for null in ((), FLAG_ARRAYS)]
+    assert got[0] == got[1]
+    p = proven(be, c, comp)
+    assert got[0] == (p.result.mpk, p.result.n_qualified, p.result.phase4_error, p.verdict4, p.finalise_status,
+                      p.recovery_index)
+    assert got[0][2] == 1 and got[0][4] == FIN_PHASE4_ERROR
+
+
+def test_null_flag_arrays_full(be, full):
+    d = full
+    n, t, comp = d["n"], d["t"], d["comp"]
+    be.env_init(t, n, CK)
+    acc4, acd4, sh, rn = lists(comp)
+    C = len(d["accuser"])
+    args = d["args"] + (C, u32s(d["accuser"]), u32s(d["accused"]), d["proof"], None, len(comp), u32s(acc4),
+                        u32s(acd4), sh, rn)
+    fn = _lib.lib().dkg_ceremony_verify_full_proven
+    got = []
+    for null in ((), FLAG_ARRAYS):
+        verdicts = ((ctypes.c_int32 * C)(), (ctypes.c_int32 * n)(), (ctypes.c_int32 * len(comp))())
+        got.append(raw_proven(be, n, t, fn, args, verdicts, len(comp), null) + (list(verdicts[0]), list(verdicts[1])))
+    assert got[0] == got[1]
+    r = d["ref"]
+    assert got[0] == (r.mpk, r.n_qualified, r.phase4_error, [0] * 9, FIN_OK, -1, d["v"], d["dis"])
+
+
+@pytest.mark.parametrize("fetched", [False, True])
+@pytest.mark.parametrize("missing", ["E", "A", "s", "s_prime"])
+def test_null_required_pointer(be, golden, fetched, missing):
+    """A null E, A, s or s_prime is DKG_E_ARG, and the context serves the next call."""
+    c = golden("fault_a_generator_n10_t4.json")
+    n, t = c["n"], c["t"]
+    be.env_init(t, n, CK)
+    ones = bytes([1] * n)
+    vals = [None if k == missing else H(c[k]) for k in ("E", "A", "s", "s_prime")]
+    o, _bufs = be._ceremony_out(n, t, True)
+    if fetched:
+        rc = _lib.lib().dkg_ceremony_verify_fetched(be.ctx, n, t, *vals, ones, ones, ctypes.byref(o))
+    else:
+        rc = _lib.lib().dkg_ceremony_verify(be.ctx, n, t, *vals, ctypes.byref(o))
+    assert rc == DKG_E_ARG
+    good = [H(c[k]) for k in ("E", "A", "s", "s_prime")]
+    r = be.ceremony_verify_fetched(*good, ones, ones, n, t) if fetched else be.ceremony_verify(*good, n, t)
+    _check_ceremony(c, r, n)
+
+
+def no_times(x):
+    if isinstance(x, CeremonyResult):
+        return dataclasses.replace(x, ms=None)
+    if isinstance(x, ProvenResult):
+        return dataclasses.replace(x, result=no_times(x.result))
+    if isinstance(x, tuple):
+        return tuple(no_times(v) for v in x)
+    return x
+
+
+def test_entry_points_share_one_context(be, amany, full):
+    """The six verify entry points one after the other on one context, then in reverse order: every one
+    returns what it returned before (no device buffer of one call is another's under the same name)."""
+    c, comp = amany
+    d = full
+    n, t = c["n"], c["t"]
+    assert (d["n"], d["t"]) == (n, t)
+    be.env_init(t, n, CK)
+    plain = tuple(H(c[k]) for k in ("E", "A", "s", "s_prime"))
+    ones, f3 = bytes([1] * n), bytes([int(i != 2) for i in range(n)])
+    calls = [
+        lambda: be.ceremony_verify(*plain, n, t),
+        lambda: be.ceremony_verify_fetched(*plain, ones, f3, n, t),
+        lambda: be.ceremony_verify_full(*d["args"][:5], n, t),
+        lambda: be.ceremony_verify_full_complaints(*d["args"], d["accuser"], d["accused"], d["proof"], n, t),
+        lambda: be.ceremony_verify_fetched_proven(*plain, ones, f3, *lists(comp), n, t),
+        lambda: be.ceremony_verify_full_proven(*d["args"], d["accuser"], d["accused"], d["proof"],
+                                               *lists(d["comp"]), n, t),
+    ]
+    first = [no_times(f()) for f in calls]
+    again = [no_times(f()) for f in reversed(calls)][::-1]
+    for k, (x, y) in enumerate(zip(first, again)):
+        assert x == y, k
+    _check_ceremony(c, first[0], n)
+    assert no_times(first[3]) == no_times((d["ref"], d["v"], d["dis"]))
