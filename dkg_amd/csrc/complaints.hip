@@ -113,6 +113,7 @@ DKG_DEV void sc_load_reduced(sc& r, const uint32_t* p) {
   uint32_t w[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) w[j] = p[j];
+  w[7] &= 0x7fffffffu;  // from_bits, as k_reduce_scalars
   sc_reduce256(r, w);
 }
 DKG_DEV void sc_store(uint32_t* p, const sc& s) {

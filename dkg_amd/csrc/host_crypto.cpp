@@ -202,6 +202,13 @@ Zl zl_from_bytes_wide(const uint8_t* in, size_t len) {
   return r;
 }
 
+Zl zl_from_bits(const uint8_t in[32]) {
+  uint8_t b[32];
+  for (int i = 0; i < 32; i++) b[i] = in[i];
+  b[31] &= 0x7f;
+  return zl_from_bytes_wide(b, 32);
+}
+
 Zl zl_from_u64(uint64_t x) {
   uint8_t b[8];
   for (int i = 0; i < 8; i++) b[i] = (uint8_t)(x >> (8 * i));

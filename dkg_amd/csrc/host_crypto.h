@@ -18,6 +18,7 @@ struct Zl {  // canonical element of Z_l, little-endian 64-bit limbs
   uint64_t w[4];
 };
 Zl zl_from_bytes_wide(const uint8_t* in, size_t len);  // any length, big-endian fold of LE bytes
+Zl zl_from_bits(const uint8_t in[32]);  // Scalar::from_bits (groups.rs:29-36): bit 255 dropped, reduced
 Zl zl_from_u64(uint64_t x);
 void zl_to_bytes(uint8_t out[32], const Zl& a);
 Zl zl_add(const Zl& a, const Zl& b);

@@ -2187,6 +2187,7 @@ __global__ void k_reduce_scalars(size_t count, const uint32_t* __restrict__ in, 
   if (e >= count) return;
   uint32_t w[8];
   ld_words8(w, in + 8 * e);
+  w[7] &= 0x7fffffffu;  // Scalar::from_bits drops bit 255 (groups.rs:29-36), as the decryption's k_sym_xor
   sc r;
   sc_reduce256(r, w);
   st_words8(out + 8 * e, r.v);

@@ -234,7 +234,7 @@ void fixed_base(size_t count, const uint32_t* scalars, const uint32_t* tab, uint
 // Transpose dealer-major point SoA [40][D*N] (element i*N+k) to position-major [40][N][npad].
 void to_position_major(size_t D, size_t N, size_t npad, const uint32_t* in, uint32_t* out,
                        hipStream_t stream);
-// Scalar reduction of 256-bit inputs to canonical (from_bits semantics, groups.rs:29-36).
+// Scalar reduction of 256-bit inputs to canonical (from_bits semantics, groups.rs:29-36: bit 255 dropped).
 void reduce_scalars(size_t count, const uint32_t* in, uint32_t* out, hipStream_t stream);
 // Modular sum over dealers with mask: out[j] = sum_i mask[i] * s[i][j]  (round-3 final share)
 void sum_shares(size_t D, size_t n, const uint32_t* s, const uint8_t* mask, uint32_t* out, hipStream_t stream,

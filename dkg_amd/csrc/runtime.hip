@@ -241,7 +241,8 @@ void comb_for_point(dkg_ctx* ctx, const uint8_t p[32], uint32_t* tab, bool* ok, 
   *ok = v != 0;
 }
 
-// Upload scalars (32-byte encodings) and reduce them mod l (from_bits semantics, groups.rs:29-36).
+// Upload scalars (32-byte encodings) as Scalar::from_bytes reads them (from_bits, groups.rs:29-36: bit
+// 255 dropped), reduced mod l.
 uint32_t* upload_scalars(dkg_ctx* ctx, const char* name, const uint8_t* host, size_t count) {
   uint32_t* raw = buf<uint32_t>(ctx, "scalar_raw", 32 * count);
   uint32_t* red = buf<uint32_t>(ctx, name, 32 * count);
@@ -1145,7 +1146,7 @@ std::vector<dkgh::Zl> lagrange_zero_coeffs(size_t n, const uint8_t* in_set) {
 dkgh::Zl lagrange_dot(const std::vector<dkgh::Zl>& lam, const uint8_t* ys, size_t n) {
   dkgh::Zl acc = dkgh::zl_from_u64(0);
   for (size_t j = 0; j < n; j++)
-    if (!dkgh::zl_is_zero(lam[j])) acc = dkgh::zl_add(acc, dkgh::zl_mul(lam[j], dkgh::zl_from_bytes_wide(ys + 32 * j, 32)));
+    if (!dkgh::zl_is_zero(lam[j])) acc = dkgh::zl_add(acc, dkgh::zl_mul(lam[j], dkgh::zl_from_bits(ys + 32 * j)));
   return acc;
 }
 
@@ -1897,7 +1898,7 @@ void msm_host(dkg_ctx* ctx, size_t B, size_t N, const uint8_t* scalars, const ui
     for (size_t k = 0; k < N; k++) ok[b] &= okh[b * N + k];
 }
 
-dkgh::Zl zl32(const uint8_t* p) { return dkgh::zl_from_bytes_wide(p, 32); }
+dkgh::Zl zl32(const uint8_t* p) { return dkgh::zl_from_bits(p); }  // a scalar off the wire
 void put32(std::vector<uint8_t>& v, const uint8_t* p) { v.insert(v.end(), p, p + 32); }
 void putzl(std::vector<uint8_t>& v, const dkgh::Zl& z) {
   uint8_t b[32];
@@ -3146,7 +3147,7 @@ int dkg_finalise_parties(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* qualif
       lamS = lagrange_zero_coeffs(n, S.data());
       yrows.resize(recon.size() * n);
       for (size_t r = 0; r < recon.size(); r++)
-        for (size_t j = 0; j < n; j++) yrows[r * n + j] = zl_from_bytes_wide(s + 32 * (recon[r] * n + j), 32);
+        for (size_t j = 0; j < n; j++) yrows[r * n + j] = zl_from_bits(s + 32 * (recon[r] * n + j));
     }
     Zl PS = one;
     for (size_t j = 0; j < n; j++)

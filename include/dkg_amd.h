@@ -3,7 +3,9 @@
  * share-verification hot path of danielSanchezQ/dkg (Pedersen-VSS DKG over Ristretto255).
  *
  * Encodings (identical to the reference's wire values):
- *   scalar = 32 bytes little-endian, canonical mod l      (groups.rs:23-27)
+ *   scalar = 32 bytes little-endian, canonical mod l      (groups.rs:23-27); a scalar input that is
+ *            not canonical is read as Scalar::from_bytes reads it (from_bits, groups.rs:29-36):
+ *            bit 255 is dropped and the rest reduced mod l
  *   point  = 32 bytes compressed Ristretto255             (groups.rs:72-76)
  * Every buffer is caller-owned host memory unless a function name ends in `_device`
  * (then the pointers are HIP device pointers).  No pointer is retained after return.
