@@ -192,7 +192,8 @@ class Backend:
 
     def set_combine(self, mode: int):
         """Recombination of a degree split: 0 short lattice multipliers for 2..4 pieces (default),
-        1 powers of y = j^L; decisions are identical (dkg_ctx_set_combine)."""
+        1 powers of y = j^L; 3 short multipliers as per-scalar NAF chains at every U (0 and 2 run
+        pairwise joint-sparse-form chains at U = 2, 4); decisions are identical (dkg_ctx_set_combine)."""
         _check(self._ctx, _lib.lib().dkg_ctx_set_combine(self._ctx, mode))
 
     def set_stepping_formula(self, mode: int):

@@ -392,6 +392,47 @@ DKG_DEV void ge_madd_signed(ge_p3& r, const ge_p3& p, const ge_aff& q, bool neg,
   }
 }
 
+// ge_madd_signed for an addend whose (y+x, y-x) the caller already exchanged when neg is set (as it
+// loaded them): no selected copies of the two fields, 20 VGPRs fewer live.  Otherwise the same
+// operations and bounds.
+template <bool IL = false>
+DKG_DEV void ge_madd_swapped(ge_p3& r, const ge_p3& p, const ge_aff& q, bool neg, bool with_t = true) {
+  fe a, b, e, h, t;
+  const fe& qa = q.ymx;
+  const fe& qb = q.ypx;
+  if constexpr (IL && DKG_PW) {
+    fe u;
+    fe_sub(t, p.Y, p.X);
+    fe_add(u, p.Y, p.X);
+    fe_mul2(a, t, qa, b, u, qb);
+  } else {
+    fe_sub(t, p.Y, p.X);
+    fe_mul(a, t, qa);
+    fe_add(t, p.Y, p.X);
+    fe_mul(b, t, qb);
+  }
+  fe_sub(e, b, a);
+  fe_add(h, b, a);
+  fe_mul(a, p.T, q.xy2d);   // c
+  fe na;
+  fe_neg(na, a);            // -c = 2p - c <= 2p limbwise
+  fe_cmov(a, na, neg);      // a = +/-c
+  fe_dbl(b, p.Z);
+  fe_carry(b, b);           // d = 2Z, tight
+  fe_sub(t, b, a);          // f = d - (+/-c)
+  fe_add(b, b, a);          // g = d + (+/-c)
+  if constexpr (IL && DKG_PW) {
+    fe_mul2(r.X, e, t, r.Y, b, h);
+    if (with_t) fe_mul2(r.Z, b, t, r.T, e, h);
+    else fe_mul(r.Z, b, t);
+  } else {
+    fe_mul(r.X, e, t);
+    fe_mul(r.Y, b, h);
+    fe_mul(r.Z, b, t);
+    if (with_t) fe_mul(r.T, e, h);
+  }
+}
+
 // ---- Ristretto255 (RFC 9496 section 4.3) ----
 
 // (was_square, r) = SQRT_RATIO_M1(u, v); u, v tight.

@@ -29,6 +29,10 @@ bool zl_is_zero(const Zl& a);
 
 // lattice.cpp: a short (b, a_1, .., a_{K-1}) with a_u = b y^u (mod l), b > 0, 2 <= K <= 5, as
 // magnitudes (32 bytes LE) and signs; (1, y, .., y^(K-1)) when no shorter row checks out.
-bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign);
+// jsf: price the candidate rows for the pairwise joint-sparse-form chain instead of per-scalar NAFs.
+bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign, bool jsf = false);
+// Joint sparse form of two 256-bit magnitudes (lattice.cpp); false if it does not fit 256 positions.
+bool jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t* da, int8_t* db, int16_t* top,
+                int npos = 256);
 
 }  // namespace dkgh

@@ -1751,6 +1751,201 @@ void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv
     hipLaunchKernelGGL((k_combine_aff<5, 2>), grid, dim3(64), 0, stream, width, pstride, nrecv, digits, top, A, R, j0);
 }
 
+// Pairwise joint sparse form.  The digits of pieces (2p, 2p+1) are the JSF of their two multipliers
+// (runtime.hip split_short): about half the columns of a pair are nonzero, and a column with both
+// digits set adds the pair's sum or difference ONCE -- 190 additions per item at K = 4 instead of
+// the 254 of four NAFs.  The sums do not fit next to the K addends (LDS and VGPRs hold about 5.5),
+// and need not: the digits are wave-uniform and known ahead, so the chain streams them.
+//
+// pair_sums: S_p = Q_2p + Q_2p+1 and D_p = Q_2p - Q_2p+1 by the complete formula (they share c, d,
+// hence f, g and Z; 14 products for both), written with their dense Z copies as piece planes
+// K + 2p and K + 2p + 1 of R / Rz; affine_pieces then normalises all K + 2 floor(K/2) planes.
+// Q_2p = +/-Q_2p+1 and identity padding give the identity with Z != 0 (complete formula), so the
+// normalisation's shared inversion is safe.
+__global__ __launch_bounds__(256) void k_pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv,
+                                                   uint32_t* R, uint32_t* Rz, size_t j0, size_t jn) {
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t j = j0 + gid % jn, rest = gid / jn, c = rest % width, p = rest / width;
+  if (p >= pieces / 2) return;
+  const size_t e0 = ((2 * p) * pstride + c) * nrecv + j, e1 = e0 + pstride * nrecv;
+  const size_t es = ((pieces + 2 * p) * pstride + c) * nrecv + j, ed = es + pstride * nrecv;
+  ge_p3 a, s;
+  ge_cached q;
+  {
+    ge_p3 b;
+    pt_load_aos(b, R, e1);
+    ge_to_cached(q, b);
+  }
+  pt_load_aos(a, R, e0);
+  fe ym, yp, f, g, x, y, e, h;
+  fe_mul(x, a.T, q.T2d);    // c
+  fe_mul(y, a.Z, q.Z2);     // d
+  fe_sub(f, y, x);          // f = d - c <= 1.5*2^27
+  fe_add(g, y, x);          // g = d + c <= 2^27
+  fe_sub(ym, a.Y, a.X);
+  fe_add(yp, a.Y, a.X);
+  fe_mul(s.Z, g, f);        // both results' Z
+  fe_mul(x, ym, q.YmX);     // the sum: ge_add's operands
+  fe_mul(y, yp, q.YpX);
+  fe_sub(e, y, x);
+  fe_add(h, y, x);
+  fe_mul(s.X, e, f);
+  fe_mul(s.Y, g, h);
+  fe_mul(s.T, e, h);
+  pt_store_aos<DKG_STEP_NT != 0>(R, es, s);
+  fe_mul(x, ym, q.YpX);     // the difference: ge_sub's (f and g change places)
+  fe_mul(y, yp, q.YmX);
+  fe_sub(e, y, x);
+  fe_add(h, y, x);
+  fe_mul(s.X, e, g);
+  fe_mul(s.Y, f, h);
+  fe_mul(s.T, e, h);
+  pt_store_aos<DKG_STEP_NT != 0>(R, ed, s);
+  uint2* zs = reinterpret_cast<uint2*>(Rz + es * 10);
+  uint2* zd = reinterpret_cast<uint2*>(Rz + ed * 10);
+#pragma unroll
+  for (int k = 0; k < 5; k++) zs[k] = zd[k] = make_uint2(s.Z.v[2 * k], s.Z.v[2 * k + 1]);
+}
+
+void pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv, uint32_t* R, uint32_t* Rz,
+               hipStream_t stream, size_t j0, size_t jn) {
+  if (!jn) jn = nrecv - j0;
+  if (!width || !jn || pieces < 2) return;
+  const size_t lanes = (pieces / 2) * width * jn;
+  hipLaunchKernelGGL(k_pair_sums, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, width, pstride, pieces,
+                     nrecv, R, Rz, j0, jn);
+}
+
+// The streamed addend of the chain's next both-nonzero column, event e: bits 0-1 its plane after the
+// K pieces' (pair e / 2, its sum or difference), bit 2 set when the column subtracts it -- y+x and
+// y-x are then loaded into each other's place, which spares the addition its selected copies (8-byte
+// loads: y-x starts at word 10) -- or nothing (JSF_EV_NONE).  Plain vector loads into VGPRs, issued
+// one both-nonzero column ahead, so that they fly during the additions and doublings between.
+// A0: receiver j's slot of column 0 in plane K (uniform); slot = column * nrecv, this lane's slot from
+// there.  The lane's address is rebuilt here from the one VGPR (the opaque copy keeps the 64-bit
+// address from being hoisted out of the chain's loop, where it would live in two).
+DKG_DEV void jsf_fetch(ge_aff& q, const uint32_t* __restrict__ A0, uint32_t slot, size_t plane, uint32_t e) {
+  if (e == JSF_EV_NONE) return;
+  asm volatile("" : "+v"(slot));
+  const uint32_t* a = A0 + (size_t)slot * AFFP_WORDS + (e & 3u) * plane;
+  const uint2* f0 = reinterpret_cast<const uint2*>(a + ((e & 4u) ? 10 : 0));
+  const uint2* f1 = reinterpret_cast<const uint2*>(a + ((e & 4u) ? 0 : 10));
+  const uint2* f2 = reinterpret_cast<const uint2*>(a + 20);
+#pragma unroll
+  for (int i = 0; i < 5; i++) {
+    const uint2 u = f0[i], v = f1[i], w = f2[i];
+    q.ypx.v[2 * i] = u.x;
+    q.ypx.v[2 * i + 1] = u.y;
+    q.ymx.v[2 * i] = v.x;
+    q.ymx.v[2 * i + 1] = v.y;
+    q.xy2d.v[2 * i] = w.x;
+    q.xy2d.v[2 * i + 1] = w.y;
+  }
+}
+
+struct JsfStream {  // the streamed addend and where the next ones come from
+  ge_aff q;
+  const uint32_t* A0;   // the receiver's slot of column 0 in plane K
+  uint32_t slot;        // this lane's column * nrecv (slots from A0; < 2^32 for any table that fits memory)
+  size_t plane;         // words between planes
+  const uint32_t* ev;   // the receiver's event list: plane and sign of every both-nonzero column, in
+  uint32_t next;        // chain order, JSF_EV_NONE-terminated; `next` follows the one in flight
+  int k;
+};
+
+// pair P of K / 2: pieces 2P (digit e0) and 2P + 1 (e1); the first K / 2 pieces sit in LDS
+template <int P, int K, int KL>
+DKG_DEV void jsf_position(ge_p3& acc, uint32_t w, const uint32_t* qs, const ge_aff* qr, JsfStream& s, bool last) {
+  if constexpr (2 * P < K) {
+    const int e0 = (int8_t)(w >> (16 * P)), e1 = (int8_t)(w >> (16 * P + 8));
+    bool t = last;  // else a doubling follows: no T
+    if constexpr (2 * P + 2 < K) t = t || (w >> (16 * P + 16)) != 0;
+    if (e0 != 0 && e1 != 0) {
+      // +/-(Q_2P + Q_2P+1) when the digits agree, +/-(Q_2P - Q_2P+1) when they differ: the sign is e0's
+      // (fetched with y+x and y-x exchanged when e0 < 0: jsf_fetch)
+      ge_madd_swapped<DKG_AFF_IL != 0>(acc, acc, s.q, e0 < 0, t);
+      const uint32_t e = s.next;
+      s.next = (uint32_t)__builtin_amdgcn_readfirstlane(s.ev[s.k]);
+      s.k++;
+      jsf_fetch(s.q, s.A0, s.slot, s.plane, e);
+    } else if (e0 != 0 || e1 != 0) {
+      constexpr int U0 = 2 * P, U1 = 2 * P + 1;
+      if constexpr (U1 < KL) {
+        const int u = e0 != 0 ? U0 : U1;
+        ge_madd_lds<DKG_AFF_IL != 0>(acc, acc, qs + u * AFF_WORDS * 64 + threadIdx.x, (e0 | e1) < 0, 64, t);
+      } else if (e0 != 0) {
+        if constexpr (U0 < KL) ge_madd_lds<DKG_AFF_IL != 0>(acc, acc, qs + U0 * AFF_WORDS * 64 + threadIdx.x, e0 < 0, 64, t);
+        else ge_madd_signed<DKG_AFF_IL != 0>(acc, acc, qr[U0 - KL], e0 < 0, t);
+      } else {
+        ge_madd_signed<DKG_AFF_IL != 0>(acc, acc, qr[U1 - KL], e1 < 0, t);
+      }
+    }
+    jsf_position<P + 1, K, KL>(acc, w, qs, qr, s, last);
+  }
+}
+
+// K = 2 or 4 pieces, the first KL addends in LDS and the others in VGPRs as in k_combine_aff; the
+// pair sums of planes K.. stream through one 30-word VGPR buffer.  ev: [nrecv][JSF_EV_WORDS].
+template <int K, int KL>
+__global__ __launch_bounds__(64, 2) void k_combine_jsf(size_t width, size_t pstride, size_t nrecv,
+                                                       const uint32_t* __restrict__ digits,
+                                                       const int16_t* __restrict__ top,
+                                                       const uint32_t* __restrict__ ev,
+                                                       const uint32_t* __restrict__ A, uint32_t* __restrict__ R,
+                                                       size_t j0) {
+  static_assert(K % 2 == 0 && K <= 4, "whole pairs in one digit word");
+  __shared__ uint32_t qs[KL * AFF_WORDS * 64];
+  const size_t c = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const size_t j = j0 + blockIdx.y;
+  const bool live = c < width;
+  const size_t cc = live ? c : 0;
+  ge_aff qr[K - KL > 0 ? K - KL : 1];
+  aff_addends<0, K, KL>(qs, qr, A, pstride, cc, nrecv, j);
+  const uint32_t* dw = digits + j * 256;
+  const int tp = top[j];
+  JsfStream s;
+  s.A0 = A + ((size_t)K * pstride * nrecv + j) * AFFP_WORDS;
+  s.slot = (uint32_t)(cc * nrecv);
+  s.plane = pstride * nrecv * AFFP_WORDS;
+  s.ev = ev + j * JSF_EV_WORDS;
+  s.next = (uint32_t)__builtin_amdgcn_readfirstlane(s.ev[1]);
+  s.k = 2;
+  // the register-resident addends have landed before the chain starts: the loop's first use of them
+  // would otherwise wait for every load in flight, the streamed addend's included
+#pragma unroll
+  for (int u = 0; u < K - KL; u++) {
+#pragma unroll
+    for (int i = 0; i < 10; i++)
+      asm volatile("" : "+v"(qr[u].ypx.v[i]), "+v"(qr[u].ymx.v[i]), "+v"(qr[u].xy2d.v[i]));
+  }
+  fe_zero(s.q.ypx);  // defined even if no column has both digits set
+  fe_zero(s.q.ymx);
+  fe_zero(s.q.xy2d);
+  jsf_fetch(s.q, s.A0, s.slot, s.plane, (uint32_t)__builtin_amdgcn_readfirstlane(s.ev[0]));
+  ge_p3 acc;
+  ge_identity(acc);
+#pragma unroll 1
+  for (int b = tp; b >= 0; b--) {
+    // readfirstlane returns a signed int: keep the word unsigned, the pair tests shift it right
+    const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane(dw[b]);
+    if (b != tp) ge_dbl_lean<DKG_AFF_IL != 0>(acc, acc, w != 0 || b == 0);
+    jsf_position<0, K, KL>(acc, w, qs, qr, s, b == 0);
+  }
+  if (live) pt_store_aos<DKG_COMB_NT != 0>(R, (size_t)s.slot + j, acc);  // live: cc = c
+}
+
+void combine_short_jsf(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* digits,
+                       const int16_t* top, const uint32_t* ev, const uint32_t* A, uint32_t* R, hipStream_t stream,
+                       size_t j0, size_t jn) {
+  if (!jn) jn = nrecv - j0;
+  if (!width || !jn || (pieces != 2 && pieces != 4)) return;
+  const dim3 grid((unsigned)((width + 63) / 64), (unsigned)jn);
+  if (pieces == 2)
+    hipLaunchKernelGGL((k_combine_jsf<2, 1>), grid, dim3(64), 0, stream, width, pstride, nrecv, digits, top, ev, A, R, j0);
+  else
+    hipLaunchKernelGGL((k_combine_jsf<4, 2>), grid, dim3(64), 0, stream, width, pstride, nrecv, digits, top, ev, A, R, j0);
+}
+
 void combine(size_t width, size_t pstride, size_t pieces, size_t nrecv, const int8_t* digits, const int16_t* top,
              uint32_t* R, hipStream_t stream) {
   if (!width || !nrecv || pieces < 2) return;

@@ -171,6 +171,21 @@ void affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv, co
 void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* digits,
                        const int16_t* top, const uint32_t* A, uint32_t* R, hipStream_t stream, size_t j0 = 0,
                        size_t jn = 0);
+// Pairwise joint sparse form (pieces = 2 or 4).  pair_sums writes Q_2p + Q_2p+1 and Q_2p - Q_2p+1 of
+// every pair p as piece planes pieces + 2p and pieces + 2p + 1 of R and Rz (complete formula: Z != 0),
+// so R, Rz and A hold pieces + 2 floor(pieces / 2) planes and affine_pieces runs over all of them.
+void pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv, uint32_t* R, uint32_t* Rz,
+               hipStream_t stream, size_t j0 = 0, size_t jn = 0);
+// combine_short_aff over JSF digits (runtime.hip split_short): a column with both digits of a pair
+// set adds the pair's sum or difference, streamed from its plane of A one such column ahead.
+// ev [nrecv][JSF_EV_WORDS]: one word per both-nonzero column in chain order -- positions downwards,
+// pair 0 before pair 1: bits 0-1 the plane after the pieces' (2 pair + 1 if the digits differ), bit
+// 2 set if the pair's first digit is negative -- then JSF_EV_NONE to the end of the row.
+constexpr uint32_t JSF_EV_NONE = 0xffu;
+constexpr size_t JSF_EV_WORDS = 384;  // <= 2/3 of 256 positions per pair, two pairs, two ahead
+void combine_short_jsf(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* digits,
+                       const int16_t* top, const uint32_t* ev, const uint32_t* A, uint32_t* R, hipStream_t stream,
+                       size_t j0 = 0, size_t jn = 0);
 // K3c: decision[i][j] = (g s_ij + h s'_ij == R[i][j]) (round 2) or (g s_ij == R[i][j]) (round 4);
 // dealer_ok[i] == 0 forces 0; self ((i + dealer_base) mod nmod == j + recv_base, nmod = parties per
 // ceremony, so batched ceremonies stacked dealer-wise work too) gives 2.

@@ -20,7 +20,9 @@
 // The row used is not simply the shortest: every combination sum_i c_i B_i, c_i in {-4..4}, of the
 // reduced basis is priced as the recombination chain runs -- (NAF length - 1) doublings plus one
 // addition per nonzero NAF digit of each entry -- and the cheapest is kept (5.5 % less chain work
-// than the shortest row on average at U = 4, n = 1024).
+// than the shortest row on average at U = 4, n = 1024).  For the pairwise chain (jsf) entries
+// (0,1) and (2,3) are priced by their joint sparse form instead: its length, and one addition per
+// nonzero column (a column with both digits set adds the pair's sum or difference once).
 #include <math.h>
 #include <string.h>
 
@@ -123,12 +125,35 @@ void i_naf_shape(const I512& a, int& len, int& weight) {
     if (h) len = 64 * i + 64 - __builtin_clzll(h);
   }
 }
-// issue-slot estimate of the recombination chain for the row v (doubling ~1815, mixed addition ~2002)
-double chain_cost(const I512* v, int K) {
+// JSF of (|a|, |b|), both below 2^253: length (highest nonzero column + 1) and joint weight (nonzero
+// columns: a both-nonzero column is ONE addition of a pair sum in the chain)
+void i_jsf_shape(const I512& a, const I512& b, int& len, int& weight) {
+  const I512 ma = i_neg_p(a) ? i_neg(a) : a, mb = i_neg_p(b) ? i_neg(b) : b;
+  uint8_t ba[32], bb[32];
+  for (int i = 0; i < 32; i++) {
+    ba[i] = (uint8_t)(ma.w[i / 8] >> (8 * (i % 8)));
+    bb[i] = (uint8_t)(mb.w[i / 8] >> (8 * (i % 8)));
+  }
+  int8_t da[256], db[256];
+  int16_t tp;
+  const int bits = i_bits(ma) > i_bits(mb) ? i_bits(ma) : i_bits(mb);
+  jsf_digits(ba, bb, da, db, &tp, bits + 2 < 256 ? bits + 2 : 256);  // one position past the top bit
+  len = tp + 1;
+  weight = 0;
+  for (int i = 0; i <= tp; i++) weight += (da[i] | db[i]) != 0;
+}
+// issue-slot estimate of the recombination chain for the row v (doubling ~1815, mixed addition ~2002):
+// per-scalar NAFs, or (jsf) pairs (0,1), (2,3) in joint sparse form and a leftover entry's NAF
+double chain_cost(const I512* v, int K, bool jsf) {
   int top = 0, adds = 0;
   for (int u = 0; u < K; u++) {
     int len, w;
-    i_naf_shape(v[u], len, w);
+    if (jsf && u + 1 < K) {
+      i_jsf_shape(v[u], v[u + 1], len, w);
+      u++;
+    } else {
+      i_naf_shape(v[u], len, w);
+    }
     top = top > len ? top : len;
     adds += w;
   }
@@ -187,7 +212,46 @@ void gram_schmidt(const I512 (*B)[KMAX], int K, long double (*mu)[KMAX], long do
 
 }  // namespace
 
-bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign) {
+// Solinas' joint sparse form of (a, b), 32 bytes LE each: digits in {-1, 0, 1} with
+// sum da[i] 2^i = a, sum db[i] 2^i = b, at least one zero column among any three consecutive
+// positions, and the fewest nonzero columns of any joint signed-binary form.  *top = the highest
+// position with a nonzero digit (-1: both zero).  False when the form does not end within 256
+// positions (an input of 2^255 or more can carry out); inputs below 2^253 end by position 253.
+// Only positions below npos are written (the caller knows both inputs are below 2^(npos - 1)).
+bool jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t* da, int8_t* db, int16_t* top, int npos) {
+  uint64_t k[2][5] = {{0}};
+  for (int i = 0; i < 32; i++) {
+    k[0][i / 8] |= (uint64_t)a[i] << (8 * (i % 8));
+    k[1][i / 8] |= (uint64_t)b[i] << (8 * (i % 8));
+  }
+  int c[2] = {0, 0};  // carries: the running value of scalar s at position i is (k[s] >> i) + c[s]
+  *top = -1;
+  for (int i = 0; i < npos; i++) {
+    int l[2], u[2];
+    for (int s = 0; s < 2; s++) {  // the low three bits of the running value (it may reach 8: 0 mod 8)
+      const int w = i >> 6, sh = i & 63;
+      uint64_t lo = k[s][w] >> sh;
+      if (sh > 61) lo |= k[s][w + 1] << (64 - sh);
+      l[s] = (int)(lo & 7) + c[s];
+    }
+    for (int s = 0; s < 2; s++) {
+      if (!(l[s] & 1)) {
+        u[s] = 0;
+      } else {
+        u[s] = (l[s] & 3) == 1 ? 1 : -1;
+        if (((l[s] & 7) == 3 || (l[s] & 7) == 5) && (l[1 - s] & 3) == 2) u[s] = -u[s];
+      }
+    }
+    for (int s = 0; s < 2; s++)
+      if (2 * c[s] == 1 + u[s]) c[s] = 1 - c[s];
+    da[i] = (int8_t)u[0];
+    db[i] = (int8_t)u[1];
+    if (u[0] | u[1]) *top = (int16_t)i;
+  }
+  return c[0] == 0 && c[1] == 0;
+}
+
+bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign, bool jsf) {
   if (K < 2 || K > KMAX) return false;
   I512 B[KMAX][KMAX];
   Zl p = zl_from_u64(1), pw[KMAX];
@@ -245,7 +309,7 @@ bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign) {
       for (int u = 0; u < K; u++) mult[i][c + CR][u] = i_mul_shift(B[i][u], c, 0);
   I512 v[KMAX];
   for (int u = 0; u < K; u++) v[u] = i_from_zl(pw[u]);  // fallback: the powers themselves
-  double best = chain_cost(v, K);
+  double best = chain_cost(v, K, jsf);
   I512 win[KMAX];
   bool have = false;
   int ncomb = 1;
@@ -266,7 +330,7 @@ bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign) {
       small = i_bits(c[u]) < 253;
     }
     if (!small) continue;
-    const double cost = chain_cost(c, K);
+    const double cost = chain_cost(c, K, jsf);
     if (!(cost < best)) continue;
     if (zl_is_zero(zl_of(c[0]))) continue;  // b must be invertible mod l ((l, 0, .., 0) is not)
     best = cost;

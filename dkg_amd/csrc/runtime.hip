@@ -70,7 +70,9 @@ struct dkg_ctx {
   size_t last_split_len = 0;            // and its piece length L
   size_t ydig_n = 0, ydig_L = 0;        // key of the cached combine multipliers (v.ydig)
   int combine_mode = 0;                 // recombination: 0 short vectors for U <= 5 (4 with
-                                        // projective addends), 1 powers of y, 2 = 0
+                                        // projective addends), pairwise JSF chains at U = 2, 4 with
+                                        // affine addends; 1 powers of y; 2 = 0; 3 short vectors
+                                        // with per-scalar NAF chains at every U
   int last_combine = 0;                 // 1: the last verify_device recombined with powers, 2: short vectors
   int last_binomial = 0;                // 1: the last verify_device ran the per-wave binomial
   int step_formula = 0;                 // stepping additions: 0 dedicated + complete redo of marked
@@ -88,6 +90,7 @@ struct dkg_ctx {
   int addend_mode = 0;                  // short vectors' addends: 0 affine Niels (affine_pieces, mixed
                                         // additions), 1 cached projective (read from R)
   size_t sdig_n = 0, sdig_L = 0, sdig_K = 0;  // key of the cached short multipliers (v.sdig)
+  int sdig_jsf = -1;                    // ... and their recoding (0 NAFs, 1 pairwise JSF)
   // the last verify_device's evaluations R[c][j] (point-major, column c = dealer for one segment),
   // their scale b_j 2^256 mod l (null: R holds P(j) itself) and the columns' decode mask: read by the
   // complaint verification, which runs the pipeline without its checks (VerifySeg::dec == null)
@@ -388,7 +391,11 @@ constexpr size_t SHORT_MAX = 5;
 #define DKG_AUTO_SHORT5 0
 #endif
 
-double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, bool short_mult) {
+// short_mult: 0 powers of y, 1 short multipliers as per-scalar NAFs, 2 pairwise JSF where built
+constexpr int SM_POWERS = 0, SM_NAF = 1, SM_JSF = 2;
+bool jsf_built(size_t U) { return U == 2 || U == 4; }  // k_combine_jsf
+
+double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, int short_mult) {
   const double DBL = 1000, ADD = 1400, SIMDS = 1024, THR = 4.5, LAT = 8, LAT_ILP = 6, LAUNCH = 3e-3 * 2.4e6;
   const size_t Lr = last_piece_len(N, U, L), off = L - Lr;  // the last piece: Lr positions, starts at step off
   auto cost = [&](size_t m) {  // one binomial position-step: add + multiplication by m
@@ -437,8 +444,13 @@ double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, bool 
     // length (~1/3 nonzero); powers of y: pairwise joint chains, an even U starting with one
     // product (253 doublings + ~85 NAF additions), then (ceil(U/2) - 1) joint y^2 / y steps (253
     // doublings + ~170 additions)
+    // pairwise JSF (U = 2, 4): a pair's joint form has every second column nonzero, a leftover
+    // piece's NAF every third; the 2 floor(U/2) pair sums cost 7 products each to form and ~16 to
+    // normalise (k_pair_sums, k_affine_pieces: ~23 of an addition's 8)
     const double bits = 253.0 * (U - 1) / U;
-    const double per = short_mult && U <= SHORT_MAX ? bits * 950 + U * bits / 3 * ADD
+    const bool jsf = short_mult == SM_JSF && jsf_built(U);
+    const double adds = jsf ? (U / 2) * bits / 2 + (U % 2) * bits / 3 : U * bits / 3;
+    const double per = short_mult && U <= SHORT_MAX ? bits * 950 + adds * ADD + (jsf ? 2 * (U / 2) * 23.0 / 8 * ADD : 0.0)
                                             : (U % 2 == 0 ? 253 * 950 + 85 * ADD : 0.0) +
                                                   ((U + 1) / 2 - 1) * (253 * 950 + 170 * ADD);
     const double waves = (double)cols / 64 * n;
@@ -454,7 +466,7 @@ double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, bool 
 // piece (N = 550, U = 2: 320 + 230 instead of 275 + 275, two tables of 5 and 4 waves instead of
 // 5 + 5 with 45 idle lanes each).  When all pieces of a column fit one stepping workgroup
 // (N <= 512) ceil(N / U) always wins: N = 512, U = 3 runs 171 + 171 + 170 on 512 lanes.
-size_t split_len(size_t cols, size_t n, size_t N, size_t U, bool short_mult = true) {
+size_t split_len(size_t cols, size_t n, size_t N, size_t U, int short_mult = SM_JSF) {
   const size_t L1 = (N + U - 1) / U;
   if (U == 1) return L1;
   const size_t L64 = (L1 + 63) / 64 * 64;
@@ -462,13 +474,19 @@ size_t split_len(size_t cols, size_t n, size_t N, size_t U, bool short_mult = tr
   return split_model_ms(cols, n, N, U, L64, short_mult) < split_model_ms(cols, n, N, U, L1, short_mult) ? L64 : L1;
 }
 
-double split_model_ms(size_t cols, size_t n, size_t N, size_t U, bool short_mult = true) {
+double split_model_ms(size_t cols, size_t n, size_t N, size_t U, int short_mult = SM_JSF) {
   return split_model_ms(cols, n, N, U, split_len(cols, n, N, U, short_mult), short_mult);
+}
+
+// the recombination the context's settings select (JSF needs the affine addends' planes)
+int short_kind(const dkg_ctx* ctx) {
+  if (ctx->combine_mode == 1) return SM_POWERS;
+  return ctx->combine_mode == 3 || ctx->addend_mode != 0 ? SM_NAF : SM_JSF;
 }
 
 size_t choose_split(dkg_ctx* ctx, size_t cols, size_t n, size_t N) {
   if (ctx->split > 0) return std::min<size_t>((size_t)ctx->split, N);
-  const bool sm = ctx->combine_mode != 1;
+  const int sm = short_kind(ctx);
   const double base = split_model_ms(cols, n, N, 1, sm);
   std::vector<double> ms(17, 0.0);
   double best_ms = base;
@@ -479,7 +497,7 @@ size_t choose_split(dkg_ctx* ctx, size_t cols, size_t n, size_t N) {
     // they are parity-tested (forced splits) but their shard timings are unmeasured, so by default
     // the model ranks U = 5 with powers as before (it then never wins) -- dkg_ctx_set_split(5)
     // runs them
-    ms[U] = split_model_ms(cols, n, N, U, sm && (U <= 4 || (ctx->addend_mode == 0 && DKG_AUTO_SHORT5)));
+    ms[U] = split_model_ms(cols, n, N, U, U <= 4 || (ctx->addend_mode == 0 && DKG_AUTO_SHORT5) ? sm : SM_POWERS);
     best_ms = std::min(best_ms, ms[U]);
     umax = U;
   }
@@ -548,9 +566,9 @@ void split_digits(dkg_ctx* ctx, size_t n, size_t L, const int8_t** digits, const
 // Short recombination multipliers (lattice.cpp) of receivers j = 1..n for a K-way split, K <= 4
 // (k_combine_short): digits [n][256] u32, byte u of word b = the signed NAF digit at position b of
 // the scalar of piece u; top [n] int16 = the highest position with a nonzero digit; scale [n][8]
-// words = b_j 2^256 mod l, the checks' Montgomery factor taking s to b_j s.  Cached per (n, L, K).
+// words = b_j 2^256 mod l, the checks' Montgomery factor taking s to b_j s.  Cached per (n, L, K, recoding).
 // (one LLL per receiver, ~1 ms at K = 4: spread over up to 16 host threads)
-void short_vectors(size_t n, size_t L, size_t K, std::vector<uint8_t>& mag, std::vector<int8_t>& sign) {
+void short_vectors(size_t n, size_t L, size_t K, std::vector<uint8_t>& mag, std::vector<int8_t>& sign, bool jsf) {
   mag.assign(n * K * 32, 0);
   sign.assign(n * K, 1);
   auto rows = [&](size_t j0, size_t j1) {
@@ -560,7 +578,7 @@ void short_vectors(size_t n, size_t L, size_t K, std::vector<uint8_t>& mag, std:
         if (e & 1) y = dkgh::zl_mul(y, x);
         x = dkgh::zl_mul(x, x);
       }
-      dkgh::short_multipliers(y, (int)K, reinterpret_cast<uint8_t(*)[32]>(&mag[j * K * 32]), &sign[j * K]);
+      dkgh::short_multipliers(y, (int)K, reinterpret_cast<uint8_t(*)[32]>(&mag[j * K * 32]), &sign[j * K], jsf);
     }
   };
   const size_t nt = std::min<size_t>({(size_t)std::max(1u, std::thread::hardware_concurrency()), 16, (n + 63) / 64});
@@ -570,43 +588,90 @@ void short_vectors(size_t n, size_t L, size_t K, std::vector<uint8_t>& mag, std:
   for (auto& t : th) t.join();
 }
 
-void split_short(dkg_ctx* ctx, size_t n, size_t L, size_t K, const uint32_t** digits, const int16_t** top,
-                 const uint32_t** scale) {
+// The chain's digit words for the rows (mag, sign) of short_vectors: hd [2][n][256] (word 0: pieces
+// 0..3, word 1: 4..), ht [n].  jsf: pairs (0,1) and (2,3) are recoded jointly in Solinas' joint
+// sparse form (magnitudes first, then each scalar's sign on its digits), a leftover piece keeps its
+// NAF; hev [n][JSF_EV_WORDS] then lists the pair-sum plane and sign of every both-nonzero column in
+// chain order (kernels_decl.inc combine_short_jsf).  A JSF may be one position longer than the NAF:
+// entries are below 2^253, so 256 positions hold it.
+bool short_digit_words(size_t n, size_t K, bool jsf, const std::vector<uint8_t>& mag, const std::vector<int8_t>& sign,
+                       std::vector<uint32_t>& hd, std::vector<int16_t>& ht, std::vector<uint32_t>* hev) {
+  hd.assign(2 * 256 * n, 0);
+  ht.assign(n, -1);
+  if (hev) hev->assign(dkgk::JSF_EV_WORDS * n, dkgk::JSF_EV_NONE);
+  for (size_t j = 0; j < n; j++) {
+    auto put = [&](size_t u, const int8_t* d) {
+      for (int b = 0; b < 256; b++)
+        hd[(u / 4) * 256 * n + 256 * j + b] |= (uint32_t)(uint8_t)(int8_t)(d[b] * sign[j * K + u]) << (8 * (u % 4));
+    };
+    for (size_t u = 0; u < K; u++) {
+      int8_t d[256], d1[256];
+      int16_t tp;
+      if (jsf && u + 1 < K) {
+        if (!dkgh::jsf_digits(&mag[(j * K + u) * 32], &mag[(j * K + u + 1) * 32], d, d1, &tp)) return false;
+        put(u, d);
+        put(u + 1, d1);
+        u++;
+      } else {
+        naf_digits(&mag[(j * K + u) * 32], d, &tp);
+        put(u, d);
+      }
+      ht[j] = std::max(ht[j], tp);
+    }
+    if (jsf && hev) {
+      size_t k = 0;
+      for (int b = ht[j]; b >= 0; b--) {
+        const uint32_t w = hd[256 * j + b];
+        for (size_t p = 0; p < K / 2 && p < 2; p++) {
+          const int e0 = (int8_t)(w >> (16 * p)), e1 = (int8_t)(w >> (16 * p + 8));
+          if (!e0 || !e1) continue;
+          if (k + 2 >= dkgk::JSF_EV_WORDS) return false;  // never for a JSF (<= 2/3 of the columns)
+          (*hev)[dkgk::JSF_EV_WORDS * j + k++] = (uint32_t)(2 * p + (e0 != e1) + (e0 < 0 ? 4 : 0));
+        }
+      }
+    }
+  }
+  return true;
+}
+
+void split_short(dkg_ctx* ctx, size_t n, size_t L, size_t K, bool jsf, const uint32_t** digits, const int16_t** top,
+                 const uint32_t** scale, const uint32_t** events) {
   uint32_t* dd = buf<uint32_t>(ctx, "v.sdig", 2 * 4 * 256 * n);  // word 0: pieces 0..3, word 1: 4..
   int16_t* dt = buf<int16_t>(ctx, "v.stop", 2 * n);
   uint32_t* ds = buf<uint32_t>(ctx, "v.sscale", 32 * n);
+  uint32_t* de = buf<uint32_t>(ctx, "v.sev", 4 * dkgk::JSF_EV_WORDS * n);
   *digits = dd;
   *top = dt;
   *scale = ds;
-  if (ctx->sdig_n == n && ctx->sdig_L == L && ctx->sdig_K == K) return;
+  *events = de;
+  if (ctx->sdig_n == n && ctx->sdig_L == L && ctx->sdig_K == K && ctx->sdig_jsf == (int)jsf) return;
   std::vector<uint8_t> mag;
   std::vector<int8_t> sign;
-  short_vectors(n, L, K, mag, sign);
-  std::vector<uint32_t> hd(2 * 256 * n, 0), hs(8 * n, 0);
-  std::vector<int16_t> ht(n, -1);
+  short_vectors(n, L, K, mag, sign, jsf);
+  std::vector<uint32_t> hd, hs(8 * n, 0), hev;
+  std::vector<int16_t> ht;
+  if (!short_digit_words(n, K, jsf, mag, sign, hd, ht, &hev)) {
+    ctx->err = "split_short: a joint sparse form does not fit its digit words";
+    throw Fail{DKG_E_ARG};
+  }
   uint8_t r256[33] = {0};
   r256[32] = 1;
   const dkgh::Zl R = dkgh::zl_from_bytes_wide(r256, 33);  // 2^256 mod l
   for (size_t j = 0; j < n; j++) {
-    for (size_t u = 0; u < K; u++) {
-      int8_t d[256];
-      int16_t tp;
-      naf_digits(&mag[(j * K + u) * 32], d, &tp);
-      ht[j] = std::max(ht[j], tp);
-      for (int b = 0; b < 256; b++)
-        hd[(u / 4) * 256 * n + 256 * j + b] |= (uint32_t)(uint8_t)(int8_t)(d[b] * sign[j * K + u]) << (8 * (u % 4));
-    }
     const dkgh::Zl b = dkgh::zl_from_bytes_wide(&mag[j * K * 32], 32);  // b > 0
     uint8_t w[32];
     dkgh::zl_to_bytes(w, dkgh::zl_mul(b, R));
     memcpy(&hs[8 * j], w, 32);
   }
+  ctx->sdig_jsf = -1;  // the key holds only once every copy is queued
   h2d(ctx, dd, hd.data(), 4 * hd.size());
   h2d(ctx, dt, ht.data(), 2 * n);
   h2d(ctx, ds, hs.data(), 4 * hs.size());
+  h2d(ctx, de, hev.data(), 4 * hev.size());
   ctx->sdig_n = n;
   ctx->sdig_L = L;
   ctx->sdig_K = K;
+  ctx->sdig_jsf = (int)jsf;
 }
 
 // One or two segments on device, as ONE pipeline over "virtual dealers" (table columns).  With two
@@ -632,7 +697,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   const size_t groups = (D + 63) / 64, gw = 64 * nseg;  // columns per dealer group
   const size_t npad = groups * gw;
   // degree split: U pieces of L positions; piece u of column c is table column u * npad + c
-  const size_t U = choose_split(ctx, npad, n, N), L = split_len(npad, n, N, U, ctx->combine_mode != 1), W = U * npad;
+  const size_t U = choose_split(ctx, npad, n, N), L = split_len(npad, n, N, U, short_kind(ctx)), W = U * npad;
   const size_t Lr = last_piece_len(N, U, L);  // the last piece's length (L or shorter)
   const bool whole = ctx->step_mode == 1 || ((ctx->step_mode == 0 || ctx->step_mode == 3) && stepping_whole_pays(npad, U, L, Lr));
   // the stepping keeps product scanning even at 2 waves per SIMD (8-way n=1024 shard, one stream:
@@ -648,7 +713,14 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   uint32_t* e0 = buf<uint32_t>(ctx, "v.binom0", PTB * L * W);
   uint32_t* e1 = buf<uint32_t>(ctx, "v.binom1", PTB * L * W);
   uint32_t* eT = buf<uint32_t>(ctx, "v.binomT", PTB * L * W);  // column-major copy for the stepping
-  uint32_t* R = buf<uint32_t>(ctx, "v.R", PTB * W * n);
+  // short multipliers up to SHORT_MAX pieces with affine addends, 4 with projective ones
+  const bool short_mult = U > 1 && U <= (ctx->addend_mode == 0 ? SHORT_MAX : 4) && ctx->combine_mode != 1;
+  // pairwise JSF chains: the pairs' sums and differences are 2 floor(U/2) more piece planes of R, Rz
+  // and Aff after the U stepped ones (the chunk offsets do not change)
+  // (k_combine_jsf keeps a lane's column * n in 32 bits: any table that fits device memory)
+  const bool jsf = short_mult && short_kind(ctx) == SM_JSF && jsf_built(U) && (uint64_t)npad * n < (1ull << 32);
+  const size_t WP = jsf ? (U + 2 * (U / 2)) * npad : W;
+  uint32_t* R = buf<uint32_t>(ctx, "v.R", PTB * WP * n);
   uint32_t *sa = nullptr, *sb = nullptr;
   if (L > 512) {
     sa = buf<uint32_t>(ctx, "v.step_a", PTB * W * n);
@@ -656,20 +728,18 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   }
   const int8_t* ydig = nullptr;
   const int16_t* ytop = nullptr;
-  const uint32_t *sdig = nullptr, *sscale = nullptr;  // short multipliers: R holds b_j P(j)
+  const uint32_t *sdig = nullptr, *sscale = nullptr, *sev = nullptr;  // short multipliers: R holds b_j P(j)
   const int16_t* stop = nullptr;
-  // short multipliers up to SHORT_MAX pieces with affine addends, 4 with projective ones
-  const bool short_mult = U > 1 && U <= (ctx->addend_mode == 0 ? SHORT_MAX : 4) && ctx->combine_mode != 1;
   // stepping flags of the dedicated additions: chunk c0's words start at stepping_flag_words(c0, U)
   uint32_t* sflags = ctx->step_formula == 0
                          ? buf<uint32_t>(ctx, "v.sflags", 4 * dkgk::stepping_flag_words(npad, U)) : nullptr;
   ctx->last_step_flags = sflags;
   ctx->last_step_flag_words = sflags ? dkgk::stepping_flag_words(npad, U) : 0;
   // affine addends: one 128-B slot per (piece column, receiver), like R
-  uint32_t* Aff = short_mult && ctx->addend_mode == 0 ? buf<uint32_t>(ctx, "v.Aff", 4 * AFFP_WORDS_H * W * n) : nullptr;
+  uint32_t* Aff = short_mult && ctx->addend_mode == 0 ? buf<uint32_t>(ctx, "v.Aff", 4 * AFFP_WORDS_H * WP * n) : nullptr;
   // the stepping's dense copy of each stored point's Z (40 B), read by the affine normalisation
-  uint32_t* Rz = Aff ? buf<uint32_t>(ctx, "v.Rz", 40 * W * n) : nullptr;
-  if (short_mult) split_short(ctx, n, L, U, &sdig, &stop, &sscale);
+  uint32_t* Rz = Aff ? buf<uint32_t>(ctx, "v.Rz", 40 * WP * n) : nullptr;
+  if (short_mult) split_short(ctx, n, L, U, jsf, &sdig, &stop, &sscale, &sev);
   else if (U > 1) split_digits(ctx, n, L, &ydig, &ytop);
   ctx->last_combine = U > 1 ? (short_mult ? 2 : 1) : 0;
   ctx->last_R = R;
@@ -799,7 +869,12 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
               Rz ? Rz + c0 * n * 10 : nullptr, tail_a, tail_b))
       throw Fail{DKG_E_ARG};  // stepping flag words: an internal layout error, never silently dropped
     if (tm) HCK(hipEventRecord(ctx->pev[2], st));
-    if (short_mult && Aff) {
+    if (jsf) {
+      dkgk::pair_sums(w, npad, U, n, R + c0 * n * PT_WORDS_H, Rz + c0 * n * 10, st);
+      dkgk::affine_pieces(w, npad, U + 2 * (U / 2), n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st,
+                          Rz + c0 * n * 10);
+      dkgk::combine_short_jsf(w, npad, U, n, sdig, stop, sev, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
+    } else if (short_mult && Aff) {
       dkgk::affine_pieces(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, Rz + c0 * n * 10);
       dkgk::combine_short_aff(w, npad, U, n, sdig, stop, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
     } else if (short_mult) dkgk::combine_short(w, npad, U, n, sdig, stop, R + c0 * n * PT_WORDS_H, st);
@@ -2577,7 +2652,7 @@ int dkg_ctx_set_stepping(dkg_ctx* ctx, int mode) {
 int dkg_ctx_last_split(const dkg_ctx* ctx) { return ctx ? ctx->last_split : 0; }
 size_t dkg_ctx_last_split_len(const dkg_ctx* ctx) { return ctx ? ctx->last_split_len : 0; }
 int dkg_ctx_set_combine(dkg_ctx* ctx, int mode) {
-  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  if (!ctx || mode < 0 || mode > 3) return DKG_E_ARG;
   ctx->combine_mode = mode;
   return DKG_OK;
 }
@@ -2613,9 +2688,36 @@ int dkg_split_multipliers(size_t n, size_t L, int pieces, uint8_t* mag, int8_t* 
   try {
     std::vector<uint8_t> m;
     std::vector<int8_t> sg;
-    short_vectors(n, L, (size_t)pieces, m, sg);
+    short_vectors(n, L, (size_t)pieces, m, sg, jsf_built((size_t)pieces));  // the default mode's rows
     memcpy(mag, m.data(), m.size());
     memcpy(sign, sg.data(), sg.size());
+  } catch (const std::exception&) {
+    return DKG_E_NOMEM;
+  }
+  return DKG_OK;
+}
+int dkg_jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t da[256], int8_t db[256], int16_t* top) {
+  if (!a || !b || !da || !db || !top) return DKG_E_ARG;
+  return dkgh::jsf_digits(a, b, da, db, top) ? DKG_OK : DKG_E_ARG;
+}
+int dkg_split_digits(size_t n, size_t L, int pieces, int mode, int8_t* digits, int16_t* top) {
+  if (!n || !L || pieces < 2 || pieces > (int)SHORT_MAX || mode < 0 || mode > 3 || mode == 1 || !digits || !top)
+    return DKG_E_ARG;
+  try {
+    const size_t K = (size_t)pieces;
+    const bool jsf = mode != 3 && jsf_built(K);
+    std::vector<uint8_t> m;
+    std::vector<int8_t> sg;
+    short_vectors(n, L, K, m, sg, jsf);
+    std::vector<uint32_t> hd;
+    std::vector<int16_t> ht;
+    if (!short_digit_words(n, K, jsf, m, sg, hd, ht, nullptr)) return DKG_E_ARG;
+    for (size_t j = 0; j < n; j++) {
+      top[j] = ht[j];
+      for (size_t u = 0; u < K; u++)
+        for (size_t b = 0; b < 256; b++)
+          digits[(j * K + u) * 256 + b] = (int8_t)(hd[(u / 4) * 256 * n + 256 * j + b] >> (8 * (u % 4)));
+    }
   } catch (const std::exception&) {
     return DKG_E_NOMEM;
   }
