@@ -170,6 +170,11 @@ def lib():
                                                      ctypes.POINTER(CeremonyOut), p, p, p]
     L.dkg_ceremony_verify_full_proven.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p, u8p, sz, p, p,
                                                   u8p, u8p, ctypes.POINTER(CeremonyOut), p, p, p, p, p]
+    L.dkg_ceremony_batch_verify_proven.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, p, u8p, u8p,
+                                                   ctypes.POINTER(BatchOut), p, p, p]
+    L.dkg_ceremony_batch_verify_full_proven.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, p, u8p,
+                                                        u8p, sz, p, p, p, u8p, u8p, ctypes.POINTER(BatchOut), p, p, p, p,
+                                                        p, p, p]
     L.dkg_dealer_coeffs.argtypes = [u8p, ctypes.c_uint32, sz, sz, sz, p, p]
     L.dkg_scalar_sum_device.argtypes = [p, sz, sz, p, p, p]
     L.dkg_point_sum_device.argtypes = [p, sz, p, p, p]
@@ -231,4 +236,5 @@ EXPORTED = [
     "dkg_ceremony_batch_verify_full", "dkg_ctx_set_batch_full_chunk",
     "dkg_complaints_prove", "dkg_complaints_verify", "dkg_ctx_set_complaint_eval", "dkg_ceremony_verify_full_complaints",
     "dkg_complaints3_verify", "dkg_ceremony_verify_fetched_proven", "dkg_ceremony_verify_full_proven",
+    "dkg_ceremony_batch_verify_proven", "dkg_ceremony_batch_verify_full_proven",
 ]

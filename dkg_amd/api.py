@@ -969,6 +969,84 @@ def ceremony_batch_verify_full(be: "Backend", B: int, n: int, t: int, E: bytes, 
     return r
 
 
+@dataclass
+class BatchProvenResult:
+    """A batch whose ceremonies follow the PROVEN complaints (ceremony_batch_verify_proven,
+    ceremony_batch_verify_full_proven).  `ceremony`, `accused*` as given; verdict4 / verdict in input
+    order; finalise_status, recovery_index per ceremony as ProvenResult's; full mode adds the round-1
+    complaints' verdict and dissent [B*n].  ceremony(c) is one ceremony's view: the fields of
+    BatchResult.ceremony(c) plus its own verdicts (in their relative order), dissent and status."""
+    result: BatchResult
+    ceremony4: List[int]
+    verdict4: List[int]
+    finalise_status: List[int]
+    recovery_index: List[int]
+    ceremony2: Optional[List[int]] = None
+    verdict: Optional[List[int]] = None
+    dissent: Optional[List[int]] = None
+
+    def ceremony(self, c: int) -> dict:
+        n = self.result.n
+        d = self.result.ceremony(c)
+        d["verdict4"] = [v for g, v in zip(self.ceremony4, self.verdict4) if g == c]
+        d["finalise_status"], d["recovery_index"] = self.finalise_status[c], self.recovery_index[c]
+        if self.verdict is not None:
+            d["verdict"] = [v for g, v in zip(self.ceremony2, self.verdict) if g == c]
+            d["dissent"] = self.dissent[c * n:(c + 1) * n]
+            sz = 32 * n * n
+            d["s"], d["s_prime"] = self.result.s[sz * c:sz * (c + 1)], self.result.s_prime[sz * c:sz * (c + 1)]
+        return d
+
+
+def _opt(b):
+    return None if b is None else bytes(b)
+
+
+def ceremony_batch_verify_proven(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, s: bytes, s_prime: bytes,
+                                 ceremony4: Sequence[int], accusers4: Sequence[int], accused4: Sequence[int],
+                                 share4: bytes, randomness4: bytes, fetched1: Optional[bytes] = None,
+                                 fetched3: Optional[bytes] = None) -> BatchProvenResult:
+    """Backend.ceremony_verify_fetched_proven for every ceremony of a batch
+    (dkg_ceremony_batch_verify_proven): complaint c belongs to ceremony4[c] (0-based), accusers4 /
+    accused4 are 1-based within it; any order.  fetched1 / fetched3 [B*n], None = all present."""
+    C4 = len(accusers4)
+    o, bufs = _batch_out(B, n, True)
+    res4 = _carray(ctypes.c_int32, C4)
+    st, ri = _carray(ctypes.c_int32, B), _carray(ctypes.c_int32, B)
+    u32 = ctypes.c_uint32
+    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_proven(
+        be.ctx, B, n, t, E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(u32, C4, ceremony4),
+        _carray(u32, C4, accusers4), _carray(u32, C4, accused4), share4, randomness4, ctypes.byref(o), res4, st, ri))
+    return BatchProvenResult(_batch_result(B, n, t, o, bufs), list(ceremony4), list(res4)[:C4], list(st)[:B],
+                             list(ri)[:B])
+
+
+def ceremony_batch_verify_full_proven(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, e1: bytes, ct: bytes,
+                                      sk: bytes, pk: bytes, ceremony: Sequence[int], accusers: Sequence[int],
+                                      accused: Sequence[int], proofs: bytes, ceremony4: Sequence[int],
+                                      accusers4: Sequence[int], accused4: Sequence[int], share4: bytes,
+                                      randomness4: bytes, fetched3: Optional[bytes] = None) -> BatchProvenResult:
+    """Backend.ceremony_verify_full_proven for every ceremony of a batch
+    (dkg_ceremony_batch_verify_full_proven): sk, pk [B][n][32]; the round-1 complaints (ceremony,
+    accusers, accused, proofs [C][192]) and the round-4 complaints (ceremony4, ...) as flat lists over
+    the batch.  The result also carries the decrypted s / s_prime."""
+    C, C4 = len(accusers), len(accusers4)
+    o, bufs = _batch_out(B, n, True)
+    size = 32 * B * n * n
+    s, sp = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
+    res, res4, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4), _carray(ctypes.c_int32, B * n)
+    st, ri = _carray(ctypes.c_int32, B), _carray(ctypes.c_int32, B)
+    u32 = ctypes.c_uint32
+    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_full_proven(
+        be.ctx, B, n, t, E, A, e1, ct, sk, pk, C, _carray(u32, C, ceremony), _carray(u32, C, accusers),
+        _carray(u32, C, accused), proofs, _opt(fetched3), C4, _carray(u32, C4, ceremony4), _carray(u32, C4, accusers4),
+        _carray(u32, C4, accused4), share4, randomness4, ctypes.byref(o), s, sp, res, dis, res4, st, ri))
+    r = _batch_result(B, n, t, o, bufs)
+    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
+    return BatchProvenResult(r, list(ceremony4), list(res4)[:C4], list(st)[:B], list(ri)[:B], list(ceremony),
+                             list(res)[:C], list(dis)[:B * n])
+
+
 class Environment:
     """committee.rs:24-28 / :72-83 — threshold, nr_members and the Pedersen commitment key h."""
 

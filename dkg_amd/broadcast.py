@@ -309,6 +309,17 @@ def intake_phase4(n: int, msgs: Sequence[Optional[BroadcastPhase4]]) -> Tuple[Li
     return accuser, accused, b"".join(share), b"".join(randomness)
 
 
+def _hybrid_items(n: int, p1: Phase1Intake) -> Tuple[bytes, bytes]:
+    """A full-mode phase-1 intake as the (e1, ct) arrays of the C ABI: items (dealer i, recipient q, w) at
+    (i n + q) 2 + w, w = 0 the randomness, e1 and e2 apart."""
+    e1, ct = bytearray(64 * n * n), bytearray(64 * n * n)
+    for k in range(n * n):
+        for w, src in enumerate((p1.randomness, p1.share)):
+            e1[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k:64 * k + 32]
+            ct[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k + 32:64 * k + 64]
+    return bytes(e1), bytes(ct)
+
+
 def verify_broadcasts_proven(be, n: int, t: int, phase1: Sequence[Optional[BroadcastPhase1]],
                              phase3: Sequence[Optional[BroadcastPhase3]],
                              phase4: Sequence[Optional[BroadcastPhase4]],
@@ -331,14 +342,80 @@ def verify_broadcasts_proven(be, n: int, t: int, phase1: Sequence[Optional[Broad
         p1 = intake_phase1(n, t, phase1, mode=1)
         if not all(p1.fetched1):
             raise ValueError("full mode needs every phase-1 broadcast")
-        # items (dealer i, recipient q, w) at (i n + q) 2 + w, w = 0 the randomness: e1 and e2 apart
-        e1, ct = bytearray(64 * n * n), bytearray(64 * n * n)
-        for k in range(n * n):
-            for w, src in enumerate((p1.randomness, p1.share)):
-                e1[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k:64 * k + 32]
-                ct[32 * (2 * k + w):32 * (2 * k + w + 1)] = src[64 * k + 32:64 * k + 64]
+        e1, ct = _hybrid_items(n, p1)
         acc2, acd2, proofs = intake_phase2(n, phase2)
-        r = be.ceremony_verify_full_proven(p1.E, A, bytes(e1), bytes(ct), sk, pk, acc2, acd2, proofs, acc4, acd4, sh4,
+        r = be.ceremony_verify_full_proven(p1.E, A, e1, ct, sk, pk, acc2, acd2, proofs, acc4, acd4, sh4,
                                            rn4, n, t, fetched3=f3)
     r.result.fetch_invalid = list(p1.fetch_invalid)  # receivers whose round 2 aborts (committee.rs:277-280)
     return r
+
+
+def intake_batch_phase2(n: int, batch: Sequence[Sequence[Optional[BroadcastPhase2]]]):
+    """intake_phase2 for every ceremony of a batch, concatenated with the 0-based ceremony index of each
+    complaint: (ceremony, accuser, accused, proofs) as ceremony_batch_verify_full_proven takes them."""
+    ceremony: List[int] = []
+    accuser: List[int] = []
+    accused: List[int] = []
+    proofs: List[bytes] = []
+    for c, msgs in enumerate(batch):
+        acc, acd, prf = intake_phase2(n, msgs)
+        ceremony += [c] * len(acc)
+        accuser += acc
+        accused += acd
+        proofs.append(prf)
+    return ceremony, accuser, accused, b"".join(proofs)
+
+
+def intake_batch_phase4(n: int, batch: Sequence[Sequence[Optional[BroadcastPhase4]]]):
+    """intake_phase4 for every ceremony of a batch: (ceremony, accuser, accused, share, randomness)."""
+    ceremony: List[int] = []
+    accuser: List[int] = []
+    accused: List[int] = []
+    share: List[bytes] = []
+    randomness: List[bytes] = []
+    for c, msgs in enumerate(batch):
+        acc, acd, sh, rn = intake_phase4(n, msgs)
+        ceremony += [c] * len(acc)
+        accuser += acc
+        accused += acd
+        share.append(sh)
+        randomness.append(rn)
+    return ceremony, accuser, accused, b"".join(share), b"".join(randomness)
+
+
+def batch_proven_arguments(n: int, t: int, phase1, phase3, phase4, phase2=None, sk=None, pk=None) -> dict:
+    """The broadcasts of B ceremonies (phase1[c], phase3[c], phase4[c], phase2[c]: one list of n messages
+    per ceremony, as verify_broadcasts_proven takes one; sk, pk: one [n][32] per ceremony) as the keyword
+    arguments of ceremony_batch_verify_proven (sk is None) or ceremony_batch_verify_full_proven.  Host
+    work only."""
+    B = len(phase1)
+    if len(phase3) != B or len(phase4) != B:
+        raise ValueError("one list of broadcasts per ceremony expected")
+    full = sk is not None
+    if full and (pk is None or phase2 is None or len(phase2) != B or len(sk) != B or len(pk) != B):
+        raise ValueError("full mode needs the member keys and the phase-2 broadcasts of every ceremony")
+    p1 = [intake_phase1(n, t, m, mode=1 if full else 0) for m in phase1]
+    p3 = [intake_phase3(n, t, m) for m in phase3]
+    cer4, acc4, acd4, sh4, rn4 = intake_batch_phase4(n, phase4)
+    args = dict(B=B, n=n, t=t, E=b"".join(p.E for p in p1), A=b"".join(a for a, _ in p3),
+                fetched3=b"".join(f for _, f in p3), ceremony4=cer4, accusers4=acc4, accused4=acd4, share4=sh4,
+                randomness4=rn4)
+    if full:
+        if not all(all(p.fetched1) for p in p1):
+            raise ValueError("full mode needs every phase-1 broadcast")
+        items = [_hybrid_items(n, p) for p in p1]
+        cer2, acc2, acd2, proofs = intake_batch_phase2(n, phase2)
+        args.update(e1=b"".join(e for e, _ in items), ct=b"".join(c for _, c in items), sk=b"".join(sk),
+                    pk=b"".join(pk), ceremony=cer2, accusers=acc2, accused=acd2, proofs=proofs)
+    else:
+        args.update(s=b"".join(p.share for p in p1), s_prime=b"".join(p.randomness for p in p1),
+                    fetched1=b"".join(p.fetched1 for p in p1))
+    return args
+
+
+def verify_broadcasts_batch_proven(be, n: int, t: int, phase1, phase3, phase4, phase2=None, sk=None, pk=None):
+    """verify_broadcasts_proven for a batch of ceremonies in one call (a BatchProvenResult)."""
+    from . import api
+    args = batch_proven_arguments(n, t, phase1, phase3, phase4, phase2, sk, pk)
+    fn = api.ceremony_batch_verify_proven if sk is None else api.ceremony_batch_verify_full_proven
+    return fn(be, **args)

@@ -217,20 +217,23 @@ void cmp_ladder(size_t cnt, bool joint, const uint32_t* bp, const uint32_t* bq, 
 
 // ------------------------------------------------------------------ P_i(j) per pair
 // Horner in the exponent, k_horner generalised to a list of (row, index) pairs: lane = pair
-// list[k] = complaint c, row = accused[c] - 1 of the decoded commitments Eext (element row * N + k),
-// index x = accuser[c] (< 2^nb).  The indices differ between lanes, so x * acc is a branch-free
+// list[k] = complaint c, row = crow[c] - 1 of the decoded commitments Eext (element row * N + k),
+// index x = xs[c] (< 2^nb).  The commitment row is its own array, apart from the evaluation index:
+// one ceremony passes (accuser, accused); a batch passes the accuser within its ceremony and the
+// accused's row among the gathered rows (k_gather_rows), so lanes of one wave may walk rows of
+// different ceremonies.  The indices differ between lanes, so x * acc is a branch-free
 // double-and-add over nb bits (a bit no lane of the wave has set skips its addition).  R: point-major
 // [c][40].
 __global__ __launch_bounds__(64, 2) void k_cmp_horner(size_t cnt, const uint32_t* __restrict__ list,
-                                                      const uint32_t* __restrict__ accuser,
-                                                      const uint32_t* __restrict__ accused,
+                                                      const uint32_t* __restrict__ xs,
+                                                      const uint32_t* __restrict__ crow,
                                                       const uint32_t* __restrict__ Eext, size_t stride, size_t N, int nb,
                                                       uint32_t* __restrict__ R) {
   const size_t k = (size_t)blockIdx.x * 64 + threadIdx.x;
   const bool live = k < cnt;
   const size_t c = list[live ? k : 0];
-  const uint32_t x = accuser[c];
-  const size_t row = (size_t)(accused[c] - 1) * N;
+  const uint32_t x = xs[c];
+  const size_t row = (size_t)(crow[c] - 1) * N;
   ge_p3 acc;
   pt_load(acc, Eext, stride, row + N - 1);
 #pragma unroll 1
@@ -256,10 +259,10 @@ __global__ __launch_bounds__(64, 2) void k_cmp_horner(size_t cnt, const uint32_t
   if (live) pt_store_aos(R, c, acc);
 }
 
-void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* accuser, const uint32_t* accused, const uint32_t* Eext,
+void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint32_t* crow, const uint32_t* Eext,
                 size_t stride, size_t N, int nb, uint32_t* R, hipStream_t stream) {
   if (!cnt) return;
-  hipLaunchKernelGGL(k_cmp_horner, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, stream, cnt, list, accuser, accused,
+  hipLaunchKernelGGL(k_cmp_horner, dim3((unsigned)((cnt + 63) / 64)), dim3(64), 0, stream, cnt, list, xs, crow,
                      Eext, stride, N, nb, R);
 }
 
@@ -268,8 +271,9 @@ void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* accuser, const
 // = e1_rand | ct_rand | e1_share | ct_share, proofs [C][48 words] = K_share | K_rand | c1 | r1 | c2 | r2.
 // Out: the points to decode Pc [5C][8] (pk_accuser, e1_share, K_share, e1_rand, K_rand), the
 // responses rs [2C][8] and negated challenges nc [2C][8] (canonical), the decrypted scalars p12
-// [2C][8] (p1 = share, p2 = randomness), and the ladders' base indices.
-__global__ __launch_bounds__(256) void k_cv_prep(size_t C, const uint32_t* __restrict__ accuser,
+// [2C][8] (p1 = share, p2 = randomness), and the ladders' base indices.  party [C]: the accuser's
+// 1-based slot in pk -- the accuser itself for one ceremony, g n + accuser in a batch of [B][n] keys.
+__global__ __launch_bounds__(256) void k_cv_prep(size_t C, const uint32_t* __restrict__ party,
                                                  const uint32_t* __restrict__ pk, const uint32_t* __restrict__ enc,
                                                  const uint32_t* __restrict__ proofs, uint32_t* __restrict__ Pc,
                                                  uint32_t* __restrict__ rs, uint32_t* __restrict__ nc,
@@ -283,7 +287,7 @@ __global__ __launch_bounds__(256) void k_cv_prep(size_t C, const uint32_t* __res
   const uint32_t* e1 = e + (m ? 0 : 16);
   const uint32_t* ct = e + (m ? 8 : 24);
   const uint32_t* K = P + 8 * m;
-  if (m == 0) copy8(Pc + 8 * (5 * c), pk + 8 * (size_t)(accuser[c] - 1));
+  if (m == 0) copy8(Pc + 8 * (5 * c), pk + 8 * (size_t)(party[c] - 1));
   copy8(Pc + 8 * (5 * c + 1 + 2 * m), e1);
   copy8(Pc + 8 * (5 * c + 2 + 2 * m), K);
   sc x, y;
@@ -299,11 +303,11 @@ __global__ __launch_bounds__(256) void k_cv_prep(size_t C, const uint32_t* __res
   bq2[idx] = (uint32_t)(5 * c + 2 + 2 * m);
 }
 
-void cv_prep(size_t C, const uint32_t* accuser, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
+void cv_prep(size_t C, const uint32_t* party, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
              uint32_t* Pc, uint32_t* rs, uint32_t* nc, uint32_t* p12, uint32_t* bp1, uint32_t* bp2, uint32_t* bq2,
              hipStream_t stream) {
   if (!C) return;
-  hipLaunchKernelGGL(k_cv_prep, dim3((unsigned)((2 * C + 255) / 256)), dim3(256), 0, stream, C, accuser, pk, enc, proofs,
+  hipLaunchKernelGGL(k_cv_prep, dim3((unsigned)((2 * C + 255) / 256)), dim3(256), 0, stream, C, party, pk, enc, proofs,
                      Pc, rs, nc, p12, bp1, bp2, bq2);
 }
 
@@ -311,7 +315,8 @@ void cv_prep(size_t C, const uint32_t* accuser, const uint32_t* pk, const uint32
 // the quirk of ProofOfMisbehaviour::verify (broadcast.rs:271-283), eq[2c + 1] = (h p2 + g p1 == P), the
 // accusation (:87-96).  ridx[c]: bit 31 clear = element of Rh (k_cmp_horner, P itself); set = element
 // of Rt, the difference tables' evaluations, which hold b_j P(j) when `scale` is given (b_j 2^256 mod
-// l at scale + 8 (j - 1)): the scalars are then taken to b_j p first, as k_check does.
+// l at scale + 8 (j - 1)): the scalars are then taken to b_j p first, as k_check does.  `accuser` is
+// the evaluation index j within the ceremony (the scale slot), never a party or commitment row.
 __global__ __launch_bounds__(256, DKG_COMB_WAVES) void k_cv_check(size_t C, const uint32_t* __restrict__ accuser,
                                                   const uint32_t* __restrict__ p12, const uint32_t* __restrict__ ridx,
                                                   const uint32_t* __restrict__ Rh, const uint32_t* __restrict__ Rt,
@@ -348,10 +353,11 @@ void cv_check(size_t C, const uint32_t* accuser, const uint32_t* p12, const uint
 
 // Verdict of complaint c (the codes of dkg_complaint1_verify, and 4 when the accused published no
 // phase-1 broadcast, committee.rs:377-380).  a1c / a2c [2C][8]: the encoded announcements g r - pk c,
-// e1 r - K c; pok [5C] decode flags of k_cv_prep's points; rowok [n] = the accused row decodes;
-// fetched (may be null) [n].
-__global__ __launch_bounds__(256) void k_cv_final(size_t C, const uint32_t* __restrict__ accuser,
-                                                  const uint32_t* __restrict__ accused,
+// e1 r - K c; pok [5C] decode flags of k_cv_prep's points.  party [C] as k_cv_prep's; crow [C]: the
+// accused's 1-based commitment row, which indexes rowok (= the row decodes) and fetched (may be
+// null) -- the accused itself for one ceremony, its gathered row in a batch.
+__global__ __launch_bounds__(256) void k_cv_final(size_t C, const uint32_t* __restrict__ party,
+                                                  const uint32_t* __restrict__ crow,
                                                   const uint32_t* __restrict__ pk, const uint32_t* __restrict__ enc,
                                                   const uint32_t* __restrict__ proofs,
                                                   const uint32_t* __restrict__ a1c, const uint32_t* __restrict__ a2c,
@@ -360,8 +366,8 @@ __global__ __launch_bounds__(256) void k_cv_final(size_t C, const uint32_t* __re
                                                   int32_t* __restrict__ verdict) {
   const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const size_t i = accused[c] - 1;
-  const uint32_t* pkj = pk + 8 * (size_t)(accuser[c] - 1);
+  const size_t i = crow[c] - 1;
+  const uint32_t* pkj = pk + 8 * (size_t)(party[c] - 1);
   bool valid = true;
 #pragma unroll 1
   for (int m = 0; m < 2; m++) {
@@ -383,11 +389,11 @@ __global__ __launch_bounds__(256) void k_cv_final(size_t C, const uint32_t* __re
   verdict[c] = v;
 }
 
-void cv_final(size_t C, const uint32_t* accuser, const uint32_t* accused, const uint32_t* pk, const uint32_t* enc,
+void cv_final(size_t C, const uint32_t* party, const uint32_t* crow, const uint32_t* pk, const uint32_t* enc,
               const uint32_t* proofs, const uint32_t* a1c, const uint32_t* a2c, const uint8_t* pok, const uint8_t* rowok,
               const uint8_t* fetched, const uint8_t* eq, int32_t* verdict, hipStream_t stream) {
   if (!C) return;
-  hipLaunchKernelGGL(k_cv_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, accuser, accused, pk, enc,
+  hipLaunchKernelGGL(k_cv_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, party, crow, pk, enc,
                      proofs, a1c, a2c, pok, rowok, fetched, eq, verdict);
 }
 
@@ -480,15 +486,18 @@ void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8
 }
 
 // ------------------------------------------------------------------ round-4 complaints: prep / check / final
-// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) for C complaints of one ceremony, lane =
-// complaint.  A complaint discloses the accuser's decrypted pair; it holds when the pair passes against
-// the accused's E row and fails against its A row.  Both rows live in ONE decoded array of 2n rows (E
-// rows 0..n-1, A rows n..2n-1), so complaint c is the two evaluation items 2c = (row i, index j) and
-// 2c + 1 = (row n + i, index j) of k_cmp_horner / the difference tables.
+// MisbehavingPartiesRound3::verify (broadcast.rs:104-144) for C complaints, lane = complaint.  A
+// complaint discloses the accuser's decrypted pair; it holds when the pair passes against the
+// accused's E row and fails against its A row.  Both rows live in ONE decoded array of 2 `arows` rows
+// (E rows 0..arows-1, A rows arows..2 arows-1), so complaint c is the two evaluation items 2c = (row
+// i, index j) and 2c + 1 = (row arows + i, index j) of k_cmp_horner / the difference tables.  One
+// ceremony: arows = n and the rows i = crow[c] are the accused dealers; a batch: the arows gathered
+// rows (k_gather_rows), crow[c] the accused's place among them.  j = accuser[c], the index within
+// the ceremony.
 // prep: share / randomness [C][8] raw -> sr [2C][8] canonical (k_reduce_scalars' reduction, what the
 // host-driven primitive's upload applies), and the items' index lists acc2 / acd2 [2C].
-__global__ __launch_bounds__(256) void k_c3_prep(size_t C, uint32_t n, const uint32_t* __restrict__ accuser,
-                                                 const uint32_t* __restrict__ accused,
+__global__ __launch_bounds__(256) void k_c3_prep(size_t C, uint32_t arows, const uint32_t* __restrict__ accuser,
+                                                 const uint32_t* __restrict__ crow,
                                                  const uint32_t* __restrict__ share,
                                                  const uint32_t* __restrict__ randomness, uint32_t* __restrict__ sr,
                                                  uint32_t* __restrict__ acc2, uint32_t* __restrict__ acd2) {
@@ -500,21 +509,21 @@ __global__ __launch_bounds__(256) void k_c3_prep(size_t C, uint32_t n, const uin
   sc_load_reduced(x, randomness + 8 * c);
   sc_store(sr + 8 * (2 * c + 1), x);
   acc2[2 * c] = acc2[2 * c + 1] = accuser[c];
-  acd2[2 * c] = accused[c];
-  acd2[2 * c + 1] = n + accused[c];
+  acd2[2 * c] = crow[c];
+  acd2[2 * c + 1] = arows + crow[c];
 }
 
-void c3_prep(size_t C, size_t n, const uint32_t* accuser, const uint32_t* accused, const uint32_t* share,
+void c3_prep(size_t C, size_t arows, const uint32_t* accuser, const uint32_t* crow, const uint32_t* share,
              const uint32_t* randomness, uint32_t* sr, uint32_t* acc2, uint32_t* acd2, hipStream_t stream) {
   if (!C) return;
-  hipLaunchKernelGGL(k_c3_prep, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, (uint32_t)n, accuser,
-                     accused, share, randomness, sr, acc2, acd2);
+  hipLaunchKernelGGL(k_c3_prep, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, (uint32_t)arows, accuser,
+                     crow, share, randomness, sr, acc2, acd2);
 }
 
 // eq[2c] = (g share + h randomness == P^E_i(j)), eq[2c + 1] = (g share == P^A_i(j)): one walk of the g
 // comb serves both sides, the h comb's terms are added to it.  ridx [2C] per item as k_cv_check's
 // (bit 31: Rt, the tables' b_j P(j) when `scale` is given); both items of a complaint take the same
-// source, so the scalars are scaled once.
+// source, so the scalars are scaled once.  `accuser` is the evaluation index (the scale slot).
 __global__ __launch_bounds__(256, DKG_COMB_WAVES) void k_c3_check(size_t C, const uint32_t* __restrict__ accuser,
                                                   const uint32_t* __restrict__ sr, const uint32_t* __restrict__ ridx,
                                                   const uint32_t* __restrict__ Rh, const uint32_t* __restrict__ Rt,
@@ -552,19 +561,23 @@ void c3_check(size_t C, const uint32_t* accuser, const uint32_t* sr, const uint3
 
 // Verdict of complaint c as Phases<Phase4>::proceed treats it (committee.rs:636-670): 4 the accused is
 // disqualified (:639), 5 it has no phase-3 broadcast -- absent, or its A row does not decode -- so the
-// complaint holds unverified (:643), else the codes of dkg_complaint3_verify.  rowok [2n] decode flags
-// of the E rows then the A rows; qualified / fetched3 [n] may be null (all 1).
-__global__ __launch_bounds__(256) void k_c3_final(size_t C, size_t n, const uint32_t* __restrict__ accused,
+// complaint holds unverified (:643), else the codes of dkg_complaint3_verify.  rowok [2 arows] decode
+// flags of the E rows then the A rows, indexed by the commitment row crow[c] (k_c3_prep); qualified /
+// fetched3 (may be null: all 1) are per dealer, indexed by the accused's 1-based dealer row drow[c].
+// One ceremony passes `accused` for both and arows = n; a batch passes the gathered row and g n +
+// accused.
+__global__ __launch_bounds__(256) void k_c3_final(size_t C, size_t arows, const uint32_t* __restrict__ crow,
+                                                  const uint32_t* __restrict__ drow,
                                                   const uint8_t* __restrict__ rowok,
                                                   const uint8_t* __restrict__ qualified,
                                                   const uint8_t* __restrict__ fetched3, const uint8_t* __restrict__ eq,
                                                   int32_t* __restrict__ verdict) {
   const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  const size_t i = accused[c] - 1;
+  const size_t i = crow[c] - 1, d = drow[c] - 1;
   int32_t v;
-  if (qualified && !qualified[i]) v = 4;
-  else if ((fetched3 && !fetched3[i]) || !rowok[n + i]) v = 5;
+  if (qualified && !qualified[d]) v = 4;
+  else if ((fetched3 && !fetched3[d]) || !rowok[arows + i]) v = 5;
   else if (!rowok[i]) v = -1;
   else if (!eq[2 * c]) v = 3;     // FalseClaimedEquality (broadcast.rs:129-130)
   else if (eq[2 * c + 1]) v = 2;  // FalseClaimedInequality (:131-132)
@@ -572,11 +585,128 @@ __global__ __launch_bounds__(256) void k_c3_final(size_t C, size_t n, const uint
   verdict[c] = v;
 }
 
-void c3_final(size_t C, size_t n, const uint32_t* accused, const uint8_t* rowok, const uint8_t* qualified,
-              const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict, hipStream_t stream) {
+void c3_final(size_t C, size_t arows, const uint32_t* crow, const uint32_t* drow, const uint8_t* rowok,
+              const uint8_t* qualified, const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict,
+              hipStream_t stream) {
   if (!C) return;
-  hipLaunchKernelGGL(k_c3_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, n, accused, rowok,
+  hipLaunchKernelGGL(k_c3_final, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, arows, crow, drow, rowok,
                      qualified, fetched3, eq, verdict);
+}
+
+// ------------------------------------------------------------------ batches of ceremonies: gathers, masks, dissent
+// The complaint stage of a batch (runtime.hip batch_complaints) addresses B stacked ceremonies: dealer
+// row g n + i is dealer i of ceremony g.  Only the accused rows are decoded a second time: the host
+// lists the distinct accused dealer rows (0-based, `rows` [R]) and this kernel copies their compressed
+// commitments into out [R][N][8] -- and, with srcA, the same rows of A behind them ([2R][N][8], the E
+// rows then the A rows, as k_c3_prep addresses them).  One thread per 16 bytes.
+__global__ __launch_bounds__(256) void k_gather_rows(size_t R, size_t N, const uint32_t* __restrict__ rows,
+                                                     const uint4* __restrict__ srcE, const uint4* __restrict__ srcA,
+                                                     uint4* __restrict__ out) {
+  const size_t q = 2 * N;  // uint4 per row
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (srcA ? 2 : 1) * R * q) return;
+  const size_t r = idx / q, w = idx % q;
+  const bool a = r >= R;
+  const size_t src = (size_t)rows[a ? r - R : r] * q + w;
+  out[idx] = a ? srcA[src] : srcE[src];
+}
+
+void gather_rows(size_t R, size_t N, const uint32_t* rows, const uint32_t* srcE, const uint32_t* srcA, uint32_t* out,
+                 hipStream_t stream) {
+  const size_t total = (srcA ? 2 : 1) * R * 2 * N;
+  if (!total) return;
+  hipLaunchKernelGGL(k_gather_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, R, N, rows,
+                     (const uint4*)srcE, (const uint4*)srcA, (uint4*)out);
+}
+
+// enc [C][32 words] = e1_rand | ct_rand | e1_share | ct_share: the pair the accused broadcast to the
+// accuser (broadcast.rs:57), from the batch's device-resident ciphertexts, items (dealer row, q, w)
+// at ((drow - 1) n + q) 2 + w with w = 0 the randomness.  drow [C]: the accused's 1-based dealer row
+// g n + accused, accuser [C] the 1-based recipient within the ceremony.  One thread per 16 bytes.
+__global__ __launch_bounds__(256) void k_gather_enc(size_t C, size_t n, const uint32_t* __restrict__ drow,
+                                                    const uint32_t* __restrict__ accuser,
+                                                    const uint4* __restrict__ e1, const uint4* __restrict__ ct,
+                                                    uint4* __restrict__ enc) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= 8 * C) return;
+  const size_t c = idx >> 3, part = (idx >> 1) & 3, h = idx & 1;  // part: e1_rand, ct_rand, e1_share, ct_share
+  const size_t item = ((size_t)(drow[c] - 1) * n + (accuser[c] - 1)) * 2 + (part >> 1);
+  enc[idx] = ((part & 1) ? ct : e1)[2 * item + h];
+}
+
+void gather_enc(size_t C, size_t n, const uint32_t* drow, const uint32_t* accuser, const uint32_t* e1,
+                const uint32_t* ct, uint32_t* enc, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_gather_enc, dim3((unsigned)((8 * C + 255) / 256)), dim3(256), 0, stream, C, n, drow, accuser,
+                     (const uint4*)e1, (const uint4*)ct, (uint4*)enc);
+}
+
+// The verdicts as the rounds' masks over the V dealer rows.  Round 2 (threads [0, C2); committee.rs:381-394):
+// a verdict 0 clears cmask[accused row] and sets pair[accused row][accuser], the proven-pair matrix
+// k_dissent reads.  Round 4 (threads [C2, C2 + C4); :643, :664-669): a verdict 0 or 5 sets
+// proven4[accused row].  The caller presets cmask to 1 and pair / proven4 to 0.  Several complaints
+// may write one byte: they all write the same value (plain byte stores).
+__global__ __launch_bounds__(256) void k_proven_masks(size_t C2, size_t n, const uint32_t* __restrict__ drow2,
+                                                      const uint32_t* __restrict__ accuser2,
+                                                      const int32_t* __restrict__ verdict2, size_t C4,
+                                                      const uint32_t* __restrict__ drow4,
+                                                      const int32_t* __restrict__ verdict4, uint8_t* __restrict__ cmask,
+                                                      uint8_t* __restrict__ pair, uint8_t* __restrict__ proven4) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < C2) {
+    if (verdict2[idx] != 0) return;
+    const size_t d = drow2[idx] - 1;
+    cmask[d] = 0;
+    pair[d * n + (accuser2[idx] - 1)] = 1;
+  } else if (idx < C2 + C4) {
+    const size_t c = idx - C2;
+    const int32_t v = verdict4[c];
+    if (v == 0 || v == 5) proven4[drow4[c] - 1] = 1;
+  }
+}
+
+void proven_masks(size_t C2, size_t n, const uint32_t* drow2, const uint32_t* accuser2, const int32_t* verdict2,
+                  size_t C4, const uint32_t* drow4, const int32_t* verdict4, uint8_t* cmask, uint8_t* pair,
+                  uint8_t* proven4, hipStream_t stream) {
+  if (!(C2 + C4)) return;
+  hipLaunchKernelGGL(k_proven_masks, dim3((unsigned)((C2 + C4 + 255) / 256)), dim3(256), 0, stream, C2, n, drow2,
+                     accuser2, verdict2, C4, drow4, verdict4, cmask, pair, proven4);
+}
+
+// dissent[g n + j] = the dealers i of ceremony g that receiver j rejected (dec2 [V][n], REJECT = 0)
+// without a proven complaint of its own against them (pair [V][n], k_proven_masks).  Thread = (g, j):
+// consecutive lanes read consecutive bytes of each dealer row.
+__global__ __launch_bounds__(256) void k_dissent(size_t V, size_t n, const uint8_t* __restrict__ dec2,
+                                                 const uint8_t* __restrict__ pair, int32_t* __restrict__ dissent) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= V) return;
+  const size_t g = idx / n, j = idx % n;
+  int32_t v = 0;
+  for (size_t i = 0; i < n; i++) {
+    const size_t at = (g * n + i) * n + j;
+    v += dec2[at] == 0 && !pair[at];
+  }
+  dissent[idx] = v;
+}
+
+void dissent_rows(size_t V, size_t n, const uint8_t* dec2, const uint8_t* pair, int32_t* dissent, hipStream_t stream) {
+  if (!V) return;
+  hipLaunchKernelGGL(k_dissent, dim3((unsigned)((V + 255) / 256)), dim3(256), 0, stream, V, n, dec2, pair, dissent);
+}
+
+// out[i] = dok[column of dealer i of segment seg], i < D: a segment's per-dealer flags out of the
+// verification's interleaved column layout (the inverse of and_dealer_mask's addressing)
+__global__ __launch_bounds__(256) void k_segment_mask(size_t D, uint32_t nseg, uint32_t seg,
+                                                      const uint8_t* __restrict__ dok, uint8_t* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= D) return;
+  out[i] = dok[(i / 64) * 64 * nseg + seg * 64 + i % 64];
+}
+
+void segment_mask(size_t D, int nseg, int seg, const uint8_t* dok, uint8_t* out, hipStream_t stream) {
+  if (!D) return;
+  hipLaunchKernelGGL(k_segment_mask, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, stream, D, (uint32_t)nseg,
+                     (uint32_t)seg, dok, out);
 }
 
 }  // namespace dkgk

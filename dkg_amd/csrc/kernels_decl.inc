@@ -305,16 +305,21 @@ void bdec_mul(size_t keys, size_t n, const uint32_t* sk, const uint32_t* R_ext, 
 size_t cmp_ladder_table_words(size_t cnt);
 void cmp_ladder(size_t cnt, bool joint, const uint32_t* bp, const uint32_t* bq, const uint32_t* sa, const uint32_t* sb,
                 const uint32_t* Pext, size_t pstride, uint32_t* T, uint32_t* out, hipStream_t stream);
-// R[c] (point-major) = sum_k accuser[c]^k Eext[(accused[c] - 1) * N + k] for the complaints c in list[0..cnt)
-void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* accuser, const uint32_t* accused, const uint32_t* Eext,
+// Three per-complaint index arrays, all 1-based, which one ceremony fills with (accuser, accuser,
+// accused) and a batch of stacked ceremonies with different values: the EVALUATION INDEX xs /
+// accuser (the accuser within its ceremony: Horner's multiplier, the scale slot), the PARTY ROW
+// party (the accuser's slot in pk: g n + accuser) and the COMMITMENT ROW crow (the accused's row of
+// the decoded commitments, of rowok and of fetched: its place among the gathered rows, gather_rows).
+// R[c] (point-major) = sum_k xs[c]^k Eext[(crow[c] - 1) * N + k] for the complaints c in list[0..cnt)
+void cmp_horner(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint32_t* crow, const uint32_t* Eext,
                 size_t stride, size_t N, int nb, uint32_t* R, hipStream_t stream);
-void cv_prep(size_t C, const uint32_t* accuser, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
+void cv_prep(size_t C, const uint32_t* party, const uint32_t* pk, const uint32_t* enc, const uint32_t* proofs,
              uint32_t* Pc, uint32_t* rs, uint32_t* nc, uint32_t* p12, uint32_t* bp1, uint32_t* bp2, uint32_t* bq2,
              hipStream_t stream);
 void cv_check(size_t C, const uint32_t* accuser, const uint32_t* p12, const uint32_t* ridx, const uint32_t* Rh,
               const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
               hipStream_t stream);
-void cv_final(size_t C, const uint32_t* accuser, const uint32_t* accused, const uint32_t* pk, const uint32_t* enc,
+void cv_final(size_t C, const uint32_t* party, const uint32_t* crow, const uint32_t* pk, const uint32_t* enc,
               const uint32_t* proofs, const uint32_t* a1c, const uint32_t* a2c, const uint8_t* pok, const uint8_t* rowok,
               const uint8_t* fetched, const uint8_t* eq, int32_t* verdict, hipStream_t stream);
 void cp_prep(size_t C, const uint32_t* sk, const uint32_t* enc, const uint32_t* w, uint32_t* Pc, uint32_t* ls,
@@ -326,16 +331,36 @@ void qualified_complaints(size_t rows, size_t n, const uint8_t* dec, const uint8
                           hipStream_t stream);
 // round-4 complaints (MisbehavingPartiesRound3::verify, broadcast.rs:104-144), lane = complaint: the
 // reduced scalars sr [2C][8] = (share, randomness) and the evaluation items' lists acc2 / acd2 [2C]
-// (item 2c: E row accused - 1, item 2c + 1: A row n + accused - 1 of the decoded 2n rows);
-void c3_prep(size_t C, size_t n, const uint32_t* accuser, const uint32_t* accused, const uint32_t* share,
+// (item 2c: E row crow - 1, item 2c + 1: A row arows + crow - 1 of the decoded 2 arows rows; one
+// ceremony: arows = n, crow = accused);
+void c3_prep(size_t C, size_t arows, const uint32_t* accuser, const uint32_t* crow, const uint32_t* share,
              const uint32_t* randomness, uint32_t* sr, uint32_t* acc2, uint32_t* acd2, hipStream_t stream);
 // eq[2c] = (g share + h randomness == P^E), eq[2c + 1] = (g share == P^A); ridx [2C], Rh, Rt, scale as cv_check;
 void c3_check(size_t C, const uint32_t* accuser, const uint32_t* sr, const uint32_t* ridx, const uint32_t* Rh,
               const uint32_t* Rt, const uint32_t* scale, const uint32_t* tab_g, const uint32_t* tab_h, uint8_t* eq,
               hipStream_t stream);
-// the verdicts (rowok [2n]; qualified, fetched3 [n] may be null)
-void c3_final(size_t C, size_t n, const uint32_t* accused, const uint8_t* rowok, const uint8_t* qualified,
-              const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict, hipStream_t stream);
+// the verdicts (rowok [2 arows] by crow; qualified, fetched3, may be null, by the 1-based dealer row drow)
+void c3_final(size_t C, size_t arows, const uint32_t* crow, const uint32_t* drow, const uint8_t* rowok,
+              const uint8_t* qualified, const uint8_t* fetched3, const uint8_t* eq, int32_t* verdict,
+              hipStream_t stream);
+// ---- the complaint stage of batched ceremonies (dealer row g n + i = dealer i of ceremony g)
+// out [R][N][8] = rows `rows[r]` (0-based dealer rows) of srcE; with srcA, [2R][N][8]: then those of srcA
+void gather_rows(size_t R, size_t N, const uint32_t* rows, const uint32_t* srcE, const uint32_t* srcA, uint32_t* out,
+                 hipStream_t stream);
+// enc [C][32 words] = the pair dealer row drow[c] (1-based) sent recipient accuser[c] of its ceremony,
+// from the batch's e1 / ct [V][n][2][8]
+void gather_enc(size_t C, size_t n, const uint32_t* drow, const uint32_t* accuser, const uint32_t* e1,
+                const uint32_t* ct, uint32_t* enc, hipStream_t stream);
+// verdict 0 of a round-2 complaint: cmask[drow2 - 1] = 0, pair[(drow2 - 1) n + accuser2 - 1] = 1; verdict
+// 0 or 5 of a round-4 complaint: proven4[drow4 - 1] = 1 (the masks preset by the caller; with C2 == 0
+// cmask / pair may be null)
+void proven_masks(size_t C2, size_t n, const uint32_t* drow2, const uint32_t* accuser2, const int32_t* verdict2,
+                  size_t C4, const uint32_t* drow4, const int32_t* verdict4, uint8_t* cmask, uint8_t* pair,
+                  uint8_t* proven4, hipStream_t stream);
+// dissent[g n + j] = #{i : dec2[g n + i][j] == REJECT and not pair[g n + i][j]}, V = groups * n
+void dissent_rows(size_t V, size_t n, const uint8_t* dec2, const uint8_t* pair, int32_t* dissent, hipStream_t stream);
+// out[i] = dok[column of dealer i of segment seg] (and_dealer_mask's layout), i < D
+void segment_mask(size_t D, int nseg, int seg, const uint8_t* dok, uint8_t* out, hipStream_t stream);
 
 // ---- committee verification by interpolation (interp.hip)
 // F[d][k] = sum_j W[k][j] s[d][j] (and F' from s'; sp may be null), WT[j][k] = W[k][j] in Montgomery form

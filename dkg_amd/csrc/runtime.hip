@@ -11,6 +11,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/dkg_amd.h"
@@ -34,6 +35,7 @@ struct dkg_ctx {
   hipEvent_t ev[8] = {};
   hipEvent_t pev[5] = {};               // phase profiling inside verify_device (nsub == 1)
   hipEvent_t hev[9] = {};               // full mode: encrypt / decrypt kernels (nsub == 1)
+  hipEvent_t bpev[3] = {};              // batches by proven complaints: around the two complaint stages
   int hy_timed = 0;                     // hev[] hold the phases of the last serialised encrypt (1)
                                         // and / or decrypt (2) since the last collect_hybrid_phases
   static constexpr int MAX_SUB = 8;
@@ -97,6 +99,7 @@ struct dkg_ctx {
   const uint32_t* last_R = nullptr;
   const uint32_t* last_scale = nullptr;
   const uint8_t* last_dok = nullptr;
+  int last_dok_nseg = 1;                // its segments (columns interleaved as and_dealer_mask addresses them)
   int complaint_eval = 0;               // P_i(j) of the complaints: 0 by the dealer's complaint count,
                                         // 1 per-pair Horner, 2 difference tables
   // round-1 commitments of the ceremony being verified, in extended form on this device (set by
@@ -745,6 +748,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   ctx->last_R = R;
   ctx->last_scale = sscale;
   ctx->last_dok = dok;
+  ctx->last_dok_nseg = nseg;
   // padding columns, and the positions past t of the last piece, are the identity
   if (npad != D * nseg || U * L != N) dkgk::fill_identity(L * W, Cpm, home);
   HCK(hipMemsetAsync(pok, 1, npad * N, home));
@@ -1593,8 +1597,26 @@ struct BatchRound1 {
 // for one ceremony (2*B*n virtual dealers in the fused pipeline); the per-ceremony combine steps
 // (qualification, complaints, round-3 sums, mpk) are grouped kernels.  Every output equals what B
 // separate ceremonies produce.
+// BatchProven (may be null): the batch decides by the PROVEN complaints, as receivers_rounds with
+// RoundMasks -- the device masks its complaint stage left (batch_complaints), the host arrays that
+// receive the stage's outputs in the batch's one round trip, and the host outcome vectors that
+// batch_proven_outcome reads afterwards.
+struct BatchProven {
+  // device, [V] unless noted; null = absent
+  const uint8_t* a_ok = nullptr;     // the intake mask of the phase-3 broadcasts (verify_rounds' a_ok)
+  const uint8_t* cmask = nullptr;    // no verified round-2 complaint against the dealer (round2_device)
+  const uint8_t* pair = nullptr;     // [V][n] proven (accused, accuser) pairs, for the dissent
+  const uint8_t* proven4 = nullptr;  // some round-4 complaint against the dealer holds
+  const int32_t *dver2 = nullptr, *dver4 = nullptr;  // the verdicts [C2], [C4]
+  size_t C2 = 0, C4 = 0;
+  // host outputs (may be null)
+  int32_t *verdict2 = nullptr, *verdict4 = nullptr, *dissent = nullptr;
+  // host outcome, filled by batch_receivers: a_present[i] = dealer i has a usable phase-3 broadcast
+  std::vector<uint8_t> qualified, reconstruct, r2_error, r4_error, phase4_error, a_present;
+};
 void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t* Ecomp, const uint32_t* Acomp,
-                     const uint32_t* s, const uint32_t* sp, dkg_batch_out* out, const uint8_t* e_ok = nullptr) {
+                     const uint32_t* s, const uint32_t* sp, dkg_batch_out* out, const uint8_t* e_ok = nullptr,
+                     BatchProven* bp = nullptr) {
   const size_t N = t + 1, V = B * n;
   uint8_t* dec2 = buf<uint8_t>(ctx, "b.dec2", V * n);
   uint8_t* dec4 = buf<uint8_t>(ctx, "b.dec4", V * n);
@@ -1614,7 +1636,7 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
   // dealers' shares (:433-476), round 4's rejections reconstruct qualified dealers (:660-670) and the
   // honest set -- qualified, not reconstructed -- sums the master key (:726-805).
   auto round3 = [&] {
-    round2_device(ctx, B, n, dec2, qmask, rej2, cnt);
+    round2_device(ctx, B, n, dec2, qmask, rej2, cnt, bp ? bp->cmask : nullptr);
     wait_shares(ctx, ctx->stream);  // shares evaluated on the side stream (BatchRound1)
     dkgk::sum_shares(n, n, s, qmask, fs, ctx->stream, B);
     dkgk::fixed_base(V, fs, ctx->tab_gw, pub, ctx->stream);
@@ -1623,10 +1645,27 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
   };
   // e_ok (may be null; [V] on the device): full mode's decode mask of each dealer's ciphertexts -- a row
   // that did not decode is missing data (DKG_MISSING in round 2), as in receivers_rounds
-  verify_rounds(ctx, n, t, V, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, e_ok, nullptr, false);
+  verify_rounds(ctx, n, t, V, 0, Ecomp, Acomp, s, sp, dec2, dec4, ctx->ev[2], round3, e_ok, bp ? bp->a_ok : nullptr,
+                false);
   // round 4 (committee.rs:515-522, 567-569, 660-670): rows of disqualified dealers SKIPPED
   round4_device(ctx, B, n, t, dec4, qmask, rej4, r4d);
-  dkgk::mask_not_and(V, rej4, qmask, hmask, ctx->stream);
+  // the proven complaints' mask stands in for the rejections, as in receivers_rounds (:636-670)
+  const uint8_t* acc4 = bp && bp->proven4 ? bp->proven4 : rej4;
+  dkgk::mask_not_and(V, acc4, qmask, hmask, ctx->stream);
+  // by proven complaints the host outcome also needs, per dealer, whether its phase-3 broadcast is
+  // usable (present and decodable: proven_outcome's a_ok): the verification's own flags of the A
+  // columns, which carry the intake mask -- no second decode of the V N commitments
+  uint8_t* apres = nullptr;
+  int32_t* ddis = nullptr;
+  if (bp) {
+    apres = buf<uint8_t>(ctx, "b.apres", V);
+    if (ctx->verify_mode == 1) dkgk::segment_mask(V, 1, 0, buf<uint8_t>(ctx, "i.dokA", V), apres, ctx->stream);
+    else dkgk::segment_mask(V, ctx->last_dok_nseg, ctx->last_dok_nseg - 1, ctx->last_dok, apres, ctx->stream);
+    if (bp->dissent) {  // from the device's dec2 and the proven pairs: dec2 is not downloaded for it
+      ddis = buf<int32_t>(ctx, "b.dissent", 4 * V);
+      dkgk::dissent_rows(V, n, dec2, bp->pair, ddis, ctx->stream);
+    }
+  }
   HCK(hipEventRecord(ctx->ev[4], ctx->stream));
   // finalise (committee.rs:726-805): mpk_c = sum of the honest A_i0 (+ g * reconstructed secrets)
   uint32_t* A0 = buf<uint32_t>(ctx, "b.A0ext", PTB * V);
@@ -1654,18 +1693,24 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
     size_t bytes;
     const char* name;
   };
+  if (bp) bp->a_present.resize(V);
   const Out outs[] = {{qualified.data(), rej2, V, "hb.rej2"},  // inverted below
                       {complaints.data(), cnt, 4 * V, "hb.cnt"},
-                      {h_rej4.data(), rej4, V, "hb.rej4"},
+                      {h_rej4.data(), acc4, V, "hb.rej4"},
                       {r4e.data(), r4d, V, "hb.r4err"},
                       {out->mpk, mpk_c, 32 * B, "hb.mpk"},
                       {out->final_share, fs, 32 * V, "hb.final"},
                       {out->public_share, pubc, 32 * V, "hb.pub"},
                       {out->dec2, dec2, V * n, "hb.dec2"},
-                      {out->dec4, dec4, V * n, "hb.dec4"}};  // SKIPPED rows applied
+                      {out->dec4, dec4, V * n, "hb.dec4"},  // SKIPPED rows applied
+                      // by proven complaints: the complaint stage's outputs share the round trip
+                      {bp ? bp->a_present.data() : nullptr, apres, V, "hb.apres"},
+                      {bp ? bp->verdict2 : nullptr, bp ? bp->dver2 : nullptr, bp ? 4 * bp->C2 : 0, "hb.ver2"},
+                      {bp ? bp->verdict4 : nullptr, bp ? bp->dver4 : nullptr, bp ? 4 * bp->C4 : 0, "hb.ver4"},
+                      {ddis ? bp->dissent : nullptr, ddis, 4 * V, "hb.dissent"}};
   void* staged[sizeof(outs) / sizeof(outs[0])] = {};
   for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); k++)
-    if (outs[k].host) {
+    if (outs[k].host && outs[k].bytes) {
       staged[k] = hbuf(ctx, outs[k].name, outs[k].bytes);
       d2h(ctx, staged[k], outs[k].dev, outs[k].bytes);
     }
@@ -1738,6 +1783,13 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
       for (size_t i = c * n; i < (c + 1) * n; i++) q += qualified[i];
       out->n_qualified[c] = q;
     }
+  if (bp) {
+    bp->qualified = std::move(qualified);
+    bp->reconstruct = std::move(recon);
+    bp->r2_error = std::move(r2err);
+    bp->r4_error = std::move(r4e);
+    bp->phase4_error = std::move(p4err);
+  }
 }
 
 void batch_times(dkg_ctx* ctx, dkg_batch_out* out, bool round1) {
@@ -2278,7 +2330,7 @@ void complaints3_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t
   uint8_t* eq = buf<uint8_t>(ctx, "c3_eq", 2 * C);
   dkgk::c3_check(C, dacc, sr, ev.dridx, ev.Rh, ev.Rt, ev.scale, ctx->tab_gw, ctx->tab_hw, eq, st);
   int32_t* dver = buf<int32_t>(ctx, "c3_verdict", 4 * C);
-  dkgk::c3_final(C, n, dacd, rowok, dq, df3, eq, dver, st);
+  dkgk::c3_final(C, n, dacd, dacd, rowok, dq, df3, eq, dver, st);  // commitment row = dealer row = accused
   check_launch(ctx);
   d2h(ctx, verdict, dver, 4 * C);
   sync(ctx);  // the staging vectors (ev) live until here
@@ -2317,26 +2369,251 @@ struct Complaints4 {
 // without one that nobody complained about is in no set: every party's finalise reaches the expect
 // at committee.rs:791-795 with indexed_committed_shares[i] never stored (:527-530).  Dealers are
 // visited in index order and the first failure wins (:745-797); mpk is zeroed on a panic.
+// The finalising parties' common outcome of one ceremony from its sets [n]: the DKG_FIN_* status
+// and, in *index, the dealer of INSUFFICIENT / PANIC (else -1).
+int32_t finalise_outcome(size_t n, size_t t, const uint8_t* qualified, const uint8_t* recon, const uint8_t* r2_error,
+                         const uint8_t* r4_error, const uint8_t* a_ok, bool phase4_error, int32_t* index) {
+  *index = -1;
+  if (phase4_error) return DKG_FIN_PHASE4_ERROR;
+  const bool insufficient = recovery_fails(disclosing_parties(n, qualified, recon, r2_error, r4_error), t);
+  for (size_t i = 0; i < n; i++) {
+    int32_t status = DKG_FIN_OK;
+    if (recon[i] && insufficient) status = DKG_FIN_INSUFFICIENT;
+    else if (!recon[i] && qualified[i] && !a_ok[i]) status = DKG_FIN_PANIC;
+    if (status != DKG_FIN_OK) {
+      *index = (int32_t)i;
+      return status;
+    }
+  }
+  return DKG_FIN_OK;
+}
+
 void proven_outcome(size_t n, size_t t, const Complaints4& c4, const uint8_t* a_ok, const RoundsResult& r,
                     uint8_t* mpk) {
   const uint8_t *qualified = r.qualified.data(), *recon = r.reconstruct.data();
   for (size_t c = 0; c < c4.C; c++)
     if (!qualified[c4.accused[c] - 1]) c4.verdict[c] = DKG_COMPLAINT_IGNORED;
-  int32_t status = DKG_FIN_OK, index = -1;
-  if (r.phase4_error) {
-    status = DKG_FIN_PHASE4_ERROR;
-  } else {
-    const bool insufficient =
-        recovery_fails(disclosing_parties(n, qualified, recon, r.r2_error.data(), r.r4_error.data()), t);
-    for (size_t i = 0; i < n && status == DKG_FIN_OK; i++) {
-      if (recon[i] && insufficient) status = DKG_FIN_INSUFFICIENT;
-      else if (!recon[i] && qualified[i] && !a_ok[i]) status = DKG_FIN_PANIC;
-      if (status != DKG_FIN_OK) index = (int32_t)i;
-    }
-  }
+  int32_t index = -1;
+  const int32_t status =
+      finalise_outcome(n, t, qualified, recon, r.r2_error.data(), r.r4_error.data(), a_ok, r.phase4_error, &index);
   if (status == DKG_FIN_PANIC) memset(mpk, 0, 32);
   if (c4.finalise_status) *c4.finalise_status = status;
   if (c4.recovery_index) *c4.recovery_index = index;
+}
+
+// ---- the proven-complaint rule for batches of ceremonies: the complaint stage on the device
+// The broadcast complaints of a whole batch as the flat host arrays of the C ABI: complaint c belongs
+// to ceremony[c] (0-based), accuser / accused are 1-based within it; any order, duplicates allowed.
+struct BatchComplaints2 {
+  const uint8_t* pk;  // [B][n][32]
+  size_t C;
+  const uint32_t *ceremony, *accuser, *accused;
+  const uint8_t* proofs;
+  int32_t *verdict, *dissent;  // [C], [B][n] (may be null)
+};
+struct BatchComplaints4 {
+  size_t C;
+  const uint32_t *ceremony, *accuser, *accused;
+  const uint8_t *share, *randomness;
+  int32_t *verdict, *finalise_status, *recovery_index;  // [C], [B], [B] (the last two may be null)
+};
+
+bool batch_complaint_args_ok(size_t B, size_t n, size_t C, const uint32_t* ceremony, const uint32_t* accuser,
+                             const uint32_t* accused, std::initializer_list<const void*> payload) {
+  if (!C) return true;
+  if (!ceremony) return false;
+  for (size_t c = 0; c < C; c++)
+    if (ceremony[c] >= B) return false;
+  return complaint_args_ok(n, C, accuser, accused, payload);
+}
+
+// The per-complaint index arrays of one round's complaints (host, O(C)): the evaluation index x =
+// accuser, the party row g n + accuser, the 1-based dealer row g n + accused, and the commitment row
+// = the accused's place (1-based) among the DISTINCT accused dealer rows `rows` (0-based), which are
+// all the stage decodes.
+struct ComplaintIndex {
+  std::vector<uint32_t> party, drow, crow, rows;
+};
+ComplaintIndex complaint_index(size_t n, size_t C, const uint32_t* ceremony, const uint32_t* accuser,
+                               const uint32_t* accused) {
+  ComplaintIndex ix;
+  ix.party.resize(C), ix.drow.resize(C), ix.crow.resize(C);
+  std::unordered_map<uint32_t, uint32_t> place;
+  for (size_t c = 0; c < C; c++) {
+    const uint32_t base = ceremony[c] * (uint32_t)n;
+    ix.party[c] = base + accuser[c];
+    ix.drow[c] = base + accused[c];
+    auto it = place.find(ix.drow[c]);
+    if (it == place.end()) {
+      ix.rows.push_back(ix.drow[c] - 1);
+      it = place.emplace(ix.drow[c], (uint32_t)ix.rows.size()).first;
+    }
+    ix.crow[c] = it->second;
+  }
+  return ix;
+}
+
+// Both complaint stages of a batch, queued on ctx->stream after the batch's uploads and before its
+// rounds; no host synchronisation, host work O(C), a launch count that does not depend on B and no
+// copy per row, ceremony or complaint.  Round 4 first, as verify_ceremony.  Device inputs: Ec, Ac
+// [V][N][8]; e1, ct [V][n][2][8] (with c2); fetched3 [V] (may be null).  Always the per-complaint
+// Horner walk (k_cmp_horner): ctx->complaint_eval does not apply.  Leaves the masks and the device
+// verdicts in bp; the index arrays go through one pinned staging buffer.
+void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t* Ec, const uint32_t* Ac,
+                      const uint32_t* e1, const uint32_t* ct, const BatchComplaints2* c2, const BatchComplaints4& c4,
+                      const uint8_t* fetched3, BatchProven& bp) {
+  const size_t N = t + 1, V = B * n, C2 = c2 ? c2->C : 0, C4 = c4.C;
+  hipStream_t st = ctx->stream;
+  int nb = 1;
+  while ((n >> nb) != 0) nb++;
+  const ComplaintIndex i4 = complaint_index(n, C4, c4.ceremony, c4.accuser, c4.accused);
+  const ComplaintIndex i2 = c2 ? complaint_index(n, C2, c2->ceremony, c2->accuser, c2->accused) : ComplaintIndex{};
+  const size_t R4 = i4.rows.size(), R2 = i2.rows.size(), iota = std::max(2 * C4, C2);
+  // one upload: x4 | crow4 | drow4 | rows4 | x2 | party2 | crow2 | drow2 | rows2 | 0, 1, 2, ..
+  const size_t words = 3 * C4 + R4 + 4 * C2 + R2 + iota;
+  uint32_t* hix = hbuf<uint32_t>(ctx, "hb.bp_idx", 4 * words);
+  uint32_t* dix = buf<uint32_t>(ctx, "bp.idx", 4 * words);
+  size_t at = 0;
+  auto put = [&](const uint32_t* src, size_t cnt) {
+    const uint32_t* d = dix + at;
+    if (cnt) memcpy(hix + at, src, 4 * cnt);
+    at += cnt;
+    return d;
+  };
+  const uint32_t* x4 = put(c4.accuser, C4);
+  const uint32_t* crow4 = put(i4.crow.data(), C4);
+  const uint32_t* drow4 = put(i4.drow.data(), C4);
+  const uint32_t* rows4 = put(i4.rows.data(), R4);
+  const uint32_t* x2 = put(c2 ? c2->accuser : nullptr, C2);
+  const uint32_t* party2 = put(i2.party.data(), C2);
+  const uint32_t* crow2 = put(i2.crow.data(), C2);
+  const uint32_t* drow2 = put(i2.drow.data(), C2);
+  const uint32_t* rows2 = put(i2.rows.data(), R2);
+  const uint32_t* seq = dix + at;  // list and ridx of the Horner walks: item k is element k of Rh
+  for (size_t k = 0; k < iota; k++) hix[at + k] = (uint32_t)k;
+  h2d(ctx, dix, hix, 4 * words);
+  HCK(hipEventRecord(ctx->bpev[0], st));
+  // ---- round 4 (k_c3_*): the E and A rows of the accused dealers, gathered and decoded once
+  uint8_t* proven4 = buf<uint8_t>(ctx, "bp.proven4", V);
+  int32_t* dver4 = buf<int32_t>(ctx, "bp.verdict4", 4 * C4);
+  HCK(hipMemsetAsync(proven4, 0, V, st));
+  if (C4) {
+    uint32_t* rc = buf<uint32_t>(ctx, "bp.rows4", 32 * 2 * R4 * N);
+    uint32_t* rext = buf<uint32_t>(ctx, "bp.rows4_ext", PTB * 2 * R4 * N);
+    uint8_t* pok = buf<uint8_t>(ctx, "bp.rows4_pok", 2 * R4 * N);
+    uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows4_ok", 2 * R4);
+    dkgk::gather_rows(R4, N, rows4, Ec, Ac, rc, st);
+    dkgk::decode_points(rc, 2 * R4 * N, rext, 2 * R4 * N, pok, st);
+    dkgk::dealer_ok(2 * R4, N, pok, rowok, st);
+    uint32_t* dsh = buf<uint32_t>(ctx, "bp.share", 32 * C4);
+    uint32_t* drn = buf<uint32_t>(ctx, "bp.rand", 32 * C4);
+    h2d(ctx, dsh, c4.share, 32 * C4);
+    h2d(ctx, drn, c4.randomness, 32 * C4);
+    uint32_t* sr = buf<uint32_t>(ctx, "bp.sr", 32 * 2 * C4);
+    uint32_t* acc2 = buf<uint32_t>(ctx, "bp.acc2", 4 * 2 * C4);
+    uint32_t* acd2 = buf<uint32_t>(ctx, "bp.acd2", 4 * 2 * C4);
+    dkgk::c3_prep(C4, R4, x4, crow4, dsh, drn, sr, acc2, acd2, st);
+    uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh4", PTB * 2 * C4);
+    dkgk::cmp_horner(2 * C4, seq, acc2, acd2, rext, 2 * R4 * N, N, nb, Rh, st);
+    uint8_t* eq = buf<uint8_t>(ctx, "bp.eq4", 2 * C4);
+    dkgk::c3_check(C4, x4, sr, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
+    // the qualified set is applied on the host (IGNORED, batch_proven_outcome), as verify_ceremony does
+    dkgk::c3_final(C4, R4, crow4, drow4, rowok, nullptr, fetched3, eq, dver4, st);
+  }
+  HCK(hipEventRecord(ctx->bpev[1], st));
+  // ---- round 2 (k_cv_*): the E rows of the accused dealers, the ciphertext pairs from the batch's own
+  uint8_t *cmask = nullptr, *pair = nullptr;
+  int32_t* dver2 = nullptr;
+  if (c2) {
+    cmask = buf<uint8_t>(ctx, "bp.cmask", V);
+    pair = buf<uint8_t>(ctx, "bp.pair", V * n);
+    dver2 = buf<int32_t>(ctx, "bp.verdict2", 4 * C2);
+    HCK(hipMemsetAsync(cmask, 1, V, st));
+    HCK(hipMemsetAsync(pair, 0, V * n, st));
+  }
+  if (C2) {
+    uint32_t* rc = buf<uint32_t>(ctx, "bp.rows2", 32 * R2 * N);
+    uint32_t* rext = buf<uint32_t>(ctx, "bp.rows2_ext", PTB * R2 * N);
+    uint8_t* pok = buf<uint8_t>(ctx, "bp.rows2_pok", R2 * N);
+    uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows2_ok", R2);
+    dkgk::gather_rows(R2, N, rows2, Ec, nullptr, rc, st);
+    dkgk::decode_points(rc, R2 * N, rext, R2 * N, pok, st);
+    dkgk::dealer_ok(R2, N, pok, rowok, st);
+    uint32_t* dpk = buf<uint32_t>(ctx, "bp.pk", 32 * V);
+    uint32_t* dprf = buf<uint32_t>(ctx, "bp.proofs", 192 * C2);
+    uint32_t* denc = buf<uint32_t>(ctx, "bp.enc", 128 * C2);
+    h2d(ctx, dpk, c2->pk, 32 * V);
+    h2d(ctx, dprf, c2->proofs, 192 * C2);
+    dkgk::gather_enc(C2, n, drow2, x2, e1, ct, denc, st);
+    // from here as complaints_verify_core, with the party and commitment rows in place of the indices
+    uint32_t* Pc = buf<uint32_t>(ctx, "bp.Pc", 32 * 5 * C2);
+    uint32_t* rs = buf<uint32_t>(ctx, "bp.rs", 32 * 2 * C2);
+    uint32_t* nc = buf<uint32_t>(ctx, "bp.nc", 32 * 2 * C2);
+    uint32_t* p12 = buf<uint32_t>(ctx, "bp.p12", 32 * 2 * C2);
+    uint32_t* bp1 = buf<uint32_t>(ctx, "bp.bp1", 4 * 2 * C2);
+    uint32_t* bp2 = buf<uint32_t>(ctx, "bp.bp2", 4 * 2 * C2);
+    uint32_t* bq2 = buf<uint32_t>(ctx, "bp.bq2", 4 * 2 * C2);
+    dkgk::cv_prep(C2, party2, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
+    uint32_t* Pext = buf<uint32_t>(ctx, "bp.Pext", PTB * 5 * C2);
+    uint8_t* ppok = buf<uint8_t>(ctx, "bp.Ppok", 5 * C2);
+    dkgk::decode_points(Pc, 5 * C2, Pext, 5 * C2, ppok, st);
+    uint32_t* T = buf<uint32_t>(ctx, "bp.T", 4 * dkgk::cmp_ladder_table_words(2 * C2));
+    uint32_t* S1 = buf<uint32_t>(ctx, "bp.S1", PTB * 2 * C2);
+    uint32_t* S2 = buf<uint32_t>(ctx, "bp.S2", PTB * 2 * C2);
+    uint32_t* G = buf<uint32_t>(ctx, "bp.G", PTB * 2 * C2);
+    dkgk::cmp_ladder(2 * C2, false, bp1, nullptr, nc, nullptr, Pext, 5 * C2, T, S1, st);
+    dkgk::cmp_ladder(2 * C2, true, bp2, bq2, rs, nc, Pext, 5 * C2, T, S2, st);
+    dkgk::fixed_base(2 * C2, rs, ctx->tab_gw, G, st);
+    dkgk::add_points(2 * C2, S1, G, 2 * C2, S1, st);
+    uint32_t* a1c = buf<uint32_t>(ctx, "bp.a1c", 32 * 2 * C2);
+    uint32_t* a2c = buf<uint32_t>(ctx, "bp.a2c", 32 * 2 * C2);
+    dkgk::encode_points(S1, 2 * C2, 2 * C2, a1c, st);
+    dkgk::encode_points(S2, 2 * C2, 2 * C2, a2c, st);
+    uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh2", PTB * C2);
+    dkgk::cmp_horner(C2, seq, x2, crow2, rext, R2 * N, N, nb, Rh, st);
+    uint8_t* eq = buf<uint8_t>(ctx, "bp.eq2", 2 * C2);
+    dkgk::cv_check(C2, x2, p12, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
+    dkgk::cv_final(C2, party2, crow2, dpk, denc, dprf, a1c, a2c, ppok, rowok, nullptr, eq, dver2, st);
+  }
+  // ---- the verdicts as the rounds' masks
+  dkgk::proven_masks(C2, n, drow2, x2, dver2, C4, drow4, dver4, cmask, pair, proven4, st);
+  HCK(hipEventRecord(ctx->bpev[2], st));
+  check_launch(ctx);
+  bp.a_ok = fetched3;
+  bp.cmask = cmask;
+  bp.pair = pair;
+  bp.proven4 = proven4;
+  bp.dver2 = dver2;
+  bp.dver4 = dver4;
+  bp.C2 = C2;
+  bp.C4 = C4;
+  bp.verdict2 = c2 ? c2->verdict : nullptr;
+  bp.dissent = c2 ? c2->dissent : nullptr;
+  bp.verdict4 = c4.verdict;
+}
+
+// After the batch's sync: the stages' device times, and per ceremony what proven_outcome does for one --
+// the verdicts against dealers that round 2 disqualified become IGNORED, the finalising parties' common
+// outcome, and a zeroed mpk where they panic.
+void batch_proven_outcome(dkg_ctx* ctx, size_t B, size_t n, size_t t, bool have_c2, const BatchComplaints4& c4,
+                          const BatchProven& bp, dkg_batch_out* out) {
+  float ms = 0;
+  HCK(hipEventElapsedTime(&ms, ctx->bpev[0], ctx->bpev[1]));
+  ctx->phase_ms["bproven.c4"] = ms;
+  HCK(hipEventElapsedTime(&ms, ctx->bpev[1], ctx->bpev[2]));
+  if (have_c2) ctx->phase_ms["bproven.c2"] = ms;
+  else ctx->phase_ms.erase("bproven.c2");
+  for (size_t c = 0; c < c4.C; c++)
+    if (!bp.qualified[(size_t)c4.ceremony[c] * n + c4.accused[c] - 1]) c4.verdict[c] = DKG_COMPLAINT_IGNORED;
+  for (size_t g = 0; g < B; g++) {
+    const size_t o = g * n;
+    int32_t index = -1;
+    const int32_t status = finalise_outcome(n, t, &bp.qualified[o], &bp.reconstruct[o], &bp.r2_error[o], &bp.r4_error[o],
+                                            &bp.a_present[o], bp.phase4_error[g] != 0, &index);
+    if (status == DKG_FIN_PANIC && out->mpk) memset(out->mpk + 32 * g, 0, 32);
+    if (c4.finalise_status) c4.finalise_status[g] = status;
+    if (c4.recovery_index) c4.recovery_index[g] = index;
+  }
 }
 
 // One ceremony to verify, as the host pointers of the C ABI (null = absent).  The shares come either
@@ -2537,6 +2814,7 @@ int dkg_ctx_create(int device, dkg_ctx** out) {
     for (auto& e : ctx->ev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->pev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->hev) HCK(hipEventCreate(&e));
+    for (auto& e : ctx->bpev) HCK(hipEventCreate(&e));
     for (auto& st : ctx->sub) HCK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest));
     HCK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, least));
     HCK(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
@@ -2581,6 +2859,8 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   for (auto& e : ctx->pev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->hev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : ctx->bpev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->join)
     if (e) (void)hipEventDestroy(e);
@@ -4143,6 +4423,107 @@ int dkg_ceremony_batch_verify_full(dkg_ctx* ctx, size_t B, size_t n, size_t t, c
     decrypt_batch_device(ctx, B, n, dsk, de1, dct, rs, rsp, iok, eok);
     batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok);
     collect_bfull_phases(ctx);
+    if (s_out) d2h(ctx, s_out, rs, 32 * V * n);
+    if (s_prime_out) d2h(ctx, s_prime_out, rsp, 32 * V * n);
+    sync(ctx);
+    batch_times(ctx, out, false);
+    return DKG_OK;
+  });
+}
+
+// ---- batches that decide by the proven complaints (batch_complaints, batch_proven_outcome)
+int dkg_ceremony_batch_verify_proven(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                     const uint8_t* s, const uint8_t* s_prime, const uint8_t* fetched1,
+                                     const uint8_t* fetched3, size_t C4, const uint32_t* ceremony4,
+                                     const uint32_t* accuser4, const uint32_t* accused4, const uint8_t* share4,
+                                     const uint8_t* randomness4, dkg_batch_out* out, int32_t* verdict4,
+                                     int32_t* finalise_status, int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !s || !s_prime) return DKG_E_ARG;
+    if (B == 0) return DKG_OK;
+    if (B * n >= ((size_t)1 << 31) ||
+        !batch_complaint_args_ok(B, n, C4, ceremony4, accuser4, accused4, {share4, randomness4, verdict4}))
+      return DKG_E_ARG;
+    const size_t N = t + 1, V = B * n;
+    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
+    h2d(ctx, Ec, E, 32 * V * N);
+    h2d(ctx, Ac, A, 32 * V * N);
+    uint32_t* ds = upload_scalars(ctx, "bat_s", s, V * n);
+    uint32_t* dsp = upload_scalars(ctx, "bat_sp", s_prime, V * n);
+    uint8_t *df1 = nullptr, *df3 = nullptr;
+    if (fetched1) {
+      df1 = buf<uint8_t>(ctx, "bp.f1", V);
+      h2d(ctx, df1, fetched1, V);
+    }
+    if (fetched3) {
+      df3 = buf<uint8_t>(ctx, "bp.f3", V);
+      h2d(ctx, df3, fetched3, V);
+    }
+    const BatchComplaints4 c4{C4, ceremony4, accuser4, accused4, share4, randomness4, verdict4, finalise_status,
+                              recovery_index};
+    BatchProven bp;
+    batch_complaints(ctx, B, n, t, Ec, Ac, nullptr, nullptr, nullptr, c4, df3, bp);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    batch_receivers(ctx, B, n, t, Ec, Ac, ds, dsp, out, df1, &bp);
+    batch_proven_outcome(ctx, B, n, t, false, c4, bp, out);
+    batch_times(ctx, out, false);
+    return DKG_OK;
+  });
+}
+
+int dkg_ceremony_batch_verify_full_proven(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* E,
+                                          const uint8_t* A, const uint8_t* e1, const uint8_t* ct, const uint8_t* sk,
+                                          const uint8_t* pk, size_t C, const uint32_t* ceremony,
+                                          const uint32_t* accuser, const uint32_t* accused, const uint8_t* proofs,
+                                          const uint8_t* fetched3, size_t C4, const uint32_t* ceremony4,
+                                          const uint32_t* accuser4, const uint32_t* accused4, const uint8_t* share4,
+                                          const uint8_t* randomness4, dkg_batch_out* out, uint8_t* s_out,
+                                          uint8_t* s_prime_out, int32_t* verdict, int32_t* dissent, int32_t* verdict4,
+                                          int32_t* finalise_status, int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
+    if (B == 0) return DKG_OK;
+    if (B * n >= ((size_t)1 << 31) ||
+        !batch_complaint_args_ok(B, n, C, ceremony, accuser, accused, {proofs, verdict}) ||
+        !batch_complaint_args_ok(B, n, C4, ceremony4, accuser4, accused4, {share4, randomness4, verdict4}))
+      return DKG_E_ARG;
+    const size_t N = t + 1, V = B * n, items = 2 * V * n;
+    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
+    h2d(ctx, Ec, E, 32 * V * N);
+    h2d(ctx, Ac, A, 32 * V * N);
+    uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
+    uint32_t* de1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
+    h2d(ctx, de1, e1, 32 * items);
+    h2d(ctx, dct, ct, 32 * items);
+    uint8_t* df3 = nullptr;
+    if (fetched3) {
+      df3 = buf<uint8_t>(ctx, "bp.f3", V);
+      h2d(ctx, df3, fetched3, V);
+    }
+    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
+    const BatchComplaints2 c2{pk, C, ceremony, accuser, accused, proofs, verdict, dissent};
+    const BatchComplaints4 c4{C4, ceremony4, accuser4, accused4, share4, randomness4, verdict4, finalise_status,
+                              recovery_index};
+    BatchProven bp;
+    batch_complaints(ctx, B, n, t, Ec, Ac, de1, dct, &c2, c4, df3, bp);  // before the timed region, as one ceremony's
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    bf_reset(ctx);
+    decrypt_batch_device(ctx, B, n, dsk, de1, dct, rs, rsp, iok, eok);
+    batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok, &bp);
+    collect_bfull_phases(ctx);
+    batch_proven_outcome(ctx, B, n, t, true, c4, bp, out);
     if (s_out) d2h(ctx, s_out, rs, 32 * V * n);
     if (s_prime_out) d2h(ctx, s_prime_out, rsp, 32 * V * n);
     sync(ctx);

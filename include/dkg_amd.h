@@ -700,6 +700,49 @@ int dkg_ceremony_verify_full_proven(dkg_ctx *ctx, size_t n, size_t t, const uint
                                     int32_t *dissent, int32_t *verdict4, int32_t *finalise_status,
                                     int32_t *recovery_index);
 
+/* ---- batches of ceremonies that decide by the proven complaints ----
+ * dkg_ceremony_batch_verify / _verify_full keep the rejection rule in both rounds; these two calls
+ * decide every ceremony of the batch as the single-ceremony *_proven calls decide one.  Complaints are
+ * flat arrays over the whole batch: complaint c belongs to ceremony[c] (0-based, < B), accuser[c] and
+ * accused[c] are 1-based within 1..n of that ceremony.  Any order: ceremonies interleaved, duplicates
+ * allowed; verdicts are written in input order.  Every output for ceremony c -- each dkg_batch_out
+ * field, verdict, verdict4, dissent[c], finalise_status[c], recovery_index[c] -- equals what the
+ * matching single-ceremony call returns on ceremony c's slices and its own complaints in their
+ * relative order: DKG_COMPLAINT_IGNORED against dealers round 2 disqualified, DKG_COMPLAINT_NO_PHASE3,
+ * DKG_FIN_PANIC with that ceremony's mpk zeroed, DKG_FIN_INSUFFICIENT with the first reconstructed
+ * dealer.  The proven rule holds for every ceremony of the call, also one without a complaint: there
+ * nobody is disqualified except rows with missing data, and nobody is reconstructed.
+ * B == 0 returns DKG_OK; C == 0 (C4 == 0) allows null complaint arrays; ceremony[c] >= B, an index
+ * outside 1..n or a null required pointer returns DKG_E_ARG.  Requires dkg_env_init (h).
+ * The complaints are verified on the device before the rounds, with no host synchronisation up to the
+ * batch's one round trip: only the distinct accused rows are decoded a second time, the ciphertext
+ * pairs are read from the batch's own e1 / ct, and P_i(j) is always one Horner walk per complaint --
+ * dkg_ctx_set_complaint_eval does not apply.  Outputs do not depend on dkg_ctx_set_batch_full_chunk.
+ * dkg_ctx_phase_ms "bproven.c4" / "bproven.c2": the device time of the round-4 / round-2 complaint
+ * stage of the last such call (-1 for a stage it did not run).
+ * dkg_complaints_prove takes one secret key per complaint, so it serves the complaints of any number
+ * of ceremonies in one call as it is: there is no batch variant of it. */
+/* dkg_ceremony_verify_fetched_proven for every ceremony of a batch.  fetched1, fetched3 [B*n] may be
+ * NULL (all present).  verdict4 [C4]; finalise_status, recovery_index [B] (may be NULL). */
+int dkg_ceremony_batch_verify_proven(dkg_ctx *ctx, size_t B, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                     const uint8_t *s, const uint8_t *s_prime, const uint8_t *fetched1,
+                                     const uint8_t *fetched3, size_t C4, const uint32_t *ceremony4,
+                                     const uint32_t *accuser4, const uint32_t *accused4, const uint8_t *share4,
+                                     const uint8_t *randomness4, dkg_batch_out *out, int32_t *verdict4,
+                                     int32_t *finalise_status, int32_t *recovery_index);
+/* dkg_ceremony_verify_full_proven for every ceremony of a batch.  sk, pk [B][n][32]; proofs [C][192];
+ * verdict [C]; dissent [B][n] (may be NULL); fetched3 [B*n] (may be NULL); s_out, s_prime_out as
+ * dkg_ceremony_batch_verify_full. */
+int dkg_ceremony_batch_verify_full_proven(dkg_ctx *ctx, size_t B, size_t n, size_t t, const uint8_t *E,
+                                          const uint8_t *A, const uint8_t *e1, const uint8_t *ct, const uint8_t *sk,
+                                          const uint8_t *pk, size_t C, const uint32_t *ceremony,
+                                          const uint32_t *accuser, const uint32_t *accused, const uint8_t *proofs,
+                                          const uint8_t *fetched3, size_t C4, const uint32_t *ceremony4,
+                                          const uint32_t *accuser4, const uint32_t *accused4, const uint8_t *share4,
+                                          const uint8_t *randomness4, dkg_batch_out *out, uint8_t *s_out,
+                                          uint8_t *s_prime_out, int32_t *verdict, int32_t *dissent, int32_t *verdict4,
+                                          int32_t *finalise_status, int32_t *recovery_index);
+
 /* ---- synthetic inputs: the seeded RNG convention ----
  * dealer seed = BLAKE2b-256("dkg-amd/v1/dealer" || master[32] || u32le ceremony || u32le dealer);
  * coefficients = ChaCha20Rng(seed): hiding b_0..b_t first, then sharing a_0..a_t (committee.rs:143-146),
