@@ -1757,63 +1757,162 @@ void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv
 // the 254 of four NAFs.  The sums do not fit next to the K addends (LDS and VGPRs hold about 5.5),
 // and need not: the digits are wave-uniform and known ahead, so the chain streams them.
 //
-// pair_sums: S_p = Q_2p + Q_2p+1 and D_p = Q_2p - Q_2p+1 by the complete formula (they share c, d,
-// hence f, g and Z; 14 products for both), written with their dense Z copies as piece planes
-// K + 2p and K + 2p + 1 of R / Rz; affine_pieces then normalises all K + 2 floor(K/2) planes.
-// Q_2p = +/-Q_2p+1 and identity padding give the identity with Z != 0 (complete formula), so the
-// normalisation's shared inversion is safe.
-__global__ __launch_bounds__(256) void k_pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv,
-                                                   uint32_t* R, uint32_t* Rz, size_t j0, size_t jn) {
-  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t j = j0 + gid % jn, rest = gid / jn, c = rest % width, p = rest / width;
-  if (p >= pieces / 2) return;
-  const size_t e0 = ((2 * p) * pstride + c) * nrecv + j, e1 = e0 + pstride * nrecv;
-  const size_t es = ((pieces + 2 * p) * pstride + c) * nrecv + j, ed = es + pstride * nrecv;
-  ge_p3 a, s;
-  ge_cached q;
-  {
-    ge_p3 b;
-    pt_load_aos(b, R, e1);
-    ge_to_cached(q, b);
-  }
-  pt_load_aos(a, R, e0);
-  fe ym, yp, f, g, x, y, e, h;
-  fe_mul(x, a.T, q.T2d);    // c
-  fe_mul(y, a.Z, q.Z2);     // d
-  fe_sub(f, y, x);          // f = d - c <= 1.5*2^27
-  fe_add(g, y, x);          // g = d + c <= 2^27
-  fe_sub(ym, a.Y, a.X);
-  fe_add(yp, a.Y, a.X);
-  fe_mul(s.Z, g, f);        // both results' Z
-  fe_mul(x, ym, q.YmX);     // the sum: ge_add's operands
-  fe_mul(y, yp, q.YpX);
-  fe_sub(e, y, x);
-  fe_add(h, y, x);
-  fe_mul(s.X, e, f);
-  fe_mul(s.Y, g, h);
-  fe_mul(s.T, e, h);
-  pt_store_aos<DKG_STEP_NT != 0>(R, es, s);
-  fe_mul(x, ym, q.YpX);     // the difference: ge_sub's (f and g change places)
-  fe_mul(y, yp, q.YmX);
-  fe_sub(e, y, x);
-  fe_add(h, y, x);
-  fe_mul(s.X, e, g);
-  fe_mul(s.Y, f, h);
-  fe_mul(s.T, e, h);
-  pt_store_aos<DKG_STEP_NT != 0>(R, ed, s);
-  uint2* zs = reinterpret_cast<uint2*>(Rz + es * 10);
-  uint2* zd = reinterpret_cast<uint2*>(Rz + ed * 10);
-#pragma unroll
-  for (int k = 0; k < 5; k++) zs[k] = zd[k] = make_uint2(s.Z.v[2 * k], s.Z.v[2 * k + 1]);
+// affine_pairs: the affine Niels addends of a pair's pieces and of S_p = Q_2p + Q_2p+1 and D_p =
+// Q_2p - Q_2p+1, in one pass; the projective S_p and D_p never reach memory.  With the complete
+// addition's c = T_0 2d T_1, d = 2 Z_0 Z_1, f = d - c, g = d + c, and e, h of the sum, e', h' of the
+// difference (Y-X and Y+X of Q_2p+1 change places), the affine results are
+//   x_S = e / g, y_S = h / f, x_D = e' / f, y_D = h' / g,
+// so the one inverse of Z_S = f g serves both: 1/g = f / Z_S, 1/f = g / Z_S.  Montgomery's trick as in
+// k_affine_pieces, over three elements per receiver: Z_0 Z_1 and Z_S enter the lane's running product
+// (pass 1: 6 products; Z and T are words 20..39 of the record, X and Y are not read), and the
+// exclusive prefix of the receiver is parked in its slot of plane 2p.  After the inversion pass 2
+// walks the receivers backwards, recomputes c, d, f, g (cheaper than their round trip through
+// memory) and writes the four slots: 33 products per receiver, 9.75 per addend with pass 1, plus
+// 1 / AFFQ_RUN of an inversion.  A lane's chain stays within ONE column (two pieces of it): identity
+// padding columns carry Z = 0 (comment above k_binom_wave) and poison only their own lanes, whose
+// outputs nothing reads.  Q_2p = +/-Q_2p+1 and identity + identity give f, g != 0 (complete
+// formula), so the shared inverse is safe for every real column.
+constexpr int AFFQ_RUN = 32;  // receivers per lane (fewer in a launch too small to fill the GPU)
+
+DKG_DEV void ld_zt(fe& z, fe& t, const uint32_t* R, size_t e) {  // Z, T of point e: words 20..39
+  const uint4* p4 = reinterpret_cast<const uint4*>(R + e * PT_WORDS) + 5;
+  const uint4 a = p4[0], b = p4[1], c = p4[2], d = p4[3], f = p4[4];
+  z = fe{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y}};
+  t = fe{{c.z, c.w, d.x, d.y, d.z, d.w, f.x, f.y, f.z, f.w}};
+}
+DKG_DEV void ld_xy(fe& x, fe& y, const uint32_t* R, size_t e) {  // X, Y of point e: words 0..19
+  const uint4* p4 = reinterpret_cast<const uint4*>(R + e * PT_WORDS);
+  const uint4 a = p4[0], b = p4[1], c = p4[2], d = p4[3], f = p4[4];
+  x = fe{{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y}};
+  y = fe{{c.z, c.w, d.x, d.y, d.z, d.w, f.x, f.y, f.z, f.w}};
+}
+// z01 = Z_0 Z_1, f = d - c, g = d + c of the complete addition (d = 2 z01 carried: f <= 1.5*2^27)
+DKG_DEV void pair_fg(fe& z01, fe& f, fe& g, const fe& z0, const fe& t0, const fe& z1, const fe& t1, const fe& d2) {
+  fe c, d;
+  fe_mul(z01, z0, z1);
+  fe_mul(c, t0, t1);
+  fe_mul(c, c, d2);
+  fe_dbl(d, z01);
+  fe_carry(d, d);
+  fe_sub(f, d, c);
+  fe_add(g, d, c);
+}
+// the slot of the affine point (x, y)
+DKG_DEV void st_niels(uint32_t* slot, const fe& x, const fe& y, const fe& d2) {
+  fe ypx, ymx, t;
+  fe_mul(t, x, y);
+  fe_mul(t, t, d2);
+  fe_add(ypx, y, x);
+  fe_sub(ymx, y, x);
+  st_fe3(slot, ypx, ymx, t);
 }
 
-void pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv, uint32_t* R, uint32_t* Rz,
-               hipStream_t stream, size_t j0, size_t jn) {
+// Receivers [j0, j0 + jn) of rows nrecv long; one lane per (pair, column) and run of receivers, laid
+// out as in k_affine_pieces: ls lanes share a run of ls * rl receivers, rl <= AFFQ_RUN per lane.
+__global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv,
+                                                      const uint32_t* __restrict__ R, uint32_t* __restrict__ A,
+                                                      size_t j0, size_t jn, unsigned ls, unsigned rl) {
+  const size_t span = (size_t)ls * rl, runs = (jn + span - 1) / span;
+  const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t item = gid / ls;
+  if (item >= (pieces / 2) * width * runs) return;
+  const size_t c = item % width, rest = item / width, run = rest % runs, p = rest / runs;
+  const size_t plane = pstride * nrecv;  // points from one piece plane to the next
+  const size_t e0 = (2 * p * pstride + c) * nrecv + j0;
+  const size_t jb = run * span + (gid % ls);  // receivers j0 + jb + ls i, i < cnt
+  const int cnt = jb < jn ? (int)min((size_t)rl, (jn - jb + ls - 1) / ls) : 0;
+  auto pt = [&](int i) { return e0 + jb + ls * (size_t)i; };  // Q_2p(j); Q_2p+1(j) one plane on
+  fe d2;
+  fe_ld(d2, ge_const::D2);
+  fe acc;
+  fe_one(acc);
+#pragma unroll 1
+  for (int i = 0; i < cnt; i++) {
+    uint4* a4 = reinterpret_cast<uint4*>(A + pt(i) * AFFP_WORDS);
+    a4[0] = make_uint4(acc.v[0], acc.v[1], acc.v[2], acc.v[3]);
+    a4[1] = make_uint4(acc.v[4], acc.v[5], acc.v[6], acc.v[7]);
+    a4[2] = make_uint4(acc.v[8], acc.v[9], 0u, 0u);
+    fe z0, t0, z1, t1, z01, f, g;
+    ld_zt(z0, t0, R, pt(i));
+    ld_zt(z1, t1, R, pt(i) + plane);
+    pair_fg(z01, f, g, z0, t0, z1, t1, d2);
+    fe_mul(acc, acc, z01);
+    fe_mul(f, f, g);  // Z_S
+    fe_mul(acc, acc, f);
+  }
+  fe inv;
+  fe_invert(inv, acc);
+#pragma unroll 1
+  for (int i = cnt - 1; i >= 0; i--) {
+    const size_t e = pt(i);
+    uint32_t* slot = A + e * AFFP_WORDS;
+    fe z0, t0, z1, t1, z01, f, g, zs, iz0, iz1;
+    ld_zt(z0, t0, R, e);
+    ld_zt(z1, t1, R, e + plane);
+    pair_fg(z01, f, g, z0, t0, z1, t1, d2);
+    fe_mul(zs, f, g);
+    {
+      const uint4* a4 = reinterpret_cast<const uint4*>(slot);
+      const uint4 q0 = a4[0], q1 = a4[1], q2 = a4[2];
+      const fe pre = {{q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y}};
+      fe t, i01;
+      fe_mul(t, inv, pre);      // 1 / (Z_0 Z_1 Z_S)
+      fe_mul(inv, inv, z01);
+      fe_mul(inv, inv, zs);     // 1 / (the earlier receivers' product)
+      fe_mul(i01, t, zs);       // 1 / (Z_0 Z_1)
+      fe_mul(zs, t, z01);       // 1 / Z_S
+      fe_mul(iz0, i01, z1);
+      fe_mul(iz1, i01, z0);
+    }
+    fe_mul(f, f, zs);           // 1 / g
+    fe_mul(g, g, zs);           // 1 / f
+    fe ym0, yp0, ym1, yp1;
+    {
+      fe X, Y, x, y;
+      ld_xy(X, Y, R, e);
+      fe_sub(ym0, Y, X);
+      fe_add(yp0, Y, X);
+      fe_mul(x, X, iz0);
+      fe_mul(y, Y, iz0);
+      st_niels(slot, x, y, d2);
+      ld_xy(X, Y, R, e + plane);
+      fe_sub(ym1, Y, X);
+      fe_add(yp1, Y, X);
+      fe_mul(x, X, iz1);
+      fe_mul(y, Y, iz1);
+      st_niels(slot + plane * AFFP_WORDS, x, y, d2);
+    }
+    fe a, b, eh, x, y;
+    fe_mul(a, ym0, ym1);        // the sum: ge_add's operands
+    fe_mul(b, yp0, yp1);
+    fe_sub(eh, b, a);           // e
+    fe_mul(x, eh, f);           // x_S = e / g
+    fe_add(eh, b, a);           // h
+    fe_mul(y, eh, g);           // y_S = h / f
+    st_niels(slot + pieces * plane * AFFP_WORDS, x, y, d2);  // planes pieces + 2p, pieces + 2p + 1
+    fe_mul(a, ym0, yp1);        // the difference: ge_sub's (f and g change places)
+    fe_mul(b, yp0, ym1);
+    fe_sub(eh, b, a);           // e'
+    fe_mul(x, eh, g);           // x_D = e' / f
+    fe_add(eh, b, a);           // h'
+    fe_mul(y, eh, f);           // y_D = h' / g
+    st_niels(slot + (pieces + 1) * plane * AFFP_WORDS, x, y, d2);
+  }
+}
+
+void affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
+                  hipStream_t stream, size_t j0, size_t jn) {
   if (!jn) jn = nrecv - j0;
   if (!width || !jn || pieces < 2) return;
-  const size_t lanes = (pieces / 2) * width * jn;
-  hipLaunchKernelGGL(k_pair_sums, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, width, pstride, pieces,
-                     nrecv, R, Rz, j0, jn);
+  // a lane's two passes and inversion are one dependent chain: a launch of under one wave per SIMD
+  // (a dealer shard of few columns) runs shorter chains on more lanes, down to 8 receivers per lane
+  unsigned rl = AFFQ_RUN;
+  while (rl > 8 && (pieces / 2) * width * ((jn + rl - 1) / rl) < 65536) rl /= 2;
+  unsigned ls = 32;  // lanes per run, fewer for a short receiver part (affine_pieces)
+  while (ls > 1 && (size_t)(ls / 2) * rl >= jn) ls /= 2;
+  const size_t runs = (jn + (size_t)ls * rl - 1) / ((size_t)ls * rl), lanes = (pieces / 2) * width * runs * ls;
+  hipLaunchKernelGGL(k_affine_pairs, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, width, pstride,
+                     pieces, nrecv, R, A, j0, jn, ls, rl);
 }
 
 // The streamed addend of the chain's next both-nonzero column, event e: bits 0-1 its plane after the

@@ -171,11 +171,13 @@ void affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv, co
 void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* digits,
                        const int16_t* top, const uint32_t* A, uint32_t* R, hipStream_t stream, size_t j0 = 0,
                        size_t jn = 0);
-// Pairwise joint sparse form (pieces = 2 or 4).  pair_sums writes Q_2p + Q_2p+1 and Q_2p - Q_2p+1 of
-// every pair p as piece planes pieces + 2p and pieces + 2p + 1 of R and Rz (complete formula: Z != 0),
-// so R, Rz and A hold pieces + 2 floor(pieces / 2) planes and affine_pieces runs over all of them.
-void pair_sums(size_t width, size_t pstride, size_t pieces, size_t nrecv, uint32_t* R, uint32_t* Rz,
-               hipStream_t stream, size_t j0 = 0, size_t jn = 0);
+// Pairwise joint sparse form (pieces = 2 or 4).  affine_pairs is affine_pieces for the JSF chains: it
+// writes the affine addends of the pieces AND of Q_2p + Q_2p+1 and Q_2p - Q_2p+1 of every pair p, the
+// latter as planes pieces + 2p and pieces + 2p + 1 of A, so A holds pieces + 2 floor(pieces / 2)
+// planes of pstride columns and R only the pieces' (the projective sums are never stored; one
+// inverse serves a pair's sum and difference).  It reads Z from R itself: no dense Z copy.
+void affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
+                  hipStream_t stream, size_t j0 = 0, size_t jn = 0);
 // combine_short_aff over JSF digits (runtime.hip split_short): a column with both digits of a pair
 // set adds the pair's sum or difference, streamed from its plane of A one such column ahead.
 // ev [nrecv][JSF_EV_WORDS]: one word per both-nonzero column in chain order -- positions downwards,

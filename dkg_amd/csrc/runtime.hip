@@ -448,12 +448,12 @@ double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, int s
     // product (253 doublings + ~85 NAF additions), then (ceil(U/2) - 1) joint y^2 / y steps (253
     // doublings + ~170 additions)
     // pairwise JSF (U = 2, 4): a pair's joint form has every second column nonzero, a leftover
-    // piece's NAF every third; the 2 floor(U/2) pair sums cost 7 products each to form and ~16 to
-    // normalise (k_pair_sums, k_affine_pieces: ~23 of an addition's 8)
+    // piece's NAF every third; a pair's four addends cost 39 products (k_affine_pairs) against the
+    // 15.5 of its two pieces alone (k_affine_pieces): ~11.75 of an addition's 8 per sum or difference
     const double bits = 253.0 * (U - 1) / U;
     const bool jsf = short_mult == SM_JSF && jsf_built(U);
     const double adds = jsf ? (U / 2) * bits / 2 + (U % 2) * bits / 3 : U * bits / 3;
-    const double per = short_mult && U <= SHORT_MAX ? bits * 950 + adds * ADD + (jsf ? 2 * (U / 2) * 23.0 / 8 * ADD : 0.0)
+    const double per = short_mult && U <= SHORT_MAX ? bits * 950 + adds * ADD + (jsf ? 2 * (U / 2) * 11.75 / 8 * ADD : 0.0)
                                             : (U % 2 == 0 ? 253 * 950 + 85 * ADD : 0.0) +
                                                   ((U + 1) / 2 - 1) * (253 * 950 + 170 * ADD);
     const double waves = (double)cols / 64 * n;
@@ -718,12 +718,12 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   uint32_t* eT = buf<uint32_t>(ctx, "v.binomT", PTB * L * W);  // column-major copy for the stepping
   // short multipliers up to SHORT_MAX pieces with affine addends, 4 with projective ones
   const bool short_mult = U > 1 && U <= (ctx->addend_mode == 0 ? SHORT_MAX : 4) && ctx->combine_mode != 1;
-  // pairwise JSF chains: the pairs' sums and differences are 2 floor(U/2) more piece planes of R, Rz
-  // and Aff after the U stepped ones (the chunk offsets do not change)
+  // pairwise JSF chains: the pairs' sums and differences are 2 floor(U/2) more piece planes of Aff
+  // after the U stepped ones (the chunk offsets do not change); R holds the stepped ones only
   // (k_combine_jsf keeps a lane's column * n in 32 bits: any table that fits device memory)
   const bool jsf = short_mult && short_kind(ctx) == SM_JSF && jsf_built(U) && (uint64_t)npad * n < (1ull << 32);
   const size_t WP = jsf ? (U + 2 * (U / 2)) * npad : W;
-  uint32_t* R = buf<uint32_t>(ctx, "v.R", PTB * WP * n);
+  uint32_t* R = buf<uint32_t>(ctx, "v.R", PTB * W * n);
   uint32_t *sa = nullptr, *sb = nullptr;
   if (L > 512) {
     sa = buf<uint32_t>(ctx, "v.step_a", PTB * W * n);
@@ -741,7 +741,8 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   // affine addends: one 128-B slot per (piece column, receiver), like R
   uint32_t* Aff = short_mult && ctx->addend_mode == 0 ? buf<uint32_t>(ctx, "v.Aff", 4 * AFFP_WORDS_H * WP * n) : nullptr;
   // the stepping's dense copy of each stored point's Z (40 B), read by the affine normalisation
-  uint32_t* Rz = Aff ? buf<uint32_t>(ctx, "v.Rz", 40 * WP * n) : nullptr;
+  // (k_affine_pieces; the JSF chains' k_affine_pairs reads Z and T from R, so there is none)
+  uint32_t* Rz = Aff && !jsf ? buf<uint32_t>(ctx, "v.Rz", 40 * W * n) : nullptr;
   if (short_mult) split_short(ctx, n, L, U, jsf, &sdig, &stop, &sscale, &sev);
   else if (U > 1) split_digits(ctx, n, L, &ydig, &ytop);
   ctx->last_combine = U > 1 ? (short_mult ? 2 : 1) : 0;
@@ -874,9 +875,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
       throw Fail{DKG_E_ARG};  // stepping flag words: an internal layout error, never silently dropped
     if (tm) HCK(hipEventRecord(ctx->pev[2], st));
     if (jsf) {
-      dkgk::pair_sums(w, npad, U, n, R + c0 * n * PT_WORDS_H, Rz + c0 * n * 10, st);
-      dkgk::affine_pieces(w, npad, U + 2 * (U / 2), n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st,
-                          Rz + c0 * n * 10);
+      dkgk::affine_pairs(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st);
       dkgk::combine_short_jsf(w, npad, U, n, sdig, stop, sev, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
     } else if (short_mult && Aff) {
       dkgk::affine_pieces(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, Rz + c0 * n * 10);

@@ -14,7 +14,7 @@ weights) straight from the header text, so the checker cannot drift from the cod
   * fe_tobytes32's canonical reduction sees a value below 2p (one conditional subtraction suffices).
 The group formulas (ge_to_cached, ge_add, ge_sub, ge_madd, ge_msub, ge_dbl / _rt / _lean,
 ge_add_signed, ge_add_lds incl. its negated path, ge_madd_signed / ge_madd_lds and the affine
-addends of k_affine_pieces, the stepping's dedicated ge_add_ded_lds (and fe_tight_zero's operand), the comb entry selection of combw_mul_add,
+addends of k_affine_pieces and k_affine_pairs, the stepping's dedicated ge_add_ded_lds (and fe_tight_zero's operand), the comb entry selection of combw_mul_add,
 ristretto_eq, decode / encode) are run on the bounds; point coordinates are iterated to a fixpoint
 (every stored coordinate is again an input), so the invariant "a coordinate is TIGHT" is closed.
 
@@ -371,6 +371,39 @@ def affine_addend(p, where="affine_pieces"):
     return (fe_add(y, x, where), fe_sub(y, x, where), fe_mul(fe_mul(T, zi, where), D2, where))
 
 
+def affine_pair(p0, p1, where="affine_pairs"):
+    """kernels.hip k_affine_pairs: the four affine addends of a pair -- Q_0, Q_1 as affine_addend, and
+    the sum and difference from the complete addition's e, h, e', h' over the shared inverse of
+    Z_S = f g (1/g = f / Z_S, 1/f = g / Z_S): x_S = e / g, y_S = h / f, x_D = e' / f, y_D = h' / g."""
+    X0, Y0, Z0, T0 = p0
+    X1, Y1, Z1, T1 = p1
+    z01 = fe_mul(Z0, Z1, where)
+    c = fe_mul(fe_mul(T0, T1, where), D2, where)
+    d = fe_carry(fe_add(z01, z01, where), where)    # fe_dbl + fe_carry
+    f = fe_sub(d, c, where)
+    g = fe_add(d, c, where)
+    zs = fe_mul(f, g, where)
+    # every inverse is a product of (products of) z01, zs, the parked prefix and fe_invert's output
+    izs = fe_mul(fe_mul(zs, z01, where), zs, where)
+    i01 = fe_mul(izs, zs, where)
+    ig, i_f = fe_mul(f, izs, where), fe_mul(g, izs, where)
+
+    def niels(x, y):                                # st_niels: y+x and y-x left uncarried
+        return (fe_add(y, x, where), fe_sub(y, x, where), fe_mul(fe_mul(x, y, where), D2, where))
+
+    out = []
+    for (X, Y, Zo) in ((X0, Y0, Z1), (X1, Y1, Z0)):
+        iz = fe_mul(i01, Zo, where)
+        out.append(niels(fe_mul(X, iz, where), fe_mul(Y, iz, where)))
+    ym0, yp0 = fe_sub(Y0, X0, where), fe_add(Y0, X0, where)
+    ym1, yp1 = fe_sub(Y1, X1, where), fe_add(Y1, X1, where)
+    for (qa, qb, ix, iy) in ((ym1, yp1, ig, i_f), (yp1, ym1, i_f, ig)):   # the sum, the difference
+        a, b = fe_mul(ym0, qa, where), fe_mul(yp0, qb, where)
+        e, h = fe_sub(b, a, where), fe_add(b, a, where)
+        out.append(niels(fe_mul(e, ix, where), fe_mul(h, iy, where)))
+    return out
+
+
 def ge_to_cached_ded(p):
     X, Y, Z, T = p
     return (fe_add(Y, X, "to_cached_ded"), fe_sub(Y, X, "to_cached_ded"), fe_add(Z, Z, "to_cached_ded"),
@@ -536,6 +569,7 @@ def run():
         aff = (fe_carry(fe_add(tight, tight)), fe_carry(fe_sub(tight, tight)), fe_mul(fe_mul(tight, tight), D2))
         outs += [ge_madd(pt, comb8_entry(*aff), "comb8 madd"), ge_madd(pt, aff, "ge_msub", minus=True)]
         outs += [ge_madd_signed(pt, affine_addend(pt)), ge_add_ded(pt, ge_to_cached_ded(pt))]
+        outs += [ge_madd_signed(pt, q, "ge_madd_signed(affine_pairs)") for q in affine_pair(pt, pt)]
         outs += [ristretto_decode(), ristretto_elligator()]
         ristretto_encode(pt)
         new = vmax(tight, *[x for o in outs for x in o])
