@@ -846,7 +846,6 @@ class BatchResult:
 
 
 def _batch_out(B, n, big):
-    import struct  # noqa: F401
     V = B * n
     sizes = {"mpk": 32 * B, "n_qualified": 4 * B, "phase4_error": B, "qualified": V, "r2_error": V, "r4_error": V,
              "complaints2": 4 * V,
@@ -915,27 +914,42 @@ def _batch_result(B, n, t, o, bufs):
             "total": o.ms_total})
 
 
+def _batch_call(be, fn, B, n, t, args, tail=(), big=True, cached=False):
+    """One batch entry point, fn(ctx, B, n, t, *args, out, *tail), as a BatchResult.  cached: the output
+    buffers are kept on the backend for the next batch of the same shape (the result holds copies)."""
+    key = (B, n, big)
+    cache = getattr(be, "_batch_bufs", None) if cached else None
+    if cache is None or cache[0] != key:
+        cache = (key,) + _batch_out(B, n, big)
+        if cached:
+            be._batch_bufs = cache
+    o, bufs = cache[1], cache[2]
+    _check(be.ctx, fn(be.ctx, B, n, t, *args, ctypes.byref(o), *tail))
+    return _batch_result(B, n, t, o, bufs)
+
+
+def _batch_call_shares(be, fn, B, n, t, args, tail=()):
+    """_batch_call for the full verify entry points, fn(.., out, s_out, s_prime_out, *tail): the result
+    also carries the decrypted s / s_prime [B*n][n][32]."""
+    size = 32 * B * n * n
+    s, sp = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
+    r = _batch_call(be, fn, B, n, t, args, (s, sp) + tuple(tail))
+    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
+    return r
+
+
 def ceremony_batch_device(be: "Backend", B: int, n: int, t: int, d_a: int, d_b: int, big: bool = False) -> BatchResult:
     """B honest ceremonies from device coefficients [B*n][t+1][32] (dkg_ceremony_batch_device).  The
     output buffers are kept on the backend for the next batch of the same shape (the result holds
     copies): a 10,000-ceremony batch no longer allocates and zeroes ~5 MB of host buffers per call."""
-    key = (B, n, big)
-    cache = getattr(be, "_batch_bufs", None)
-    if cache is None or cache[0] != key:
-        cache = (key,) + _batch_out(B, n, big)
-        be._batch_bufs = cache
-    o, bufs = cache[1], cache[2]
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_device(be.ctx, B, n, t, ctypes.c_void_p(d_a), ctypes.c_void_p(d_b),
-                                                          ctypes.byref(o)))
-    return _batch_result(B, n, t, o, bufs)
+    vp = ctypes.c_void_p
+    return _batch_call(be, _lib.lib().dkg_ceremony_batch_device, B, n, t, (vp(d_a), vp(d_b)), big=big, cached=True)
 
 
 def ceremony_batch_verify(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, s: bytes,
                           s_prime: bytes) -> BatchResult:
     """Receiver side of B ceremonies from (possibly tampered) broadcast values (dkg_ceremony_batch_verify)."""
-    o, bufs = _batch_out(B, n, True)
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify(be.ctx, B, n, t, E, A, s, s_prime, ctypes.byref(o)))
-    return _batch_result(B, n, t, o, bufs)
+    return _batch_call(be, _lib.lib().dkg_ceremony_batch_verify, B, n, t, (E, A, s, s_prime))
 
 
 def ceremony_batch_full_device(be: "Backend", B: int, n: int, t: int, d_a: int, d_b: int, d_r: int, sk: bytes,
@@ -944,29 +958,16 @@ def ceremony_batch_full_device(be: "Backend", B: int, n: int, t: int, d_a: int, 
     [B*n][t+1][32], encryption randomness d_r [B*n][n][2][32] (enc_randomness_device(master, c0, B, 0, n, n,
     t, d_r)), sk / pk = member_keys_batch output.  Output buffers are kept on the backend as in
     ceremony_batch_device."""
-    key = (B, n, big)
-    cache = getattr(be, "_batch_bufs", None)
-    if cache is None or cache[0] != key:
-        cache = (key,) + _batch_out(B, n, big)
-        be._batch_bufs = cache
-    o, bufs = cache[1], cache[2]
     vp = ctypes.c_void_p
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_full_device(be.ctx, B, n, t, vp(d_a), vp(d_b), vp(d_r), sk, pk,
-                                                               ctypes.byref(o)))
-    return _batch_result(B, n, t, o, bufs)
+    return _batch_call(be, _lib.lib().dkg_ceremony_batch_full_device, B, n, t, (vp(d_a), vp(d_b), vp(d_r), sk, pk),
+                       big=big, cached=True)
 
 
 def ceremony_batch_verify_full(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, e1: bytes, ct: bytes,
                                sk: bytes) -> BatchResult:
     """Receiver side of B full-mode ceremonies from (possibly tampered) broadcast values
     (dkg_ceremony_batch_verify_full); the result also carries the decrypted s / s_prime."""
-    o, bufs = _batch_out(B, n, True)
-    size = 32 * B * n * n
-    s, sp = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_full(be.ctx, B, n, t, E, A, e1, ct, sk, ctypes.byref(o), s, sp))
-    r = _batch_result(B, n, t, o, bufs)
-    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
-    return r
+    return _batch_call_shares(be, _lib.lib().dkg_ceremony_batch_verify_full, B, n, t, (E, A, e1, ct, sk))
 
 
 @dataclass
@@ -1010,15 +1011,14 @@ def ceremony_batch_verify_proven(be: "Backend", B: int, n: int, t: int, E: bytes
     (dkg_ceremony_batch_verify_proven): complaint c belongs to ceremony4[c] (0-based), accusers4 /
     accused4 are 1-based within it; any order.  fetched1 / fetched3 [B*n], None = all present."""
     C4 = len(accusers4)
-    o, bufs = _batch_out(B, n, True)
     res4 = _carray(ctypes.c_int32, C4)
     st, ri = _carray(ctypes.c_int32, B), _carray(ctypes.c_int32, B)
     u32 = ctypes.c_uint32
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_proven(
-        be.ctx, B, n, t, E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(u32, C4, ceremony4),
-        _carray(u32, C4, accusers4), _carray(u32, C4, accused4), share4, randomness4, ctypes.byref(o), res4, st, ri))
-    return BatchProvenResult(_batch_result(B, n, t, o, bufs), list(ceremony4), list(res4)[:C4], list(st)[:B],
-                             list(ri)[:B])
+    r = _batch_call(
+        be, _lib.lib().dkg_ceremony_batch_verify_proven, B, n, t,
+        (E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(u32, C4, ceremony4),
+         _carray(u32, C4, accusers4), _carray(u32, C4, accused4), share4, randomness4), (res4, st, ri))
+    return BatchProvenResult(r, list(ceremony4), list(res4)[:C4], list(st)[:B], list(ri)[:B])
 
 
 def ceremony_batch_verify_full_proven(be: "Backend", B: int, n: int, t: int, E: bytes, A: bytes, e1: bytes, ct: bytes,
@@ -1031,18 +1031,14 @@ def ceremony_batch_verify_full_proven(be: "Backend", B: int, n: int, t: int, E: 
     accusers, accused, proofs [C][192]) and the round-4 complaints (ceremony4, ...) as flat lists over
     the batch.  The result also carries the decrypted s / s_prime."""
     C, C4 = len(accusers), len(accusers4)
-    o, bufs = _batch_out(B, n, True)
-    size = 32 * B * n * n
-    s, sp = ctypes.create_string_buffer(max(size, 1)), ctypes.create_string_buffer(max(size, 1))
     res, res4, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4), _carray(ctypes.c_int32, B * n)
     st, ri = _carray(ctypes.c_int32, B), _carray(ctypes.c_int32, B)
     u32 = ctypes.c_uint32
-    _check(be.ctx, _lib.lib().dkg_ceremony_batch_verify_full_proven(
-        be.ctx, B, n, t, E, A, e1, ct, sk, pk, C, _carray(u32, C, ceremony), _carray(u32, C, accusers),
-        _carray(u32, C, accused), proofs, _opt(fetched3), C4, _carray(u32, C4, ceremony4), _carray(u32, C4, accusers4),
-        _carray(u32, C4, accused4), share4, randomness4, ctypes.byref(o), s, sp, res, dis, res4, st, ri))
-    r = _batch_result(B, n, t, o, bufs)
-    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
+    r = _batch_call_shares(
+        be, _lib.lib().dkg_ceremony_batch_verify_full_proven, B, n, t,
+        (E, A, e1, ct, sk, pk, C, _carray(u32, C, ceremony), _carray(u32, C, accusers), _carray(u32, C, accused),
+         proofs, _opt(fetched3), C4, _carray(u32, C4, ceremony4), _carray(u32, C4, accusers4),
+         _carray(u32, C4, accused4), share4, randomness4), (res, dis, res4, st, ri))
     return BatchProvenResult(r, list(ceremony4), list(res4)[:C4], list(st)[:B], list(ri)[:B], list(ceremony),
                              list(res)[:C], list(dis)[:B * n])
 

@@ -257,6 +257,14 @@ uint32_t* upload_scalars(dkg_ctx* ctx, const char* name, const uint8_t* host, si
   return red;
 }
 
+// Upload an optional byte mask: null (absent) stays null.
+const uint8_t* upload_mask(dkg_ctx* ctx, const char* name, const uint8_t* host, size_t bytes) {
+  if (!host) return nullptr;
+  uint8_t* d = buf<uint8_t>(ctx, name, bytes);
+  h2d(ctx, d, host, bytes);
+  return d;
+}
+
 // Nontemporal stores for binomial step r over `columns` table columns (all chunks run their steps
 // together): when the step's rows read + written, 2 (r + 1) columns 160 B, exceed DKG_BINOM_NT_BYTES
 // (kernels.hip binom_pt_store).  The environment variable overrides the default for A/B runs.
@@ -2070,8 +2078,8 @@ int need_env(dkg_ctx* ctx) {
   return DKG_OK;
 }
 
-// The argument prologue of the entry points that need the commitment key: the environment is set,
-// (t, n) are admissible and none of `required` is null.
+// The argument prologue of the entry points that need the commitment key, one ceremony's and a
+// batch's alike: the environment is set, (t, n) are admissible and none of `required` is null.
 int ceremony_args(dkg_ctx* ctx, size_t n, size_t t, std::initializer_list<const void*> required) {
   const int rc = need_env(ctx);
   if (rc) return rc;
@@ -2170,6 +2178,43 @@ void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, c
   ev.Rh = Rh;
 }
 
+// The announcements of C round-2 complaints' proofs (dl_equality/zkp.rs:60-63): a1 = g r - pk c (comb +
+// one-base walk), a2 = e1 r - K c (Straus), both encoded, with p12 and the decode mask ppok [5C] of
+// the complaints' points as k_cv_check / k_cv_final read them.  Device: party [C] the accuser's 1-based
+// row of pk; enc [C][128], proofs [C][192].  One ceremony and a batch share the cv_* buffers.
+struct Announcements {
+  const uint32_t *p12, *a1c, *a2c;
+  const uint8_t* ppok;
+};
+Announcements complaint_announcements(dkg_ctx* ctx, size_t C, const uint32_t* party, const uint32_t* dpk,
+                                      const uint32_t* denc, const uint32_t* dprf, hipStream_t st) {
+  // scalars, the points to decode, SymmetricKey::process of both ciphertexts
+  uint32_t* Pc = buf<uint32_t>(ctx, "cv_Pc", 32 * 5 * C);
+  uint32_t* rs = buf<uint32_t>(ctx, "cv_rs", 32 * 2 * C);
+  uint32_t* nc = buf<uint32_t>(ctx, "cv_nc", 32 * 2 * C);
+  uint32_t* p12 = buf<uint32_t>(ctx, "cv_p12", 32 * 2 * C);
+  uint32_t* bp1 = buf<uint32_t>(ctx, "cv_bp1", 4 * 2 * C);
+  uint32_t* bp2 = buf<uint32_t>(ctx, "cv_bp2", 4 * 2 * C);
+  uint32_t* bq2 = buf<uint32_t>(ctx, "cv_bq2", 4 * 2 * C);
+  dkgk::cv_prep(C, party, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
+  uint32_t* Pext = buf<uint32_t>(ctx, "cv_Pext", PTB * 5 * C);
+  uint8_t* ppok = buf<uint8_t>(ctx, "cv_Ppok", 5 * C);
+  dkgk::decode_points(Pc, 5 * C, Pext, 5 * C, ppok, st);
+  uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(2 * C));
+  uint32_t* S1 = buf<uint32_t>(ctx, "cv_S1", PTB * 2 * C);
+  uint32_t* S2 = buf<uint32_t>(ctx, "cv_S2", PTB * 2 * C);
+  uint32_t* G = buf<uint32_t>(ctx, "cv_G", PTB * 2 * C);
+  dkgk::cmp_ladder(2 * C, false, bp1, nullptr, nc, nullptr, Pext, 5 * C, T, S1, st);
+  dkgk::cmp_ladder(2 * C, true, bp2, bq2, rs, nc, Pext, 5 * C, T, S2, st);
+  dkgk::fixed_base(2 * C, rs, ctx->tab_gw, G, st);
+  dkgk::add_points(2 * C, S1, G, 2 * C, S1, st);
+  uint32_t* a1c = buf<uint32_t>(ctx, "cv_a1c", 32 * 2 * C);
+  uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
+  dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
+  dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
+  return {p12, a1c, a2c, ppok};
+}
+
 // MisbehavingPartiesRound1::verify (broadcast.rs:50-99) for C complaints of one ceremony.  Device: dpk
 // [n][8] member keys, Ec [n][N][8] commitments; host: accuser / accused (1-based, validated by the
 // caller), fetched1 (may be null), enc [C][128], proofs [C][192].  verdict [C] on the host; rowok_host
@@ -2195,48 +2240,20 @@ void complaints_verify_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const ui
   uint32_t* dacd = buf<uint32_t>(ctx, "cv_accused", 4 * C);
   uint32_t* denc = buf<uint32_t>(ctx, "cv_enc", 128 * C);
   uint32_t* dprf = buf<uint32_t>(ctx, "cv_proofs", 192 * C);
-  uint8_t* dfet = nullptr;
   h2d(ctx, dacc, accuser, 4 * C);
   h2d(ctx, dacd, accused, 4 * C);
   h2d(ctx, denc, enc, 128 * C);
   h2d(ctx, dprf, proofs, 192 * C);
-  if (fetched1) {
-    dfet = buf<uint8_t>(ctx, "cv_fetched", n);
-    h2d(ctx, dfet, fetched1, n);
-  }
-  // scalars, the points to decode, SymmetricKey::process of both ciphertexts
-  uint32_t* Pc = buf<uint32_t>(ctx, "cv_Pc", 32 * 5 * C);
-  uint32_t* rs = buf<uint32_t>(ctx, "cv_rs", 32 * 2 * C);
-  uint32_t* nc = buf<uint32_t>(ctx, "cv_nc", 32 * 2 * C);
-  uint32_t* p12 = buf<uint32_t>(ctx, "cv_p12", 32 * 2 * C);
-  uint32_t* bp1 = buf<uint32_t>(ctx, "cv_bp1", 4 * 2 * C);
-  uint32_t* bp2 = buf<uint32_t>(ctx, "cv_bp2", 4 * 2 * C);
-  uint32_t* bq2 = buf<uint32_t>(ctx, "cv_bq2", 4 * 2 * C);
-  dkgk::cv_prep(C, dacc, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
-  uint32_t* Pext = buf<uint32_t>(ctx, "cv_Pext", PTB * 5 * C);
-  uint8_t* ppok = buf<uint8_t>(ctx, "cv_Ppok", 5 * C);
-  dkgk::decode_points(Pc, 5 * C, Pext, 5 * C, ppok, st);
-  // announcements (dl_equality/zkp.rs:60-63): a1 = g r - pk c (comb + one-base walk), a2 = e1 r - K c (Straus)
-  uint32_t* T = buf<uint32_t>(ctx, "cv_T", 4 * dkgk::cmp_ladder_table_words(2 * C));
-  uint32_t* S1 = buf<uint32_t>(ctx, "cv_S1", PTB * 2 * C);
-  uint32_t* S2 = buf<uint32_t>(ctx, "cv_S2", PTB * 2 * C);
-  uint32_t* G = buf<uint32_t>(ctx, "cv_G", PTB * 2 * C);
-  dkgk::cmp_ladder(2 * C, false, bp1, nullptr, nc, nullptr, Pext, 5 * C, T, S1, st);
-  dkgk::cmp_ladder(2 * C, true, bp2, bq2, rs, nc, Pext, 5 * C, T, S2, st);
-  dkgk::fixed_base(2 * C, rs, ctx->tab_gw, G, st);
-  dkgk::add_points(2 * C, S1, G, 2 * C, S1, st);
-  uint32_t* a1c = buf<uint32_t>(ctx, "cv_a1c", 32 * 2 * C);
-  uint32_t* a2c = buf<uint32_t>(ctx, "cv_a2c", 32 * 2 * C);
-  dkgk::encode_points(S1, 2 * C, 2 * C, a1c, st);
-  dkgk::encode_points(S2, 2 * C, 2 * C, a2c, st);
+  const uint8_t* dfet = upload_mask(ctx, "cv_fetched", fetched1, n);
+  const Announcements an = complaint_announcements(ctx, C, dacc, dpk, denc, dprf, st);
   // P_i(j): per accused dealer, the difference tables of its row or one Horner walk per complaint
   ComplaintEvals ev;
   complaint_evals(ctx, n, t, n, C, accuser, accused, dacc, dacd, Ec, Eext, ev);
   const uint32_t *dridx = ev.dridx, *Rh = ev.Rh, *Rt = ev.Rt, *scale = ev.scale;
   uint8_t* eq = buf<uint8_t>(ctx, "cv_eq", 2 * C);
-  dkgk::cv_check(C, dacc, p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+  dkgk::cv_check(C, dacc, an.p12, dridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
   int32_t* dver = buf<int32_t>(ctx, "cv_verdict", 4 * C);
-  dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, a1c, a2c, ppok, rowok, dfet, eq, dver, st);
+  dkgk::cv_final(C, dacc, dacd, dpk, denc, dprf, an.a1c, an.a2c, an.ppok, rowok, dfet, eq, dver, st);
   check_launch(ctx);
   d2h(ctx, verdict, dver, 4 * C);
   sync(ctx);  // the staging vectors (ev) live until here
@@ -2303,15 +2320,8 @@ void complaints3_core(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t
   h2d(ctx, dacd, accused, 4 * C);
   h2d(ctx, dsh, share, 32 * C);
   h2d(ctx, drn, randomness, 32 * C);
-  uint8_t *dq = nullptr, *df3 = nullptr;
-  if (qualified) {
-    dq = buf<uint8_t>(ctx, "c3_qualified", n);
-    h2d(ctx, dq, qualified, n);
-  }
-  if (fetched3) {
-    df3 = buf<uint8_t>(ctx, "c3_fetched3", n);
-    h2d(ctx, df3, fetched3, n);
-  }
+  const uint8_t* dq = upload_mask(ctx, "c3_qualified", qualified, n);
+  const uint8_t* df3 = upload_mask(ctx, "c3_fetched3", fetched3, n);
   uint32_t* sr = buf<uint32_t>(ctx, "c3_sr", 32 * 2 * C);
   uint32_t* acc2 = buf<uint32_t>(ctx, "c3_acc2", 4 * 2 * C);
   uint32_t* acd2 = buf<uint32_t>(ctx, "c3_acd2", 4 * 2 * C);
@@ -2452,15 +2462,23 @@ ComplaintIndex complaint_index(size_t n, size_t C, const uint32_t* ceremony, con
   return ix;
 }
 
+// What verify_batch has put on the device of a BatchInput (null = absent): E, A [V][N][8]; plaintext
+// shares s, s_prime [V][n][8] or, in full mode, sk [V][8] and e1, ct [V][n][2][8]; the masks [V].
+struct BatchDevice {
+  const uint32_t *E = nullptr, *A = nullptr;
+  const uint32_t *s = nullptr, *s_prime = nullptr;
+  const uint32_t *sk = nullptr, *e1 = nullptr, *ct = nullptr;
+  const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;
+};
+
 // Both complaint stages of a batch, queued on ctx->stream after the batch's uploads and before its
 // rounds; no host synchronisation, host work O(C), a launch count that does not depend on B and no
-// copy per row, ceremony or complaint.  Round 4 first, as verify_ceremony.  Device inputs: Ec, Ac
-// [V][N][8]; e1, ct [V][n][2][8] (with c2); fetched3 [V] (may be null).  Always the per-complaint
-// Horner walk (k_cmp_horner): ctx->complaint_eval does not apply.  Leaves the masks and the device
-// verdicts in bp; the index arrays go through one pinned staging buffer.
-void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t* Ec, const uint32_t* Ac,
-                      const uint32_t* e1, const uint32_t* ct, const BatchComplaints2* c2, const BatchComplaints4& c4,
-                      const uint8_t* fetched3, BatchProven& bp) {
+// copy per row, ceremony or complaint.  Round 4 first, as verify_ceremony.  c2 comes with full mode
+// only (dev.e1, dev.ct).  Always the per-complaint Horner walk (k_cmp_horner): ctx->complaint_eval
+// does not apply.  Leaves the masks and the device verdicts in bp; the index arrays go through one
+// pinned staging buffer.
+void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDevice& dev, const BatchComplaints2* c2,
+                      const BatchComplaints4& c4, BatchProven& bp) {
   const size_t N = t + 1, V = B * n, C2 = c2 ? c2->C : 0, C4 = c4.C;
   hipStream_t st = ctx->stream;
   int nb = 1;
@@ -2501,7 +2519,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t
     uint32_t* rext = buf<uint32_t>(ctx, "bp.rows4_ext", PTB * 2 * R4 * N);
     uint8_t* pok = buf<uint8_t>(ctx, "bp.rows4_pok", 2 * R4 * N);
     uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows4_ok", 2 * R4);
-    dkgk::gather_rows(R4, N, rows4, Ec, Ac, rc, st);
+    dkgk::gather_rows(R4, N, rows4, dev.E, dev.A, rc, st);
     dkgk::decode_points(rc, 2 * R4 * N, rext, 2 * R4 * N, pok, st);
     dkgk::dealer_ok(2 * R4, N, pok, rowok, st);
     uint32_t* dsh = buf<uint32_t>(ctx, "bp.share", 32 * C4);
@@ -2517,7 +2535,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t
     uint8_t* eq = buf<uint8_t>(ctx, "bp.eq4", 2 * C4);
     dkgk::c3_check(C4, x4, sr, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
     // the qualified set is applied on the host (IGNORED, batch_proven_outcome), as verify_ceremony does
-    dkgk::c3_final(C4, R4, crow4, drow4, rowok, nullptr, fetched3, eq, dver4, st);
+    dkgk::c3_final(C4, R4, crow4, drow4, rowok, nullptr, dev.fetched3, eq, dver4, st);
   }
   HCK(hipEventRecord(ctx->bpev[1], st));
   // ---- round 2 (k_cv_*): the E rows of the accused dealers, the ciphertext pairs from the batch's own
@@ -2535,7 +2553,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t
     uint32_t* rext = buf<uint32_t>(ctx, "bp.rows2_ext", PTB * R2 * N);
     uint8_t* pok = buf<uint8_t>(ctx, "bp.rows2_pok", R2 * N);
     uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows2_ok", R2);
-    dkgk::gather_rows(R2, N, rows2, Ec, nullptr, rc, st);
+    dkgk::gather_rows(R2, N, rows2, dev.E, nullptr, rc, st);
     dkgk::decode_points(rc, R2 * N, rext, R2 * N, pok, st);
     dkgk::dealer_ok(R2, N, pok, rowok, st);
     uint32_t* dpk = buf<uint32_t>(ctx, "bp.pk", 32 * V);
@@ -2543,42 +2561,20 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t
     uint32_t* denc = buf<uint32_t>(ctx, "bp.enc", 128 * C2);
     h2d(ctx, dpk, c2->pk, 32 * V);
     h2d(ctx, dprf, c2->proofs, 192 * C2);
-    dkgk::gather_enc(C2, n, drow2, x2, e1, ct, denc, st);
-    // from here as complaints_verify_core, with the party and commitment rows in place of the indices
-    uint32_t* Pc = buf<uint32_t>(ctx, "bp.Pc", 32 * 5 * C2);
-    uint32_t* rs = buf<uint32_t>(ctx, "bp.rs", 32 * 2 * C2);
-    uint32_t* nc = buf<uint32_t>(ctx, "bp.nc", 32 * 2 * C2);
-    uint32_t* p12 = buf<uint32_t>(ctx, "bp.p12", 32 * 2 * C2);
-    uint32_t* bp1 = buf<uint32_t>(ctx, "bp.bp1", 4 * 2 * C2);
-    uint32_t* bp2 = buf<uint32_t>(ctx, "bp.bp2", 4 * 2 * C2);
-    uint32_t* bq2 = buf<uint32_t>(ctx, "bp.bq2", 4 * 2 * C2);
-    dkgk::cv_prep(C2, party2, dpk, denc, dprf, Pc, rs, nc, p12, bp1, bp2, bq2, st);
-    uint32_t* Pext = buf<uint32_t>(ctx, "bp.Pext", PTB * 5 * C2);
-    uint8_t* ppok = buf<uint8_t>(ctx, "bp.Ppok", 5 * C2);
-    dkgk::decode_points(Pc, 5 * C2, Pext, 5 * C2, ppok, st);
-    uint32_t* T = buf<uint32_t>(ctx, "bp.T", 4 * dkgk::cmp_ladder_table_words(2 * C2));
-    uint32_t* S1 = buf<uint32_t>(ctx, "bp.S1", PTB * 2 * C2);
-    uint32_t* S2 = buf<uint32_t>(ctx, "bp.S2", PTB * 2 * C2);
-    uint32_t* G = buf<uint32_t>(ctx, "bp.G", PTB * 2 * C2);
-    dkgk::cmp_ladder(2 * C2, false, bp1, nullptr, nc, nullptr, Pext, 5 * C2, T, S1, st);
-    dkgk::cmp_ladder(2 * C2, true, bp2, bq2, rs, nc, Pext, 5 * C2, T, S2, st);
-    dkgk::fixed_base(2 * C2, rs, ctx->tab_gw, G, st);
-    dkgk::add_points(2 * C2, S1, G, 2 * C2, S1, st);
-    uint32_t* a1c = buf<uint32_t>(ctx, "bp.a1c", 32 * 2 * C2);
-    uint32_t* a2c = buf<uint32_t>(ctx, "bp.a2c", 32 * 2 * C2);
-    dkgk::encode_points(S1, 2 * C2, 2 * C2, a1c, st);
-    dkgk::encode_points(S2, 2 * C2, 2 * C2, a2c, st);
+    dkgk::gather_enc(C2, n, drow2, x2, dev.e1, dev.ct, denc, st);
+    // the party rows stand where one ceremony has the accusers, the commitment rows where it has the accused
+    const Announcements an = complaint_announcements(ctx, C2, party2, dpk, denc, dprf, st);
     uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh2", PTB * C2);
     dkgk::cmp_horner(C2, seq, x2, crow2, rext, R2 * N, N, nb, Rh, st);
     uint8_t* eq = buf<uint8_t>(ctx, "bp.eq2", 2 * C2);
-    dkgk::cv_check(C2, x2, p12, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
-    dkgk::cv_final(C2, party2, crow2, dpk, denc, dprf, a1c, a2c, ppok, rowok, nullptr, eq, dver2, st);
+    dkgk::cv_check(C2, x2, an.p12, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
+    dkgk::cv_final(C2, party2, crow2, dpk, denc, dprf, an.a1c, an.a2c, an.ppok, rowok, nullptr, eq, dver2, st);
   }
   // ---- the verdicts as the rounds' masks
   dkgk::proven_masks(C2, n, drow2, x2, dver2, C4, drow4, dver4, cmask, pair, proven4, st);
   HCK(hipEventRecord(ctx->bpev[2], st));
   check_launch(ctx);
-  bp.a_ok = fetched3;
+  bp.a_ok = dev.fetched3;
   bp.cmask = cmask;
   bp.pair = pair;
   bp.proven4 = proven4;
@@ -2650,16 +2646,8 @@ int verify_ceremony(dkg_ctx* ctx, size_t n, size_t t, const CeremonyInput& in, d
     m.proven4 = dp4;
     for (size_t i = 0; i < n; i++) a_ok[i] = (!in.fetched3 || in.fetched3[i]) && rowok[n + i];
   }
-  if (in.fetched1) {
-    uint8_t* f1 = buf<uint8_t>(ctx, "cer_f1", n);
-    h2d(ctx, f1, in.fetched1, n);
-    m.e_ok = f1;
-  }
-  if (in.fetched3) {
-    uint8_t* f3 = buf<uint8_t>(ctx, "cer_f3", n);
-    h2d(ctx, f3, in.fetched3, n);
-    m.a_ok = f3;
-  }
+  m.e_ok = upload_mask(ctx, "cer_f1", in.fetched1, n);
+  m.a_ok = upload_mask(ctx, "cer_f3", in.fetched3, n);
   std::vector<uint8_t> enc, cmask;
   if (in.c2) {
     const Complaints2& c = *in.c2;
@@ -2728,6 +2716,71 @@ int verify_ceremony(dkg_ctx* ctx, size_t n, size_t t, const CeremonyInput& in, d
   if (in.c4) proven_outcome(n, t, *in.c4, a_ok.data(), r, out->mpk);
   if (in.c2 && in.c2->dissent)
     complaint_dissent(ctx, n, in.c2->C, in.c2->accuser, in.c2->accused, in.c2->verdict, in.c2->dissent);
+  return DKG_OK;
+}
+
+// B stacked ceremonies to verify, as the host pointers of the C ABI (null = absent), in the manner of
+// CeremonyInput: plaintext shares (s, s_prime) or full mode (e1, ct, sk); the presence of c4 selects
+// the proven rule, c2 comes with full mode only.  s_out / s_prime_out receive the decrypted shares.
+struct BatchInput {
+  const uint8_t *E = nullptr, *A = nullptr;                   // required
+  const uint8_t *s = nullptr, *s_prime = nullptr;             // plaintext shares, or
+  const uint8_t *e1 = nullptr, *ct = nullptr, *sk = nullptr;  //   encrypted shares and the members' keys
+  const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;     // intake masks
+  const BatchComplaints2* c2 = nullptr;
+  const BatchComplaints4* c4 = nullptr;
+  uint8_t *s_out = nullptr, *s_prime_out = nullptr;
+};
+
+// Rounds 2-5 of a batch from its broadcast values: every dkg_ceremony_batch_verify* entry point.  The
+// complaint stage is queued before the timed region (ev[0]), which covers the decryption and the
+// rounds as ms_* report.
+int verify_batch(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchInput& in, dkg_batch_out* out) {
+  const size_t N = t + 1, V = B * n, items = 2 * V * n;
+  const bool full = in.e1 != nullptr;
+  BatchDevice d;
+  uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
+  uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
+  h2d(ctx, Ec, in.E, 32 * V * N);
+  h2d(ctx, Ac, in.A, 32 * V * N);
+  d.E = Ec, d.A = Ac;
+  if (full) {
+    d.sk = upload_scalars(ctx, "bfm_sk", in.sk, V);
+    uint32_t* de1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
+    h2d(ctx, de1, in.e1, 32 * items);
+    h2d(ctx, dct, in.ct, 32 * items);
+    d.e1 = de1, d.ct = dct;
+  } else {
+    d.s = upload_scalars(ctx, "bat_s", in.s, V * n);
+    d.s_prime = upload_scalars(ctx, "bat_sp", in.s_prime, V * n);
+  }
+  d.fetched1 = upload_mask(ctx, "bp.f1", in.fetched1, V);
+  d.fetched3 = upload_mask(ctx, "bp.f3", in.fetched3, V);
+  BatchProven bp;
+  if (in.c4) batch_complaints(ctx, B, n, t, d, full ? in.c2 : nullptr, *in.c4, bp);
+  HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+  HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+  const uint8_t* e_ok = d.fetched1;
+  if (full) {
+    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
+    bf_reset(ctx);
+    decrypt_batch_device(ctx, B, n, d.sk, d.e1, d.ct, rs, rsp, iok, eok);
+    d.s = rs, d.s_prime = rsp;
+    e_ok = eok;  // the decode mask of the dealer's ciphertexts
+  }
+  batch_receivers(ctx, B, n, t, d.E, d.A, d.s, d.s_prime, out, e_ok, in.c4 ? &bp : nullptr);
+  if (full) collect_bfull_phases(ctx);
+  if (in.c4) batch_proven_outcome(ctx, B, n, t, in.c2 != nullptr, *in.c4, bp, out);
+  if (full) {
+    if (in.s_out) d2h(ctx, in.s_out, d.s, 32 * V * n);
+    if (in.s_prime_out) d2h(ctx, in.s_prime_out, d.s_prime, 32 * V * n);
+    sync(ctx);
+  }
+  batch_times(ctx, out, false);
   return DKG_OK;
 }
 
@@ -3847,10 +3900,8 @@ int dkg_shard_finalise_device(dkg_ctx* ctx, size_t n, size_t t, size_t world_siz
 int dkg_ceremony_batch_device(dkg_ctx* ctx, size_t B, size_t n, size_t t, const void* d_a, const void* d_b,
                               dkg_batch_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out});
+    if (rc || !B) return rc;
     const size_t N = t + 1, V = B * n;
     HCK(hipEventRecord(ctx->ev[0], ctx->stream));
     uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
@@ -3871,22 +3922,11 @@ int dkg_ceremony_batch_device(dkg_ctx* ctx, size_t B, size_t n, size_t t, const 
 int dkg_ceremony_batch_verify(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
                               const uint8_t* s, const uint8_t* s_prime, dkg_batch_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !s || !s_prime) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
-    const size_t N = t + 1, V = B * n;
-    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
-    h2d(ctx, Ec, E, 32 * V * N);
-    h2d(ctx, Ac, A, 32 * V * N);
-    uint32_t* ds = upload_scalars(ctx, "bat_s", s, V * n);
-    uint32_t* dsp = upload_scalars(ctx, "bat_sp", s_prime, V * n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    batch_receivers(ctx, B, n, t, Ec, Ac, ds, dsp, out);
-    batch_times(ctx, out, false);
-    return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, s, s_prime});
+    if (rc || !B) return rc;
+    BatchInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime;
+    return verify_batch(ctx, B, n, t, in, out);
   });
 }
 
@@ -4357,10 +4397,8 @@ int dkg_decrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* sk
 int dkg_ceremony_batch_full_device(dkg_ctx* ctx, size_t B, size_t n, size_t t, const void* d_a, const void* d_b,
                                    const void* d_r, const uint8_t* sk, const uint8_t* pk, dkg_batch_out* out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !sk || !pk) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out, sk, pk});
+    if (rc || !B) return rc;
     if (!d_a || !d_b || !d_r) return DKG_E_ARG;
     const size_t N = t + 1, V = B * n, items = 2 * V * n;
     uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
@@ -4398,35 +4436,11 @@ int dkg_ceremony_batch_verify_full(dkg_ctx* ctx, size_t B, size_t n, size_t t, c
                                    const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, dkg_batch_out* out,
                                    uint8_t* s_out, uint8_t* s_prime_out) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
-    const size_t N = t + 1, V = B * n, items = 2 * V * n;
-    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
-    h2d(ctx, Ec, E, 32 * V * N);
-    h2d(ctx, Ac, A, 32 * V * N);
-    uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
-    uint32_t* de1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
-    uint32_t* dct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
-    h2d(ctx, de1, e1, 32 * items);
-    h2d(ctx, dct, ct, 32 * items);
-    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
-    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    bf_reset(ctx);
-    decrypt_batch_device(ctx, B, n, dsk, de1, dct, rs, rsp, iok, eok);
-    batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok);
-    collect_bfull_phases(ctx);
-    if (s_out) d2h(ctx, s_out, rs, 32 * V * n);
-    if (s_prime_out) d2h(ctx, s_prime_out, rsp, 32 * V * n);
-    sync(ctx);
-    batch_times(ctx, out, false);
-    return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, e1, ct, sk});
+    if (rc || !B) return rc;
+    BatchInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk, in.s_out = s_out, in.s_prime_out = s_prime_out;
+    return verify_batch(ctx, B, n, t, in, out);
   });
 }
 
@@ -4438,39 +4452,16 @@ int dkg_ceremony_batch_verify_proven(dkg_ctx* ctx, size_t B, size_t n, size_t t,
                                      const uint8_t* randomness4, dkg_batch_out* out, int32_t* verdict4,
                                      int32_t* finalise_status, int32_t* recovery_index) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !s || !s_prime) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, s, s_prime});
+    if (rc || !B) return rc;
     if (B * n >= ((size_t)1 << 31) ||
         !batch_complaint_args_ok(B, n, C4, ceremony4, accuser4, accused4, {share4, randomness4, verdict4}))
       return DKG_E_ARG;
-    const size_t N = t + 1, V = B * n;
-    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
-    h2d(ctx, Ec, E, 32 * V * N);
-    h2d(ctx, Ac, A, 32 * V * N);
-    uint32_t* ds = upload_scalars(ctx, "bat_s", s, V * n);
-    uint32_t* dsp = upload_scalars(ctx, "bat_sp", s_prime, V * n);
-    uint8_t *df1 = nullptr, *df3 = nullptr;
-    if (fetched1) {
-      df1 = buf<uint8_t>(ctx, "bp.f1", V);
-      h2d(ctx, df1, fetched1, V);
-    }
-    if (fetched3) {
-      df3 = buf<uint8_t>(ctx, "bp.f3", V);
-      h2d(ctx, df3, fetched3, V);
-    }
     const BatchComplaints4 c4{C4, ceremony4, accuser4, accused4, share4, randomness4, verdict4, finalise_status,
                               recovery_index};
-    BatchProven bp;
-    batch_complaints(ctx, B, n, t, Ec, Ac, nullptr, nullptr, nullptr, c4, df3, bp);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    batch_receivers(ctx, B, n, t, Ec, Ac, ds, dsp, out, df1, &bp);
-    batch_proven_outcome(ctx, B, n, t, false, c4, bp, out);
-    batch_times(ctx, out, false);
-    return DKG_OK;
+    BatchInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime, in.fetched1 = fetched1, in.fetched3 = fetched3, in.c4 = &c4;
+    return verify_batch(ctx, B, n, t, in, out);
   });
 }
 
@@ -4484,50 +4475,19 @@ int dkg_ceremony_batch_verify_full_proven(dkg_ctx* ctx, size_t B, size_t n, size
                                           uint8_t* s_prime_out, int32_t* verdict, int32_t* dissent, int32_t* verdict4,
                                           int32_t* finalise_status, int32_t* recovery_index) {
   return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || !out || !E || !A || !e1 || !ct || !sk || !pk) return DKG_E_ARG;
-    if (B == 0) return DKG_OK;
+    const int rc = ceremony_args(ctx, n, t, {out, E, A, e1, ct, sk, pk});
+    if (rc || !B) return rc;
     if (B * n >= ((size_t)1 << 31) ||
         !batch_complaint_args_ok(B, n, C, ceremony, accuser, accused, {proofs, verdict}) ||
         !batch_complaint_args_ok(B, n, C4, ceremony4, accuser4, accused4, {share4, randomness4, verdict4}))
       return DKG_E_ARG;
-    const size_t N = t + 1, V = B * n, items = 2 * V * n;
-    uint32_t* Ec = buf<uint32_t>(ctx, "bat_E", 32 * V * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "bat_A", 32 * V * N);
-    h2d(ctx, Ec, E, 32 * V * N);
-    h2d(ctx, Ac, A, 32 * V * N);
-    uint32_t* dsk = upload_scalars(ctx, "bfm_sk", sk, V);
-    uint32_t* de1 = buf<uint32_t>(ctx, "bfm_e1", 32 * items);
-    uint32_t* dct = buf<uint32_t>(ctx, "bfm_ct", 32 * items);
-    h2d(ctx, de1, e1, 32 * items);
-    h2d(ctx, dct, ct, 32 * items);
-    uint8_t* df3 = nullptr;
-    if (fetched3) {
-      df3 = buf<uint8_t>(ctx, "bp.f3", V);
-      h2d(ctx, df3, fetched3, V);
-    }
-    uint32_t* rs = buf<uint32_t>(ctx, "bfm_s", 32 * V * n);
-    uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
     const BatchComplaints2 c2{pk, C, ceremony, accuser, accused, proofs, verdict, dissent};
     const BatchComplaints4 c4{C4, ceremony4, accuser4, accused4, share4, randomness4, verdict4, finalise_status,
                               recovery_index};
-    BatchProven bp;
-    batch_complaints(ctx, B, n, t, Ec, Ac, de1, dct, &c2, c4, df3, bp);  // before the timed region, as one ceremony's
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-    bf_reset(ctx);
-    decrypt_batch_device(ctx, B, n, dsk, de1, dct, rs, rsp, iok, eok);
-    batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok, &bp);
-    collect_bfull_phases(ctx);
-    batch_proven_outcome(ctx, B, n, t, true, c4, bp, out);
-    if (s_out) d2h(ctx, s_out, rs, 32 * V * n);
-    if (s_prime_out) d2h(ctx, s_prime_out, rsp, 32 * V * n);
-    sync(ctx);
-    batch_times(ctx, out, false);
-    return DKG_OK;
+    BatchInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk, in.fetched3 = fetched3, in.c2 = &c2, in.c4 = &c4;
+    in.s_out = s_out, in.s_prime_out = s_prime_out;
+    return verify_batch(ctx, B, n, t, in, out);
   });
 }
 

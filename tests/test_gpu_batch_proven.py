@@ -389,19 +389,41 @@ def raw_full(be, a, **over):
              ceremony4=u32s(a["ceremony4"]), accuser4=u32s(a["accusers4"]), accused4=u32s(a["accused4"]),
              share4=a["share4"], randomness4=a["randomness4"], verdict=(i32 * max(C, 1))(),
              dissent=(i32 * max(B * n, 1))(), verdict4=(i32 * max(C4, 1))(), status=(i32 * max(B, 1))(),
-             index=(i32 * max(B, 1))())
+             index=(i32 * max(B, 1))(), s_out=s, s_prime_out=sp)
     c.update(over)
     rc = _lib.lib().dkg_ceremony_batch_verify_full_proven(
         be.ctx, B, n, t, c["E"], c["A"], c["e1"], c["ct"], c["sk"], c["pk"], c["C"], c["ceremony"], c["accuser"],
         c["accused"], c["proofs"], c["fetched3"], c["C4"], c["ceremony4"], c["accuser4"], c["accused4"], c["share4"],
-        c["randomness4"], ctypes.byref(o), s, sp, c["verdict"], c["dissent"], c["verdict4"], c["status"], c["index"])
+        c["randomness4"], ctypes.byref(o), c["s_out"], c["s_prime_out"], c["verdict"], c["dissent"], c["verdict4"],
+        c["status"], c["index"])
     if rc != DKG_OK or B == 0:
         return rc, None
     r = api._batch_result(B, n, t, o, bufs)
-    r.s, r.s_prime = s.raw[:size], sp.raw[:size]
+    r.s, r.s_prime = (x and x.raw[:size] for x in (c["s_out"], c["s_prime_out"]))
     return rc, api.BatchProvenResult(r, a["ceremony4"][:c["C4"]], list(c["verdict4"] or [])[:c["C4"]],
-                                     list(c["status"])[:B], list(c["index"])[:B], a["ceremony"][:c["C"]],
-                                     list(c["verdict"] or [])[:c["C"]], list(c["dissent"])[:B * n])
+                                     list(c["status"] or [])[:B], list(c["index"] or [])[:B], a["ceremony"][:c["C"]],
+                                     list(c["verdict"] or [])[:c["C"]], list(c["dissent"] or [])[:B * n])
+
+
+def raw_plain(be, a, **over):
+    """dkg_ceremony_batch_verify_proven through the C ABI with plain_args' dictionary, as raw_full."""
+    B, n, t, C4 = a["B"], a["n"], a["t"], len(a["accusers4"])
+    o, bufs = api._batch_out(B, n, True)
+    i32 = ctypes.c_int32
+    c = dict(E=a["E"], A=a["A"], s=a["s"], s_prime=a["s_prime"], fetched1=a["fetched1"], fetched3=a["fetched3"], C4=C4,
+             ceremony4=u32s(a["ceremony4"]), accuser4=u32s(a["accusers4"]), accused4=u32s(a["accused4"]),
+             share4=a["share4"], randomness4=a["randomness4"], verdict4=(i32 * max(C4, 1))(),
+             status=(i32 * max(B, 1))(), index=(i32 * max(B, 1))())
+    c.update(over)
+    rc = _lib.lib().dkg_ceremony_batch_verify_proven(
+        be.ctx, B, n, t, c["E"], c["A"], c["s"], c["s_prime"], c["fetched1"], c["fetched3"], c["C4"], c["ceremony4"],
+        c["accuser4"], c["accused4"], c["share4"], c["randomness4"], ctypes.byref(o), c["verdict4"], c["status"],
+        c["index"])
+    if rc != DKG_OK or B == 0:
+        return rc, None
+    return rc, api.BatchProvenResult(api._batch_result(B, n, t, o, bufs), a["ceremony4"][:c["C4"]],
+                                     list(c["verdict4"] or [])[:c["C4"]], list(c["status"] or [])[:B],
+                                     list(c["index"] or [])[:B])
 
 
 @gpu
@@ -540,3 +562,158 @@ def test_wire_call(be, golden):
     for g, c in enumerate(cers):
         same_as_single(r.ceremony(g), single_full(be, c), True)
     assert sorted(r.ceremony(0)["verdict"]) == [0, 0, 0, 1, 2] and r.ceremony(1)["verdict4"] == [3, 2]
+
+
+# ---------------- 9. the four verify entry points behind one driver ----------------
+def stripped(r):
+    """A BatchResult or BatchProvenResult without its times."""
+    if isinstance(r, api.BatchProvenResult):
+        return no_times(r)
+    return dataclasses.replace(r, ms=None, complaints2=list(r.complaints2))
+
+
+def stack_plain_args(stack):
+    """The stack as a plaintext batch: the shares its full-mode call decrypted, the round-4 complaints."""
+    a, r = stack["args"], stack["r"].result
+    return dict({k: a[k] for k in ("B", "n", "t", "E", "A", "ceremony4", "accusers4", "accused4", "share4",
+                                   "randomness4", "fetched3")}, s=r.s, s_prime=r.s_prime, fetched1=None)
+
+
+def four_calls(stack):
+    """[(name, call(backend))]: dkg_ceremony_batch_verify, _full, _proven, _full_proven on the stack's inputs."""
+    a, p = stack["args"], stack_plain_args(stack)
+    shape = (a["B"], a["n"], a["t"], a["E"], a["A"])
+    return [("verify", lambda b: dkg_amd.ceremony_batch_verify(b, *shape, p["s"], p["s_prime"])),
+            ("verify_full", lambda b: dkg_amd.ceremony_batch_verify_full(b, *shape, a["e1"], a["ct"], a["sk"])),
+            ("verify_proven", lambda b: dkg_amd.ceremony_batch_verify_proven(b, **p)),
+            ("verify_full_proven", lambda b: dkg_amd.ceremony_batch_verify_full_proven(b, **a))]
+
+
+@pytest.fixture(scope="module")
+def four_refs(stack):
+    """Each of the four calls on a context that has served nothing else."""
+    fresh = dkg_amd.Backend(0)
+    try:
+        fresh.env_init(T4, N10, CK)
+        return {name: stripped(call(fresh)) for name, call in four_calls(stack)}
+    finally:
+        fresh.close()
+
+
+@gpu
+def test_four_entry_points_one_context(be, stack, four_refs):
+    be.env_init(T4, N10, CK)
+    calls = four_calls(stack)
+    got = {}
+    for name, call in calls + calls[::-1]:
+        got[name] = stripped(call(be))
+        assert got[name] == four_refs[name], name
+    assert got["verify_full_proven"] == no_times(stack["r"])
+    p = stack_plain_args(stack)
+    sz = 32 * N10 * N10
+    for c, cer in enumerate(stack["cers"]):
+        same_as_single(got["verify_full_proven"].ceremony(c), stack["singles"][c], True)
+        one = dict(cer, s=p["s"][sz * c:sz * (c + 1)], s_prime=p["s_prime"][sz * c:sz * (c + 1)])
+        same_as_single(got["verify_proven"].ceremony(c), single_plain(be, one), False)
+
+
+# ---------------- 10. the announcement buffers, shared by one ceremony's and the batch's complaints ----------------
+def more_complaints(cer, times):
+    """complaints_verify's arguments for ceremony `cer` with its round-1 complaints listed `times` times."""
+    n, c2 = cer["n"], cer["c2"] * times
+    return dict(n=n, t=cer["t"], accusers=[x[0] for x in c2], accused=[x[1] for x in c2], pk=cer["pk"], E=cer["E"],
+                enc=b"".join(enc_of(cer["e1"], cer["ct"], n, i - 1, q - 1) for q, i, _ in c2),
+                proofs=b"".join(x[2] for x in c2))
+
+
+@gpu
+def test_shared_announcement_buffers(be, stack):
+    cer, want = stack["cers"][1], no_times(stack["r"])
+    C2 = len(stack["args"]["accusers"])
+    own, more = more_complaints(cer, 1), more_complaints(cer, 3)
+    # fewer than the batch's, and more: the buffers grow from either side
+    assert len(own["accusers"]) < C2 < len(more["accusers"])
+    verdicts = stack["singles"][1].verdict
+    assert verdicts == [0, 0, 0, 2, 1]
+    proven = {i for (_, i, _), v in zip(cer["c2"], verdicts) if v == 0}
+    qualified = [int(i + 1 not in proven) for i in range(N10)]  # every row decodes
+    assert sum(qualified) < N10
+
+    def batch(b):
+        assert no_times(dkg_amd.ceremony_batch_verify_full_proven(b, **stack["args"])) == want
+
+    def single(b, a, times):
+        assert b.complaints_verify(**a) == (verdicts * times, qualified)
+
+    be.env_init(T4, N10, CK)
+    batch(be)
+    single(be, more, 3)
+    batch(be)
+    fresh = dkg_amd.Backend(0)
+    try:
+        fresh.env_init(T4, N10, CK)
+        single(fresh, own, 1)
+        batch(fresh)
+        single(fresh, more, 3)
+        batch(fresh)
+        single(fresh, own, 1)
+    finally:
+        fresh.close()
+
+
+# ---------------- 11. null optional outputs with complaints present ----------------
+@gpu
+def test_null_optional_outputs(be, stack):
+    be.env_init(T4, N10, CK)
+    a, want = stack["args"], no_times(stack["r"])
+    assert a["accusers"] and a["accusers4"]
+    rc, r = raw_full(be, a, dissent=None, status=None, index=None, s_out=None, s_prime_out=None)
+    assert rc == DKG_OK
+    assert (r.result.s, r.result.s_prime, r.dissent, r.finalise_status, r.recovery_index) == (None, None, [], [], [])
+    r.result.s, r.result.s_prime = want.result.s, want.result.s_prime
+    assert no_times(r) == dataclasses.replace(want, dissent=[], finalise_status=[], recovery_index=[])
+    p = stack_plain_args(stack)
+    rc, full = raw_plain(be, p)
+    assert rc == DKG_OK and no_times(full) == no_times(dkg_amd.ceremony_batch_verify_proven(be, **p))
+    rc, r = raw_plain(be, p, status=None, index=None)
+    assert rc == DKG_OK
+    assert no_times(r) == dataclasses.replace(no_times(full), finalise_status=[], recovery_index=[])
+
+
+# ---------------- 12. required pointers of the four entry points ----------------
+@gpu
+def test_required_pointers(be, stack):
+    n, t = N10, T4
+    be.env_init(t, n, CK)
+    a, p = stack["args"], stack_plain_args(stack)
+    B = a["B"]
+    L_ = _lib.lib()
+
+    def verify(**over):
+        c = dict(p, **over)
+        o, _bufs = api._batch_out(B, n, True)
+        return L_.dkg_ceremony_batch_verify(be.ctx, B, n, t, c["E"], c["A"], c["s"], c["s_prime"], ctypes.byref(o))
+
+    def verify_full(**over):
+        c = dict(a, **over)
+        o, _bufs = api._batch_out(B, n, True)
+        return L_.dkg_ceremony_batch_verify_full(be.ctx, B, n, t, c["E"], c["A"], c["e1"], c["ct"], c["sk"],
+                                                 ctypes.byref(o), None, None)
+
+    entries = [(verify, ("E", "A", "s", "s_prime")), (verify_full, ("E", "A", "e1", "ct", "sk")),
+               (lambda **over: raw_plain(be, p, **over)[0], ("E", "A", "s", "s_prime")),
+               (lambda **over: raw_full(be, a, **over)[0], ("E", "A", "e1", "ct", "sk", "pk"))]
+    for call, required in entries:
+        for key in required:
+            assert call(**{key: None}) == DKG_E_ARG, (required, key)
+        assert call() == DKG_OK, required  # the context serves a correct call afterwards
+    rc, r = raw_full(be, a)
+    assert rc == DKG_OK and no_times(r) == no_times(stack["r"])
+    # an empty batch is done before its complaint arrays are looked at
+    none4 = dict(ceremony4=None, accuser4=None, accused4=None, share4=None, randomness4=None, verdict4=None)
+    none2 = dict(ceremony=None, accuser=None, accused=None, proofs=None, verdict=None)
+    assert raw_full(be, dict(a, B=0), **none2, **none4)[0] == DKG_OK
+    assert raw_plain(be, dict(p, B=0), **none4)[0] == DKG_OK
+    # .. and only then: the same arrays with B > 0
+    assert raw_full(be, a, **none2, **none4)[0] == DKG_E_ARG
+    assert raw_plain(be, p, **none4)[0] == DKG_E_ARG
