@@ -5,5 +5,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "step_map.h"
 #include "kernels_decl.inc"
 

@@ -1002,7 +1002,13 @@ void to_column_major(size_t width, size_t npad, size_t N, const uint32_t* e, uin
 // laid out like e) instead of e; j1 < nrecv leaves the table after step j1 - 1 in `sout` (another
 // buffer: a part's redo launch restarts from the unchanged `sin`, and rewrites `sout` for the
 // workgroups it redoes before the next part reads it).
-template <int MAXBS, bool DED, bool PARTS>
+//
+// BAND: the banded lane map (step_map.h) of a launch whose S = bs / P equal segments fill the
+// workgroup (stepping()'s step_band: one block per table, no up / down streams, no receiver parts):
+// wave w holds positions [wB, (w+1)B), B = 64 / S, of every segment, so it is dead as a whole from
+// step nrecv - wB on: its additions are skipped (it still writes its cached form and arrives at
+// both barriers of every step).
+template <int MAXBS, bool DED, bool PARTS, bool BAND = false>
 __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_stepping(
     size_t ndealers, size_t npad, size_t N, const uint32_t* __restrict__ e, size_t nrecv, size_t pos0, int P,
     const uint32_t* __restrict__ up,  // NULL: top block
@@ -1021,8 +1027,14 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   __shared__ uint32_t cols[PT_WORDS * MAXBS];
   const int l = threadIdx.x, bs = blockDim.x;
   const int Ncol = (nseg - 1) * P + Plast;
-  const int slot = l / Ncol, p = l - slot * Ncol;
-  const int sg = min(p / P, nseg - 1), q = p - sg * P;
+  int slot, sg, q, nxt = 0;
+  if constexpr (BAND) {  // Plast == P, bs = S P (step_band)
+    const StepLane m = step_band_lane(l, 64 / (bs / P), bs);
+    slot = m.seg / nseg, sg = m.seg - slot * nseg, q = m.q, nxt = m.next;
+  } else {
+    const int p = l % Ncol;
+    slot = l / Ncol, sg = min(p / P, nseg - 1), q = p - sg * P;
+  }
   const int Pseg = sg == nseg - 1 ? Plast : P;
   const size_t dl = (size_t)blockIdx.x * (bs / Ncol) + slot;
   const bool live = slot < bs / Ncol && dl < ndealers;
@@ -1048,19 +1060,21 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   const uint4* upd = (up && live) ? reinterpret_cast<const uint4*>(up + d * nrecv * PT_WORDS) : nullptr;
   uint4* downd = (down && live) ? reinterpret_cast<uint4*>(down + d * nrecv * PT_WORDS) : nullptr;
   uint32_t* mine = cols + l;
-  uint32_t* base = cols + (l - q);
-  const uint32_t* nbr = base + ((q + 1) % Pseg);
+  uint32_t* base = cols + (l - q);  // not banded: the segment's lanes are consecutive
+  const uint32_t* nbr = BAND ? cols + nxt : base + ((q + 1) % Pseg);
   bool bad = false;
   // PARTS = false: the whole receiver range, and nothing of the part machinery in the kernel (the
   // loop body sits at the 128-VGPR budget)
   const size_t jbeg = PARTS ? j0 : 0, jend = PARTS ? j1 : nrecv;
   for (size_t j = jbeg; j < jend; j++) {
+    // (a dead wave's cached form is not skipped: the addition reuses its Y + X, Y - X and 2 Z, and
+    // under a condition of its own the addition block recomputes them, +30 instructions per live step)
     {
       ge_cached c0;
       if (DED) ge_to_cached_ded(c0, D);
       else ge_to_cached(c0, D);
       if (q == 0) {
-        if (downd) {
+        if (!BAND && downd) {
           const uint4* w4 = reinterpret_cast<const uint4*>(&c0);
 #pragma unroll
           for (int k = 0; k < PT_WORDS / 4; k++) downd[j * (PT_WORDS / 4) + k] = w4[k];
@@ -1069,7 +1083,7 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         lds_put_cached(mine, c0, MAXBS);
       }
     }
-    if (top_lane && upd) {  // the block above's lowest position, parked in column 0
+    if (!BAND && top_lane && upd) {  // the block above's lowest position, parked in column 0
       ge_cached u;
       uint4* u4 = reinterpret_cast<uint4*>(&u);
 #pragma unroll
@@ -1079,8 +1093,9 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
     __syncthreads();
     // D_pos after step j reaches an output only through D_0 after step j + pos, so positions with
     // pos + j >= nrecv are dead for the rest of the launch: a wave whose lowest position is past
-    // that line skips its additions (the last 64 steps of every piece's upper wave at L = 128)
-    if (live && pos + 1 < Nlive && (q + 1 < Pseg || up) && pos + j < nrecv) {
+    // that line skips its additions (contiguous map: the last 64 steps of every piece's upper wave
+    // at L = 128; banded: the last wB steps of wave w)
+    if (live && pos + 1 < Nlive && (q + 1 < Pseg || (!BAND && up)) && pos + j < nrecv) {
       if (DED) {
         ge_add_ded_lds(D, D, nbr, MAXBS);
         bad |= real && fe_tight_zero(D.Z);
@@ -1163,21 +1178,41 @@ bool stepping_whole_columns(size_t L, size_t pieces, size_t last_len) {
 // waves per SIMD of that round: issue-shared, at a rate that still grows from 2 to 4 resident
 // waves (occ 0.7 .. 1: n=4096 at U=5 runs 448-lane tables at 3.5 waves per SIMD 16 % slower
 // than U=4's 512-lane ones at 4, profiles/r02_split_ab.txt), latency-bound below.
-double stepping_cycles(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole) {
+//
+// nrecv > 0: the issue-bound term counts only the wave-steps that still issue additions (a wave
+// whose lowest position p0 has p0 + j >= nrecv skips them): wave w of a banded workgroup
+// (step_band) stops at step nrecv - wB, a wave of the contiguous map at nrecv minus the lowest
+// position among its 64 lanes.  The chain of a latency-bound round is wave 0's and keeps n steps.
+double step_live_share(const StepShape& s, size_t P, size_t nseg, size_t Plast, size_t nrecv) {
+  if (!nrecv || s.nblk > 1) return 1.0;
+  const int B = step_band((int)s.bs, (int)P, (int)nseg, (int)Plast);
+  const size_t Ncol = (nseg - 1) * P + Plast, waves = s.bs / 64;
+  double steps = 0;
+  for (size_t w = 0; w < waves; w++) {
+    size_t p0 = B ? w * B : P;
+    for (size_t l = 64 * w; !B && l < 64 * w + 64; l++) p0 = std::min(p0, (l % Ncol) % P);
+    steps += nrecv > p0 ? (double)(nrecv - p0) : 0.0;
+  }
+  return steps / ((double)waves * nrecv);
+}
+
+double stepping_cycles(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole, size_t nrecv) {
   const double THR = 4.5, LAT = 8, SIMDS = 1024;
   if (!last_len || last_len > N) last_len = N;
-  auto launch = [&](const StepShape& s, double np) {
+  auto launch = [&](const StepShape& s, double np, size_t P, size_t nseg, size_t Plast) {
     const double per_cu = std::min(std::floor(1024.0 / s.maxbs), std::floor(16.0 / (s.bs / 64.0)));
     const double wgs = std::ceil((double)cols / s.per) * np * s.nblk, cap = 256 * per_cu;
     const double rounds = std::ceil(wgs / cap), in_round = wgs / rounds;
     const double w = in_round * (s.bs / 64.0) / SIMDS;
     const double occ = std::min(1.0, std::max(0.7, 0.7 + 0.15 * (w - 2)));
-    return rounds * std::max(w * THR / occ, LAT);
+    return rounds * std::max(w * THR / occ * step_live_share(s, P, nseg, Plast, nrecv), LAT);
   };
-  if (whole && stepping_whole_columns(N, pieces, last_len)) return launch(stepping_shape((pieces - 1) * N + last_len), 1);
+  if (whole && stepping_whole_columns(N, pieces, last_len))
+    return launch(stepping_shape((pieces - 1) * N + last_len), 1, N, pieces, last_len);
   const StepShape sh = stepping_shape(N);
-  if (sh.nblk > 1 || last_len == N) return launch(sh, (double)pieces);
-  return (pieces > 1 ? launch(sh, (double)(pieces - 1)) : 0.0) + launch(stepping_shape(last_len), 1);
+  if (sh.nblk > 1 || last_len == N) return launch(sh, (double)pieces, sh.P, 1, sh.P);
+  return (pieces > 1 ? launch(sh, (double)(pieces - 1), sh.P, 1, sh.P) : 0.0) +
+         launch(stepping_shape(last_len), 1, last_len, 1, last_len);
 }
 
 double stepping_waves_per_simd(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole) {
@@ -1239,9 +1274,32 @@ void step_launch(int maxbs, dim3 grid, dim3 block, hipStream_t stream, size_t nd
                               Nlive, piece0, nseg, Plast, flags, cr, 0, nrecv, nullptr, nullptr, N, N);
 }
 
+// A banded launch (step_band): one block per table, the whole receiver range, no streams.
+template <bool DED>
+void step_launch_band(int maxbs, dim3 grid, dim3 block, hipStream_t stream, size_t ndealers, size_t npad, size_t N,
+                      const uint32_t* e, size_t nrecv, int P, uint32_t* R, size_t pstride, size_t Nlive,
+                      unsigned piece0, int nseg, uint32_t* flags, const ColReal& cr) {
+  uint32_t* Rz = R ? cr.Rz : nullptr;
+  if (maxbs == 192)
+    hipLaunchKernelGGL((k_stepping<192, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+                       nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
+                       nrecv, nullptr, nullptr, N, N);
+  else if (maxbs == 256)
+    hipLaunchKernelGGL((k_stepping<256, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+                       nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
+                       nrecv, nullptr, nullptr, N, N);
+  else
+    hipLaunchKernelGGL((k_stepping<512, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+                       nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
+                       nrecv, nullptr, nullptr, N, N);
+}
+
 // Dead-position repack: worth its state copies when the dead lane-steps are a large share of the
 // launch (about N / 2n of them: config 5, n = 64, t = 31, 24 %), not for long tables of big
-// ceremonies whose dead positions fill only the upper wave of the last N steps (n = 1024: 3 %).
+// ceremonies.  There the banded map (step_map.h) harvests the dead waves without a copy: with S
+// segments per workgroup a wave dies every B = 64 / S positions, and what is left are the triangles
+// inside a band, about B / 2n of the additions (n = 1024: 1.6 % at B = 32, 0.8 % at B = 16, against
+// 3.2 % with 64 consecutive positions per wave).
 constexpr size_t TAIL_MIN_P = 4;
 int stepping_tail_phases(size_t N, size_t nrecv, size_t pieces) {
   if (pieces != 1 || N > 512 || N < 2 * TAIL_MIN_P || 10 * N < 2 * nrecv || nrecv + 1 < N) return 1;
@@ -1279,6 +1337,16 @@ bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t 
     if (!fits((size_t)grid.x * grid.y)) return false;
     uint32_t* f = flags ? flags + foff : nullptr;
     foff += (size_t)grid.x * grid.y;
+    // equal segments that fill the workgroup: the banded lane map, same grid and the same map in
+    // the complete relaunch (flags[wg] stays one word per workgroup)
+    if (step_band((int)s.bs, (int)s.P, nseg, Plast)) {
+      if (f)
+        step_launch_band<true>((int)s.maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, (int)s.P, R, pstride,
+                               Nlive, piece0, nseg, f, cr);
+      step_launch_band<false>((int)s.maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, (int)s.P, R, pstride,
+                              Nlive, piece0, nseg, f, cr);
+      return true;
+    }
     run((int)s.maxbs, grid, block, 0, (int)s.P, nullptr, nullptr, R, Nlive, piece0, nseg, Plast, f);
     return true;
   };

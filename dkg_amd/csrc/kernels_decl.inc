@@ -119,8 +119,10 @@ double step_occupancy(size_t bs, size_t maxbs);
 // the stepping then runs one slot per column over all pieces
 bool stepping_whole_columns(size_t L, size_t pieces, size_t last_len);
 // cost model of stepping()'s launches over `cols` columns: SIMD cycles per (receiver step x
-// instruction of one addition); compare modes / splits with it
-double stepping_cycles(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole);
+// instruction of one addition); compare modes / splits with it.  nrecv > 0: issue-bound rounds pay
+// only for the wave-steps whose wave still adds (dead positions: banded or contiguous lane map,
+// step_map.h); 0 prices every wave for the whole launch
+double stepping_cycles(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole, size_t nrecv = 0);
 // resident waves per SIMD in a round of stepping()'s main launch over `cols` columns
 double stepping_waves_per_simd(size_t cols, size_t N, size_t pieces, size_t last_len, bool whole);
 // last_len (0: N): length of a shorter last piece (its table positions >= last_len are not read)

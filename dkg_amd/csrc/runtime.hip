@@ -468,7 +468,8 @@ double split_model_ms(size_t cols, size_t n, size_t N, size_t U, size_t L, int s
     cyc += std::max(waves * per * THR / SIMDS, per * LAT);  // the 2-slot variant runs at 2 waves/SIMD as fast
   }
   // stepping: n dependent additions per lane, in the launches k_stepping gets (dkgk::stepping_cycles)
-  cyc += n * ADD * dkgk::stepping_cycles(cols, L, U, Lr, stepping_whole_pays(cols, U, L, Lr));
+  // (less the wave-steps of waves whose positions are all dead: the banded lane map, step_map.h)
+  cyc += n * ADD * dkgk::stepping_cycles(cols, L, U, Lr, stepping_whole_pays(cols, U, L, Lr), n);
   return cyc / 2.4e6;
 }
 
@@ -3059,6 +3060,15 @@ int dkg_split_digits(size_t n, size_t L, int pieces, int mode, int8_t* digits, i
 double dkg_split_model_ms(size_t columns, size_t n, size_t t, int pieces) {
   if (pieces < 1 || t + 1 < (size_t)pieces) return -1;
   return split_model_ms(columns, n, t + 1, (size_t)pieces);
+}
+
+int dkg_stepping_lane_map(int lanes, int seg_len, int nseg, int last_len, int lane, int out[3]) {
+  if (lanes <= 0 || lanes % 64 || lanes > 512 || lane < 0 || lane >= lanes || !out) return -1;
+  const int B = step_band(lanes, seg_len, nseg, last_len);
+  if (!B) return 0;
+  const StepLane m = step_band_lane(lane, B, lanes);
+  out[0] = m.seg, out[1] = m.q, out[2] = m.next;
+  return B;
 }
 
 size_t dkg_split_len(size_t columns, size_t n, size_t t, int pieces) {

@@ -138,6 +138,12 @@ int dkg_ctx_set_stepping_formula(dkg_ctx *ctx, int mode);
 /* Workgroups of the last verification's stepping that were recomputed by the complete formula
  * (synchronises the context's stream; 0 in mode 1; -1 on error). */
 long long dkg_ctx_stepping_redos(dkg_ctx *ctx);
+/* The stepping's banded lane map ("Dead positions"): a `lanes`-lane workgroup
+ * made of slots of `nseg` segments, `seg_len` lanes each except a slot's last (`last_len`).  Returns
+ * the band width B (wave w holds positions [wB, (w+1)B) of every segment) and fills out[0..2] with
+ * lane `lane`'s segment, its position there and the lane that holds the next position; returns 0,
+ * out untouched, when such a workgroup keeps 64 consecutive positions per wave, -1 on bad input. */
+int dkg_stepping_lane_map(int lanes, int seg_len, int nseg, int last_len, int lane, int out[3]);
 /* 1 when the last single-ceremony or dealer-shard call reran its verification with the complete
  * formula because a dedicated addition of the per-step binomial met Z = 0 (an exceptional pair, e.g.
  * a crafted all-identity commitment row), else 0 (-1 on a NULL ctx). */
