@@ -208,6 +208,15 @@ class Backend:
             raise DkgError(_lib.DKG_E_DEVICE, "dkg_ctx_stepping_redos failed")
         return r
 
+    def zero_tests(self, limbs) -> list:
+        """Test aid (dkg_zero_tests): for each element of ten 32-bit limbs, the tuple (one-limb filter,
+        full zero test, filtered guard) as the device computes them."""
+        count = len(limbs)
+        arr = (ctypes.c_uint32 * (10 * max(count, 1)))(*[v for el in limbs for v in el])
+        out = ctypes.create_string_buffer(3 * max(count, 1))
+        _check(self._ctx, _lib.lib().dkg_zero_tests(self._ctx, count, arr, out))
+        return [tuple(out.raw[3 * i:3 * i + 3]) for i in range(count)]
+
     def binomial_reruns(self) -> int:
         """1 when the last ceremony / shard call reran its verification with the complete formula
         (a dedicated addition of the per-step binomial met an exceptional pair), else 0."""

@@ -963,6 +963,19 @@ DKG_DEV bool fe_tight_zero(const fe& a) {
   }
   return (z == 0u) | (q == 0u);
 }
+// The one-limb filter of fe_tight_zero: both representations of 0 have limb 9 equal to 0 or 2^25 - 1,
+// so a value whose limb 9 is neither is not zero -- for ANY limbs, since fe_tight_zero then has
+// z != 0 and q != 0.  An fe_mul / fe_sq output keeps limb 9 below 2^25 (tools/fe_bounds.py), and a
+// random one passes the filter with probability 2^-24.  Two VALU instructions and a compare.
+DKG_DEV bool fe_maybe_zero(const fe& a) { return ((a.v[9] + 1u) & 0x1fffffeu) == 0u; }
+// bad |= on && fe_tight_zero(a), with the full test behind a wave-uniform branch that is taken only
+// when some lane of the wave passes the filter: the same value as the plain test on every input.
+#ifndef DKG_ZERO_FILTER  // A/B: 0 runs the full test on every call (profiles/step_scaled_ab.txt)
+#define DKG_ZERO_FILTER 1
+#endif
+DKG_DEV void fe_zero_guard(bool& bad, const fe& a, bool on = true) {
+  if (!DKG_ZERO_FILTER || __builtin_amdgcn_ballot_w64(on && fe_maybe_zero(a)) != 0) bad |= on && fe_tight_zero(a);
+}
 DKG_DEV void fe_cmov(fe& r, const fe& a, bool c) {
 #pragma unroll
   for (int i = 0; i < 10; i++) r.v[i] = c ? a.v[i] : r.v[i];

@@ -24,6 +24,11 @@ __device__ static const uint32_t D[10] = {0x35978a3u, 0xd37284u, 0x3156ebdu, 0x6
                                           0x179e898u, 0x3a03cbbu, 0x1ce7198u, 0x2e2b6ffu, 0x1480db3u};
 __device__ static const uint32_t D2[10] = {0x2b2f159u, 0x1a6e509u, 0x22add7au, 0xd4141du, 0x38052u,
                                            0xf3d130u, 0x3407977u, 0x19ce331u, 0x1c56dffu, 0x901b67u};
+// 4d and 16d: the normalisations of scaled records (points.h) fold the state's factors into them
+__device__ static const uint32_t D4[10] = {0x165e2b2u, 0x14dca13u, 0x55baf5u, 0x1a8283bu, 0x700a4u,
+                                           0x1e7a260u, 0x280f2eeu, 0x139c663u, 0x38adbffu, 0x12036ceu};
+__device__ static const uint32_t D16[10] = {0x1978aeeu, 0x137284du, 0x156ebd6u, 0xa0a0ecu, 0x1c0293u,
+                                            0x19e8980u, 0x203cbbbu, 0xe7198eu, 0x22b6ffeu, 0x80db3bu};
 __device__ static const uint32_t SQRT_M1[10] = {0x20ea0b0u, 0x186c9d2u, 0x8f189du, 0x35697fu,
                                                 0xbd0c60u, 0x1fbd7a7u, 0x2804c9eu, 0x1e16569u,
                                                 0x4fc1du, 0xae0c92u};

@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include "points.h"
 
 namespace dkgk {
@@ -462,7 +463,7 @@ __device__ __forceinline__ void mul_small_ded_lds(ge_p3& y, uint32_t m, uint32_t
     ge_dbl_lean<IL>(y, y, nz || i == 0);
     if (nz) {
       ge_add_ded_lds_s<IL>(y, y, q, (neg & bit) != 0, 64, i == 0);  // T only for the result
-      bad |= fe_tight_zero(y.Z);
+      fe_zero_guard(bad, y.Z);
     }
   }
 }
@@ -664,6 +665,8 @@ __global__ __launch_bounds__(64, IL ? 2 : DKG_BINOM_STEP_WAVES) void k_binom_ste
   if constexpr (DED) {
     bool bad = false;
     ge_add_ded_lds(x, x, q);                   // e_{m-1} + e_m
+    // the full test on this one addition: the filtered guard's branch here costs the non-IL kernel its
+    // 128th VGPR and 12 B of scratch (the chain's additions below do take it)
     bad |= fe_tight_zero(x.Z);
     mul_small_ded_lds<IL || DKG_BINOM_IL != 0>(x, (uint32_t)m, q, bad);  // * m
     const size_t gcol = col_base + (size_t)grp * blockDim.x + threadIdx.x;
@@ -863,7 +866,7 @@ __global__ __launch_bounds__(64, PF ? 2 : (CARRY ? DKG_BINOM_WAVE_WAVES : 4)) vo
       if constexpr (CARRY) carry = x;    // the old e_{m-1}: the next item's e_m
       if constexpr (DED) {
         ge_add_ded_lds(x, x, q);         // e_{m-1} + e_m
-        bad |= fe_tight_zero(x.Z);
+        fe_zero_guard(bad, x.Z, real);
         mul_small_ded_lds<DKG_WAVE_IL != 0>(x, (uint32_t)m, q, bad);  // * m
       } else {
         ge_add_lds(x, x, q, false);        // e_{m-1} + e_m
@@ -985,6 +988,44 @@ void to_column_major(size_t width, size_t npad, size_t N, const uint32_t* e, uin
                      dim3(256), 0, stream, width, npad, N, e, eT, pstride);
 }
 
+// Test aid: the zero tests of fe25519.h on caller-supplied limbs, one element per lane.  out[3 e ..]:
+// fe_maybe_zero, fe_tight_zero, and fe_zero_guard's value (the filter's ballot is taken over the
+// wave the element sits in, as in the kernels that use it).
+__global__ __launch_bounds__(64) void k_zero_tests(size_t count, const uint32_t* __restrict__ limbs,
+                                                   uint8_t* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = e < count;
+  fe a;
+#pragma unroll
+  for (int i = 0; i < 10; i++) a.v[i] = live ? limbs[10 * e + i] : 1u;
+  bool guard = false;
+  fe_zero_guard(guard, a, live);
+  if (live) {
+    out[3 * e] = fe_maybe_zero(a) ? 1 : 0;
+    out[3 * e + 1] = fe_tight_zero(a) ? 1 : 0;
+    out[3 * e + 2] = guard ? 1 : 0;
+  }
+}
+void zero_tests(size_t count, const uint32_t* limbs, uint8_t* out, hipStream_t stream) {
+  if (!count) return;
+  hipLaunchKernelGGL(k_zero_tests, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, count, limbs, out);
+}
+
+// The stepping's store of one evaluation: the point-major record, and Z once more in a dense 40-B
+// record when the affine normalisation reads only Z in its first pass (Rz)
+DKG_DEV void step_store_r(uint32_t* __restrict__ R, uint32_t* __restrict__ Rz, size_t e, const ge_p3& D) {
+  pt_store_aos<DKG_STEP_NT != 0>(R, e, D);
+  if (Rz) {
+    uint2* z2 = reinterpret_cast<uint2*>(Rz + e * 10);
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+      if (DKG_STEP_NT) __builtin_nontemporal_store(D.Z.v[2 * k], reinterpret_cast<uint32_t*>(z2 + k));
+      if (DKG_STEP_NT) __builtin_nontemporal_store(D.Z.v[2 * k + 1], reinterpret_cast<uint32_t*>(z2 + k) + 1);
+      if (!DKG_STEP_NT) z2[k] = make_uint2(D.Z.v[2 * k], D.Z.v[2 * k + 1]);
+    }
+  }
+}
+
 // One launch covers position block [pos0, pos0 + P) of every dealer.  Lanes are cut into column
 // slots of Ncol = (nseg - 1) P + Plast lanes, one dealer column each, holding nseg segments: pieces
 // piece0 + blockIdx.y + s of a degree-split table, P lanes each except the last (Plast).  nseg = 1:
@@ -1008,7 +1049,18 @@ void to_column_major(size_t width, size_t npad, size_t N, const uint32_t* e, uin
 // wave w holds positions [wB, (w+1)B), B = 64 / S, of every segment, so it is dead as a whole from
 // step nrecv - wB on: its additions are skipped (it still writes its cached form and arrives at
 // both barriers of every step).
-template <int MAXBS, bool DED, bool PARTS, bool BAND = false>
+//
+// SC: R (and Rz) take SCALED records (X, Y, 2Z, T/2) (points.h, scaled state) for a reader that folds
+// the constants into its normalisation (k_affine_pairs, k_affine_pieces: stepping()'s r_scaled).  The
+// dedicated loop then runs on the scaled state -- converted once at the load from e, published
+// without a doubling, stored as it stands -- and `up` / `down` carry the scaled cached form between
+// the block launches of the dedicated pass.  The complete instantiation keeps proper coordinates
+// (its streams too: the redo pass relaunches every block of a marked column) and converts at the
+// store, so a buffer has ONE convention per launch flag: R and Rz scaled under SC whichever
+// formula wrote them, e / sin / sout always proper.  Every other reader of R (k_combine*, the checks
+// at U = 1, complaint tables, the tail phases) gets SC = false: converting at the store costs more
+// than the loop's doublings wherever most waves hold a position 0.
+template <int MAXBS, bool DED, bool PARTS, bool BAND = false, bool SC = false>
 __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_stepping(
     size_t ndealers, size_t npad, size_t N, const uint32_t* __restrict__ e, size_t nrecv, size_t pos0, int P,
     const uint32_t* __restrict__ up,  // NULL: top block
@@ -1056,6 +1108,8 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
   } else {
     ge_identity(D);
   }
+  static_assert(!SC || !PARTS, "a part's states are proper: scaled records only from whole launches");
+  if constexpr (SC && DED) ge_to_scaled(D, D);
   const bool top_lane = live && (q == Pseg - 1);
   const uint4* upd = (up && live) ? reinterpret_cast<const uint4*>(up + d * nrecv * PT_WORDS) : nullptr;
   uint4* downd = (down && live) ? reinterpret_cast<uint4*>(down + d * nrecv * PT_WORDS) : nullptr;
@@ -1071,7 +1125,8 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
     // under a condition of its own the addition block recomputes them, +30 instructions per live step)
     {
       ge_cached c0;
-      if (DED) ge_to_cached_ded(c0, D);
+      if constexpr (DED && SC) ge_to_cached_sc(c0, D);
+      else if constexpr (DED) ge_to_cached_ded(c0, D);
       else ge_to_cached(c0, D);
       if (q == 0) {
         if (!BAND && downd) {
@@ -1096,25 +1151,22 @@ __global__ __launch_bounds__(MAXBS) __attribute__((amdgpu_waves_per_eu(4, 4))) v
     // that line skips its additions (contiguous map: the last 64 steps of every piece's upper wave
     // at L = 128; banded: the last wB steps of wave w)
     if (live && pos + 1 < Nlive && (q + 1 < Pseg || (!BAND && up)) && pos + j < nrecv) {
-      if (DED) {
-        ge_add_ded_lds(D, D, nbr, MAXBS);
-        bad |= real && fe_tight_zero(D.Z);
+      if constexpr (DED) {
+        if constexpr (SC) ge_add_sc_lds(D, D, nbr, MAXBS);
+        else ge_add_ded_lds(D, D, nbr, MAXBS);
+        fe_zero_guard(bad, D.Z, real);
       } else {
         ge_add_lds(D, D, nbr, false, MAXBS);
       }
     }
     __syncthreads();  // every column read before the next step overwrites it
     if (live && q == 0 && R) {
-      pt_store_aos<DKG_STEP_NT != 0>(R, d * nrecv + j, D);
-      // Z once more in a dense 40-B record: the affine normalisation reads only Z in its first pass
-      if (Rz) {
-        uint2* z2 = reinterpret_cast<uint2*>(Rz + (d * nrecv + j) * 10);
-#pragma unroll
-        for (int k = 0; k < 5; k++) {
-          if (DKG_STEP_NT) __builtin_nontemporal_store(D.Z.v[2 * k], reinterpret_cast<uint32_t*>(z2 + k));
-          if (DKG_STEP_NT) __builtin_nontemporal_store(D.Z.v[2 * k + 1], reinterpret_cast<uint32_t*>(z2 + k) + 1);
-          if (!DKG_STEP_NT) z2[k] = make_uint2(D.Z.v[2 * k], D.Z.v[2 * k + 1]);
-        }
+      if constexpr (SC && !DED) {  // the complete redo of a scaled R: converted here (rare launches)
+        ge_p3 o;
+        ge_to_scaled(o, D);
+        step_store_r(R, Rz, d * nrecv + j, o);
+      } else {
+        step_store_r(R, Rz, d * nrecv + j, D);
       }
     }
   }
@@ -1239,57 +1291,60 @@ struct ColReal {  // which table columns belong to real dealers (k_stepping's `r
   uint32_t* Rz;
 };
 
-template <bool DED, bool PARTS>
+template <bool DED, bool PARTS, bool SC = false>
 void step_launch_p(int maxbs, dim3 grid, dim3 block, hipStream_t stream, size_t ndealers, size_t npad, size_t N,
                    const uint32_t* e, size_t nrecv, size_t pos0, int P, const uint32_t* up, uint32_t* down,
                    uint32_t* R, size_t pstride, size_t Nlive, unsigned piece0, int nseg, int Plast, uint32_t* flags,
                    const ColReal& cr, size_t j0, size_t j1, const uint32_t* sin, uint32_t* sout, size_t nin,
                    size_t nout) {
   if (maxbs == 192)
-    hipLaunchKernelGGL((k_stepping<192, DED, PARTS>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
+    hipLaunchKernelGGL((k_stepping<192, DED, PARTS, false, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
                        up, down, R, pstride, Nlive, piece0, nseg, Plast, flags, cr.col0, cr.dreal, cr.gw,
                        R ? cr.Rz : nullptr, j0, j1, sin, sout, nin, nout);
   else if (maxbs == 256)
-    hipLaunchKernelGGL((k_stepping<256, DED, PARTS>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
+    hipLaunchKernelGGL((k_stepping<256, DED, PARTS, false, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
                        up, down, R, pstride, Nlive, piece0, nseg, Plast, flags, cr.col0, cr.dreal, cr.gw,
                        R ? cr.Rz : nullptr, j0, j1, sin, sout, nin, nout);
   else
-    hipLaunchKernelGGL((k_stepping<512, DED, PARTS>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
+    hipLaunchKernelGGL((k_stepping<512, DED, PARTS, false, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, pos0, P,
                        up, down, R, pstride, Nlive, piece0, nseg, Plast, flags, cr.col0, cr.dreal, cr.gw,
                        R ? cr.Rz : nullptr, j0, j1, sin, sout, nin, nout);
 }
 
-template <bool DED>
+template <bool DED, bool SC = false>
 void step_launch(int maxbs, dim3 grid, dim3 block, hipStream_t stream, size_t ndealers, size_t npad, size_t N,
                  const uint32_t* e, size_t nrecv, size_t pos0, int P, const uint32_t* up, uint32_t* down,
                  uint32_t* R, size_t pstride, size_t Nlive, unsigned piece0, int nseg, int Plast, uint32_t* flags,
                  const ColReal& cr, size_t j0, size_t j1, const uint32_t* sin, uint32_t* sout, size_t nin = 0,
                  size_t nout = 0) {
-  if (j0 != 0 || j1 != nrecv)
-    step_launch_p<DED, true>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, R, pstride,
-                             Nlive, piece0, nseg, Plast, flags, cr, j0, j1, sin, sout, nin ? nin : N,
-                             nout ? nout : N);
-  else
-    step_launch_p<DED, false>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, R, pstride,
-                              Nlive, piece0, nseg, Plast, flags, cr, 0, nrecv, nullptr, nullptr, N, N);
+  if constexpr (!SC) {  // scaled records come from whole launches only (stepping() never asks for parts)
+    if (j0 != 0 || j1 != nrecv) {
+      step_launch_p<DED, true>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, R,
+                               pstride, Nlive, piece0, nseg, Plast, flags, cr, j0, j1, sin, sout, nin ? nin : N,
+                               nout ? nout : N);
+      return;
+    }
+  }
+  step_launch_p<DED, false, SC>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, R,
+                                pstride, Nlive, piece0, nseg, Plast, flags, cr, 0, nrecv, nullptr, nullptr, N, N);
 }
 
 // A banded launch (step_band): one block per table, the whole receiver range, no streams.
-template <bool DED>
+template <bool DED, bool SC = false>
 void step_launch_band(int maxbs, dim3 grid, dim3 block, hipStream_t stream, size_t ndealers, size_t npad, size_t N,
                       const uint32_t* e, size_t nrecv, int P, uint32_t* R, size_t pstride, size_t Nlive,
                       unsigned piece0, int nseg, uint32_t* flags, const ColReal& cr) {
   uint32_t* Rz = R ? cr.Rz : nullptr;
   if (maxbs == 192)
-    hipLaunchKernelGGL((k_stepping<192, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+    hipLaunchKernelGGL((k_stepping<192, DED, false, true, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
                        nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
                        nrecv, nullptr, nullptr, N, N);
   else if (maxbs == 256)
-    hipLaunchKernelGGL((k_stepping<256, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+    hipLaunchKernelGGL((k_stepping<256, DED, false, true, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
                        nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
                        nrecv, nullptr, nullptr, N, N);
   else
-    hipLaunchKernelGGL((k_stepping<512, DED, false, true>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
+    hipLaunchKernelGGL((k_stepping<512, DED, false, true, SC>), grid, block, 0, stream, ndealers, npad, N, e, nrecv, 0, P,
                        nullptr, nullptr, R, pstride, Nlive, piece0, nseg, P, flags, cr.col0, cr.dreal, cr.gw, Rz, 0,
                        nrecv, nullptr, nullptr, N, N);
 }
@@ -1313,8 +1368,9 @@ size_t stepping_tail_words(size_t ndealers, size_t N) { return PT_WORDS * ndeale
 bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t nrecv, uint32_t* R,
               uint32_t* stream_a, uint32_t* stream_b, hipStream_t stream, size_t pieces, size_t pstride,
               size_t last_len, bool whole, uint32_t* flags, size_t col0, size_t dreal, unsigned gw, uint32_t* Rz,
-              uint32_t* tail_a, uint32_t* tail_b) {
+              uint32_t* tail_a, uint32_t* tail_b, bool r_scaled) {
   if (!ndealers || !nrecv) return true;
+  if (r_scaled && pieces == 1) return false;  // scaled records are for the normalisation of split tables
   const ColReal cr{col0, dreal, gw ? gw : 64u, Rz};
   if (!last_len || last_len > N) last_len = N;
   // with flags (stepping_flag_words zeroed words): every launch below runs dedicated, then again
@@ -1325,12 +1381,13 @@ bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t 
   auto fits = [&](size_t words) { return !flags || foff + words <= fcap; };
   auto run = [&](int maxbs, dim3 grid, dim3 block, size_t pos0, int P, const uint32_t* up, uint32_t* down,
                  uint32_t* Rout, size_t Nlive, unsigned piece0, int nseg, int Plast, uint32_t* f) {
-    if (f) {
-      step_launch<true>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, Rout, pstride,
-                        Nlive, piece0, nseg, Plast, f, cr, 0, nrecv, nullptr, nullptr);
-    }
-    step_launch<false>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, pos0, P, up, down, Rout, pstride,
-                       Nlive, piece0, nseg, Plast, f, cr, 0, nrecv, nullptr, nullptr);
+    auto go = [&](auto ded, auto sc) {
+      step_launch<decltype(ded)::value, decltype(sc)::value>(maxbs, grid, block, stream, ndealers, npad, N, e, nrecv,
+                                                             pos0, P, up, down, Rout, pstride, Nlive, piece0, nseg,
+                                                             Plast, f, cr, 0, nrecv, nullptr, nullptr);
+    };
+    if (f) r_scaled ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+    r_scaled ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
   };
   auto launch = [&](const StepShape& s, size_t Nlive, unsigned piece0, size_t np, int nseg, int Plast) {
     const dim3 grid((unsigned)((ndealers + s.per - 1) / s.per), (unsigned)np), block((unsigned)s.bs);
@@ -1340,11 +1397,13 @@ bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t 
     // equal segments that fill the workgroup: the banded lane map, same grid and the same map in
     // the complete relaunch (flags[wg] stays one word per workgroup)
     if (step_band((int)s.bs, (int)s.P, nseg, Plast)) {
-      if (f)
-        step_launch_band<true>((int)s.maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, (int)s.P, R, pstride,
-                               Nlive, piece0, nseg, f, cr);
-      step_launch_band<false>((int)s.maxbs, grid, block, stream, ndealers, npad, N, e, nrecv, (int)s.P, R, pstride,
-                              Nlive, piece0, nseg, f, cr);
+      auto go = [&](auto ded, auto sc) {
+        step_launch_band<decltype(ded)::value, decltype(sc)::value>((int)s.maxbs, grid, block, stream, ndealers, npad,
+                                                                    N, e, nrecv, (int)s.P, R, pstride, Nlive, piece0,
+                                                                    nseg, f, cr);
+      };
+      if (f) r_scaled ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+      r_scaled ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
       return true;
     }
     run((int)s.maxbs, grid, block, 0, (int)s.P, nullptr, nullptr, R, Nlive, piece0, nseg, Plast, f);
@@ -1405,14 +1464,15 @@ bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t 
         uint32_t* up = nullptr;
         for (size_t b = sh.nblk; b-- > 0;) {
           uint32_t* down = b ? ((sh.nblk - 1 - b) % 2 ? stream_b : stream_a) : nullptr;
-          if (pass == 0)
-            step_launch<true>(512, grid, block, stream, ndealers, npad, N, e, nrecv, b * sh.P, (int)sh.P, up, down,
-                              b ? nullptr : R, pstride, Nlive, piece0, 1, (int)sh.P, f, cr, 0, nrecv,
-                              nullptr, nullptr);
-          else
-            step_launch<false>(512, grid, block, stream, ndealers, npad, N, e, nrecv, b * sh.P, (int)sh.P, up, down,
-                               b ? nullptr : R, pstride, Nlive, piece0, 1, (int)sh.P, f, cr, 0, nrecv,
-                              nullptr, nullptr);
+          // (both passes keep their own convention in the streams: k_stepping's SC)
+          auto go = [&](auto ded, auto sc) {
+            step_launch<decltype(ded)::value, decltype(sc)::value>(512, grid, block, stream, ndealers, npad, N, e,
+                                                                   nrecv, b * sh.P, (int)sh.P, up, down,
+                                                                   b ? nullptr : R, pstride, Nlive, piece0, 1,
+                                                                   (int)sh.P, f, cr, 0, nrecv, nullptr, nullptr);
+          };
+          if (pass == 0) r_scaled ? go(std::true_type{}, std::true_type{}) : go(std::true_type{}, std::false_type{});
+          else r_scaled ? go(std::false_type{}, std::true_type{}) : go(std::false_type{}, std::false_type{});
           up = down;
         }
       }
@@ -1632,6 +1692,9 @@ DKG_DEV void ld_z(fe& z, const uint32_t* R, const uint32_t* Rz, size_t e) {  // 
 
 // Receivers [j0, j0 + jn) of rows nrecv long; ls (a power of two <= 32) lanes share a run of
 // ls * AFF_RUN receivers, lane k taking receivers k, k + ls, .. of it.
+// SC: scaled records (X, Y, Z~, T^) = (X, Y, 2Z, T/2) (points.h): the run's inverse is doubled once, so
+// that every 1/Z~ below comes out as 2/Z~ = 1/Z, and 2d xy = 2d T/Z = 4d T^ (2/Z~) takes 4d for 2d.
+template <bool SC>
 __global__ __launch_bounds__(256) void k_affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv,
                                                        const uint32_t* __restrict__ R, uint32_t* __restrict__ A,
                                                        const uint32_t* __restrict__ Rz, size_t j0, size_t jn,
@@ -1667,8 +1730,12 @@ __global__ __launch_bounds__(256) void k_affine_pieces(size_t width, size_t pstr
   }
   fe inv;
   fe_invert(inv, acc);
+  if constexpr (SC) {
+    fe_dbl(inv, inv);
+    fe_carry(inv, inv);
+  }
   fe d2;
-  fe_ld(d2, ge_const::D2);
+  fe_ld(d2, SC ? ge_const::D4 : ge_const::D2);
 #pragma unroll 1
   for (int b = nblk - 1; b >= 0; b--) {
     fe z[AFF_BLK], q[AFF_BLK];  // q[k] = z[0] .. z[k-1] (q[0] = 1 is never formed)
@@ -1719,7 +1786,7 @@ __global__ __launch_bounds__(256) void k_affine_pieces(size_t width, size_t pstr
 }
 
 void affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
-                   hipStream_t stream, const uint32_t* Rz, size_t j0, size_t jn) {
+                   hipStream_t stream, const uint32_t* Rz, size_t j0, size_t jn, bool scaled) {
   if (!jn) jn = nrecv - j0;
   if (!width || !jn || !pieces) return;
   // lanes per run: 32, or fewer for a short receiver part so that each lane still normalises up to
@@ -1727,8 +1794,8 @@ void affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv, co
   unsigned ls = 32;
   while (ls > 1 && (size_t)(ls / 2) * AFF_RUN >= jn) ls /= 2;
   const size_t runs = (jn + (size_t)ls * AFF_RUN - 1) / ((size_t)ls * AFF_RUN), lanes = pieces * width * runs * ls;
-  hipLaunchKernelGGL(k_affine_pieces, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, width, pstride,
-                     pieces, nrecv, R, A, Rz, j0, jn, ls);
+  hipLaunchKernelGGL(scaled ? k_affine_pieces<true> : k_affine_pieces<false>, dim3((unsigned)((lanes + 255) / 256)),
+                     dim3(256), 0, stream, width, pstride, pieces, nrecv, R, A, Rz, j0, jn, ls);
 }
 
 template <int U, int K, int KL>
@@ -1855,13 +1922,20 @@ DKG_DEV void ld_xy(fe& x, fe& y, const uint32_t* R, size_t e) {  // X, Y of poin
   y = fe{{c.z, c.w, d.x, d.y, d.z, d.w, f.x, f.y, f.z, f.w}};
 }
 // z01 = Z_0 Z_1, f = d - c, g = d + c of the complete addition (d = 2 z01 carried: f <= 1.5*2^27)
-DKG_DEV void pair_fg(fe& z01, fe& f, fe& g, const fe& z0, const fe& t0, const fe& z1, const fe& t1, const fe& d2) {
+// SC, scaled records (Z~, T^) = (2Z, T/2): z01 = Z~_0 Z~_1 = 2 d and 16d T^_0 T^_1 = 2 c, so with dc =
+// 16d for 2d the same lines give 2f and 2g, and d needs neither its doubling nor its carry
+template <bool SC>
+DKG_DEV void pair_fg(fe& z01, fe& f, fe& g, const fe& z0, const fe& t0, const fe& z1, const fe& t1, const fe& dc) {
   fe c, d;
   fe_mul(z01, z0, z1);
   fe_mul(c, t0, t1);
-  fe_mul(c, c, d2);
-  fe_dbl(d, z01);
-  fe_carry(d, d);
+  fe_mul(c, c, dc);
+  if constexpr (SC) {
+    fe_copy(d, z01);
+  } else {
+    fe_dbl(d, z01);
+    fe_carry(d, d);
+  }
   fe_sub(f, d, c);
   fe_add(g, d, c);
 }
@@ -1877,7 +1951,14 @@ DKG_DEV void st_niels(uint32_t* slot, const fe& x, const fe& y, const fe& d2) {
 
 // Receivers [j0, j0 + jn) of rows nrecv long; one lane per (pair, column) and run of receivers, laid
 // out as in k_affine_pieces: ls lanes share a run of ls * rl receivers, rl <= AFFQ_RUN per lane.
-__global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv,
+// SC: scaled records (points.h).  X and Y are those of the proper point with Z = Z~ / 2, so e, h, e', h'
+// are unchanged; pair_fg<true> yields z01' = 4 Z_0 Z_1, 2f, 2g and Z_S' = 4 Z_S, and with the run's
+// inverse doubled once the lines below give 2 / (Z~_0 Z~_1) -> 1 / Z_0, 1 / Z_1 and 2 / Z_S' -> 2f / (2 Z_S)
+// = 1 / g, 1 / f: the outputs of the proper records, with pair_fg's doubling and carry gone.
+// (Two waves per SIMD stated: left to itself the allocator takes all 256 VGPRs and, for SC, two AGPRs
+// more, which halves the occupancy; told the bound it needs 193 / 212 and no scratch.)
+template <bool SC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv,
                                                       const uint32_t* __restrict__ R, uint32_t* __restrict__ A,
                                                       size_t j0, size_t jn, unsigned ls, unsigned rl) {
   const size_t span = (size_t)ls * rl, runs = (jn + span - 1) / span;
@@ -1890,8 +1971,9 @@ __global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstri
   const size_t jb = run * span + (gid % ls);  // receivers j0 + jb + ls i, i < cnt
   const int cnt = jb < jn ? (int)min((size_t)rl, (jn - jb + ls - 1) / ls) : 0;
   auto pt = [&](int i) { return e0 + jb + ls * (size_t)i; };  // Q_2p(j); Q_2p+1(j) one plane on
-  fe d2;
+  fe d2, dc;  // 2d of the Niels slots; pair_fg's constant
   fe_ld(d2, ge_const::D2);
+  fe_ld(dc, SC ? ge_const::D16 : ge_const::D2);
   fe acc;
   fe_one(acc);
 #pragma unroll 1
@@ -1903,13 +1985,17 @@ __global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstri
     fe z0, t0, z1, t1, z01, f, g;
     ld_zt(z0, t0, R, pt(i));
     ld_zt(z1, t1, R, pt(i) + plane);
-    pair_fg(z01, f, g, z0, t0, z1, t1, d2);
+    pair_fg<SC>(z01, f, g, z0, t0, z1, t1, dc);
     fe_mul(acc, acc, z01);
     fe_mul(f, f, g);  // Z_S
     fe_mul(acc, acc, f);
   }
   fe inv;
   fe_invert(inv, acc);
+  if constexpr (SC) {
+    fe_dbl(inv, inv);
+    fe_carry(inv, inv);
+  }
 #pragma unroll 1
   for (int i = cnt - 1; i >= 0; i--) {
     const size_t e = pt(i);
@@ -1917,7 +2003,7 @@ __global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstri
     fe z0, t0, z1, t1, z01, f, g, zs, iz0, iz1;
     ld_zt(z0, t0, R, e);
     ld_zt(z1, t1, R, e + plane);
-    pair_fg(z01, f, g, z0, t0, z1, t1, d2);
+    pair_fg<SC>(z01, f, g, z0, t0, z1, t1, dc);
     fe_mul(zs, f, g);
     {
       const uint4* a4 = reinterpret_cast<const uint4*>(slot);
@@ -1969,7 +2055,7 @@ __global__ __launch_bounds__(256) void k_affine_pairs(size_t width, size_t pstri
 }
 
 void affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
-                  hipStream_t stream, size_t j0, size_t jn) {
+                  hipStream_t stream, size_t j0, size_t jn, bool scaled) {
   if (!jn) jn = nrecv - j0;
   if (!width || !jn || pieces < 2) return;
   // a lane's two passes and inversion are one dependent chain: a launch of under one wave per SIMD
@@ -1979,8 +2065,8 @@ void affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv, con
   unsigned ls = 32;  // lanes per run, fewer for a short receiver part (affine_pieces)
   while (ls > 1 && (size_t)(ls / 2) * rl >= jn) ls /= 2;
   const size_t runs = (jn + (size_t)ls * rl - 1) / ((size_t)ls * rl), lanes = (pieces / 2) * width * runs * ls;
-  hipLaunchKernelGGL(k_affine_pairs, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, stream, width, pstride,
-                     pieces, nrecv, R, A, j0, jn, ls, rl);
+  hipLaunchKernelGGL(scaled ? k_affine_pairs<true> : k_affine_pairs<false>, dim3((unsigned)((lanes + 255) / 256)),
+                     dim3(256), 0, stream, width, pstride, pieces, nrecv, R, A, j0, jn, ls, rl);
 }
 
 // The streamed addend of the chain's next both-nonzero column, event e: bits 0-1 its plane after the

@@ -131,6 +131,8 @@ double stepping_waves_per_simd(size_t cols, size_t N, size_t pieces, size_t last
 // the additions then run by the dedicated formula and the workgroups that met an exceptional pair
 // are redone with the complete one (kernels.hip k_stepping).
 size_t stepping_flag_words(size_t ndealers, size_t pieces);
+// test aid (dkg_zero_tests): out[count][3] = fe_maybe_zero, fe_tight_zero, fe_zero_guard of limbs[count][10]
+void zero_tests(size_t count, const uint32_t* limbs, uint8_t* out, hipStream_t stream);
 // Rz (may be null): also a dense copy of every stored point's Z, 10 words per point at the index of
 // R (read by affine_pieces).
 // col0, dreal, gw: column c (0-based within this call) is global table column col0 + c of dealer
@@ -139,13 +141,16 @@ size_t stepping_flag_words(size_t ndealers, size_t pieces);
 // tail_a, tail_b (may be null): scratch for the dead-position repack (stepping_tail_phases > 1,
 // one unsplit table), laid out for the whole table of npad columns (this call's start at col0):
 // each >= stepping_tail_words(npad, N) words.
+// r_scaled (pieces > 1 only): R and Rz take scaled records (X, Y, 2Z, T/2) (points.h, scaled state:
+// the dedicated loop then has no doubling); their one reader must be affine_pairs or affine_pieces
+// called with scaled = true, which fold the constants into the normalisation.
 // Returns false, with nothing launched past that point, when the launches would need more flag
 // words than stepping_flag_words(ndealers, pieces).
 bool stepping(size_t ndealers, size_t npad, size_t N, const uint32_t* e, size_t nrecv, uint32_t* R,
               uint32_t* stream_a, uint32_t* stream_b, hipStream_t stream, size_t pieces = 1, size_t pstride = 0,
               size_t last_len = 0, bool whole = true, uint32_t* flags = nullptr, size_t col0 = 0,
               size_t dreal = (size_t)-1, unsigned gw = 64, uint32_t* Rz = nullptr, uint32_t* tail_a = nullptr,
-              uint32_t* tail_b = nullptr);
+              uint32_t* tail_b = nullptr, bool r_scaled = false);
 // Dead-position repack of an unsplit table (DESIGN.md section 4): position p is dead once p + j >=
 // nrecv, so from step nrecv - P/2 + 1 on only P/2 positions of a P-lane segment still add.  Phase k
 // runs steps [J_k, J_{k+1}) on segments of P_k = N / 2^k lanes (J_k = nrecv - P_k + 1: its top
@@ -165,9 +170,10 @@ void combine_short(size_t width, size_t pstride, size_t pieces, size_t nrecv, co
 // Affine addends for combine_short: A[(u * pstride + c) * nrecv + j] (32-word slots: y+x, y-x, 2dxy,
 // 2 pad) = the affine Niels form of R's piece value at the same index, for every piece u < pieces
 // and column c < width (Montgomery's trick over runs of receivers, one inversion per run).
-// j0, jn (0: the rest): receivers [j0, j0 + jn) only.
+// j0, jn (0: the rest): receivers [j0, j0 + jn) only.  scaled: R and Rz hold stepping()'s r_scaled records.
 void affine_pieces(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
-                   hipStream_t stream, const uint32_t* Rz = nullptr, size_t j0 = 0, size_t jn = 0);
+                   hipStream_t stream, const uint32_t* Rz = nullptr, size_t j0 = 0, size_t jn = 0,
+                   bool scaled = false);
 // combine_short reading its addends from affine_pieces' A (mixed additions, 7M instead of 8M); the
 // result b_j P(j) goes to R[c][j] as in combine_short.
 void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* digits,
@@ -178,8 +184,9 @@ void combine_short_aff(size_t width, size_t pstride, size_t pieces, size_t nrecv
 // latter as planes pieces + 2p and pieces + 2p + 1 of A, so A holds pieces + 2 floor(pieces / 2)
 // planes of pstride columns and R only the pieces' (the projective sums are never stored; one
 // inverse serves a pair's sum and difference).  It reads Z from R itself: no dense Z copy.
+// scaled: R holds stepping()'s r_scaled records.
 void affine_pairs(size_t width, size_t pstride, size_t pieces, size_t nrecv, const uint32_t* R, uint32_t* A,
-                  hipStream_t stream, size_t j0 = 0, size_t jn = 0);
+                  hipStream_t stream, size_t j0 = 0, size_t jn = 0, bool scaled = false);
 // combine_short_aff over JSF digits (runtime.hip split_short): a column with both digits of a pair
 // set adds the pair's sum or difference, streamed from its plane of A one such column ahead.
 // ev [nrecv][JSF_EV_WORDS]: one word per both-nonzero column in chain order -- positions downwards,

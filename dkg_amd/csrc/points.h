@@ -402,6 +402,42 @@ DKG_DEV void ge_add_ded_lds(ge_p3& r, const ge_p3& p, const uint32_t* q, int str
 #endif
 }
 
+// Scaled state (the stepping's dedicated loop, k_stepping<.., SC>).  ge_to_cached_ded doubles Z and T
+// on every step only because F = B - A and G = B + A carry a factor two by construction.  The factor
+// can live in the state: hold (X, Y, Z~, T^) = (X, Y, 2Z, T/2) of a proper extended point and publish
+// (Y+X, Y-X, Z~, T^) as it stands.  The SAME eight products then give C' = Z~1 T^2 = C/2 and D' =
+// T^1 Z~2 = D/2, hence E' = E/2, H' = H/2 with F and G exact, and
+//   X3' = E'F = X3/2,  Y3' = G H' = Y3/2,  Z3' = F G = Z3,  T3' = E'H' = T3/4:
+// the scaled form (X*, Y*, 2Z*, T*/2) of the proper representative (X3, Y3, Z3, T3)/2 of p + Q.  The
+// form is invariant under the step for accumulator and addend alike, no doubling is left, and Z3' is
+// the very value ge_add_ded_lds tests, so the exceptional pairs and the redo rule are the same
+// (tools/ded_check.py).  The second operands of the C and D products are tight instead of doubled.
+// proper -> scaled, once per lane at the table load: (2X, 2Y, 4Z, T), carried (stored coordinates and
+// the loop's first operands are TIGHT)
+DKG_DEV void ge_to_scaled(ge_p3& s, const ge_p3& p) {
+  fe_dbl(s.X, p.X);
+  fe_carry(s.X, s.X);
+  fe_dbl(s.Y, p.Y);
+  fe_carry(s.Y, s.Y);
+  fe_dbl(s.Z, p.Z);
+  fe_carry(s.Z, s.Z);       // carried after each doubling: 4Z in one pass would put 19 * 4 > 2^6 on limb 0
+  fe_dbl(s.Z, s.Z);
+  fe_carry(s.Z, s.Z);
+  fe_copy(s.T, p.T);
+}
+// the publish step: two field additions, Z~ and T^ copied through
+DKG_DEV void ge_to_cached_sc(ge_cached& c, const ge_p3& s) {
+  fe_add(c.YpX, s.Y, s.X);
+  fe_sub(c.YmX, s.Y, s.X);
+  fe_copy(c.Z2, s.Z);       // Z~ = 2Z
+  fe_copy(c.T2d, s.T);      // T^ = T/2 in the 2dT slot
+}
+// r = p + Q on scaled states, Q as ge_to_cached_sc in LDS: ge_add_ded_lds's products and pairing
+// (DKG_FE_PAIR) read the four fields in the same places; only their meaning differs (above)
+DKG_DEV void ge_add_sc_lds(ge_p3& r, const ge_p3& p, const uint32_t* q, int stride = 64) {
+  ge_add_ded_lds(r, p, q, stride);
+}
+
 // The dedicated addition with a signed addend and an optional T (the m-chains of the per-wave
 // binomial): r = p +/- Q, Q as ge_to_cached_ded in LDS, -Q = (Y-X, Y+X, 2Z, -2T) -- the fields
 // swapped and C negated exactly as ge_add_lds does (the same bounds).  `neg` wave-uniform.  Not

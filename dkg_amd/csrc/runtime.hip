@@ -361,6 +361,9 @@ double binom_ilp_waves() {  // DKG_BINOM_ILP_WAVES, overridable the same way (A/
 #ifndef DKG_BINOM_WAVE_GROUPS
 #define DKG_BINOM_WAVE_GROUPS 16384
 #endif
+#ifndef DKG_STEP_SCALED  // scaled records between the stepping and the affine normalisation (A/B: 0
+#define DKG_STEP_SCALED 1  // keeps proper points and the loop's two doublings; profiles/step_scaled_ab.txt)
+#endif
 
 bool use_ilp(const dkg_ctx* ctx, bool latency_bound) {
   return ctx->fe_mode == 2 || (ctx->fe_mode == 0 && latency_bound);
@@ -752,6 +755,10 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   // the stepping's dense copy of each stored point's Z (40 B), read by the affine normalisation
   // (k_affine_pieces; the JSF chains' k_affine_pairs reads Z and T from R, so there is none)
   uint32_t* Rz = Aff && !jsf ? buf<uint32_t>(ctx, "v.Rz", 40 * W * n) : nullptr;
+  // the stepped values' one reader is the affine normalisation: the stepping leaves scaled records
+  // (kernels.hip k_stepping SC: no doublings in its loop) and the normalisation folds the constants.
+  // Every other reader of the stepped R (k_combine*, the checks at U = 1) takes proper points.
+  const bool r_scaled = DKG_STEP_SCALED && Aff != nullptr;
   if (short_mult) split_short(ctx, n, L, U, jsf, &sdig, &stop, &sscale, &sev);
   else if (U > 1) split_digits(ctx, n, L, &ydig, &ytop);
   ctx->last_combine = U > 1 ? (short_mult ? 2 : 1) : 0;
@@ -880,14 +887,15 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
     auto step = step_ilp ? dkgk_ilp::stepping : dkgk::stepping;
     if (!step(w, W, L, eT + c0 * L, n, R + c0 * n * PT_WORDS_H, sa ? sa + c0 * n * 40 : nullptr,
               sb ? sb + c0 * n * 40 : nullptr, st, U, npad, Lr, whole, fl, c0, D, (unsigned)gw,
-              Rz ? Rz + c0 * n * 10 : nullptr, tail_a, tail_b))
+              Rz ? Rz + c0 * n * 10 : nullptr, tail_a, tail_b, r_scaled))
       throw Fail{DKG_E_ARG};  // stepping flag words: an internal layout error, never silently dropped
     if (tm) HCK(hipEventRecord(ctx->pev[2], st));
     if (jsf) {
-      dkgk::affine_pairs(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st);
+      dkgk::affine_pairs(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, 0, 0, r_scaled);
       dkgk::combine_short_jsf(w, npad, U, n, sdig, stop, sev, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
     } else if (short_mult && Aff) {
-      dkgk::affine_pieces(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, Rz + c0 * n * 10);
+      dkgk::affine_pieces(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, Rz + c0 * n * 10, 0,
+                          0, r_scaled);
       dkgk::combine_short_aff(w, npad, U, n, sdig, stop, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
     } else if (short_mult) dkgk::combine_short(w, npad, U, n, sdig, stop, R + c0 * n * PT_WORDS_H, st);
     else dkgk::combine(w, npad, U, n, ydig, ytop, R + c0 * n * PT_WORDS_H, st);
@@ -3203,6 +3211,21 @@ int dkg_poly_eval_batch(dkg_ctx* ctx, size_t D, size_t N, const uint8_t* coeffs,
     dkgk::poly_eval(D, N, c, M, x, o, ctx->stream);
     check_launch(ctx);
     d2h(ctx, out, o, 32 * D * M);
+    sync(ctx);
+    return DKG_OK;
+  });
+}
+
+int dkg_zero_tests(dkg_ctx* ctx, size_t count, const uint32_t* limbs, uint8_t* out) {
+  return guarded(ctx, [&] {
+    if (count == 0) return DKG_OK;
+    if (!limbs || !out) return DKG_E_ARG;
+    uint32_t* dl = buf<uint32_t>(ctx, "zt_limbs", 40 * count);
+    uint8_t* od = buf<uint8_t>(ctx, "zt_out", 3 * count);
+    h2d(ctx, dl, limbs, 40 * count);
+    dkgk::zero_tests(count, dl, od, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, out, od, 3 * count);
     sync(ctx);
     return DKG_OK;
   });

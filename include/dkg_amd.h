@@ -138,6 +138,11 @@ int dkg_ctx_set_stepping_formula(dkg_ctx *ctx, int mode);
 /* Workgroups of the last verification's stepping that were recomputed by the complete formula
  * (synchronises the context's stream; 0 in mode 1; -1 on error). */
 long long dkg_ctx_stepping_redos(dkg_ctx *ctx);
+/* Test aid: the device's zero tests of a field product (fe25519.h) on count elements of ten 32-bit
+ * limbs each, limbs [count][10]: out [count][3] = the one-limb filter (fe_maybe_zero), the full test
+ * (fe_tight_zero), and the filtered guard the dedicated additions use (fe_zero_guard), each 0 or 1.
+ * The guard equals the full test on every input. */
+int dkg_zero_tests(dkg_ctx *ctx, size_t count, const uint32_t *limbs, uint8_t *out);
 /* The stepping's banded lane map ("Dead positions"): a `lanes`-lane workgroup
  * made of slots of `nseg` segments, `seg_len` lanes each except a slot's last (`last_len`).  Returns
  * the band width B (wave w holds positions [wB, (w+1)B) of every segment) and fills out[0..2] with

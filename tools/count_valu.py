@@ -27,6 +27,15 @@ PRIMS = {
                          "STP(p);"),
     "fe_tight_zero": ("fe a; LD10(a.v, 0); uint32_t acc = 0;", "acc += fe_tight_zero(a) ? 1u : 0u; a.v[0] ^= acc;",
                       "ST10(a.v);"),
+    # the scaled state's addition and publish step (with the harness's 40 copies, as ge_to_cached_ded),
+    # and the filtered guard -- the tool reports a kernel's LARGEST block, which for the guard is the
+    # cold full test behind the ballot; its hot path is the filter's 3 instructions (4 slots)
+    "ge_add_sc": ("ge_p3 p; LDP(p, 0);", "ge_add_sc_lds(p, p, o + 2560 + threadIdx.x, 64);", "STP(p);"),
+    "ge_to_cached_sc": ("ge_p3 p; ge_cached q; LDP(p, 0);",
+                        "ge_to_cached_sc(q, p); p.X = q.T2d; p.Y = q.YpX; p.Z = q.Z2; p.T = q.YmX;",
+                        "STP(p);"),
+    "fe_zero_guard": ("fe a; LD10(a.v, 0); uint32_t acc = 0;",
+                      "bool b_ = false; fe_zero_guard(b_, a); acc += b_ ? 1u : 0u; a.v[0] ^= acc;", "ST10(a.v);"),
     "ge_madd_signed": ("ge_p3 p; ge_aff q; LDP(p, 0); LD10(q.ypx.v, 3000); LD10(q.ymx.v, 3640); LD10(q.xy2d.v, 4280); "
                        "bool ng = o[9999] & 1;", "ge_madd_signed(p, p, q, ng); ng = !ng;", "STP(p);"),
     "ge_madd_signed_not": ("ge_p3 p; ge_aff q; LDP(p, 0); LD10(q.ypx.v, 3000); LD10(q.ymx.v, 3640); "

@@ -7,6 +7,12 @@
     (p = a g + T1, q = b g + T2), it either returns p + q exactly or a point with Z = 0 -- never a
     wrong point with Z != 0.  That is what makes the stepping's redo rule exact: a workgroup whose
     sums all came out with Z != 0 holds the complete formula's values.
+  * the scaled-state addition (points.h ge_add_sc_lds: the same products on (X, Y, 2Z, T/2) and the
+    published (Y+X, Y-X, 2Z, T/2)) returns, on every one of those pairs, exactly (X3/2, Y3/2, Z3, T3/4)
+    of the dedicated result (X3, Y3, Z3, T3): again a scaled state, of the same point, with Z3' = 0
+    exactly where Z3 = 0; ge_to_scaled's (2X, 2Y, 4Z, T) is a scaled state of the same point; and the
+    normalisations' folded constants (k_affine_pieces<SC>, k_affine_pairs<SC>) give the affine Niels
+    slots of the proper records.
 Usage: python tools/ded_check.py   (exit status 1 on a wrong sum); tests/test_bounds.py runs it.
 """
 import os
@@ -28,6 +34,64 @@ def ded(p, q):
     C, Dd = p.Z * t2 % P, p.T * z2 % P
     E, H = (Dd + C) % P, (Dd - C) % P
     return R.Pt(E * F, G * H, G * F, E * H)
+
+
+INV2, INV4 = pow(2, P - 2, P), pow(4, P - 2, P)
+
+
+def to_scaled(p):
+    """points.h ge_to_scaled: (2X, 2Y, 4Z, T), the scaled state of the representative 2 (X, Y, Z, T)."""
+    return R.Pt(2 * p.X % P, 2 * p.Y % P, 4 * p.Z % P, p.T % P)
+
+
+def from_scaled(s):
+    """The proper point (X, Y, Z~/2, 2T^) a scaled state stands for."""
+    return R.Pt(s.X, s.Y, s.Z * INV2 % P, 2 * s.T % P)
+
+
+def ded_sc(p, q):
+    """ge_add_sc_lds on scaled states: ge_add_ded_lds's products, q published without doublings."""
+    ypx, ymx = (q.Y + q.X) % P, (q.Y - q.X) % P
+    A = (p.Y - p.X) * ypx % P
+    B = (p.Y + p.X) * ymx % P
+    F, G = (B - A) % P, (B + A) % P
+    C, Dd = p.Z * q.T % P, p.T * q.Z % P
+    E, H = (Dd + C) % P, (Dd - C) % P
+    return R.Pt(E * F, G * H, G * F, E * H)
+
+
+def niels(x, y):
+    return ((y + x) % P, (y - x) % P, 2 * R.D * x * y % P)
+
+
+def affine_niels(p):
+    zi = pow(p.Z, P - 2, P)
+    return niels(p.X * zi % P, p.Y * zi % P)
+
+
+def norm_pieces_sc(s):
+    """k_affine_pieces<SC> on a scaled record: zi = 2 / Z~, 2dxy = (T^ zi) 4d."""
+    zi = 2 * pow(s.Z, P - 2, P) % P
+    x, y = s.X * zi % P, s.Y * zi % P
+    return ((y + x) % P, (y - x) % P, s.T * zi % P * (4 * R.D % P) % P)
+
+
+def norm_pairs_sc(s0, s1):
+    """k_affine_pairs<SC> on two scaled records: the Niels slots of Q0, Q1, Q0 + Q1, Q0 - Q1."""
+    z01 = s0.Z * s1.Z % P
+    c = s0.T * s1.T % P * (16 * R.D % P) % P
+    f, g = (z01 - c) % P, (z01 + c) % P
+    zs = f * g % P
+    t = 2 * pow(z01 * zs % P, P - 2, P) % P   # the doubled inverse of this receiver's product
+    i01, izs = t * zs % P, t * z01 % P
+    iz0, iz1 = i01 * s1.Z % P, i01 * s0.Z % P
+    ig, i_f = f * izs % P, g * izs % P
+    out = [niels(s0.X * iz0 % P, s0.Y * iz0 % P), niels(s1.X * iz1 % P, s1.Y * iz1 % P)]
+    ym0, yp0, ym1, yp1 = (s0.Y - s0.X) % P, (s0.Y + s0.X) % P, (s1.Y - s1.X) % P, (s1.Y + s1.X) % P
+    for qa, qb, ix, iy in ((ym1, yp1, ig, i_f), (yp1, ym1, i_f, ig)):
+        a, b = ym0 * qa % P, yp0 * qb % P
+        out.append(niels((b - a) * ix % P, (b + a) * iy % P))
+    return out
 
 
 def same(a, b):
@@ -68,10 +132,22 @@ def torsion(rng):
 def run(seed=1, nrand=64):
     rng = random.Random(seed)
     g = R.from_uniform_bytes(bytes(range(64)))
-    stats = {"sum": 0, "Z=0": 0, "wrong": 0}
+    stats = {"sum": 0, "Z=0": 0, "wrong": 0, "scaled wrong": 0}
 
     def one(p, q):
         r = ded(p, q)
+        ps, qs = to_scaled(p), to_scaled(q)
+        rs = ded_sc(ps, qs)
+        r2 = ded(R.Pt(2 * p.X, 2 * p.Y, 2 * p.Z, 2 * p.T), R.Pt(2 * q.X, 2 * q.Y, 2 * q.Z, 2 * q.T))
+        ok = (rs.X % P, rs.Y % P, rs.Z % P, rs.T % P) == (r2.X * INV2 % P, r2.Y * INV2 % P, r2.Z % P, r2.T * INV4 % P)
+        ok = ok and same(from_scaled(ps), p) and ((rs.Z % P == 0) == (r.Z % P == 0))
+        if r.Z % P != 0:  # the records the normalisations read: the slots of the complete sum
+            ok = ok and same(from_scaled(rs), R.add(p, q)) and norm_pieces_sc(rs) == affine_niels(R.add(p, q))
+            if p.Z % P and q.Z % P:
+                neg_q = R.Pt(-q.X % P, q.Y, q.Z, -q.T % P)
+                ok = ok and norm_pairs_sc(ps, qs) == [affine_niels(p), affine_niels(q), affine_niels(R.add(p, q)),
+                                                      affine_niels(R.add(p, neg_q))]
+        stats["scaled wrong"] += 0 if ok else 1
         if r.Z % P == 0:
             stats["Z=0"] += 1
         elif same(r, R.add(p, q)):
@@ -96,4 +172,4 @@ def run(seed=1, nrand=64):
 if __name__ == "__main__":
     st, rx = run()
     print(st, "exceptional among random pairs:", rx)
-    sys.exit(1 if st["wrong"] or rx else 0)
+    sys.exit(1 if st["wrong"] or st["scaled wrong"] or rx else 0)

@@ -362,29 +362,38 @@ def ge_madd_signed(p, q, where="ge_madd_signed"):
     return (fe_mul(e, t, where), fe_mul(b, h, where), fe_mul(t, b, where), fe_mul(e, h, where))
 
 
-def affine_addend(p, where="affine_pieces"):
+def affine_addend(p, where="affine_pieces", scaled=False):
     """kernels.hip k_affine_pieces: zi = inv * prefix (products of Z), x = X zi, y = Y zi,
-    2dxy = (T zi) 2d; y+x and y-x left uncarried like the cached form."""
+    2dxy = (T zi) 2d; y+x and y-x left uncarried like the cached form.  scaled (SC): the run's inverse
+    doubled and carried once, 4d for 2d."""
     X, Y, Z, T = p
-    zi = fe_mul(fe_mul(Z, Z, where), Z, where)
+    inv = fe_mul(Z, Z, where)
+    if scaled:
+        inv = fe_carry(fe_add(inv, inv, where), where)
+    zi = fe_mul(inv, Z, where)
     x, y = fe_mul(X, zi, where), fe_mul(Y, zi, where)
-    return (fe_add(y, x, where), fe_sub(y, x, where), fe_mul(fe_mul(T, zi, where), D2, where))
+    return (fe_add(y, x, where), fe_sub(y, x, where), fe_mul(fe_mul(T, zi, where), D4 if scaled else D2, where))
 
 
-def affine_pair(p0, p1, where="affine_pairs"):
+def affine_pair(p0, p1, where="affine_pairs", scaled=False):
     """kernels.hip k_affine_pairs: the four affine addends of a pair -- Q_0, Q_1 as affine_addend, and
     the sum and difference from the complete addition's e, h, e', h' over the shared inverse of
-    Z_S = f g (1/g = f / Z_S, 1/f = g / Z_S): x_S = e / g, y_S = h / f, x_D = e' / f, y_D = h' / g."""
+    Z_S = f g (1/g = f / Z_S, 1/f = g / Z_S): x_S = e / g, y_S = h / f, x_D = e' / f, y_D = h' / g.
+    scaled (SC): pair_fg<true> -- 16d for 2d, d = z01 as it stands -- and the run's inverse doubled and
+    carried once."""
     X0, Y0, Z0, T0 = p0
     X1, Y1, Z1, T1 = p1
     z01 = fe_mul(Z0, Z1, where)
-    c = fe_mul(fe_mul(T0, T1, where), D2, where)
-    d = fe_carry(fe_add(z01, z01, where), where)    # fe_dbl + fe_carry
+    c = fe_mul(fe_mul(T0, T1, where), D16 if scaled else D2, where)
+    d = z01 if scaled else fe_carry(fe_add(z01, z01, where), where)    # fe_dbl + fe_carry
     f = fe_sub(d, c, where)
     g = fe_add(d, c, where)
     zs = fe_mul(f, g, where)
     # every inverse is a product of (products of) z01, zs, the parked prefix and fe_invert's output
-    izs = fe_mul(fe_mul(zs, z01, where), zs, where)
+    inv = fe_mul(zs, z01, where)
+    if scaled:
+        inv = fe_carry(fe_add(inv, inv, where), where)
+    izs = fe_mul(inv, zs, where)
     i01 = fe_mul(izs, zs, where)
     ig, i_f = fe_mul(f, izs, where), fe_mul(g, izs, where)
 
@@ -410,12 +419,28 @@ def ge_to_cached_ded(p):
             fe_add(T, T, "to_cached_ded 2T"))
 
 
+def ge_to_scaled(p, where="ge_to_scaled"):
+    """points.h ge_to_scaled: (2X, 2Y, 4Z, T), a carry after every doubling."""
+    X, Y, Z, T = p
+    z2 = fe_carry(fe_add(Z, Z, where), where)
+    return (fe_carry(fe_add(X, X, where), where), fe_carry(fe_add(Y, Y, where), where),
+            fe_carry(fe_add(z2, z2, where), where), T)
+
+
+def ge_to_cached_sc(p):
+    """points.h ge_to_cached_sc: Z~ and T^ published as they stand (tight, not doubled)."""
+    X, Y, Z, T = p
+    return (fe_add(Y, X, "to_cached_sc"), fe_sub(Y, X, "to_cached_sc"), Z, T)
+
+
 def tight_zero_ok(z, where):
     """fe25519.h fe_tight_zero: limbs within their widths except 1 and 5, which stay below
     2 * 2^25 - 1 (so 0 and p each have one representation)."""
     for i in range(10):
         lim = (2 * (MASK[i] + 1) - 1) if i in (1, 5) else MASK[i] + 1
         check(f"{where} fe_tight_zero operand limb {i}", z[i], lim)
+    # fe_maybe_zero: limb 9 stays in its 25 bits, so it is 0 or 2^25 - 1 in both representations of 0
+    check(f"{where} fe_maybe_zero limb 9", z[9], 1 << W[9])
 
 
 def ge_add_ded(p, q, where="ge_add_ded_lds"):
@@ -548,6 +573,8 @@ def ristretto_eq(p, q):
 # ---------------- the closed invariant ----------------
 D = fe_const_from_header("D")
 D2 = fe_const_from_header("D2")
+D4 = fe_const_from_header("D4")
+D16 = fe_const_from_header("D16")
 SQRT_M1 = fe_const_from_header("SQRT_M1")
 INVSQRT_A_MINUS_D = fe_const_from_header("INVSQRT_A_MINUS_D")
 ONE_MINUS_D_SQ = fe_const_from_header("ONE_MINUS_D_SQ")
@@ -570,6 +597,13 @@ def run():
         outs += [ge_madd(pt, comb8_entry(*aff), "comb8 madd"), ge_madd(pt, aff, "ge_msub", minus=True)]
         outs += [ge_madd_signed(pt, affine_addend(pt)), ge_add_ded(pt, ge_to_cached_ded(pt))]
         outs += [ge_madd_signed(pt, q, "ge_madd_signed(affine_pairs)") for q in affine_pair(pt, pt)]
+        # the stepping's scaled state: entered by ge_to_scaled, then closed under ge_add_sc_lds; its
+        # records feed the scaled normalisations, whose slots are addends like the proper ones'
+        sc = ge_to_scaled(pt)
+        outs += [sc, ge_add_ded(pt, ge_to_cached_sc(pt), "ge_add_sc_lds")]
+        outs += [ge_madd_signed(pt, affine_addend(pt, "affine_pieces<SC>", scaled=True), "ge_madd_signed(SC)")]
+        outs += [ge_madd_signed(pt, q, "ge_madd_signed(affine_pairs<SC>)")
+                 for q in affine_pair(pt, pt, "affine_pairs<SC>", scaled=True)]
         outs += [ristretto_decode(), ristretto_elligator()]
         ristretto_encode(pt)
         new = vmax(tight, *[x for o in outs for x in o])
