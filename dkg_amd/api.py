@@ -222,6 +222,14 @@ class Backend:
         (a dedicated addition of the per-step binomial met an exceptional pair), else 0."""
         return _lib.lib().dkg_ctx_binomial_reruns(self._ctx)
 
+    def binomial_wave_redos(self) -> int:
+        """Test aid: (piece, 64-column group) flag words of the per-wave binomial that the last
+        verification marked and rebuilt with the complete formula (0 when the complete formula ran)."""
+        r = _lib.lib().dkg_ctx_binomial_wave_redos(self._ctx)
+        if r < 0:
+            raise DkgError(_lib.DKG_E_DEVICE, "dkg_ctx_binomial_wave_redos failed")
+        return r
+
     def clock_probe(self, iters: int = 200_000) -> dict:
         """Shader clock under full VALU occupancy (dkg_ctx_clock_probe): {"sclk_mhz", "busy_ms"}."""
         mhz, ms = ctypes.c_double(), ctypes.c_double()

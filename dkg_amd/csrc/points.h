@@ -352,8 +352,9 @@ DKG_DEV void ge_add_lds(ge_p3& r, const ge_p3& p, const uint32_t* q, bool neg, i
 // prepared by ge_to_cached_ded as (Y+X, Y-X, 2Z, 2T) in LDS.  8M and no multiplication by d (the
 // cached form needs none either: the stepping saves one product per lane and step), but the formula
 // is not complete: F = 2(X1 Y2 - Y1 X2) vanishes when p - Q is 0 or the 2-torsion point, G = 2(Y1 Y2
-// - X1 X2) when p + Q meets the 4-torsion, and then the result has Z = F G = 0.  Whenever Z != 0 the
-// result is p + Q exactly (tools/ded_check.py checks both claims over every 8-torsion offset).
+// - X1 X2) when p - Q has order 4 (opposite points are not exceptional), and then the result has
+// Z = F G = 0.  Whenever Z != 0 the result is p + Q exactly (tools/ded_check.py checks both claims and
+// records the vanishing factor over every 8-torsion offset).
 // Callers test Z with fe_tight_zero and redo the work with the complete ge_add_lds.
 DKG_DEV void ge_to_cached_ded(ge_cached& c, const ge_p3& p) {
   fe_add(c.YpX, p.Y, p.X);

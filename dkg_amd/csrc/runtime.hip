@@ -81,6 +81,8 @@ struct dkg_ctx {
                                         // workgroups, 1 complete formula only
   uint32_t* last_step_flags = nullptr;  // the last verify_device's stepping flags (dedicated mode)
   size_t last_step_flag_words = 0;
+  uint32_t* last_bflags = nullptr;      // the last verify_device's per-wave binomial redo flags (v.bflags)
+  size_t last_bflag_words = 0;
   // the per-step binomial's dedicated additions: only inside the drivers that check its group flags
   // after their sync and rerun the verification with the complete formula when one is set
   // (receivers_rounds, shard_rows: binom_step_ded = true around the call)
@@ -834,6 +836,8 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
     bflags = buf<uint32_t>(ctx, "v.bflags", 4 * (W / 64));
     HCK(hipMemsetAsync(bflags, 0, 4 * (W / 64), home));
   }
+  ctx->last_bflags = bflags;
+  ctx->last_bflag_words = bflags ? W / 64 : 0;
   // the rerun guard's word (with_binom_ded): zeroed when the verification began (verify_rounds)
   uint32_t* bany = step_ded && DKG_BINOM_STEP_DED == 1 && ctx->step_formula == 0 ? ctx->binom_any : nullptr;
   // dead-position repack of an unsplit table (kernels.hip stepping_tail_phases): two scratch states
@@ -1149,6 +1153,8 @@ void verify_rounds(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dealer_bas
   // dkg_ctx_stepping_redos reports THIS verification's stepping (none if it builds no tables)
   ctx->last_step_flags = nullptr;
   ctx->last_step_flag_words = 0;
+  ctx->last_bflags = nullptr;
+  ctx->last_bflag_words = 0;
   ctx->binom_any = nullptr;
   ctx->binom_any_host = nullptr;
   if (ctx->binom_step_ded && DKG_BINOM_STEP_DED == 1) {  // both rounds' binomials mark one word
@@ -3019,6 +3025,20 @@ long long dkg_ctx_stepping_redos(dkg_ctx* ctx) {
   }
 }
 int dkg_ctx_binomial_reruns(dkg_ctx* ctx) { return ctx ? ctx->last_binom_rerun : -1; }
+long long dkg_ctx_binomial_wave_redos(dkg_ctx* ctx) {
+  if (!ctx) return -1;
+  if (!ctx->last_bflags) return 0;
+  try {
+    std::vector<uint32_t> h(ctx->last_bflag_words);
+    sync(ctx);
+    HCK(hipMemcpy(h.data(), ctx->last_bflags, 4 * h.size(), hipMemcpyDeviceToHost));
+    long long c = 0;
+    for (uint32_t x : h) c += x != 0;
+    return c;
+  } catch (const Fail& f) {
+    return -1;
+  }
+}
 int dkg_ctx_set_addends(dkg_ctx* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 1) return DKG_E_ARG;
   ctx->addend_mode = mode;
@@ -3315,6 +3335,8 @@ int dkg_verify_receiver(dkg_ctx* ctx, size_t n, size_t t, int round, size_t j, c
     if ((round != 2 && round != 4) || j >= n) return DKG_E_ARG;
     ctx->last_step_flags = nullptr;  // Horner per receiver: no stepping tables
     ctx->last_step_flag_words = 0;
+    ctx->last_bflags = nullptr;
+    ctx->last_bflag_words = 0;
     if (round == 2) {
       int rc = need_env(ctx);
       if (rc) return rc;

@@ -153,6 +153,11 @@ int dkg_stepping_lane_map(int lanes, int seg_len, int nseg, int last_len, int la
  * formula because a dedicated addition of the per-step binomial met Z = 0 (an exceptional pair, e.g.
  * a crafted all-identity commitment row), else 0 (-1 on a NULL ctx). */
 int dkg_ctx_binomial_reruns(dkg_ctx *ctx);
+/* Test aid: the (piece, 64-column group) flag words that the last verification's per-wave binomial
+ * (k_binom_wave) marked -- a dedicated addition of a real column met Z = 0 there -- and rebuilt with the
+ * complete formula (synchronises the context's stream; 0 when the complete formula or the per-step
+ * binomial ran; -1 on error).  Read after the call: the timed paths do nothing for it. */
+long long dkg_ctx_binomial_wave_redos(dkg_ctx *ctx);
 /* The short multipliers (b_j, a_j1, .., a_j(U-1)) of receivers j = 1..n for a `pieces`-way split of
  * piece length L (2 <= pieces <= 5): magnitudes mag[n][pieces][32] (little-endian), signs
  * sign[n][pieces] (+1 / -1); a_ju = b_j j^(uL) mod l and b_j > 0.  DKG_E_ARG on bad input. */

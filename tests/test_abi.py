@@ -29,6 +29,15 @@ def test_header_symbols_exported():
     assert set(names) == set(_lib.EXPORTED)
 
 
+def test_redo_counters_reject_a_null_context():
+    """The redo counters of the dedicated additions (test aids) report -1 without a context."""
+    L = _lib.lib()
+    assert "dkg_ctx_binomial_wave_redos" in declared_functions()
+    assert L.dkg_ctx_stepping_redos(None) == -1
+    assert L.dkg_ctx_binomial_wave_redos(None) == -1
+    assert L.dkg_ctx_binomial_reruns(None) == -1
+
+
 def test_env_check_matches_reference_assert():
     # committee.rs:73: assert!(threshold < (nr_members + 1) / 2)
     for t, n in [(0, 1), (0, 2), (1, 3), (4, 10), (5, 11), (511, 1024), (2047, 4096)]:

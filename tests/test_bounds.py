@@ -72,6 +72,14 @@ def test_dedicated_addition_is_exact_or_flags():
     stats, random_flags = ded_check.run(seed=2, nrand=32)
     assert stats["wrong"] == 0 and random_flags == 0
     assert stats["Z=0"] > 0  # the exceptional cases exist and are caught
+    # which factor of Z3 = F G vanishes, per relation and order of the torsion offset T: F for q = p + T
+    # with T the identity or the point of order 2, G for T of order 4, nothing for T of order 8, and
+    # nothing at all for opposite (q = -p + T), doubled or random points
+    want = {("q = p + T", 1): {"F"}, ("q = p + T", 2): {"F"}, ("q = p + T", 4): {"G"}, ("q = p + T", 8): {""}}
+    for rel in ("q = -p + T", "q = 2p + T"):
+        want.update({(rel, o): {""} for o in (1, 2, 4, 8)})
+    want[("q random", 0)] = {""}
+    assert stats["factors"] == want
 
 
 def test_tight_zero_representations():

@@ -13,6 +13,10 @@
     exactly where Z3 = 0; ge_to_scaled's (2X, 2Y, 4Z, T) is a scaled state of the same point; and the
     normalisations' folded constants (k_affine_pieces<SC>, k_affine_pairs<SC>) give the affine Niels
     slots of the proper records.
+  * which factor of Z3 = F G vanishes is recorded per relation and order of the torsion offset
+    (stats["factors"]): F exactly when q - p is the identity or the point of order 2, G exactly when
+    q - p has order 4, neither for an offset of order 8 -- and neither for q = -p + T, q = 2p + T or a
+    random q whatever T is: opposite points are not exceptional.
 Usage: python tools/ded_check.py   (exit status 1 on a wrong sum); tests/test_bounds.py runs it.
 """
 import os
@@ -25,12 +29,17 @@ import r255 as R  # noqa: E402
 P = R.P
 
 
+def ded_fg(p, q):
+    """F = B - A and G = B + A of ge_add_ded_lds (Z3 = F G)."""
+    A = (p.Y - p.X) * ((q.Y + q.X) % P) % P
+    B = (p.Y + p.X) * ((q.Y - q.X) % P) % P
+    return (B - A) % P, (B + A) % P
+
+
 def ded(p, q):
     """ge_add_ded_lds on (X, Y, Z, T) and the cached (Y+X, Y-X, 2Z, 2T) of q."""
-    ypx, ymx, z2, t2 = (q.Y + q.X) % P, (q.Y - q.X) % P, 2 * q.Z % P, 2 * q.T % P
-    A = (p.Y - p.X) * ypx % P
-    B = (p.Y + p.X) * ymx % P
-    F, G = (B - A) % P, (B + A) % P
+    z2, t2 = 2 * q.Z % P, 2 * q.T % P
+    F, G = ded_fg(p, q)
     C, Dd = p.Z * t2 % P, p.T * z2 % P
     E, H = (Dd + C) % P, (Dd - C) % P
     return R.Pt(E * F, G * H, G * F, E * H)
@@ -129,10 +138,21 @@ def torsion(rng):
     return [R.Pt(x, y, 1, x * y) for x, y in out]
 
 
+def order(t):
+    """The order (1, 2, 4 or 8) of a point of E[8]."""
+    k, r = 1, t
+    while not same(r, R.IDENTITY):
+        r, k = R.add(r, r), 2 * k
+    return k
+
+
+RELATIONS = ("q = p + T", "q = -p + T", "q = 2p + T", "q random")
+
+
 def run(seed=1, nrand=64):
     rng = random.Random(seed)
     g = R.from_uniform_bytes(bytes(range(64)))
-    stats = {"sum": 0, "Z=0": 0, "wrong": 0, "scaled wrong": 0}
+    stats = {"sum": 0, "Z=0": 0, "wrong": 0, "scaled wrong": 0, "factors": {}}
 
     def one(p, q):
         r = ded(p, q)
@@ -163,7 +183,14 @@ def run(seed=1, nrand=64):
             for rel in range(4):
                 a = rng.randrange(1, R.L)
                 b = (a, R.L - a, 2 * a % R.L, rng.randrange(1, R.L))[rel]
-                one(scaled(R.add(R.mul(g, a), t1), rng.randrange(1, P)), R.add(R.mul(g, b), t2))
+                p, q = scaled(R.add(R.mul(g, a), t1), rng.randrange(1, P)), R.add(R.mul(g, b), t2)
+                one(p, q)
+                # T = q - (b/a) p: the offset t2 - t1 for q = p + T, t2 + t1 for q = -p + T, t2 - 2 t1 ..
+                neg1 = R.Pt(-t1.X % P, t1.Y, t1.Z, -t1.T % P)
+                off = (R.add(t2, neg1), R.add(t2, t1), R.add(t2, R.add(neg1, neg1)), R.IDENTITY)[rel]
+                F, G = ded_fg(p, q)
+                stats["factors"].setdefault((RELATIONS[rel], order(off) if rel < 3 else 0), set()).add(
+                    ("F" if F == 0 else "") + ("G" if G == 0 else ""))
     one(R.IDENTITY, R.IDENTITY)
     one(g, R.IDENTITY)
     return stats, rand_exc
@@ -171,5 +198,8 @@ def run(seed=1, nrand=64):
 
 if __name__ == "__main__":
     st, rx = run()
+    fac = st.pop("factors")
     print(st, "exceptional among random pairs:", rx)
+    for (rel, o), v in sorted(fac.items()):
+        print(f"  {rel:11s} offset of order {o}: vanishing factor {sorted(v)}")
     sys.exit(1 if st["wrong"] or st["scaled wrong"] or rx else 0)
