@@ -144,6 +144,15 @@ def lib():
     L.dkg_ceremony_shard_device.argtypes = [p, sz, sz, sz, sz, p, p, p, p, p, p, ctypes.POINTER(ctypes.c_double)]
     L.dkg_ceremony_shard_verify_device.argtypes = [p, sz, sz, sz, sz, p, p, p, p, p, p, p, p,
                                                     ctypes.POINTER(ctypes.c_double)]
+    L.dkg_ceremony_shard_full_device.argtypes = [p, sz, sz, sz, sz, p, p, p, u8p, u8p, p, p, p, p, p, p,
+                                                  ctypes.POINTER(ctypes.c_double)]
+    L.dkg_ceremony_shard_verify_full_device.argtypes = [p, sz, sz, sz, sz, p, p, p, p, u8p, p, p, p, p,
+                                                         ctypes.POINTER(ctypes.c_double)]
+    L.dkg_ctx_set_key_comb.argtypes = [p, ctypes.c_int]
+    L.dkg_ctx_last_key_comb.argtypes = [p]
+    L.dkg_key_comb_choice.argtypes = [sz, sz, ctypes.c_int, ctypes.c_int]
+    L.dkg_key_comb_constants.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.dkg_key_comb_constants.restype = None
     L.dkg_ceremony_batch_device.argtypes = [p, sz, sz, sz, p, p, ctypes.POINTER(BatchOut)]
     L.dkg_ceremony_batch_verify.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(BatchOut)]
     L.dkg_dealer_coeffs_device.argtypes = [p, u8p, ctypes.c_uint32, sz, sz, sz, sz, p, p]
@@ -213,6 +222,10 @@ def lib():
     L.dkg_multi_ceremony_run_device.argtypes = [p, sz, sz, ctypes.POINTER(p), ctypes.POINTER(p),
                                                 ctypes.POINTER(CeremonyOut)]
     L.dkg_multi_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
+    L.dkg_multi_ceremony_run_full.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
+    L.dkg_multi_ceremony_run_full_device.argtypes = [p, sz, sz, ctypes.POINTER(p), ctypes.POINTER(p), ctypes.POINTER(p),
+                                                     u8p, u8p, ctypes.POINTER(CeremonyOut)]
+    L.dkg_multi_ceremony_verify_full.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     _lib = L
     return L
 
@@ -241,4 +254,7 @@ EXPORTED = [
     "dkg_complaints_prove", "dkg_complaints_verify", "dkg_ctx_set_complaint_eval", "dkg_ceremony_verify_full_complaints",
     "dkg_complaints3_verify", "dkg_ceremony_verify_fetched_proven", "dkg_ceremony_verify_full_proven",
     "dkg_ceremony_batch_verify_proven", "dkg_ceremony_batch_verify_full_proven",
+    "dkg_ceremony_shard_full_device", "dkg_ceremony_shard_verify_full_device", "dkg_ctx_set_key_comb",
+    "dkg_ctx_last_key_comb", "dkg_key_comb_choice", "dkg_key_comb_constants", "dkg_multi_ceremony_run_full",
+    "dkg_multi_ceremony_run_full_device", "dkg_multi_ceremony_verify_full",
 ]

@@ -603,6 +603,38 @@ class Backend:
             vp(d_partial), ctypes.byref(ms)))
         return ms.value
 
+    def ceremony_shard_full_device(self, n, t, d0, d1, d_a, d_b, d_r, sk: bytes, pk: bytes, d_dec2, d_dec4, d_A0,
+                                   d_partial, d_e1: Optional[int] = None, d_ct: Optional[int] = None) -> float:
+        """ceremony_shard_device in full (encrypted-share) mode: this rank's dealers' shares encrypted to
+        the n member keys (d_r: device [D][n][2][32] randomness; sk, pk host [n][32]), decrypted by all n
+        receivers, and checked.  d_e1 / d_ct (device [D][n][2][32], optional) receive the ciphertexts."""
+        ms = ctypes.c_double()
+        vp = ctypes.c_void_p
+        _check(self._ctx, _lib.lib().dkg_ceremony_shard_full_device(
+            self._ctx, n, t, d0, d1, vp(d_a), vp(d_b), vp(d_r), sk, pk, vp(d_e1), vp(d_ct), vp(d_dec2), vp(d_dec4),
+            vp(d_A0), vp(d_partial), ctypes.byref(ms)))
+        return ms.value
+
+    def ceremony_shard_verify_full_device(self, n, t, d0, d1, d_E, d_A, d_e1, d_ct, sk: bytes, d_dec2, d_dec4, d_A0,
+                                          d_partial) -> float:
+        """ceremony_shard_verify_device on received ciphertexts d_e1, d_ct (device [D][n][2][32])."""
+        ms = ctypes.c_double()
+        vp = ctypes.c_void_p
+        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_full_device(
+            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_e1), vp(d_ct), sk, vp(d_dec2), vp(d_dec4), vp(d_A0),
+            vp(d_partial), ctypes.byref(ms)))
+        return ms.value
+
+    def set_key_comb(self, mode: int):
+        """Comb of the recipient keys behind full mode's K = pk_q r: 0 (default) radix 2^10 tables, the
+        sharded full calls choosing by key_comb_choice; 1 radix 2^10 everywhere; 2 radix 16 everywhere.
+        Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_key_comb(self._ctx, mode))
+
+    def last_key_comb(self) -> int:
+        """The kind (1 or 2) the last single-ceremony encryption used."""
+        return _lib.lib().dkg_ctx_last_key_comb(self._ctx)
+
     def ceremony_shard_recon_device(self, n, t, d0, d1, qualified, reconstruct, d_s: Optional[int], d_terms: int,
                                     r2_error=None, r4_error=None) -> bool:
         """After the exchange: replace the terms of this rank's reconstructed dealers by g * a_i0
@@ -783,6 +815,26 @@ class MultiBackend:
         self._check(_lib.lib().dkg_multi_ceremony_verify(self._m, n, t, E, A, s, s_prime, ctypes.byref(o)))
         return self._result(n, t, o, bufs)
 
+    # ---- full (encrypted-share) mode: each shard encrypts, decrypts and checks its dealers' rows
+    def ceremony_full(self, a: bytes, b: bytes, r: bytes, sk: bytes, pk: bytes, n: int, t: int) -> CeremonyResult:
+        """r: host [n][n][2][32] encryption randomness (enc_randomness); sk, pk: member_keys."""
+        o, bufs = self._out(n, t)
+        self._check(_lib.lib().dkg_multi_ceremony_run_full(self._m, n, t, a, b, r, sk, pk, ctypes.byref(o)))
+        return self._result(n, t, o, bufs)
+
+    def ceremony_full_device(self, d_as, d_bs, d_rs, sk: bytes, pk: bytes, n: int, t: int) -> CeremonyResult:
+        """d_as[i], d_bs[i], d_rs[i]: device pointers on devices[i] to shard i's coefficients and randomness."""
+        k = len(self.devices)
+        pa, pb, pr = ((ctypes.c_void_p * k)(*x) for x in (d_as, d_bs, d_rs))
+        o, bufs = self._out(n, t)
+        self._check(_lib.lib().dkg_multi_ceremony_run_full_device(self._m, n, t, pa, pb, pr, sk, pk, ctypes.byref(o)))
+        return self._result(n, t, o, bufs)
+
+    def ceremony_verify_full(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, n: int, t: int) -> CeremonyResult:
+        o, bufs = self._out(n, t)
+        self._check(_lib.lib().dkg_multi_ceremony_verify_full(self._m, n, t, E, A, e1, ct, sk, ctypes.byref(o)))
+        return self._result(n, t, o, bufs)
+
 
 @dataclass
 class ShardOutcome:
@@ -815,6 +867,20 @@ def device_pci_bus_id(device: int) -> str:
 def shard_rows(n: int, world_size: int) -> int:
     """Padded per-rank block height R of the all-gathers (dkg_shard_rows)."""
     return _lib.lib().dkg_shard_rows(n, world_size)
+
+
+def key_comb_choice(keys: int, items_per_key: int, cached10: bool = False, cached16: bool = False) -> int:
+    """The cost rule of the sharded full calls (dkg_key_comb_choice): 1 = radix 2^10 tables, 2 = radix-16
+    combs, whichever builds (unless cached) and multiplies `items_per_key` items per key faster."""
+    return _lib.lib().dkg_key_comb_choice(keys, items_per_key, int(bool(cached10)), int(bool(cached16)))
+
+
+def key_comb_constants() -> dict:
+    """The rule's constants (dkg_key_comb_constants)."""
+    c = (ctypes.c_double * 6)()
+    _lib.lib().dkg_key_comb_constants(c)
+    return dict(zip(("build10_floor_us", "build10_us_per_key", "mul10_ns_per_item", "build16_floor_us",
+                     "build16_us_per_key", "mul16_ns_per_item"), c))
 
 
 def packed_row_words(n: int) -> int:

@@ -13,6 +13,9 @@
 //   decrypt: K = sk_{c,q} * e1, the width-4 window chain of k_dec_mul_w4 (hybrid.hip) with batched
 //            addressing on a flat grid: one wave per (c, q, w, group of 64 dealers).
 // decode / encode, sym_xor and dealer_ok are item-indexed already and serve a chunk as D = Bc*n rows.
+// The radix-16 combs also serve ONE ceremony's dealer shard (runtime.hip encrypt_device, kind 2): one key
+// set of n keys, D != n dealers per key (k_benc_mul's `rows`), where 2 D items per key do not repay a
+// radix-2^10 table either.
 #include "kernels.h"
 #include "points.h"
 #include "hybrid_dev.h"
@@ -75,8 +78,10 @@ void benc_tab(size_t keys, const uint32_t* pk_ext, size_t stride, uint32_t* tab,
 
 size_t benc_tab_words() { return BENC_TAB_WORDS; }
 
-// K = pk_key * r for the items of `keys` keys (ceremonies of n parties stacked key-wise).  Every wave
-// serves one key: S = ceil(2n / 64) waves per key, lane j of them the item (dealer j / 2, w = j % 2).
+// K = pk_key * r for the items of `keys` keys (key sets of n recipients stacked key-wise, `rows` dealers
+// per key set: rows = n for a batch's ceremonies, rows = D for one ceremony's dealer shard).  Every wave
+// serves one key: S = ceil(2 rows / 64) waves per key, lane j of them the item (dealer j / 2, w = j % 2);
+// key c*n + q serves items ((c*rows + i)*n + q)*2 + w, i < rows.  Only the index computation reads rows.
 // r [items][8] canonical scalars (< 2^253: the top radix-16 digit then absorbs the recoding's carry);
 // K_ext SoA [40][count].
 #ifndef DKG_BENC_WAVES
@@ -87,15 +92,16 @@ size_t benc_tab_words() { return BENC_TAB_WORDS; }
 #endif
 __global__ __launch_bounds__(256, DKG_BENC_WAVES) void k_benc_mul(size_t keys, size_t n, const uint32_t* __restrict__ r,
                                                                   const uint32_t* __restrict__ tab,
-                                                                  uint32_t* __restrict__ K_ext, size_t count) {
-  const size_t S = (2 * n + 63) / 64;
+                                                                  uint32_t* __restrict__ K_ext, size_t count,
+                                                                  size_t rows) {
+  const size_t S = (2 * rows + 63) / 64;
   const size_t wave = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const size_t key = wave / S;
   if (key >= keys) return;
   const size_t j = (wave % S) * 64 + (threadIdx.x & 63);
-  if (j >= 2 * n) return;
+  if (j >= 2 * rows) return;
   const size_t c = key / n, q = key % n, i = j >> 1, w = j & 1;
-  const size_t idx = ((c * n + i) * n + q) * 2 + w;
+  const size_t idx = ((c * rows + i) * n + q) * 2 + w;
   const uint32_t* kt = tab + key * BENC_TAB_WORDS;
   sc x;
   sc_load(x, r + 8 * idx);
@@ -131,12 +137,12 @@ __global__ __launch_bounds__(256, DKG_BENC_WAVES) void k_benc_mul(size_t keys, s
   pt_store(K_ext, count, idx, acc);
 }
 
-void benc_mul(size_t keys, size_t n, const uint32_t* r, const uint32_t* tab, uint32_t* K_ext, size_t count,
-              hipStream_t stream) {
-  if (!keys || !n) return;
-  const size_t waves = keys * ((2 * n + 63) / 64);
+void benc_mul(size_t keys, size_t n, size_t rows, const uint32_t* r, const uint32_t* tab, uint32_t* K_ext,
+              size_t count, hipStream_t stream) {
+  if (!keys || !n || !rows) return;
+  const size_t waves = keys * ((2 * rows + 63) / 64);
   hipLaunchKernelGGL(k_benc_mul, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, keys, n, r, tab, K_ext,
-                     count);
+                     count, rows);
 }
 
 // Width-4 signed window recoding of a canonical scalar (wNAF: digits 0, +-1, +-3, +-5, +-7), as

@@ -299,9 +299,11 @@ void enc_randomness(size_t rows, size_t n, size_t N, const uint32_t* seeds, uint
 // decoded keys pk_ext[.., key], key < keys
 size_t benc_tab_words();
 void benc_tab(size_t keys, const uint32_t* pk_ext, size_t stride, uint32_t* tab, hipStream_t stream);
-// K = pk_key * r for every item of the keys' ceremonies (r [items][8] canonical), K_ext SoA [40][count]
-void benc_mul(size_t keys, size_t n, const uint32_t* r, const uint32_t* tab, uint32_t* K_ext, size_t count,
-              hipStream_t stream);
+// K = pk_key * r for every item of the keys' ceremonies (r [items][8] canonical), K_ext SoA [40][count];
+// rows dealers per key set of n keys (a batch: n; one ceremony's dealer shard: D), item (c, i, q, w) at
+// ((c*rows + i)*n + q)*2 + w
+void benc_mul(size_t keys, size_t n, size_t rows, const uint32_t* r, const uint32_t* tab, uint32_t* K_ext,
+              size_t count, hipStream_t stream);
 // K = sk_key * R for every item (sk [keys][8], wave-uniform; R decoded SoA [40][count]); table:
 // bdec_mul_table_words(keys, n) words for the width-4 window's odd multiples
 size_t bdec_mul_table_words(size_t keys, size_t n);

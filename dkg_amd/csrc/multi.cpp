@@ -82,6 +82,7 @@ struct dkg_multi {
   // per shard (on its device): coefficient / broadcast inputs, decision rows, master-key terms,
   // partial final shares
   std::vector<DevBuf> in_a, in_b, in_s, in_sp, dec2, dec4, A0, part;
+  std::vector<DevBuf> in_r, in_e1, in_ct;  // full mode: encryption randomness, received ciphertexts
   // device 0: gathered blocks, compacted matrices, final / public shares
   DevBuf g_dec2, g_dec4, g_A0, g_part, c_dec2, c_dec4, fs, pub;
 
@@ -294,7 +295,9 @@ int dkg_multi_create(const int* devices, int ndev, dkg_multi** out) {
   dkg_multi* m = new dkg_multi();
   m->dev.assign(devices, devices + ndev);
   m->ctx.assign(ndev, nullptr);
-  for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part}) v->resize(ndev);
+  for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part, &m->in_r, &m->in_e1,
+                  &m->in_ct})
+    v->resize(ndev);
   int rc = guarded_multi(m, [&] {
     for (int i = 0; i < ndev; i++) {
       int r = dkg_ctx_create(m->dev[i], &m->ctx[i]);
@@ -330,7 +333,8 @@ int dkg_multi_create(const int* devices, int ndev, dkg_multi** out) {
 
 void dkg_multi_destroy(dkg_multi* m) {
   if (!m) return;
-  for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part})
+  for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part, &m->in_r, &m->in_e1,
+                  &m->in_ct})
     for (auto& b : *v) b.release();
   for (auto* b : {&m->g_dec2, &m->g_dec4, &m->g_A0, &m->g_part, &m->c_dec2, &m->c_dec4, &m->fs, &m->pub}) b->release();
   if (m->gather) {
@@ -442,6 +446,98 @@ int dkg_multi_ceremony_verify(dkg_multi* m, size_t n, size_t t, const uint8_t* E
       return dkg_ceremony_shard_verify_device(m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_s[i].p,
                                               m->in_sp[i].p, m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p,
                                               &sh[i]);
+    });
+    if (rc != DKG_OK) return rc;
+    record_shards(m, sh);
+    return finish(m, n, t, out, t0);
+  });
+}
+
+int dkg_multi_ceremony_run_full_device(dkg_multi* m, size_t n, size_t t, const void* const* d_a, const void* const* d_b,
+                                       const void* const* d_r, const uint8_t* sk, const uint8_t* pk,
+                                       dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    int rc = check_args(m, n, t, out);
+    if (rc != DKG_OK) return rc;
+    if (!d_a || !d_b || !d_r || !sk || !pk) {
+      m->err = "bad arguments: d_a, d_b, d_r, sk and pk must be non-NULL";
+      return DKG_E_ARG;
+    }
+    const double t0 = now_ms();
+    std::vector<double> sh(m->ws(), 0);
+    rc = for_shards(m, [&](int i) {
+      size_t a, b;
+      range(m, n, i, &a, &b);
+      shard_outputs(m, n, i, b - a);
+      return dkg_ceremony_shard_full_device(m->ctx[i], n, t, a, b, d_a[i], d_b[i], d_r[i], sk, pk, nullptr, nullptr,
+                                            m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, &sh[i]);
+    });
+    if (rc != DKG_OK) return rc;
+    record_shards(m, sh);
+    return finish(m, n, t, out, t0);
+  });
+}
+
+int dkg_multi_ceremony_run_full(dkg_multi* m, size_t n, size_t t, const uint8_t* a, const uint8_t* b,
+                                const uint8_t* r, const uint8_t* sk, const uint8_t* pk, dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    int rc = check_args(m, n, t, out);
+    if (rc != DKG_OK) return rc;
+    if (!a || !b || !r || !sk || !pk) {
+      m->err = "bad arguments: a, b, r, sk and pk must be non-NULL";
+      return DKG_E_ARG;
+    }
+    const size_t N = t + 1;
+    std::vector<const void*> pa(m->ws()), pb(m->ws()), pr(m->ws());
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      const size_t bytes = 32 * N * (d1 - d0), rbytes = 64 * n * (d1 - d0);
+      pa[i] = m->in_a[i].get(m->dev[i], bytes);
+      pb[i] = m->in_b[i].get(m->dev[i], bytes);
+      pr[i] = m->in_r[i].get(m->dev[i], rbytes);
+      MCK(hipMemcpy((void*)pa[i], a + 32 * N * d0, bytes, hipMemcpyHostToDevice));
+      MCK(hipMemcpy((void*)pb[i], b + 32 * N * d0, bytes, hipMemcpyHostToDevice));
+      MCK(hipMemcpy((void*)pr[i], r + 64 * n * d0, rbytes, hipMemcpyHostToDevice));
+      return DKG_OK;
+    });
+    if (rc != DKG_OK) return rc;
+    return dkg_multi_ceremony_run_full_device(m, n, t, pa.data(), pb.data(), pr.data(), sk, pk, out);
+  });
+}
+
+int dkg_multi_ceremony_verify_full(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                   const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    int rc = check_args(m, n, t, out);
+    if (rc != DKG_OK) return rc;
+    if (!E || !A || !e1 || !ct || !sk) {
+      m->err = "bad arguments: E, A, e1, ct and sk must be non-NULL";
+      return DKG_E_ARG;
+    }
+    const size_t N = t + 1;
+    double t0 = 0;
+    std::vector<double> sh(m->ws(), 0);
+    // uploads first (every shard), then the timed region
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      const size_t D = d1 - d0;
+      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_e1[i].get(m->dev[i], 64 * n * D), e1 + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_ct[i].get(m->dev[i], 64 * n * D), ct + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
+      shard_outputs(m, n, i, D);
+      return DKG_OK;
+    });
+    if (rc != DKG_OK) return rc;
+    t0 = now_ms();
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      return dkg_ceremony_shard_verify_full_device(m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_e1[i].p,
+                                                   m->in_ct[i].p, sk, m->dec2[i].p, m->dec4[i].p, m->A0[i].p,
+                                                   m->part[i].p, &sh[i]);
     });
     if (rc != DKG_OK) return rc;
     record_shards(m, sh);

@@ -51,6 +51,10 @@ struct dkg_ctx {
   bool overlap = true;                  // rounds 2 and 4 as one fused pipeline (verify_rounds)
   int split = 0;                        // degree split U of the difference tables (0: cost model)
   std::vector<uint8_t> key_tabs_pk;     // member keys whose decoded points and combs sit in hy.* (encrypt)
+  std::vector<uint8_t> key_tabs16_pk;   // ... and whose radix-16 combs sit in hy16.* (a cache of its own)
+  int key_comb = 0;                     // K = pk_q r: 0 radix 2^DKG_KEY_COMB_BITS, except that the sharded
+                                        // full calls choose by dkg_key_comb_choice; 1 / 2 force a kind
+  int last_key_comb = 0;                // the kind the last encrypt_device used (0: none yet)
   uint8_t fb_base[32] = {0};            // dkg_fixed_base_batch: the caller base whose comb sits in fb_tabw
   bool fb_valid = false;
   int binom_mode = 0;                   // binomial: 0 per-wave Horner loops (k_binom_wave) for
@@ -1827,21 +1831,36 @@ void batch_times(dkg_ctx* ctx, dkg_batch_out* out, bool round1) {
 // pk_host (optional): the same keys on the host.  Member keys outlive a ceremony (procedure_keys.rs),
 // so their decoded points and comb tables are kept in the arena and rebuilt only when the keys
 // differ from the last build's (compared byte for byte).
-void encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* pkc, const uint32_t* s, const uint32_t* sp,
-                    const uint32_t* r, uint32_t* e1, uint32_t* ct, hipStream_t st = nullptr,
-                    const uint8_t* pk_host = nullptr) {
+// K = pk_q * r comes from one of two combs of the recipient keys, each with its own arena buffers and its
+// own cache key (a kind's cache never passes for the other's): kind 1, radix 2^DKG_KEY_COMB_BITS
+// (hy.*, k_enc_mul: both products in one kernel), or kind 2, the batches' signed radix-16 combs
+// (hy16.*: k_benc_tab, then e1 = g r by fixed_base and K by k_benc_mul with D rows per key).
+// ctx->key_comb forces a kind; at 0 the kind is 1 unless the caller lets the cost rule choose
+// (choose: the sharded full calls, where a key serves 2 D items and a cold 2^10 build outweighs them).
+// Returns the keys' decode mask [n] of the kind used (device).
+const uint8_t* encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* pkc, const uint32_t* s,
+                              const uint32_t* sp, const uint32_t* r, uint32_t* e1, uint32_t* ct,
+                              hipStream_t st = nullptr, const uint8_t* pk_host = nullptr, bool choose = false) {
   const size_t items = 2 * D * n;
   if (!st) st = ctx->stream;
-  uint32_t* pk_ext = buf<uint32_t>(ctx, "hy.pk_ext", PTB * n);
-  uint8_t* pk_ok = buf<uint8_t>(ctx, "hy.pk_ok", n);
-  uint32_t* tabs = buf<uint32_t>(ctx, "hy.tabs", 4 * dkgk::key_comb_words() * n);
-  const bool cached = pk_host && ctx->key_tabs_pk.size() == 32 * n &&
-                      memcmp(ctx->key_tabs_pk.data(), pk_host, 32 * n) == 0;
-  if (!cached) {
-    ctx->key_tabs_pk.clear();  // invalid until this build is queued
+  auto same = [&](const std::vector<uint8_t>& k) {
+    return pk_host && k.size() == 32 * n && memcmp(k.data(), pk_host, 32 * n) == 0;
+  };
+  const bool cached10 = same(ctx->key_tabs_pk), cached16 = same(ctx->key_tabs16_pk);
+  const int kind = ctx->key_comb ? ctx->key_comb : choose ? dkg_key_comb_choice(n, 2 * D, cached10, cached16) : 1;
+  ctx->last_key_comb = kind;
+  std::vector<uint8_t>& held = kind == 1 ? ctx->key_tabs_pk : ctx->key_tabs16_pk;
+  uint32_t* pk_ext = buf<uint32_t>(ctx, kind == 1 ? "hy.pk_ext" : "hy16.pk_ext", PTB * n);
+  uint8_t* pk_ok = buf<uint8_t>(ctx, kind == 1 ? "hy.pk_ok" : "hy16.pk_ok", n);
+  uint32_t* tabs = kind == 1 ? buf<uint32_t>(ctx, "hy.tabs", 4 * dkgk::key_comb_words() * n)
+                             : buf<uint32_t>(ctx, "hy16.tabs", 4 * dkgk::benc_tab_words() * n);
+  if (!(kind == 1 ? cached10 : cached16)) {
+    held.clear();  // invalid until this build is queued
     dkgk::decode_points(pkc, n, pk_ext, n, pk_ok, st);
-    dkgk::build_key_combs(pk_ext, n, 0, tabs, st, n);  // one comb per recipient key: r * pk_q is fixed-base
-    if (pk_host) ctx->key_tabs_pk.assign(pk_host, pk_host + 32 * n);
+    // one comb per recipient key: r * pk_q is fixed-base
+    if (kind == 1) dkgk::build_key_combs(pk_ext, n, 0, tabs, st, n);
+    else dkgk::benc_tab(n, pk_ext, n, tabs, st);
+    if (pk_host) held.assign(pk_host, pk_host + 32 * n);
   }
   uint32_t* R = buf<uint32_t>(ctx, "hy.R", PTB * items);
   uint32_t* K = buf<uint32_t>(ctx, "hy.K", PTB * items);
@@ -1849,7 +1868,12 @@ void encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* pkc, const
   // phase events (serialised runs, nsub == 1): the bench's per-kernel roofline of full mode
   const bool tm = ctx->nsub == 1;
   if (tm) HCK(hipEventRecord(ctx->hev[0], st));
-  dkgk::enc_mul(D, n, r, ctx->tab_gw, tabs, R, K, st);
+  if (kind == 1) {
+    dkgk::enc_mul(D, n, r, ctx->tab_gw, tabs, R, K, st);
+  } else {
+    dkgk::fixed_base(items, r, ctx->tab_gw, R, st);         // e1 = G::generator() * r  (elgamal.rs:141)
+    dkgk::benc_mul(n, n, D, r, tabs, K, items, st);         // key = pk * r  (elgamal.rs:138-140)
+  }
   if (tm) HCK(hipEventRecord(ctx->hev[1], st));
   dkgk::encode_points(R, items, items, e1, st);
   dkgk::encode_points(K, items, items, Kc, st);
@@ -1858,6 +1882,7 @@ void encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* pkc, const
   if (tm) HCK(hipEventRecord(ctx->hev[3], st));
   if (tm) ctx->hy_timed |= 1;
   check_launch(ctx);
+  return pk_ok;
 }
 
 // Receivers' side: item_ok[item] = e1 decodes; dealer_ok_out[i] = all of dealer i's items decode (a
@@ -1980,7 +2005,7 @@ void encrypt_batch_device(dkg_ctx* ctx, size_t B, size_t n, const uint32_t* pkc,
     bf_mark(ctx, st, BF_ENC_TAB);
     dkgk::fixed_base(items, r + 8 * i0, ctx->tab_gw, R, st);  // e1 = G::generator() * r  (elgamal.rs:141)
     bf_mark(ctx, st, BF_ENC_E1);
-    dkgk::benc_mul(keys, n, r + 8 * i0, tab, K, items, st);   // key = pk * r  (elgamal.rs:138-140)
+    dkgk::benc_mul(keys, n, n, r + 8 * i0, tab, K, items, st);   // key = pk * r  (elgamal.rs:138-140)
     bf_mark(ctx, st, BF_ENC_MUL);
     dkgk::encode_points(R, items, items, e1 + 8 * i0, st);
     dkgk::encode_points(K, items, items, Kc, st);
@@ -3440,9 +3465,12 @@ int dkg_ceremony_verify_fetched(dkg_ctx* ctx, size_t n, size_t t, const uint8_t*
 
 // Rounds 2-5 of one rank of a dealer-sharded ceremony on its dealers [d0, d0+D): E/A compressed
 // [D][N][32], s/sp canonical [D][n][32] on the device -> decision rows, master-key terms, partial
-// final shares (layouts of dkg_ceremony_shard_device).
+// final shares (layouts of dkg_ceremony_shard_device).  e_ok (may be null; [D] on the device): 0 = the
+// dealer's round-1 data is missing, as receivers_rounds takes RoundMasks::e_ok -- full mode's decode mask
+// of the dealer's ciphertexts: a MISSING row in round 2.
 void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uint32_t* Ec, const uint32_t* Ac,
-                const uint32_t* ds, const uint32_t* dsp, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial) {
+                const uint32_t* ds, const uint32_t* dsp, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
+                const uint8_t* e_ok = nullptr) {
   const size_t N = t + 1;
   if (!D) {
     HCK(hipMemsetAsync(d_partial, 0, 32 * n, ctx->stream));
@@ -3472,7 +3500,7 @@ void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uin
         dkgk::row_reject(D, n, (const uint8_t*)d_dec2, rej, ctx->stream);
         dkgk::mask_not_and(D, rej, nullptr, qm, ctx->stream);
       },
-      nullptr, nullptr, false);
+      e_ok, nullptr, false);
   if (side_terms) HCK(hipStreamWaitEvent(ctx->stream, ctx->terms_done, 0));
   wait_shares(ctx, ctx->stream);  // shares evaluated on the side stream (round1_device)
   ctx->shares_pending = false;
@@ -3543,6 +3571,107 @@ int dkg_ceremony_shard_verify_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0
       sync(ctx);
     });
     collect_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
+    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
+    return DKG_OK;
+  });
+}
+
+// Full mode of the two calls above (dkg_ceremony_run_full_device / dkg_ceremony_verify_full on rows
+// [d0, d1)).  Items, decode masks, MISSING rows and decrypted shares are per dealer, so the hybrid stage
+// is shard-local: D dealers' items to all n keys.  With chunk streams it runs on the side stream beside
+// the check pipeline's binomial, stepping and recombination, which read no share; the checks wait for
+// the decrypted shares (shares_pending / wait_shares), and the ciphertexts' decode mask joins the dealer
+// mask there.  Serialised runs (nsub == 1) record the full.* phases.
+int dkg_ceremony_shard_full_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_a,
+                                   const void* d_b, const void* d_r, const uint8_t* sk, const uint8_t* pk, void* d_e1,
+                                   void* d_ct, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
+                                   double* ms_total) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk || !pk) return DKG_E_ARG;
+    const size_t D = d1 - d0, N = t + 1, items = 2 * D * n;
+    if (D && (!d_a || !d_b || !d_r)) return DKG_E_ARG;
+    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
+    uint32_t* dpk = buf<uint32_t>(ctx, "fm_pk", 32 * n);
+    h2d(ctx, dpk, pk, 32 * n);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    uint32_t* Ec = buf<uint32_t>(ctx, "sh_E", 32 * D * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "sh_A", 32 * D * N);
+    uint32_t* ds = buf<uint32_t>(ctx, "sh_s", 32 * D * n);     // the dealers' plaintext shares
+    uint32_t* dsp = buf<uint32_t>(ctx, "sh_sp", 32 * D * n);
+    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);    // what the receivers decrypt
+    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
+    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
+    hipStream_t hy = side ? ctx->side : ctx->stream;
+    SharesScope pending(ctx);  // on an exception the home stream still waits for the side stream's work
+    if (D) {
+      round1_device(ctx, D, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false, side);
+      uint32_t* e1 = d_e1 ? (uint32_t*)d_e1 : buf<uint32_t>(ctx, "shf_e1", 32 * items);
+      uint32_t* ct = d_ct ? (uint32_t*)d_ct : buf<uint32_t>(ctx, "shf_ct", 32 * items);
+      encrypt_device(ctx, D, n, dpk, ds, dsp, (const uint32_t*)d_r, e1, ct, hy, pk, true);  // committee.rs:169-172
+      decrypt_device(ctx, D, n, dsk, e1, ct, rs, rsp, iok, eok, hy);                        // committee.rs:282-286
+      if (side) {
+        HCK(hipEventRecord(ctx->shares_done, ctx->side));
+        ctx->shares_pending = true;
+      }
+    }
+    ExtScope ext(ctx, D, N);
+    with_binom_ded(ctx, [&] {
+      shard_rows(ctx, n, t, d0, D, Ec, Ac, rs, rsp, d_dec2, d_dec4, d_A0, d_partial, eok);
+      check_launch(ctx);
+      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+      binom_mark_copy(ctx);
+      sync(ctx);
+    });
+    collect_phases(ctx);
+    collect_hybrid_phases(ctx);
+    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
+    return DKG_OK;
+  });
+}
+
+int dkg_ceremony_shard_verify_full_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_E,
+                                          const void* d_A, const void* d_e1, const void* d_ct, const uint8_t* sk,
+                                          void* d_dec2, void* d_dec4, void* d_A0, void* d_partial, double* ms_total) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk) return DKG_E_ARG;
+    const size_t D = d1 - d0, items = 2 * D * n;
+    if (D && (!d_E || !d_A || !d_e1 || !d_ct)) return DKG_E_ARG;
+    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
+    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
+    SharesScope pending(ctx);
+    if (D) {
+      if (side) {
+        HCK(hipEventRecord(ctx->side_fork, ctx->stream));
+        HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+      }
+      decrypt_device(ctx, D, n, dsk, (const uint32_t*)d_e1, (const uint32_t*)d_ct, rs, rsp, iok, eok,
+                     side ? ctx->side : ctx->stream);
+      if (side) {
+        HCK(hipEventRecord(ctx->shares_done, ctx->side));
+        ctx->shares_pending = true;
+      }
+    }
+    with_binom_ded(ctx, [&] {
+      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, rs, rsp, d_dec2, d_dec4, d_A0,
+                 d_partial, eok);
+      check_launch(ctx);
+      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+      binom_mark_copy(ctx);
+      sync(ctx);
+    });
+    collect_phases(ctx);
+    collect_hybrid_phases(ctx);  // decryption phases only
     if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
     return DKG_OK;
   });
@@ -3854,6 +3983,46 @@ size_t dkg_packed_row_words(size_t n) { return (n + 31) / 32 + 1; }
 int dkg_fixed_base_windows(void) { return dkgk::fixed_base_windows(); }
 int dkg_key_comb_windows(void) { return dkgk::key_comb_windows(); }
 
+int dkg_ctx_set_key_comb(dkg_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  ctx->key_comb = mode;
+  return DKG_OK;
+}
+int dkg_ctx_last_key_comb(const dkg_ctx* ctx) { return ctx ? ctx->last_key_comb : 0; }
+
+// Which comb of the recipient keys serves K = pk_q r for `keys` keys with items_per_key items each (a
+// shard of D dealers: 2 D): the smaller of build (unless that kind's tables are cached) + multiplication.
+// The constants are the "fit" of profiles/shard_full_time.json (tools/shard_full_time.py on one MI355X):
+//   build = floor + per key, a two-point fit through the cold - cached difference of the whole call's
+//           device time at n = 64 (all dealers) and n = 1024 (the 8-way shard, where the side stream
+//           hides least of it): radix 2^10 957 us + 71.8 us per key (k_build_combw<10>; 74.8 us per
+//           key in profiles/r06_rocprof_full_summary.txt), radix 16 558 us + 0.79 us per key
+//           (k_benc_tab: one wave's chain of 224 doublings and 64 additions is the floor; 0.07 us per
+//           key at the batches' 640,000 keys, profiles/batch_full_time.json).  Both builds have a
+//           floor, so both kinds carry one -- with a floor on radix 16 alone, ten cold keys would take
+//           the radix-2^10 tables, which at n = 64 measure 7.9 ms against 3.0 ms;
+//   mul   = the serialised full.enc_mul phase per item (e1 = g r and K = pk r together, so the two
+//           kinds' figures differ by the K products alone): 1.63 ns (k_enc_mul) and 2.81 ns
+//           (k_fixed_base + k_benc_mul) at n = 1024, 2,097,152 items.
+// With them a cold key set takes radix 16 at every ceremony size (its build is cheaper in floor and
+// per key; the dearer products would outweigh that only past ~60,000 items per key), and a cached
+// radix-2^10 set is kept.
+constexpr double KC10_FLOOR_US = 957.0, KC10_BUILD_US = 71.8, KC10_MUL_NS = 1.63;
+constexpr double KC16_FLOOR_US = 558.0, KC16_BUILD_US = 0.79, KC16_MUL_NS = 2.81;
+
+void dkg_key_comb_constants(double c[6]) {
+  if (!c) return;
+  c[0] = KC10_FLOOR_US, c[1] = KC10_BUILD_US, c[2] = KC10_MUL_NS;
+  c[3] = KC16_FLOOR_US, c[4] = KC16_BUILD_US, c[5] = KC16_MUL_NS;
+}
+
+int dkg_key_comb_choice(size_t keys, size_t items_per_key, int cached10, int cached16) {
+  const double k = (double)keys, work = k * (double)items_per_key;
+  const double c10 = (cached10 ? 0.0 : (KC10_FLOOR_US + KC10_BUILD_US * k) * 1e3) + KC10_MUL_NS * work;  // ns
+  const double c16 = (cached16 ? 0.0 : (KC16_FLOOR_US + KC16_BUILD_US * k) * 1e3) + KC16_MUL_NS * work;
+  return c16 < c10 ? 2 : 1;
+}
+
 int dkg_decisions_pack_device(dkg_ctx* ctx, size_t rows, size_t nvalid, size_t n, size_t d0, const void* d_dec,
                               void* d_packed) {
   return guarded(ctx, [&] {
@@ -4096,8 +4265,8 @@ int dkg_encrypt_shares(dkg_ctx* ctx, size_t D, size_t n, const uint8_t* pk, cons
     uint32_t* de1 = buf<uint32_t>(ctx, "hx_e1", 32 * items);
     uint32_t* dct = buf<uint32_t>(ctx, "hx_ct", 32 * items);
     // the host keys: a repeated key set reuses its decoded points and combs (1.7 MB per key)
-    encrypt_device(ctx, D, n, dpk, ds, dsp, dr, de1, dct, nullptr, pk);
-    d2h(ctx, ok.data(), buf<uint8_t>(ctx, "hy.pk_ok", n), n);
+    const uint8_t* pk_ok = encrypt_device(ctx, D, n, dpk, ds, dsp, dr, de1, dct, nullptr, pk);
+    d2h(ctx, ok.data(), pk_ok, n);
     d2h(ctx, e1, de1, 32 * items);
     d2h(ctx, ct, dct, 32 * items);
     sync(ctx);

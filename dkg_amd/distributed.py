@@ -189,6 +189,27 @@ class ShardedCeremony:
                                                   self.A0.data_ptr(), self.part.data_ptr())
         return self._finish(ms, finalise, d_s)
 
+    def run_full(self, d_a: int, d_b: int, d_r: int, sk: bytes, pk: bytes, finalise: bool = True,
+                 d_e1: Optional[int] = None, d_ct: Optional[int] = None) -> ShardResult:
+        """run in full (encrypted-share) mode: this rank's dealers' shares are hybrid-encrypted to the n
+        sorted member keys (d_r: device [D][n][2][32] randomness; sk, pk: [n][32] bytes), decrypted by
+        all n receivers and checked (dkg_ceremony_shard_full_device).  d_e1 / d_ct optionally receive
+        the rank's round-1 ciphertexts.  The reconstruction reads the remembered decrypted shares."""
+        self._fence()
+        ms = self.be.ceremony_shard_full_device(self.n, self.t, self.d0, self.d1, d_a, d_b, d_r, sk, pk,
+                                                self.dec2.data_ptr(), self.dec4.data_ptr(), self.A0.data_ptr(),
+                                                self.part.data_ptr(), d_e1, d_ct)
+        return self._finish(ms, finalise, None)
+
+    def run_verify_full(self, d_E: int, d_A: int, d_e1: int, d_ct: int, sk: bytes,
+                        finalise: bool = True) -> ShardResult:
+        """run_verify on received ciphertexts: d_e1, d_ct device [D][n][2][32] of this rank's dealers."""
+        self._fence()
+        ms = self.be.ceremony_shard_verify_full_device(self.n, self.t, self.d0, self.d1, d_E, d_A, d_e1, d_ct, sk,
+                                                       self.dec2.data_ptr(), self.dec4.data_ptr(),
+                                                       self.A0.data_ptr(), self.part.data_ptr())
+        return self._finish(ms, finalise, None)
+
     def _finish(self, ms: float, finalise: bool, d_s: Optional[int] = None) -> ShardResult:
         n, t, ws = self.n, self.t, self.ws
         steps = {}

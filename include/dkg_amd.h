@@ -314,6 +314,44 @@ int dkg_ceremony_shard_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_
 int dkg_ceremony_shard_verify_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1, const void *d_E,
                                      const void *d_A, const void *d_s, const void *d_s_prime, void *d_dec2,
                                      void *d_dec4, void *d_A0, void *d_partial, double *ms_total);
+/* Full (encrypted-share) mode of the sharded variant: what dkg_ceremony_run_full_device does, on this
+ * rank's dealers [d0, d1) -- round 1 for the D = d1 - d0 dealers, their shares hybrid-encrypted to all
+ * n sorted member keys (committee.rs:164-172; elgamal.rs:134-193), all n receivers' decryption of those
+ * rows (committee.rs:282-286), and the round-2/4 checks on the DECRYPTED shares.  d_a, d_b as
+ * dkg_ceremony_shard_device; d_r device [D][n][2][32] canonical encryption randomness (what
+ * dkg_enc_randomness_device(.., d0, D, ..) writes); sk, pk host [n][32] (dkg_member_keys); d_e1, d_ct
+ * device [D][n][2][32] (either may be NULL) receive this rank's round-1 ciphertext broadcast.  Outputs
+ * as dkg_ceremony_shard_device; the decrypted shares become the rows dkg_ceremony_shard_recon_device
+ * reads with d_s = NULL.  Which comb serves K = pk_q r: dkg_ctx_set_key_comb. */
+int dkg_ceremony_shard_full_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1, const void *d_a,
+                                   const void *d_b, const void *d_r, const uint8_t *sk, const uint8_t *pk, void *d_e1,
+                                   void *d_ct, void *d_dec2, void *d_dec4, void *d_A0, void *d_partial,
+                                   double *ms_total);
+/* Full mode of dkg_ceremony_shard_verify_device (what dkg_ceremony_verify_full does, on rows [d0, d1)):
+ * d_e1, d_ct device [D][n][2][32] the rank's dealers' (possibly tampered) ciphertexts, sk host [n][32].
+ * A dealer with any item whose e1 does not decode is missing data: a DKG_MISSING row in round 2, like
+ * an undecodable E row.  The decrypted shares become the ctx's remembered shard rows. */
+int dkg_ceremony_shard_verify_full_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1, const void *d_E,
+                                          const void *d_A, const void *d_e1, const void *d_ct, const uint8_t *sk,
+                                          void *d_dec2, void *d_dec4, void *d_A0, void *d_partial, double *ms_total);
+/* Which comb of the recipient keys serves full mode's K = pk_q r (elgamal.rs:138-140) wherever the
+ * single-ceremony encryption runs (dkg_encrypt_shares, dkg_ceremony_run_full_device, the sharded full
+ * calls): 1 = radix 2^DKG_KEY_COMB_BITS tables (1.7 MB per key at 2^10, one mixed addition per window),
+ * 2 = signed radix-16 combs (80 KiB per key, 64 complete additions; the batches' tables).  0 (default):
+ * dkg_encrypt_shares and dkg_ceremony_run_full_device use kind 1, as they always have, and the sharded
+ * full calls choose by dkg_key_comb_choice.  Both kinds are cached by the keys' bytes, separately.
+ * Outputs do not depend on it.  DKG_E_ARG for any other mode. */
+int dkg_ctx_set_key_comb(dkg_ctx *ctx, int mode);
+/* The kind (1 or 2) of the last single-ceremony encryption on this ctx; 0 before the first. */
+int dkg_ctx_last_key_comb(const dkg_ctx *ctx);
+/* The cost rule behind mode 0 of the sharded full calls (a host function, no ctx): the kind with the
+ * smaller (cached ? 0 : build(keys)) + mul_per_item * keys * items_per_key; items_per_key = 2 D for a
+ * shard of D dealers.  A tie keeps kind 1. */
+int dkg_key_comb_choice(size_t keys, size_t items_per_key, int cached10, int cached16);
+/* The rule's constants, build(keys) = floor + per key * keys: c[0] the radix-2^BITS build's floor, us;
+ * c[1] that build, us per key; c[2] its multiplication, ns per item; c[3], c[4], c[5] the same for
+ * radix 16.  Measured: profiles/shard_full_time.json. */
+void dkg_key_comb_constants(double c[6]);
 /* Finalise step of a sharded run, after the exchange (committee.rs:747-789): for this rank's dealers
  * [d0, d1) with reconstruct[i] (host [n], the combined round-4 outcome), d_terms[i - d0] (device
  * [d1-d0][32], the rank's exchanged master-key terms, in/out) is replaced by g * a_i0 recovered by
@@ -439,6 +477,19 @@ int dkg_multi_ceremony_run_device(dkg_multi *m, size_t n, size_t t, const void *
 /* dkg_ceremony_verify over the shards (received broadcasts, host arrays as there) */
 int dkg_multi_ceremony_verify(dkg_multi *m, size_t n, size_t t, const uint8_t *E, const uint8_t *A, const uint8_t *s,
                               const uint8_t *s_prime, dkg_ceremony_out *out);
+/* Full (encrypted-share) mode over the shards (dkg_ceremony_shard_full_device per shard): a, b host
+ * [n][t+1][32], r host [n][n][2][32] (dkg_enc_randomness), sk, pk host [n][32].  out as
+ * dkg_multi_ceremony_run (E, A, s, s_prime NULL); the uploads precede the timed region. */
+int dkg_multi_ceremony_run_full(dkg_multi *m, size_t n, size_t t, const uint8_t *a, const uint8_t *b,
+                                const uint8_t *r, const uint8_t *sk, const uint8_t *pk, dkg_ceremony_out *out);
+/* d_a[i], d_b[i] [D_i][t+1][32], d_r[i] [D_i][n][2][32]: device pointers on devices[i] */
+int dkg_multi_ceremony_run_full_device(dkg_multi *m, size_t n, size_t t, const void *const *d_a,
+                                       const void *const *d_b, const void *const *d_r, const uint8_t *sk,
+                                       const uint8_t *pk, dkg_ceremony_out *out);
+/* dkg_ceremony_verify_full over the shards (dkg_ceremony_shard_verify_full_device per shard): host
+ * arrays as there. */
+int dkg_multi_ceremony_verify_full(dkg_multi *m, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                   const uint8_t *e1, const uint8_t *ct, const uint8_t *sk, dkg_ceremony_out *out);
 
 /* ---- per-party finalise: Phases<Phase5>::finalise (committee.rs:726-805) as EVERY party p runs it ----
  * Inputs are the ceremony's common outcome (host arrays [n]): qualified, reconstruct (round 4,
