@@ -1,14 +1,15 @@
 """dkg_amd — MI355X-native (gfx950 HIP) backend for the share-generation / share-verification hot
 path of the danielSanchezQ/dkg Pedersen-VSS DKG over Ristretto255.  See DESIGN.md."""
-from ._lib import (ACCEPT, COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3, MISSING, REJECT, SELF, SKIPPED, DkgError,  # noqa: F401
-                   lib)
+from ._lib import (ACCEPT, COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3, COMPLAINT_NOT_OWNED, MISSING, REJECT, SELF,  # noqa: F401
+                   SKIPPED, DkgError, lib)
 from .api import (Backend, BatchProvenResult, BatchResult, MultiBackend, CeremonyResult, ProvenResult, Environment, ceremony_batch_device,  # noqa: F401
                   ceremony_batch_full_device, ceremony_batch_verify, ceremony_batch_verify_full, ceremony_batch_verify_full_proven,
-                  ceremony_batch_verify_proven, dealer_coefficients, enc_randomness, env_check, key_comb_choice, packed_row_words,
-                  shard_range, shard_rows, split_multipliers)
+                  ceremony_batch_verify_proven, dealer_coefficients, enc_randomness, env_check, key_comb_choice, merge_verdicts,
+                  packed_row_words, shard_range, shard_rows, split_multipliers)
 
 __all__ = ["Backend", "MultiBackend", "Environment", "CeremonyResult", "BatchResult", "DkgError", "dealer_coefficients", "env_check",
            "ceremony_batch_device", "ceremony_batch_verify", "ceremony_batch_full_device", "ceremony_batch_verify_full", "enc_randomness", "split_multipliers", "lib",
            "shard_range", "shard_rows", "packed_row_words", "key_comb_choice",
            "ceremony_batch_verify_proven", "ceremony_batch_verify_full_proven", "BatchProvenResult",
-           "ACCEPT", "REJECT", "SELF", "SKIPPED", "MISSING", "ProvenResult", "COMPLAINT_IGNORED", "COMPLAINT_NO_PHASE3"]
+           "ACCEPT", "REJECT", "SELF", "SKIPPED", "MISSING", "ProvenResult", "COMPLAINT_IGNORED", "COMPLAINT_NO_PHASE3",
+           "COMPLAINT_NOT_OWNED", "merge_verdicts"]

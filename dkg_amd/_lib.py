@@ -20,6 +20,9 @@ REJECT, ACCEPT, SELF, SKIPPED, MISSING = 0, 1, 2, 3, 4
 FIN_OK, FIN_R2_ERROR, FIN_R4_ERROR, FIN_PHASE4_ERROR, FIN_INSUFFICIENT, FIN_PANIC = 0, 1, 2, 3, 4, 5
 # complaint verdicts beyond the primitives' 0..3 and -1 (dkg_complaints_verify, dkg_complaints3_verify)
 COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3 = 4, 5
+# a sharded proven call's verdict for a complaint against another rank's dealer: below every real code, so
+# that the element-wise maximum over the ranks' arrays is the ceremony's verdict list
+COMPLAINT_NOT_OWNED = -2
 
 _lib = None
 
@@ -188,6 +191,18 @@ def lib():
     L.dkg_ceremony_batch_verify_full_proven.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, p, u8p,
                                                         u8p, sz, p, p, p, u8p, u8p, ctypes.POINTER(BatchOut), p, p, p, p,
                                                         p, p, p]
+    L.dkg_ceremony_shard_verify_proven_device.argtypes = [p, sz, sz, sz, sz, p, p, p, p, u8p, u8p, sz, p, p, u8p, u8p,
+                                                           p, p, p, p, sz, p, p, ctypes.POINTER(ctypes.c_double)]
+    L.dkg_ceremony_shard_verify_full_proven_device.argtypes = [p, sz, sz, sz, sz, p, p, p, p, u8p, u8p, u8p, u8p, sz, p,
+                                                                p, u8p, sz, p, p, u8p, u8p, p, p, p, p, sz, p, p, p, p,
+                                                                ctypes.POINTER(ctypes.c_double)]
+    L.dkg_ctx_last_complaint_eval.argtypes = [p]
+    L.dkg_shard_combine_proven_device.argtypes = [p, sz, sz, sz, p, p, p, p, ctypes.c_int, p, p,
+                                                  ctypes.POINTER(ShardOutcome), p, p, p]
+    L.dkg_multi_ceremony_verify_proven.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p, u8p,
+                                                   ctypes.POINTER(CeremonyOut), p, p, p]
+    L.dkg_multi_ceremony_verify_full_proven.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, u8p, u8p, sz,
+                                                        p, p, u8p, u8p, ctypes.POINTER(CeremonyOut), p, p, p, p, p]
     L.dkg_dealer_coeffs.argtypes = [u8p, ctypes.c_uint32, sz, sz, sz, p, p]
     L.dkg_scalar_sum_device.argtypes = [p, sz, sz, p, p, p]
     L.dkg_point_sum_device.argtypes = [p, sz, p, p, p]
@@ -257,4 +272,7 @@ EXPORTED = [
     "dkg_ceremony_shard_full_device", "dkg_ceremony_shard_verify_full_device", "dkg_ctx_set_key_comb",
     "dkg_ctx_last_key_comb", "dkg_key_comb_choice", "dkg_key_comb_constants", "dkg_multi_ceremony_run_full",
     "dkg_multi_ceremony_run_full_device", "dkg_multi_ceremony_verify_full",
+    "dkg_ceremony_shard_verify_proven_device", "dkg_ceremony_shard_verify_full_proven_device",
+    "dkg_ctx_last_complaint_eval", "dkg_shard_combine_proven_device",
+    "dkg_multi_ceremony_verify_proven", "dkg_multi_ceremony_verify_full_proven",
 ]

@@ -625,6 +625,70 @@ class Backend:
             vp(d_partial), ctypes.byref(ms)))
         return ms.value
 
+    # ---- the sharded calls that decide by the proven complaints (each rank verifies those against its own dealers)
+    def ceremony_shard_verify_proven_device(self, n, t, d0, d1, d_E, d_A, d_s, d_sp, accusers4: Sequence[int],
+                                            accused4: Sequence[int], share4: bytes, randomness4: bytes, d_dec2, d_dec4,
+                                            d_A0, d_partial, flag_rows: int, d_flags, fetched1: Optional[bytes] = None,
+                                            fetched3: Optional[bytes] = None):
+        """ceremony_shard_verify_device whose round 4 follows the proven complaints.  The WHOLE broadcast
+        round-4 complaint list goes in (1-based indices); returns (ms, verdict4) with COMPLAINT_NOT_OWNED
+        for the complaints against other ranks' dealers.  d_flags: device [flag_rows] u32 flag words
+        (flag_rows = shard_rows(n, world_size)); fetched1 / fetched3: the rank's rows' intake masks."""
+        C4 = len(accusers4)
+        res4 = _carray(ctypes.c_int32, C4)
+        ms = ctypes.c_double()
+        vp = ctypes.c_void_p
+        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_proven_device(
+            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_s), vp(d_sp), _opt(fetched1), _opt(fetched3), C4,
+            _carray(ctypes.c_uint32, C4, accusers4), _carray(ctypes.c_uint32, C4, accused4), share4, randomness4,
+            vp(d_dec2), vp(d_dec4), vp(d_A0), vp(d_partial), flag_rows, vp(d_flags), res4, ctypes.byref(ms)))
+        return ms.value, list(res4)[:C4]
+
+    def ceremony_shard_verify_full_proven_device(self, n, t, d0, d1, d_E, d_A, d_e1, d_ct, sk: bytes, pk: bytes,
+                                                 accusers: Sequence[int], accused: Sequence[int], proofs: bytes,
+                                                 accusers4: Sequence[int], accused4: Sequence[int], share4: bytes,
+                                                 randomness4: bytes, d_dec2, d_dec4, d_A0, d_partial, flag_rows: int,
+                                                 d_flags, d_dissent=None, fetched1: Optional[bytes] = None,
+                                                 fetched3: Optional[bytes] = None):
+        """ceremony_shard_verify_full_device with both rounds decided by the proven complaints: returns
+        (ms, verdict, verdict4).  d_dissent: device [n] i32, the rank's dissent partial (optional)."""
+        C, C4 = len(accusers), len(accusers4)
+        res, res4 = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4)
+        ms = ctypes.c_double()
+        vp = ctypes.c_void_p
+        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_full_proven_device(
+            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_e1), vp(d_ct), sk, pk, _opt(fetched1), _opt(fetched3), C,
+            _carray(ctypes.c_uint32, C, accusers), _carray(ctypes.c_uint32, C, accused), proofs, C4,
+            _carray(ctypes.c_uint32, C4, accusers4), _carray(ctypes.c_uint32, C4, accused4), share4, randomness4,
+            vp(d_dec2), vp(d_dec4), vp(d_A0), vp(d_partial), flag_rows, vp(d_flags), vp(d_dissent), res, res4,
+            ctypes.byref(ms)))
+        return ms.value, list(res)[:C], list(res4)[:C4]
+
+    def last_complaint_eval(self) -> int:
+        """Where the last sharded proven call took P_i(j) from: 3 its own pass, 1 Horner, 2 tables, 12 both."""
+        return _lib.lib().dkg_ctx_last_complaint_eval(self._ctx)
+
+    def shard_combine_proven_device(self, n: int, t: int, world_size: int, d_pack2_g: int, d_pack4_g: int,
+                                    d_flags_g: int, d_dissent_g: Optional[int] = None, full: bool = True,
+                                    d_dec2: Optional[int] = None, d_dec4: Optional[int] = None):
+        """Combine step of the sharded proven calls (dkg_shard_combine_proven_device) from the gathered
+        packed rows, flag words [ws][R] and dissent partials [ws][n]: (ShardOutcome, dissent or None,
+        finalise_status, recovery_index)."""
+        q, r2e, rc, r4e = (ctypes.create_string_buffer(max(n, 1)) for _ in range(4))
+        c = _carray(ctypes.c_int32, n)
+        o = _lib.ShardOutcome(ctypes.cast(q, ctypes.c_void_p), ctypes.cast(c, ctypes.c_void_p),
+                              ctypes.cast(r2e, ctypes.c_void_p), ctypes.cast(rc, ctypes.c_void_p),
+                              ctypes.cast(r4e, ctypes.c_void_p), 0, 0)
+        dis = _carray(ctypes.c_int32, n) if d_dissent_g is not None else None
+        st, ri = ctypes.c_int32(), ctypes.c_int32()
+        vp = ctypes.c_void_p
+        _check(self._ctx, _lib.lib().dkg_shard_combine_proven_device(
+            self._ctx, n, t, world_size, vp(d_pack2_g), vp(d_pack4_g), vp(d_flags_g), vp(d_dissent_g),
+            int(bool(full)), vp(d_dec2), vp(d_dec4), ctypes.byref(o), dis, ctypes.byref(st), ctypes.byref(ri)))
+        out = ShardOutcome(list(q.raw[:n]), list(c)[:n], list(r2e.raw[:n]), list(rc.raw[:n]), list(r4e.raw[:n]),
+                           o.n_qualified, bool(o.phase4_error))
+        return out, (None if dis is None else list(dis)[:n]), st.value, ri.value
+
     def set_key_comb(self, mode: int):
         """Comb of the recipient keys behind full mode's K = pk_q r: 0 (default) radix 2^10 tables, the
         sharded full calls choosing by key_comb_choice; 1 radix 2^10 everywhere; 2 radix 16 everywhere.
@@ -835,6 +899,39 @@ class MultiBackend:
         self._check(_lib.lib().dkg_multi_ceremony_verify_full(self._m, n, t, E, A, e1, ct, sk, ctypes.byref(o)))
         return self._result(n, t, o, bufs)
 
+    # ---- the proven-complaint rule: each shard verifies the complaints against its own dealers
+    def ceremony_verify_proven(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, fetched1: Optional[bytes],
+                               fetched3: Optional[bytes], accusers4: Sequence[int], accused4: Sequence[int],
+                               share4: bytes, randomness4: bytes, n: int, t: int) -> ProvenResult:
+        """Backend.ceremony_verify_fetched_proven over the shards (fetched1 / fetched3 None = all present)."""
+        C4 = len(accusers4)
+        res4 = _carray(ctypes.c_int32, C4)
+        st, ri = ctypes.c_int32(), ctypes.c_int32()
+        o, bufs = self._out(n, t)
+        self._check(_lib.lib().dkg_multi_ceremony_verify_proven(
+            self._m, n, t, E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, ctypes.byref(o), res4, ctypes.byref(st),
+            ctypes.byref(ri)))
+        return ProvenResult(self._result(n, t, o, bufs), list(res4)[:C4], st.value, ri.value)
+
+    def ceremony_verify_full_proven(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, pk: bytes,
+                                    accusers: Sequence[int], accused: Sequence[int], proofs: bytes,
+                                    accusers4: Sequence[int], accused4: Sequence[int], share4: bytes,
+                                    randomness4: bytes, n: int, t: int,
+                                    fetched3: Optional[bytes] = None) -> ProvenResult:
+        """Backend.ceremony_verify_full_proven over the shards."""
+        C, C4 = len(accusers), len(accusers4)
+        res, res4, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4), _carray(ctypes.c_int32, n)
+        st, ri = ctypes.c_int32(), ctypes.c_int32()
+        o, bufs = self._out(n, t)
+        self._check(_lib.lib().dkg_multi_ceremony_verify_full_proven(
+            self._m, n, t, E, A, e1, ct, sk, pk, C, _carray(ctypes.c_uint32, C, accusers),
+            _carray(ctypes.c_uint32, C, accused), proofs, _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, ctypes.byref(o), res, dis, res4,
+            ctypes.byref(st), ctypes.byref(ri)))
+        return ProvenResult(self._result(n, t, o, bufs), list(res4)[:C4], st.value, ri.value, list(res)[:C],
+                            list(dis)[:n])
+
 
 @dataclass
 class ShardOutcome:
@@ -867,6 +964,26 @@ def device_pci_bus_id(device: int) -> str:
 def shard_rows(n: int, world_size: int) -> int:
     """Padded per-rank block height R of the all-gathers (dkg_shard_rows)."""
     return _lib.lib().dkg_shard_rows(n, world_size)
+
+
+def owning_rank(n: int, world_size: int, dealer: int) -> int:
+    """The rank whose shard_range holds the 0-based `dealer`."""
+    r = min(world_size - 1, dealer * world_size // n)
+    while shard_range(n, world_size, r)[1] <= dealer:
+        r += 1
+    while shard_range(n, world_size, r)[0] > dealer:
+        r -= 1
+    return r
+
+
+def merge_verdicts(per_rank: Sequence[Sequence[int]]) -> List[int]:
+    """The ceremony's verdict list from the ranks' arrays of a sharded proven call: the element-wise
+    maximum (COMPLAINT_NOT_OWNED is below every real code, and exactly one rank owns each complaint).
+    Raises if some complaint is owned by nobody."""
+    out = [max(col) for col in zip(*per_rank)] if per_rank else []
+    if any(v == _lib.COMPLAINT_NOT_OWNED for v in out):
+        raise ValueError("a complaint is owned by no rank")
+    return out
 
 
 def key_comb_choice(keys: int, items_per_key: int, cached10: bool = False, cached16: bool = False) -> int:

@@ -709,4 +709,115 @@ void segment_mask(size_t D, int nseg, int seg, const uint8_t* dok, uint8_t* out,
                      (uint32_t)seg, dok, out);
 }
 
+// ------------------------------------------------------------------ dealer-sharded ceremonies: a rank's own complaints
+// A rank verifies the complaints against its D dealers (runtime.hip shard_complaints).  Its fused round-2/4
+// pass has already evaluated P^E_i(j) and P^A_i(j) for every receiver j of every one of them, so the
+// complaints' evaluation items are elements of that pass's R: dealer group q of 64 holds its E rows in
+// columns [128 q, 128 q + 64) and its A rows in [128 q + 64, 128 q + 128) (verify_device, two segments),
+// and the recombined value of (column, receiver j) is element column * n + j - 1 (the piece-0 slot).
+// ridx [items C] as k_cv_check (items = 1: the E row) and k_c3_check (items = 2: E then A) read it.  lrow
+// [C]: the accused's 1-based row among the rank's dealers; accuser [C] 1-based; rowok [2D]: the E rows
+// then the A rows decode.  A complaint with a row that does not decode reads no element of R: all its
+// items name element 0 of Rh (bit 31 clear), and k_*_final give its verdict from rowok alone.
+__global__ __launch_bounds__(256) void k_shard_ridx(size_t C, uint32_t items, size_t D, size_t n,
+                                                    const uint32_t* __restrict__ lrow,
+                                                    const uint32_t* __restrict__ accuser,
+                                                    const uint8_t* __restrict__ rowok, uint32_t* __restrict__ ridx) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= C) return;
+  const size_t r = lrow[c] - 1, j = accuser[c] - 1;
+  bool ok = rowok[r] != 0;
+  if (items == 2) ok = ok && rowok[D + r] != 0;
+  for (uint32_t s = 0; s < items; s++) {
+    const size_t col = (r / 64) * 128 + (size_t)s * 64 + r % 64;
+    ridx[items * c + s] = ok ? 0x80000000u | (uint32_t)(col * n + j) : 0u;
+  }
+}
+
+void shard_ridx(size_t C, int items, size_t D, size_t n, const uint32_t* lrow, const uint32_t* accuser,
+                const uint8_t* rowok, uint32_t* ridx, hipStream_t stream) {
+  if (!C) return;
+  hipLaunchKernelGGL(k_shard_ridx, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, stream, C, (uint32_t)items, D, n,
+                     lrow, accuser, rowok, ridx);
+}
+
+// The flag words a rank sends beside its packed rows, flags [rows] (rows past D zero): bit 0 some
+// verdict-0 round-2 complaint against the dealer (cmask == 0; cmask null: no such round), bit 1 some
+// round-4 complaint against it holds (proven4), bit 2 it has no usable phase-3 broadcast (its A row does
+// not decode, a_dec == 0, or fetched3 == 0; fetched3 null = all present).
+__global__ __launch_bounds__(256) void k_shard_flags(size_t D, size_t rows, const uint8_t* __restrict__ cmask,
+                                                     const uint8_t* __restrict__ proven4,
+                                                     const uint8_t* __restrict__ a_dec,
+                                                     const uint8_t* __restrict__ fetched3,
+                                                     uint32_t* __restrict__ flags) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  uint32_t f = 0;
+  if (i < D) {
+    if (cmask && !cmask[i]) f |= 1u;
+    if (proven4[i]) f |= 2u;
+    if (!a_dec[i] || (fetched3 && !fetched3[i])) f |= 4u;
+  }
+  flags[i] = f;
+}
+
+void shard_flags(size_t D, size_t rows, const uint8_t* cmask, const uint8_t* proven4, const uint8_t* a_dec,
+                 const uint8_t* fetched3, uint32_t* flags, hipStream_t stream) {
+  if (!rows) return;
+  hipLaunchKernelGGL(k_shard_flags, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, stream, D, rows, cmask, proven4,
+                     a_dec, fetched3, flags);
+}
+
+// A rank's partial of dissent[j]: its dealers i that receiver j rejected (dec2 [D][n], REJECT = 0) without
+// a proven complaint of its own against them (pair [D][n], k_proven_masks).  Thread = receiver:
+// consecutive lanes read consecutive bytes of each row.
+__global__ __launch_bounds__(256) void k_shard_dissent(size_t D, size_t n, const uint8_t* __restrict__ dec2,
+                                                       const uint8_t* __restrict__ pair, int32_t* __restrict__ dissent) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int32_t v = 0;
+  for (size_t i = 0; i < D; i++) v += dec2[i * n + j] == 0 && !pair[i * n + j];
+  dissent[j] = v;
+}
+
+void shard_dissent(size_t D, size_t n, const uint8_t* dec2, const uint8_t* pair, int32_t* dissent, hipStream_t stream) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_shard_dissent, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, D, n, dec2, pair,
+                     dissent);
+}
+
+// The combine's side of the flag words: flags [n] (compacted) -> cmask[i] = bit 0 clear, proven4[i] = bit 1,
+// a_ok[i] = bit 2 clear.
+__global__ __launch_bounds__(256) void k_flag_masks(size_t n, const uint32_t* __restrict__ flags,
+                                                    uint8_t* __restrict__ cmask, uint8_t* __restrict__ proven4,
+                                                    uint8_t* __restrict__ a_ok) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t f = flags[i];
+  cmask[i] = (f & 1u) ? 0 : 1;
+  proven4[i] = (f & 2u) ? 1 : 0;
+  a_ok[i] = (f & 4u) ? 0 : 1;
+}
+
+void flag_masks(size_t n, const uint32_t* flags, uint8_t* cmask, uint8_t* proven4, uint8_t* a_ok, hipStream_t stream) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_flag_masks, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, flags, cmask, proven4,
+                     a_ok);
+}
+
+// out[j] = sum over the ws gathered rank blocks of in[r][j] (the ranks' dissent partials, [ws][n])
+__global__ __launch_bounds__(256) void k_sum_partials_i32(size_t ws, size_t n, const int32_t* __restrict__ in,
+                                                          int32_t* __restrict__ out) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  int32_t v = 0;
+  for (size_t r = 0; r < ws; r++) v += in[r * n + j];
+  out[j] = v;
+}
+
+void sum_partials_i32(size_t ws, size_t n, const int32_t* in, int32_t* out, hipStream_t stream) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_sum_partials_i32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ws, n, in, out);
+}
+
 }  // namespace dkgk

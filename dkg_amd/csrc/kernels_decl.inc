@@ -374,6 +374,20 @@ void proven_masks(size_t C2, size_t n, const uint32_t* drow2, const uint32_t* ac
 void dissent_rows(size_t V, size_t n, const uint8_t* dec2, const uint8_t* pair, int32_t* dissent, hipStream_t stream);
 // out[i] = dok[column of dealer i of segment seg] (and_dealer_mask's layout), i < D
 void segment_mask(size_t D, int nseg, int seg, const uint8_t* dok, uint8_t* out, hipStream_t stream);
+// ---- the complaint stage of a dealer-sharded rank (its D dealers; lrow = the accused's 1-based local row)
+// ridx [items C] of the owned complaints' items as elements of the fused pass's R (bit 31 set; items = 1:
+// the E row, 2: E then A), or element 0 of Rh for a complaint with a row that does not decode (rowok [2D])
+void shard_ridx(size_t C, int items, size_t D, size_t n, const uint32_t* lrow, const uint32_t* accuser,
+                const uint8_t* rowok, uint32_t* ridx, hipStream_t stream);
+// flags [rows]: bit 0 !cmask (null: clear), bit 1 proven4, bit 2 !a_dec or !fetched3 (null: present); rows past D zero
+void shard_flags(size_t D, size_t rows, const uint8_t* cmask, const uint8_t* proven4, const uint8_t* a_dec,
+                 const uint8_t* fetched3, uint32_t* flags, hipStream_t stream);
+// dissent[j] = #{i < D : dec2[i][j] == REJECT and not pair[i][j]}
+void shard_dissent(size_t D, size_t n, const uint8_t* dec2, const uint8_t* pair, int32_t* dissent, hipStream_t stream);
+// flags [n] -> cmask (bit 0 clear), proven4 (bit 1), a_ok (bit 2 clear)
+void flag_masks(size_t n, const uint32_t* flags, uint8_t* cmask, uint8_t* proven4, uint8_t* a_ok, hipStream_t stream);
+// out[j] = sum_r in[r][j], in [ws][n]
+void sum_partials_i32(size_t ws, size_t n, const int32_t* in, int32_t* out, hipStream_t stream);
 
 // ---- committee verification by interpolation (interp.hip)
 // F[d][k] = sum_j W[k][j] s[d][j] (and F' from s'; sp may be null), WT[j][k] = W[k][j] in Montgomery form

@@ -83,8 +83,11 @@ struct dkg_multi {
   // partial final shares
   std::vector<DevBuf> in_a, in_b, in_s, in_sp, dec2, dec4, A0, part;
   std::vector<DevBuf> in_r, in_e1, in_ct;  // full mode: encryption randomness, received ciphertexts
+  // the proven calls: packed rows [R][W + 1] u32, flag words [R] u32, dissent partials [n] i32
+  std::vector<DevBuf> pk2, pk4, flags, dis;
   // device 0: gathered blocks, compacted matrices, final / public shares
   DevBuf g_dec2, g_dec4, g_A0, g_part, c_dec2, c_dec4, fs, pub;
+  DevBuf g_pk2, g_pk4, g_flags, g_dis;  // the proven calls' gathered blocks
 
   int ws() const { return (int)ctx.size(); }
 };
@@ -161,18 +164,39 @@ void gather_blocks(dkg_multi* m, size_t n, std::vector<DevBuf>& src, DevBuf& dst
   MCK(hipStreamSynchronize(m->gather));
 }
 
+// What the proven calls add to the steps after the shards: the shards have packed their rows (pk2 / pk4)
+// and written their flag words and, in full mode, dissent partials; these join the gather, the combine
+// is dkg_shard_combine_proven_device, and the finalising parties' common outcome goes to the caller.
+struct ProvenOut {
+  bool full;
+  int32_t *dissent, *finalise_status, *recovery_index;  // host, may be null
+};
+
 // The steps after the shards (exchange, combine, reconstruction, finalise) and the host outputs.
-int finish(dkg_multi* m, size_t n, size_t t, dkg_ceremony_out* out, double t_start) {
+int finish(dkg_multi* m, size_t n, size_t t, dkg_ceremony_out* out, double t_start, const ProvenOut* pv = nullptr) {
   const int ws = m->ws();
   const int D0 = m->dev[0];
-  const size_t R = dkg_shard_rows(n, ws);
+  const size_t R = dkg_shard_rows(n, ws), PB = 4 * R * dkg_packed_row_words(n);
   double c0 = now_ms();
-  m->g_dec2.get(D0, (size_t)ws * R * n);
-  m->g_dec4.get(D0, (size_t)ws * R * n);
   m->g_A0.get(D0, (size_t)ws * R * 32);
   m->g_part.get(D0, (size_t)ws * n * 32);
-  gather_blocks(m, n, m->dec2, m->g_dec2, n, 0, R * n);
-  gather_blocks(m, n, m->dec4, m->g_dec4, n, 0, R * n);
+  if (pv) {
+    m->g_pk2.get(D0, (size_t)ws * PB);
+    m->g_pk4.get(D0, (size_t)ws * PB);
+    m->g_flags.get(D0, (size_t)ws * R * 4);
+    gather_blocks(m, n, m->pk2, m->g_pk2, 0, PB, PB);
+    gather_blocks(m, n, m->pk4, m->g_pk4, 0, PB, PB);
+    gather_blocks(m, n, m->flags, m->g_flags, 0, 4 * R, 4 * R);
+    if (pv->full) {
+      m->g_dis.get(D0, (size_t)ws * n * 4);
+      gather_blocks(m, n, m->dis, m->g_dis, 0, 4 * n, 4 * n);
+    }
+  } else {
+    m->g_dec2.get(D0, (size_t)ws * R * n);
+    m->g_dec4.get(D0, (size_t)ws * R * n);
+    gather_blocks(m, n, m->dec2, m->g_dec2, n, 0, R * n);
+    gather_blocks(m, n, m->dec4, m->g_dec4, n, 0, R * n);
+  }
   gather_blocks(m, n, m->A0, m->g_A0, 32, 0, R * 32);
   gather_blocks(m, n, m->part, m->g_part, 0, 32 * n, 32 * n);
   double c1 = now_ms();
@@ -183,18 +207,25 @@ int finish(dkg_multi* m, size_t n, size_t t, dkg_ceremony_out* out, double t_sta
   dkg_shard_outcome o{q.data(), c2.data(), r2e.data(), recon.data(), r4e.data(), 0, 0};
   void* cd2 = m->c_dec2.get(D0, n * n);
   void* cd4 = m->c_dec4.get(D0, n * n);
-  int rc = dkg_shard_combine_device(m->ctx[0], n, t, ws, m->g_dec2.p, m->g_dec4.p, cd2, cd4, &o);
+  int32_t status = DKG_FIN_OK, index = -1;
+  int rc = pv ? dkg_shard_combine_proven_device(m->ctx[0], n, t, ws, m->g_pk2.p, m->g_pk4.p, m->g_flags.p,
+                                                pv->full ? m->g_dis.p : nullptr, pv->full, cd2, cd4, &o,
+                                                pv->full ? pv->dissent : nullptr, &status, &index)
+              : dkg_shard_combine_device(m->ctx[0], n, t, ws, m->g_dec2.p, m->g_dec4.p, cd2, cd4, &o);
   if (rc != DKG_OK) {
     m->err = std::string("combine: ") + dkg_ctx_last_error(m->ctx[0]);
     return rc;
   }
+  if (pv && pv->finalise_status) *pv->finalise_status = status;
+  if (pv && pv->recovery_index) *pv->recovery_index = index;
   double c2t = now_ms();
   m->ms["combine"] = c2t - c1;
 
-  int no_mpk = o.phase4_error;
+  // nobody finalises after a Phase4 failure; a panic of every party's finalise leaves no mpk either
+  int no_mpk = o.phase4_error || status == DKG_FIN_PANIC;
   bool any = false;
   for (size_t i = 0; i < n; i++) any |= recon[i] != 0;
-  if (any && !o.phase4_error) {
+  if (any && !no_mpk) {
     // a dealer accused in round 4 enters mpk as g * a_i0 over the disclosing final parties'
     // shares (committee.rs:747-789), recovered on the device that holds its share row
     std::vector<int32_t> fail(ws, 0);
@@ -296,7 +327,7 @@ int dkg_multi_create(const int* devices, int ndev, dkg_multi** out) {
   m->dev.assign(devices, devices + ndev);
   m->ctx.assign(ndev, nullptr);
   for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part, &m->in_r, &m->in_e1,
-                  &m->in_ct})
+                  &m->in_ct, &m->pk2, &m->pk4, &m->flags, &m->dis})
     v->resize(ndev);
   int rc = guarded_multi(m, [&] {
     for (int i = 0; i < ndev; i++) {
@@ -334,9 +365,11 @@ int dkg_multi_create(const int* devices, int ndev, dkg_multi** out) {
 void dkg_multi_destroy(dkg_multi* m) {
   if (!m) return;
   for (auto* v : {&m->in_a, &m->in_b, &m->in_s, &m->in_sp, &m->dec2, &m->dec4, &m->A0, &m->part, &m->in_r, &m->in_e1,
-                  &m->in_ct})
+                  &m->in_ct, &m->pk2, &m->pk4, &m->flags, &m->dis})
     for (auto& b : *v) b.release();
-  for (auto* b : {&m->g_dec2, &m->g_dec4, &m->g_A0, &m->g_part, &m->c_dec2, &m->c_dec4, &m->fs, &m->pub}) b->release();
+  for (auto* b : {&m->g_dec2, &m->g_dec4, &m->g_A0, &m->g_part, &m->c_dec2, &m->c_dec4, &m->fs, &m->pub, &m->g_pk2,
+                  &m->g_pk4, &m->g_flags, &m->g_dis})
+    b->release();
   if (m->gather) {
     (void)hipSetDevice(m->dev[0]);
     (void)hipStreamDestroy(m->gather);
@@ -542,6 +575,163 @@ int dkg_multi_ceremony_verify_full(dkg_multi* m, size_t n, size_t t, const uint8
     if (rc != DKG_OK) return rc;
     record_shards(m, sh);
     return finish(m, n, t, out, t0);
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The broadcast complaint lists of a proven call (host, as the single-context calls take them) and where
+// the merged verdicts go.  Every shard receives the whole lists and verifies the complaints against its
+// own dealers; exactly one shard owns each complaint and the others report DKG_COMPLAINT_NOT_OWNED, which
+// is below every real code: the element-wise maximum merges the shards' arrays.
+struct ProvenLists {
+  size_t C = 0, C4 = 0;
+  const uint32_t *accuser = nullptr, *accused = nullptr, *accuser4 = nullptr, *accused4 = nullptr;
+  const uint8_t *proofs = nullptr, *share4 = nullptr, *randomness4 = nullptr;
+  int32_t *verdict = nullptr, *verdict4 = nullptr;
+};
+
+int proven_lists_ok(dkg_multi* m, const ProvenLists& c) {
+  if ((c.C && !c.verdict) || (c.C4 && !c.verdict4)) {
+    m->err = "bad arguments: verdict arrays must be non-NULL where there are complaints";
+    return DKG_E_ARG;
+  }
+  return DKG_OK;
+}
+
+void merge_verdicts(size_t C, const std::vector<std::vector<int32_t>>& per_shard, int32_t* out) {
+  for (size_t c = 0; c < C; c++) {
+    int32_t v = DKG_COMPLAINT_NOT_OWNED;
+    for (const auto& s : per_shard) v = std::max(v, s[c]);
+    out[c] = v;
+  }
+}
+
+// shard i's buffers of a proven call beside shard_outputs'
+void proven_outputs(dkg_multi* m, size_t n, int i, size_t R) {
+  const size_t PB = 4 * R * dkg_packed_row_words(n);
+  m->pk2[i].get(m->dev[i], PB);
+  m->pk4[i].get(m->dev[i], PB);
+  m->flags[i].get(m->dev[i], 4 * R);
+  m->dis[i].get(m->dev[i], 4 * n);
+}
+
+// after shard i's proven call: its raw rows as the packed blocks the gather carries
+int pack_shard(dkg_multi* m, size_t n, int i, size_t R, size_t d0, size_t D) {
+  int rc = dkg_decisions_pack_device(m->ctx[i], R, D, n, d0, m->dec2[i].p, m->pk2[i].p);
+  if (rc != DKG_OK) return rc;
+  return dkg_decisions_pack_device(m->ctx[i], R, D, n, d0, m->dec4[i].p, m->pk4[i].p);
+}
+
+}  // namespace
+
+extern "C" {
+
+int dkg_multi_ceremony_verify_proven(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                     const uint8_t* s, const uint8_t* s_prime, const uint8_t* fetched1,
+                                     const uint8_t* fetched3, size_t C4, const uint32_t* accuser4,
+                                     const uint32_t* accused4, const uint8_t* share4, const uint8_t* randomness4,
+                                     dkg_ceremony_out* out, int32_t* verdict4, int32_t* finalise_status,
+                                     int32_t* recovery_index) {
+  return guarded_multi(m, [&] {
+    int rc = check_args(m, n, t, out);
+    if (rc != DKG_OK) return rc;
+    if (!E || !A || !s || !s_prime) return DKG_E_ARG;
+    ProvenLists c;
+    c.C4 = C4, c.accuser4 = accuser4, c.accused4 = accused4, c.share4 = share4, c.randomness4 = randomness4;
+    c.verdict4 = verdict4;
+    if ((rc = proven_lists_ok(m, c)) != DKG_OK) return rc;
+    const size_t N = t + 1, R = dkg_shard_rows(n, m->ws());
+    std::vector<double> sh(m->ws(), 0);
+    std::vector<std::vector<int32_t>> v4(m->ws(), std::vector<int32_t>(C4 ? C4 : 1));
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      const size_t D = d1 - d0;
+      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_s[i].get(m->dev[i], 32 * n * D), s + 32 * n * d0, 32 * n * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_sp[i].get(m->dev[i], 32 * n * D), s_prime + 32 * n * d0, 32 * n * D,
+                    hipMemcpyHostToDevice));
+      shard_outputs(m, n, i, D);
+      proven_outputs(m, n, i, R);
+      return DKG_OK;
+    });
+    if (rc != DKG_OK) return rc;
+    const double t0 = now_ms();
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      int r = dkg_ceremony_shard_verify_proven_device(
+          m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_s[i].p, m->in_sp[i].p,
+          fetched1 ? fetched1 + d0 : nullptr, fetched3 ? fetched3 + d0 : nullptr, C4, accuser4, accused4, share4,
+          randomness4, m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, R, m->flags[i].p, v4[i].data(), &sh[i]);
+      return r != DKG_OK ? r : pack_shard(m, n, i, R, d0, d1 - d0);
+    });
+    if (rc != DKG_OK) return rc;
+    record_shards(m, sh);
+    merge_verdicts(C4, v4, verdict4);
+    const ProvenOut pv{false, nullptr, finalise_status, recovery_index};
+    return finish(m, n, t, out, t0, &pv);
+  });
+}
+
+int dkg_multi_ceremony_verify_full_proven(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                          const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, const uint8_t* pk,
+                                          size_t C, const uint32_t* accuser, const uint32_t* accused,
+                                          const uint8_t* proofs, const uint8_t* fetched3, size_t C4,
+                                          const uint32_t* accuser4, const uint32_t* accused4, const uint8_t* share4,
+                                          const uint8_t* randomness4, dkg_ceremony_out* out, int32_t* verdict,
+                                          int32_t* dissent, int32_t* verdict4, int32_t* finalise_status,
+                                          int32_t* recovery_index) {
+  return guarded_multi(m, [&] {
+    int rc = check_args(m, n, t, out);
+    if (rc != DKG_OK) return rc;
+    if (!E || !A || !e1 || !ct || !sk || !pk) {
+      m->err = "bad arguments: E, A, e1, ct, sk and pk must be non-NULL";
+      return DKG_E_ARG;
+    }
+    ProvenLists c;
+    c.C = C, c.accuser = accuser, c.accused = accused, c.proofs = proofs, c.verdict = verdict;
+    c.C4 = C4, c.accuser4 = accuser4, c.accused4 = accused4, c.share4 = share4, c.randomness4 = randomness4;
+    c.verdict4 = verdict4;
+    if ((rc = proven_lists_ok(m, c)) != DKG_OK) return rc;
+    const size_t N = t + 1, R = dkg_shard_rows(n, m->ws());
+    std::vector<double> sh(m->ws(), 0);
+    std::vector<std::vector<int32_t>> v2(m->ws(), std::vector<int32_t>(C ? C : 1));
+    std::vector<std::vector<int32_t>> v4(m->ws(), std::vector<int32_t>(C4 ? C4 : 1));
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      const size_t D = d1 - d0;
+      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_e1[i].get(m->dev[i], 64 * n * D), e1 + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
+      MCK(hipMemcpy(m->in_ct[i].get(m->dev[i], 64 * n * D), ct + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
+      shard_outputs(m, n, i, D);
+      proven_outputs(m, n, i, R);
+      return DKG_OK;
+    });
+    if (rc != DKG_OK) return rc;
+    const double t0 = now_ms();
+    rc = for_shards(m, [&](int i) {
+      size_t d0, d1;
+      range(m, n, i, &d0, &d1);
+      int r = dkg_ceremony_shard_verify_full_proven_device(
+          m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_e1[i].p, m->in_ct[i].p, sk, pk, nullptr,
+          fetched3 ? fetched3 + d0 : nullptr, C, accuser, accused, proofs, C4, accuser4, accused4, share4, randomness4,
+          m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, R, m->flags[i].p, m->dis[i].p, v2[i].data(),
+          v4[i].data(), &sh[i]);
+      return r != DKG_OK ? r : pack_shard(m, n, i, R, d0, d1 - d0);
+    });
+    if (rc != DKG_OK) return rc;
+    record_shards(m, sh);
+    merge_verdicts(C, v2, verdict);
+    merge_verdicts(C4, v4, verdict4);
+    const ProvenOut pv{true, dissent, finalise_status, recovery_index};
+    return finish(m, n, t, out, t0, &pv);
   });
 }
 

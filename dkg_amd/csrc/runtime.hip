@@ -106,8 +106,11 @@ struct dkg_ctx {
   const uint32_t* last_scale = nullptr;
   const uint8_t* last_dok = nullptr;
   int last_dok_nseg = 1;                // its segments (columns interleaved as and_dealer_mask addresses them)
+  const uint8_t* last_pok = nullptr;    // its per-point decode flags [last_npad][N], before any dealer mask
+  size_t last_npad = 0;
   int complaint_eval = 0;               // P_i(j) of the complaints: 0 by the dealer's complaint count,
                                         // 1 per-pair Horner, 2 difference tables
+  int last_complaint_eval = 0;          // dkg_ctx_last_complaint_eval: the sharded proven calls' source
   // round-1 commitments of the ceremony being verified, in extended form on this device (set by
   // the drivers that generate them, ExtScope): verify_device places them instead of decoding the
   // encodings, finalise reads A_i0 from them.  E/A [D][t+1] points, word stride ext_stride.
@@ -772,6 +775,8 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
   ctx->last_scale = sscale;
   ctx->last_dok = dok;
   ctx->last_dok_nseg = nseg;
+  ctx->last_pok = pok;
+  ctx->last_npad = npad;
   // padding columns, and the positions past t of the last piece, are the identity
   if (npad != D * nseg || U * L != N) dkgk::fill_identity(L * W, Cpm, home);
   HCK(hipMemsetAsync(pok, 1, npad * N, home));
@@ -3463,17 +3468,227 @@ int dkg_ceremony_verify_fetched(dkg_ctx* ctx, size_t n, size_t t, const uint8_t*
 
 }  // extern "C"
 
+// ---- the proven-complaint rule on a dealer shard (dkg_ceremony_shard_verify_proven_device, _full_proven_device)
+// Every fact that decides a complaint against dealer i lives on the rank that owns i: its E and A rows,
+// its e1 / ct items and their decode mask, its round-2 qualification, its fetched3 bit; the accusers'
+// keys are the pk [n] every rank takes.  So each rank verifies the complaints against its own dealers
+// (d0 < accused <= d0 + D, in their relative input order) and no exchange precedes round 3.
+// The owned complaints go up once, before the rounds: one pinned staging block
+//   accuser4 | row4 | accuser2 | row2 | share4 [C4][8] | randomness4 [C4][8] | proofs [C2][48]
+// with row = accused - d0, the accused's 1-based row among the rank's dealers.
+struct ShardProven {
+  bool full = false;  // encrypted shares: round 2 by the proven complaints too (else the rejection rule)
+  // the ceremony's broadcast complaint lists (host, as every rank receives them) and the intake masks [D]
+  const uint8_t* pk = nullptr;
+  size_t C2 = 0, C4 = 0;
+  const uint32_t *accuser2 = nullptr, *accused2 = nullptr, *accuser4 = nullptr, *accused4 = nullptr;
+  const uint8_t *proofs = nullptr, *share4 = nullptr, *randomness4 = nullptr;
+  const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;
+  int32_t *verdict2 = nullptr, *verdict4 = nullptr;
+  size_t flag_rows = 0;
+  void *d_flags = nullptr, *d_dissent = nullptr;
+  // the owned complaints: their places in the input lists, and the host copies the fallback's
+  // complaint_evals reads (acc / row per complaint; for round 4 per evaluation item, E then A)
+  std::vector<uint32_t> own2, own4, acc2h, row2h, acc4h, row4h, idx4h, item4h;
+  const uint32_t *dacc2 = nullptr, *drow2 = nullptr, *dacc4 = nullptr, *drow4 = nullptr;
+  const uint32_t *dsh = nullptr, *drn = nullptr, *dprf = nullptr, *dpk = nullptr;
+  const uint8_t *df1 = nullptr, *df3 = nullptr;
+  int32_t *hver2 = nullptr, *hver4 = nullptr;  // pinned copies of the owned complaints' verdicts
+  ComplaintEvals ev2, ev4;                     // the fallback's staging, alive until the call's sync
+};
+
+void shard_proven_upload(dkg_ctx* ctx, size_t n, size_t d0, size_t D, ShardProven& sp) {
+  auto own = [&](size_t C, const uint32_t* accuser, const uint32_t* accused, std::vector<uint32_t>& pos,
+                 std::vector<uint32_t>& acc, std::vector<uint32_t>& row) {
+    for (size_t c = 0; c < C; c++)
+      if (accused[c] > d0 && accused[c] <= d0 + D) {
+        pos.push_back((uint32_t)c);
+        acc.push_back(accuser[c]);
+        row.push_back(accused[c] - (uint32_t)d0);
+      }
+  };
+  own(sp.C4, sp.accuser4, sp.accused4, sp.own4, sp.acc4h, sp.row4h);
+  if (sp.full) own(sp.C2, sp.accuser2, sp.accused2, sp.own2, sp.acc2h, sp.row2h);
+  const size_t o2 = sp.own2.size(), o4 = sp.own4.size();
+  for (size_t k = 0; k < o4; k++) {  // items 2k, 2k + 1: rows i and D + i of the [2D] decoded rows
+    sp.idx4h.insert(sp.idx4h.end(), {sp.acc4h[k], sp.acc4h[k]});
+    sp.item4h.insert(sp.item4h.end(), {sp.row4h[k], (uint32_t)D + sp.row4h[k]});
+  }
+  const size_t words = 2 * o4 + 2 * o2 + 16 * o4 + 48 * o2;
+  uint32_t* h = hbuf<uint32_t>(ctx, "hb.sp_in", 4 * words);
+  uint32_t* d = buf<uint32_t>(ctx, "sp.in", 4 * words);
+  size_t at = 0;
+  auto put = [&](const void* src, size_t cnt) {
+    const uint32_t* p = d + at;
+    if (cnt) memcpy(h + at, src, 4 * cnt);
+    at += cnt;
+    return p;
+  };
+  sp.dacc4 = put(sp.acc4h.data(), o4);
+  sp.drow4 = put(sp.row4h.data(), o4);
+  sp.dacc2 = put(sp.acc2h.data(), o2);
+  sp.drow2 = put(sp.row2h.data(), o2);
+  sp.dsh = d + at;
+  for (size_t k = 0; k < o4; k++) put(sp.share4 + 32 * (size_t)sp.own4[k], 8);
+  sp.drn = d + at;
+  for (size_t k = 0; k < o4; k++) put(sp.randomness4 + 32 * (size_t)sp.own4[k], 8);
+  sp.dprf = d + at;
+  for (size_t k = 0; k < o2; k++) put(sp.proofs + 192 * (size_t)sp.own2[k], 48);
+  h2d(ctx, d, h, 4 * words);
+  if (sp.full) {
+    uint32_t* dpk = buf<uint32_t>(ctx, "sp.pk", 32 * n);
+    h2d(ctx, dpk, sp.pk, 32 * n);
+    sp.dpk = dpk;
+  }
+  sp.df1 = upload_mask(ctx, "sp.f1", sp.fetched1, D);
+  sp.df3 = upload_mask(ctx, "sp.f3", sp.fetched3, D);
+  sp.hver2 = hbuf<int32_t>(ctx, "hb.sp_ver2", 4 * o2);
+  sp.hver4 = hbuf<int32_t>(ctx, "hb.sp_ver4", 4 * o4);
+}
+
+// A rank without dealers (world_size > n / 2 leaves some): no flags, no dissent
+void shard_complaints_none(dkg_ctx* ctx, size_t n, ShardProven& sp) {
+  if (sp.flag_rows) HCK(hipMemsetAsync(sp.d_flags, 0, 4 * sp.flag_rows, ctx->stream));
+  if (sp.d_dissent) HCK(hipMemsetAsync(sp.d_dissent, 0, 4 * n, ctx->stream));
+  ctx->last_complaint_eval = 0;
+}
+
+// The complaint stage of a rank, queued on ctx->stream after its rounds' checks; no host synchronisation.
+// Ec, Ac [D][N][8] the rank's commitments, e1c / ctc its ciphertexts (full mode), dec2 [D][n] the round-2
+// rows just decided.  Out: qm [D] the rank's dealers' qualified mask (rej its complement) -- full mode: the
+// row is not MISSING and no complaint against it has verdict 0; else the rejection rule -- the flag words,
+// the dissent partial, and the verdicts in sp.hver2 / hver4.
+// Evaluation source 3, "the calling pass": when the rounds ran fused in group-check mode their R holds
+// P^E_i(j) and P^A_i(j) of every receiver of every dealer of the rank at once, and the complaints'
+// items are elements of it (k_shard_ridx) -- no Horner walk, no second set of tables; the rows' validity
+// is the pass's own decode flags.  Otherwise (protocol-order rounds, interpolation, a forced
+// dkg_ctx_set_complaint_eval, or an R too large for 31-bit elements): the rows are decoded once more and
+// complaint_evals decides per accused row as in dkg_complaints_verify.
+void shard_complaints(dkg_ctx* ctx, size_t n, size_t t, size_t D, const uint32_t* Ec, const uint32_t* Ac,
+                      const uint32_t* e1c, const uint32_t* ctc, const uint8_t* dec2, uint8_t* rej, uint8_t* qm,
+                      ShardProven& sp) {
+  const size_t N = t + 1, C2 = sp.own2.size(), C4 = sp.own4.size();
+  hipStream_t st = ctx->stream;
+  const size_t npad = (D + 63) / 64 * 128;
+  const bool pass = ctx->overlap && ctx->verify_mode == 0 && ctx->last_R && ctx->last_dok_nseg == 2 &&
+                    ctx->last_npad == npad && (uint64_t)npad * n < (1ull << 31);
+  const bool src3 = pass && ctx->complaint_eval == 0;
+  const uint32_t *passR = ctx->last_R, *pass_scale = ctx->last_scale;
+  uint8_t* rowok = buf<uint8_t>(ctx, "sp.rowok", 2 * D);  // the E rows, then the A rows, decode
+  const uint32_t *EA = nullptr, *EAext = nullptr, *Rh0 = nullptr;
+  if (src3) {
+    uint8_t* raw = buf<uint8_t>(ctx, "sp.rawdok", npad);  // the columns' decode flags without the dealer masks
+    dkgk::dealer_ok(npad, N, ctx->last_pok, raw, st);
+    dkgk::segment_mask(D, 2, 0, raw, rowok, st);
+    dkgk::segment_mask(D, 2, 1, raw, rowok + D, st);
+    uint32_t* id = buf<uint32_t>(ctx, "sp.Rh0", PTB);  // what a complaint against an undecodable row reads
+    dkgk::fill_identity(1, id, st);
+    Rh0 = id;
+  } else {
+    uint32_t* ea = buf<uint32_t>(ctx, "sp.EA", 32 * 2 * D * N);
+    uint32_t* ext = buf<uint32_t>(ctx, "sp.EAext", PTB * 2 * D * N);
+    uint8_t* pok = buf<uint8_t>(ctx, "sp.pok", 2 * D * N);
+    HCK(hipMemcpyAsync(ea, Ec, 32 * D * N, hipMemcpyDeviceToDevice, st));
+    HCK(hipMemcpyAsync(ea + 8 * D * N, Ac, 32 * D * N, hipMemcpyDeviceToDevice, st));
+    dkgk::decode_points(ea, 2 * D * N, ext, 2 * D * N, pok, st);
+    dkgk::dealer_ok(2 * D, N, pok, rowok, st);
+    EA = ea, EAext = ext;
+  }
+  sp.ev2 = ComplaintEvals{};
+  sp.ev4 = ComplaintEvals{};
+  uint8_t* proven4 = buf<uint8_t>(ctx, "sp.proven4", D);
+  HCK(hipMemsetAsync(proven4, 0, D, st));
+  int32_t* dver2 = buf<int32_t>(ctx, "sp.verdict2", 4 * C2);
+  int32_t* dver4 = buf<int32_t>(ctx, "sp.verdict4", 4 * C4);
+  uint8_t *cmask = nullptr, *pair = nullptr;
+  // ---- round 2 (k_cv_*): the pair dealer i sent accuser j out of the rank's own ciphertexts
+  if (sp.full) {
+    cmask = buf<uint8_t>(ctx, "sp.cmask", D);
+    pair = buf<uint8_t>(ctx, "sp.pair", D * n);
+    HCK(hipMemsetAsync(cmask, 1, D, st));
+    HCK(hipMemsetAsync(pair, 0, D * n, st));
+    if (C2) {
+      uint32_t* denc = buf<uint32_t>(ctx, "sp.enc", 128 * C2);
+      dkgk::gather_enc(C2, n, sp.drow2, sp.dacc2, e1c, ctc, denc, st);
+      const Announcements an = complaint_announcements(ctx, C2, sp.dacc2, sp.dpk, denc, sp.dprf, st);
+      const uint32_t *ridx, *Rh, *Rt, *scale;
+      if (src3) {
+        uint32_t* r = buf<uint32_t>(ctx, "sp.ridx2", 4 * C2);
+        dkgk::shard_ridx(C2, 1, D, n, sp.drow2, sp.dacc2, rowok, r, st);
+        ridx = r, Rh = Rh0, Rt = passR, scale = pass_scale;
+      } else {
+        complaint_evals(ctx, n, t, 2 * D, C2, sp.acc2h.data(), sp.row2h.data(), sp.dacc2, sp.drow2, EA, EAext, sp.ev2);
+        ridx = sp.ev2.dridx, Rh = sp.ev2.Rh, Rt = sp.ev2.Rt, scale = sp.ev2.scale;
+      }
+      uint8_t* eq = buf<uint8_t>(ctx, "sp.eq2", 2 * C2);
+      dkgk::cv_check(C2, sp.dacc2, an.p12, ridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+      dkgk::cv_final(C2, sp.dacc2, sp.drow2, sp.dpk, denc, sp.dprf, an.a1c, an.a2c, an.ppok, rowok, sp.df1, eq, dver2, st);
+      dkgk::proven_masks(C2, n, sp.drow2, sp.dacc2, dver2, 0, nullptr, nullptr, cmask, pair, proven4, st);
+    }
+    dkgk::qualified_complaints(D, n, dec2, cmask, rej, qm, st);
+  } else {
+    dkgk::row_reject(D, n, dec2, rej, st);
+    dkgk::mask_not_and(D, rej, nullptr, qm, st);
+  }
+  // ---- round 4 (k_c3_*): the rank's qualified mask gives IGNORED on the device (committee.rs:639)
+  if (C4) {
+    uint32_t* sr = buf<uint32_t>(ctx, "sp.sr", 32 * 2 * C4);
+    uint32_t* acc2x = buf<uint32_t>(ctx, "sp.acc2x", 4 * 2 * C4);
+    uint32_t* acd2x = buf<uint32_t>(ctx, "sp.acd2x", 4 * 2 * C4);
+    dkgk::c3_prep(C4, D, sp.dacc4, sp.drow4, sp.dsh, sp.drn, sr, acc2x, acd2x, st);
+    const uint32_t *ridx, *Rh, *Rt, *scale;
+    if (src3) {
+      uint32_t* r = buf<uint32_t>(ctx, "sp.ridx4", 4 * 2 * C4);
+      dkgk::shard_ridx(C4, 2, D, n, sp.drow4, sp.dacc4, rowok, r, st);
+      ridx = r, Rh = Rh0, Rt = passR, scale = pass_scale;
+    } else {
+      complaint_evals(ctx, n, t, 2 * D, 2 * C4, sp.idx4h.data(), sp.item4h.data(), acc2x, acd2x, EA, EAext, sp.ev4);
+      ridx = sp.ev4.dridx, Rh = sp.ev4.Rh, Rt = sp.ev4.Rt, scale = sp.ev4.scale;
+    }
+    uint8_t* eq = buf<uint8_t>(ctx, "sp.eq4", 2 * C4);
+    dkgk::c3_check(C4, sp.dacc4, sr, ridx, Rh, Rt, scale, ctx->tab_gw, ctx->tab_hw, eq, st);
+    dkgk::c3_final(C4, D, sp.drow4, sp.drow4, rowok, qm, sp.df3, eq, dver4, st);
+    dkgk::proven_masks(0, n, nullptr, nullptr, nullptr, C4, sp.drow4, dver4, cmask, pair, proven4, st);
+  }
+  dkgk::shard_flags(D, sp.flag_rows, cmask, proven4, rowok + D, sp.df3, (uint32_t*)sp.d_flags, st);
+  if (sp.d_dissent) dkgk::shard_dissent(D, n, dec2, pair, (int32_t*)sp.d_dissent, st);
+  d2h(ctx, sp.hver2, dver2, 4 * C2);
+  d2h(ctx, sp.hver4, dver4, 4 * C4);
+  if (src3) {
+    ctx->last_complaint_eval = 3;
+  } else {
+    const bool horner = !sp.ev2.hl.empty() || !sp.ev4.hl.empty(), tables = !sp.ev2.rows.empty() || !sp.ev4.rows.empty();
+    ctx->last_complaint_eval = horner && tables ? 12 : tables ? 2 : horner ? 1 : ctx->complaint_eval == 2 ? 2 : 1;
+  }
+}
+
+// After the call's sync: every complaint the rank does not own reads DKG_COMPLAINT_NOT_OWNED, the owned
+// ones their verdicts
+void shard_proven_verdicts(const ShardProven& sp) {
+  for (size_t c = 0; c < sp.C2; c++) sp.verdict2[c] = DKG_COMPLAINT_NOT_OWNED;
+  for (size_t c = 0; c < sp.C4; c++) sp.verdict4[c] = DKG_COMPLAINT_NOT_OWNED;
+  for (size_t k = 0; k < sp.own2.size(); k++) sp.verdict2[sp.own2[k]] = sp.hver2[k];
+  for (size_t k = 0; k < sp.own4.size(); k++) sp.verdict4[sp.own4[k]] = sp.hver4[k];
+}
+
 // Rounds 2-5 of one rank of a dealer-sharded ceremony on its dealers [d0, d0+D): E/A compressed
 // [D][N][32], s/sp canonical [D][n][32] on the device -> decision rows, master-key terms, partial
 // final shares (layouts of dkg_ceremony_shard_device).  e_ok (may be null; [D] on the device): 0 = the
 // dealer's round-1 data is missing, as receivers_rounds takes RoundMasks::e_ok -- full mode's decode mask
 // of the dealer's ciphertexts: a MISSING row in round 2.
+//
+// sp (may be null): the rank decides by the PROVEN complaints against its own dealers (ShardProven,
+// shard_complaints) -- the stage follows the checks on the stream and gives the qualified mask of the
+// partial sums; a_ok as verify_rounds takes it (the intake mask of the phase-3 broadcasts); e1c / ctc the
+// rank's ciphertexts [D][n][2][8] (full mode: the pairs the round-2 complaints are verified against).
 void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uint32_t* Ec, const uint32_t* Ac,
                 const uint32_t* ds, const uint32_t* dsp, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
-                const uint8_t* e_ok = nullptr) {
+                const uint8_t* e_ok = nullptr, ShardProven* sp = nullptr, const uint8_t* a_ok = nullptr,
+                const uint32_t* e1c = nullptr, const uint32_t* ctc = nullptr) {
   const size_t N = t + 1;
   if (!D) {
     HCK(hipMemsetAsync(d_partial, 0, 32 * n, ctx->stream));
+    if (sp) shard_complaints_none(ctx, n, *sp);
     return;
   }
   // the exchanged A_i0 encodings depend only on round 1: encoded on the side stream beside the checks
@@ -3497,13 +3712,17 @@ void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uin
   verify_rounds(
       ctx, n, t, D, d0, Ec, Ac, ds, dsp, (uint8_t*)d_dec2, (uint8_t*)d_dec4, nullptr,
       [&] {
+        if (sp) return;  // decided after both rounds, from the complaints (below)
         dkgk::row_reject(D, n, (const uint8_t*)d_dec2, rej, ctx->stream);
         dkgk::mask_not_and(D, rej, nullptr, qm, ctx->stream);
       },
-      e_ok, nullptr, false);
+      e_ok, a_ok, false);
   if (side_terms) HCK(hipStreamWaitEvent(ctx->stream, ctx->terms_done, 0));
   wait_shares(ctx, ctx->stream);  // shares evaluated on the side stream (round1_device)
   ctx->shares_pending = false;
+  // the proven rule: this sits inside the caller's with_binom_ded body, so a rerun with the complete
+  // formula reruns the stage on the rerun's tables
+  if (sp) shard_complaints(ctx, n, t, D, Ec, Ac, e1c, ctc, (const uint8_t*)d_dec2, rej, qm, *sp);
   // A dealer accused in round 4 (committee.rs:660-670) has its term replaced after the exchange,
   // once the final parties are known (dkg_ceremony_shard_recon_device): its shares stay here.
   ctx->shard_s = ds;
@@ -3676,6 +3895,118 @@ int dkg_ceremony_shard_verify_full_device(dkg_ctx* ctx, size_t n, size_t t, size
     return DKG_OK;
   });
 }
+
+// dkg_ceremony_shard_verify_device with the reference's rule for the reconstructable set, as
+// dkg_ceremony_verify_fetched_proven: round 2 keeps the rejection rule, round 4 is proven.
+int dkg_ceremony_shard_verify_proven_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_E,
+                                            const void* d_A, const void* d_s, const void* d_s_prime,
+                                            const uint8_t* fetched1, const uint8_t* fetched3, size_t C4,
+                                            const uint32_t* accuser4, const uint32_t* accused4, const uint8_t* share4,
+                                            const uint8_t* randomness4, void* d_dec2, void* d_dec4, void* d_A0,
+                                            void* d_partial, size_t flag_rows, void* d_flags, int32_t* verdict4,
+                                            double* ms_total) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !d_partial) return DKG_E_ARG;
+    const size_t D = d1 - d0;
+    if (D && (!d_E || !d_A || !d_s || !d_s_prime || !d_dec2 || !d_dec4 || !d_A0)) return DKG_E_ARG;
+    if (flag_rows < D || (flag_rows && !d_flags)) return DKG_E_ARG;
+    if (!complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4})) return DKG_E_ARG;
+    ShardProven sp;
+    sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
+    sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
+    sp.flag_rows = flag_rows, sp.d_flags = d_flags;
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    shard_proven_upload(ctx, n, d0, D, sp);
+    uint32_t* ds = buf<uint32_t>(ctx, "shv_s", 32 * D * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "shv_sp", 32 * D * n);
+    if (D) {
+      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s, ds, ctx->stream);
+      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s_prime, dsp, ctx->stream);
+    }
+    with_binom_ded(ctx, [&] {
+      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, ds, dsp, d_dec2, d_dec4, d_A0,
+                 d_partial, sp.df1, &sp, sp.df3);
+      check_launch(ctx);
+      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+      binom_mark_copy(ctx);
+      sync(ctx);
+    });
+    collect_phases(ctx);
+    shard_proven_verdicts(sp);
+    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
+    return DKG_OK;
+  });
+}
+
+// dkg_ceremony_shard_verify_full_device with both rounds decided by the proven complaints, as
+// dkg_ceremony_verify_full_proven.
+int dkg_ceremony_shard_verify_full_proven_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1,
+                                                 const void* d_E, const void* d_A, const void* d_e1, const void* d_ct,
+                                                 const uint8_t* sk, const uint8_t* pk, const uint8_t* fetched1,
+                                                 const uint8_t* fetched3, size_t C, const uint32_t* accuser,
+                                                 const uint32_t* accused, const uint8_t* proofs, size_t C4,
+                                                 const uint32_t* accuser4, const uint32_t* accused4,
+                                                 const uint8_t* share4, const uint8_t* randomness4, void* d_dec2,
+                                                 void* d_dec4, void* d_A0, void* d_partial, size_t flag_rows,
+                                                 void* d_flags, void* d_dissent, int32_t* verdict, int32_t* verdict4,
+                                                 double* ms_total) {
+  return guarded(ctx, [&] {
+    int rc = need_env(ctx);
+    if (rc) return rc;
+    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk || !pk || !d_partial) return DKG_E_ARG;
+    const size_t D = d1 - d0, items = 2 * D * n;
+    if (D && (!d_E || !d_A || !d_e1 || !d_ct || !d_dec2 || !d_dec4 || !d_A0)) return DKG_E_ARG;
+    if (flag_rows < D || (flag_rows && !d_flags)) return DKG_E_ARG;
+    if (!complaint_args_ok(n, C, accuser, accused, {proofs, verdict}) ||
+        !complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4}))
+      return DKG_E_ARG;
+    ShardProven sp;
+    sp.full = true, sp.pk = pk;
+    sp.C2 = C, sp.accuser2 = accuser, sp.accused2 = accused, sp.proofs = proofs, sp.verdict2 = verdict;
+    sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
+    sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
+    sp.flag_rows = flag_rows, sp.d_flags = d_flags, sp.d_dissent = d_dissent;
+    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
+    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+    shard_proven_upload(ctx, n, d0, D, sp);  // before the side stream forks: it reads the intake mask
+    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);
+    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
+    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
+    SharesScope pending(ctx);
+    if (D) {
+      if (side) {
+        HCK(hipEventRecord(ctx->side_fork, ctx->stream));
+        HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+      }
+      hipStream_t hy = side ? ctx->side : ctx->stream;
+      decrypt_device(ctx, D, n, dsk, (const uint32_t*)d_e1, (const uint32_t*)d_ct, rs, rsp, iok, eok, hy);
+      if (sp.df1) dkgk::and_mask(D, sp.df1, eok, hy);  // an absent phase-1 broadcast: a MISSING row as well
+      if (side) {
+        HCK(hipEventRecord(ctx->shares_done, ctx->side));
+        ctx->shares_pending = true;
+      }
+    }
+    with_binom_ded(ctx, [&] {
+      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, rs, rsp, d_dec2, d_dec4, d_A0,
+                 d_partial, eok, &sp, sp.df3, (const uint32_t*)d_e1, (const uint32_t*)d_ct);
+      check_launch(ctx);
+      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+      binom_mark_copy(ctx);
+      sync(ctx);
+    });
+    collect_phases(ctx);
+    collect_hybrid_phases(ctx);  // decryption phases only
+    shard_proven_verdicts(sp);
+    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
+    return DKG_OK;
+  });
+}
+
+int dkg_ctx_last_complaint_eval(const dkg_ctx* ctx) { return ctx ? ctx->last_complaint_eval : 0; }
 
 int dkg_ceremony_shard_recon_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const uint8_t* qualified,
                                     const uint8_t* reconstruct, const uint8_t* r2_error, const uint8_t* r4_error,
@@ -4053,6 +4384,72 @@ int dkg_shard_combine_packed_device(dkg_ctx* ctx, size_t n, size_t t, size_t wor
       dkgk::unpack_ranks(n, world_size, R, (const uint32_t*)d_pack2_g, dec2, ctx->stream);
       dkgk::unpack_ranks(n, world_size, R, (const uint32_t*)d_pack4_g, dec4, ctx->stream);
     });
+  });
+}
+
+// The combine of the sharded proven calls: dkg_shard_combine_packed_device's, except that the two sets
+// follow the ranks' flag words (round2_device's cmask path and the proven4 mask, as receivers_rounds_once
+// takes them), plus the sum of the dissent partials and the finalising parties' common outcome.
+int dkg_shard_combine_proven_device(dkg_ctx* ctx, size_t n, size_t t, size_t world_size, const void* d_pack2_g,
+                                    const void* d_pack4_g, const void* d_flags_g, const void* d_dissent_g, int full,
+                                    void* d_dec2, void* d_dec4, dkg_shard_outcome* out, int32_t* dissent,
+                                    int32_t* finalise_status, int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    if (!out || !d_pack2_g || !d_pack4_g || !d_flags_g || !world_size || world_size > n ||
+        dkg_env_check(t, n) != DKG_OK || (dissent && !d_dissent_g))
+      return DKG_E_ARG;
+    const size_t R = dkg_shard_rows(n, world_size);
+    hipStream_t st = ctx->stream;
+    uint8_t* dec2 = d_dec2 ? (uint8_t*)d_dec2 : buf<uint8_t>(ctx, "sc.dec2", n * n);
+    uint8_t* dec4 = d_dec4 ? (uint8_t*)d_dec4 : buf<uint8_t>(ctx, "sc.dec4", n * n);
+    uint8_t* qmask = buf<uint8_t>(ctx, "sc.qmask", n);
+    dkgk::unpack_ranks(n, world_size, R, (const uint32_t*)d_pack2_g, dec2, st);
+    dkgk::unpack_ranks(n, world_size, R, (const uint32_t*)d_pack4_g, dec4, st);
+    uint32_t* flags = buf<uint32_t>(ctx, "scp.flags", 4 * n);
+    uint8_t* masks = buf<uint8_t>(ctx, "scp.masks", 3 * n);  // cmask | proven4 | a_ok
+    dkgk::compact_ranks(n, world_size, R, 4, d_flags_g, flags, st);
+    dkgk::flag_masks(n, flags, masks, masks + n, masks + 2 * n, st);
+    uint8_t* rej2 = buf<uint8_t>(ctx, "sc.rej2", n);
+    int32_t* cnt = buf<int32_t>(ctx, "sc.cnt", 4 * n);
+    uint8_t* rej4 = buf<uint8_t>(ctx, "sc.rej4", n);
+    uint8_t* r4d = buf<uint8_t>(ctx, "sc.r4err", n);
+    round2_device(ctx, 1, n, dec2, qmask, rej2, cnt, full ? masks : nullptr);
+    round4_device(ctx, 1, n, t, dec4, qmask, rej4, r4d);
+    int32_t* dsum = buf<int32_t>(ctx, "scp.dissent", 4 * n);
+    if (dissent) dkgk::sum_partials_i32(world_size, n, (const int32_t*)d_dissent_g, dsum, st);
+    check_launch(ctx);
+    uint8_t* h = hbuf<uint8_t>(ctx, "scp.out", 12 * n);  // rej2 | proven4 | r4err | a_ok | cnt | dissent
+    d2h(ctx, h, rej2, n);
+    d2h(ctx, h + n, masks + n, n);
+    d2h(ctx, h + 2 * n, r4d, n);
+    d2h(ctx, h + 3 * n, masks + 2 * n, n);
+    d2h(ctx, h + 4 * n, cnt, 4 * n);
+    if (dissent) d2h(ctx, h + 8 * n, dsum, 4 * n);
+    sync(ctx);
+    std::vector<uint8_t> q(h, h + n), r2e(n), recon(h + n, h + 2 * n), r4e(h + 2 * n, h + 3 * n);
+    std::vector<int32_t> c(n);
+    memcpy(c.data(), h + 4 * n, 4 * n);
+    round2_host(n, t, q.data(), c.data(), r2e.data());
+    round4_host(n, q.data(), recon.data());  // reconstruct = qualified && some complaint holds (:639, :664-669)
+    int32_t nq = 0, nr = 0;
+    for (size_t i = 0; i < n; i++) {
+      nq += q[i];
+      nr += recon[i];
+    }
+    if (out->qualified) memcpy(out->qualified, q.data(), n);
+    if (out->complaints2) memcpy(out->complaints2, c.data(), 4 * n);
+    if (out->r2_error) memcpy(out->r2_error, r2e.data(), n);
+    if (out->reconstruct) memcpy(out->reconstruct, recon.data(), n);
+    if (out->r4_error) memcpy(out->r4_error, r4e.data(), n);
+    out->n_qualified = nq;
+    out->phase4_error = nq - nr <= (int32_t)t;  // committee.rs:673-677
+    if (dissent) memcpy(dissent, h + 8 * n, 4 * n);
+    int32_t index = -1;
+    const int32_t status = finalise_outcome(n, t, q.data(), recon.data(), r2e.data(), r4e.data(), h + 3 * n,
+                                            out->phase4_error != 0, &index);
+    if (finalise_status) *finalise_status = status;
+    if (recovery_index) *recovery_index = index;
+    return DKG_OK;
   });
 }
 

@@ -11,6 +11,11 @@ with the "nccl" backend, gloo in the CPU tests) of:
   * every dealer's compressed master-key term (A_i0, or g * a_i0 recovered by Lagrange
     interpolation on the owning rank for dealers accused in round 4),
   * each rank's partial final shares (sum over its qualified dealers of s_ij).
+The proven runs (run_verify_proven / run_verify_full_proven: each rank verifies the broadcast complaints
+against its own dealers, dkg_ceremony_shard_verify_proven_device / _full_proven_device) add to that block
+  * one flag word per row (a proven round-1 complaint, a round-4 complaint that holds, no phase-3
+    broadcast) and each rank's partial of dissent[j],
+still in ONE all-gather, and merge the ranks' verdict arrays with one all_reduce(MAX) per round.
 This module holds only the collectives.  The protocol layer runs in the library, behind the C ABI:
 dkg_shard_combine_device derives the common outcome (qualified set, complaints, r2 errors, SKIPPED
 rows, reconstruction set, r4 errors, Phase4 failure) with the single-GPU drivers' own code, and
@@ -60,9 +65,15 @@ class ShardResult:
                  (dkg_shard_finalise_device)"""
 
     def __init__(self, decisions: Decisions, final_share, public_share, mpk: Optional[bytes], ms_shard: float,
-                 ms_steps: Optional[Dict[str, float]] = None):
+                 ms_steps: Optional[Dict[str, float]] = None, verdict=None, verdict4=None, dissent=None,
+                 finalise_status: Optional[int] = None, recovery_index: Optional[int] = None):
         self.decisions, self._fs, self._pub = decisions, final_share, public_share
         self.mpk, self.ms_shard, self.ms_steps = mpk, ms_shard, dict(ms_steps or {})
+        # the proven runs (run_verify_proven / run_verify_full_proven), else None: the ceremony's merged
+        # verdict lists (round 2: full mode only), dissent [n] (full mode), and the finalising parties'
+        # common outcome in the dkg_amd._lib.FIN_* codes with the dealer of INSUFFICIENT / PANIC
+        self.verdict, self.verdict4, self.dissent = verdict, verdict4, dissent
+        self.finalise_status, self.recovery_index = finalise_status, recovery_index
 
     @staticmethod
     def _host(v):
@@ -129,6 +140,8 @@ class ShardedCeremony:
         self.fs = torch.empty(n * 32, **u8)
         self.pub = torch.empty(n * 32, **u8)
         self.D, self.R = D, R
+        self.p_send = None          # the proven runs' send block (_proven_init), allocated on first use
+        self._last_proven = False
 
     def _fence(self):
         """The library runs on its own HIP streams: before it reads buffers torch produced (the
@@ -150,10 +163,134 @@ class ShardedCeremony:
         """This rank's raw rows [D][n] -> its packed block [R][W+1] (dkg_decisions_pack_device)."""
         self.be.decisions_pack_device(self.R, self.D, self.n, self.d0, dec.data_ptr(), out.data_ptr())
 
-    def exchange_bytes(self) -> int:
+    def exchange_bytes(self, proven: Optional[bool] = None) -> int:
         """Bytes one rank contributes to the all-gather of one ceremony (without the round-4
-        reconstruction's second gather of the master-key terms)."""
-        return self.S
+        reconstruction's second gather of the master-key terms).  proven: the send block of the proven
+        runs, which carries [R] flag words and [n] dissent words more; None = the kind of the last run."""
+        if proven is None:
+            proven = self._last_proven
+        return self.S + 4 * self.R + 4 * self.n if proven else self.S
+
+    # ---- the proven runs: each rank verifies the complaints against its own dealers
+    def _proven_init(self):
+        """The proven runs' send block, still gathered in ONE collective: the packed block's [round-2
+        rows | round-4 rows | master-key terms | partial final shares], then [R] u32 flag words and [n]
+        i32 dissent partials.  The existing runs' block and buffers stay as they are."""
+        if not self.packed:
+            raise ValueError("the proven runs exchange packed rows: ShardedCeremony(packed=True)")
+        if self.p_send is not None:
+            return
+        torch, R, n, ws, S2 = self.torch, self.R, self.n, self.ws, self.S2
+        u8 = dict(dtype=torch.uint8, device=self.dev)
+        i32 = dict(dtype=torch.int32, device=self.dev)
+        self.SP = self.S + 4 * R + 4 * n
+        self.p_send = torch.zeros(self.SP, **u8)
+        self.pp2 = self.p_send[:S2].view(torch.int32)
+        self.pp4 = self.p_send[S2:2 * S2].view(torch.int32)
+        self.pA0 = self.p_send[2 * S2:2 * S2 + R * 32]
+        self.ppart = self.p_send[2 * S2 + R * 32:self.S]
+        self.pflags = self.p_send[self.S:self.S + 4 * R].view(torch.int32)
+        self.pdis = self.p_send[self.S + 4 * R:].view(torch.int32)
+        self.g_allp = torch.empty(ws * self.SP, **u8)
+        self.g_flags = torch.empty(ws * R, **i32)
+        self.g_dis = torch.empty(ws * n, **i32)
+
+    def exchange_proven(self):
+        """exchange() for the proven runs' block: also the gathered flag words [ws][R] and dissent
+        partials [ws][n]."""
+        self._pack(self.dec2, self.pp2)
+        self._pack(self.dec4, self.pp4)
+        self._all_gather(self.g_allp, self.p_send)
+        S2, R, ws, S, n, u8 = self.S2, self.R, self.ws, self.S, self.n, self.torch.uint8
+        g = self.g_allp.view(ws, self.SP)
+        self.g_dec2.view(u8).view(ws, S2).copy_(g[:, :S2])
+        self.g_dec4.view(u8).view(ws, S2).copy_(g[:, S2:2 * S2])
+        self.g_A0.view(ws, R * 32).copy_(g[:, 2 * S2:2 * S2 + R * 32])
+        self.g_part.view(ws, n * 32).copy_(g[:, 2 * S2 + R * 32:S])
+        self.g_flags.view(u8).view(ws, 4 * R).copy_(g[:, S:S + 4 * R])
+        self.g_dis.view(u8).view(ws, 4 * n).copy_(g[:, S + 4 * R:])
+        return self.g_dec2, self.g_dec4, self.g_A0, self.g_part, self.g_flags, self.g_dis
+
+    def _merge_verdicts(self, v):
+        """One all_reduce(MAX) over the ranks' verdict arrays: COMPLAINT_NOT_OWNED is below every real code
+        and exactly one rank owns each complaint.  Staged through the host under gloo, as _all_gather."""
+        if not len(v):
+            return []
+        host = self.dist.get_backend() == "gloo"
+        tt = self.torch.tensor(list(v), dtype=self.torch.int32, device="cpu" if host else self.dev)
+        self.dist.all_reduce(tt, op=self.dist.ReduceOp.MAX)
+        return tt.cpu().tolist()
+
+    def run_verify_proven(self, d_E: int, d_A: int, d_s: int, d_sp: int, accusers4, accused4, share4: bytes,
+                          randomness4: bytes, fetched1: Optional[bytes] = None, fetched3: Optional[bytes] = None,
+                          finalise: bool = True) -> ShardResult:
+        """run_verify whose reconstructable set follows the PROVEN round-4 complaints (round 2 keeps the
+        rejection rule: plaintext shares).  The whole broadcast complaint list goes to every rank (1-based
+        indices; share4 / randomness4 [C4][32]); fetched1 / fetched3: this rank's rows' intake masks."""
+        self._proven_init()
+        self._fence()
+        ms, v4 = self.be.ceremony_shard_verify_proven_device(
+            self.n, self.t, self.d0, self.d1, d_E, d_A, d_s, d_sp, accusers4, accused4, share4, randomness4,
+            self.dec2.data_ptr(), self.dec4.data_ptr(), self.pA0.data_ptr(), self.ppart.data_ptr(), self.R,
+            self.pflags.data_ptr(), fetched1=fetched1, fetched3=fetched3)
+        return self._finish_proven(ms, finalise, False, [], v4, d_s)
+
+    def run_verify_full_proven(self, d_E: int, d_A: int, d_e1: int, d_ct: int, sk: bytes, pk: bytes, accusers,
+                               accused, proofs: bytes, accusers4, accused4, share4: bytes, randomness4: bytes,
+                               fetched1: Optional[bytes] = None, fetched3: Optional[bytes] = None,
+                               finalise: bool = True) -> ShardResult:
+        """run_verify_full with both sets decided by the proven complaints: round-1 complaints (accusers,
+        accused, proofs [C][192]) against this ceremony's own ciphertexts, round-4 complaints as
+        run_verify_proven."""
+        self._proven_init()
+        self._fence()
+        ms, v, v4 = self.be.ceremony_shard_verify_full_proven_device(
+            self.n, self.t, self.d0, self.d1, d_E, d_A, d_e1, d_ct, sk, pk, accusers, accused, proofs, accusers4,
+            accused4, share4, randomness4, self.dec2.data_ptr(), self.dec4.data_ptr(), self.pA0.data_ptr(),
+            self.ppart.data_ptr(), self.R, self.pflags.data_ptr(), self.pdis.data_ptr(), fetched1=fetched1,
+            fetched3=fetched3)
+        return self._finish_proven(ms, finalise, True, v, v4, None)
+
+    def _finish_proven(self, ms: float, finalise: bool, full: bool, v, v4, d_s: Optional[int]) -> ShardResult:
+        from ._lib import FIN_PANIC, FIN_PHASE4_ERROR
+
+        n, t, ws = self.n, self.t, self.ws
+        self._last_proven = True
+        steps = {}
+        c0 = time.perf_counter()
+        self.exchange_proven()
+        verdict, verdict4 = self._merge_verdicts(v), self._merge_verdicts(v4)
+        self._fence()
+        c1 = time.perf_counter()
+        steps["exchange"] = (c1 - c0) * 1e3
+        o, dissent, status, index = self.be.shard_combine_proven_device(
+            n, t, ws, self.g_dec2.data_ptr(), self.g_dec4.data_ptr(), self.g_flags.data_ptr(),
+            self.g_dis.data_ptr() if full else None, full, self.c_dec2.data_ptr(), self.c_dec4.data_ptr())
+        dec = Decisions(self.c_dec2.view(n, n), self.c_dec4.view(n, n), np.array(o.qualified, dtype=np.uint8),
+                        np.array(o.complaints2, dtype=np.int32), np.array(o.r2_error, dtype=np.uint8),
+                        np.array(o.reconstruct, dtype=np.uint8), np.array(o.r4_error, dtype=np.uint8),
+                        o.phase4_error)
+        extra = dict(verdict=verdict if full else None, verdict4=verdict4, dissent=dissent, finalise_status=status,
+                     recovery_index=index)
+        c2 = time.perf_counter()
+        steps["combine"] = (c2 - c1) * 1e3
+        if not finalise:
+            return ShardResult(dec, None, None, None, ms, steps, **extra)
+        # nobody finalises after a Phase4 failure, and a panic of every party's finalise leaves no mpk
+        no_mpk = status in (FIN_PHASE4_ERROR, FIN_PANIC)
+        if dec.reconstruct.any() and not no_mpk:
+            no_mpk = self.be.ceremony_shard_recon_device(n, t, self.d0, self.d1, dec.qualified, dec.reconstruct, d_s,
+                                                         self.pA0.data_ptr(), dec.r2_error, dec.r4_error)
+            if not no_mpk:
+                self._all_gather(self.g_A0, self.pA0)
+                self._fence()
+        c3 = time.perf_counter()
+        steps["recon"] = (c3 - c2) * 1e3
+        mpk = self.be.shard_finalise_device(n, t, ws, self.g_A0.data_ptr(), self.g_part.data_ptr(), dec.qualified,
+                                            no_mpk, self.fs.data_ptr(), self.pub.data_ptr())
+        fs, pub = self.fs.clone(), self.pub.clone()
+        steps["finalise"] = (time.perf_counter() - c3) * 1e3
+        return ShardResult(dec, fs, pub, None if no_mpk else mpk, ms, steps, **extra)
 
     def exchange(self):
         """All-gather every rank's send block (one collective), then split the gathered [ws][S] blocks
@@ -212,6 +349,7 @@ class ShardedCeremony:
 
     def _finish(self, ms: float, finalise: bool, d_s: Optional[int] = None) -> ShardResult:
         n, t, ws = self.n, self.t, self.ws
+        self._last_proven = False
         steps = {}
         c0 = time.perf_counter()
         self.exchange()

@@ -810,6 +810,114 @@ int dkg_ceremony_batch_verify_full_proven(dkg_ctx *ctx, size_t B, size_t n, size
                                           uint8_t *s_prime_out, int32_t *verdict, int32_t *dissent, int32_t *verdict4,
                                           int32_t *finalise_status, int32_t *recovery_index);
 
+/* ---- dealer-sharded ceremonies that decide by the proven complaints ----
+ * dkg_ceremony_shard_verify_device / _shard_verify_full_device keep the rejection rule; these two calls
+ * decide a rank's dealers as the single-ceremony *_proven calls decide all of them.  Every fact that
+ * decides a complaint against dealer i lives on the rank that owns i (its E and A rows, its e1 / ct items
+ * and their decode mask, its round-2 qualification, its fetched3 bit; the accusers' keys are the pk [n]
+ * every rank takes), so each rank verifies the complaints against its own dealers and no exchange
+ * precedes round 3.
+ * Complaints: the WHOLE broadcast lists of the ceremony, host arrays as the single-ceremony calls take
+ * them (accuser, accused 1-based; every rank passes the same lists, as a broadcast channel delivers
+ * them).  The rank owns complaint c iff d0 < accused[c] <= d1 and verifies its owned complaints in their
+ * relative input order, duplicates allowed, against its own rows: the ciphertext pair of complaint
+ * (i, j) is items ((i - d0 - 1) n + j - 1) 2 + {0, 1} of d_e1 / d_ct (i, j 1-based), the commitments rows
+ * i - d0 - 1 of d_E / d_A.  verdict [C] / verdict4 [C4] (host, out): the owned complaints' verdicts, codes
+ * and precedence exactly those of dkg_complaints_verify and dkg_complaints3_verify (DKG_COMPLAINT_IGNORED
+ * for a round-2 complaint against a dealer with fetched1 == 0 and for a round-4 complaint against a
+ * dealer round 2 disqualified; DKG_COMPLAINT_NO_PHASE3); every other complaint reads
+ * DKG_COMPLAINT_NOT_OWNED, which is below every real code, so that the element-wise maximum over the
+ * ranks' arrays is the ceremony's verdict list (exactly one rank owns each complaint).
+ * C == 0 / C4 == 0 allow null complaint arrays and still apply the proven rule: nobody is disqualified
+ * except MISSING rows, nobody is reconstructed.  An index outside 1..n, or a null required pointer with
+ * C > 0, is DKG_E_ARG.  d1 == d0 (a rank without dealers: world_size > n / 2 leaves some) works.
+ * fetched1, fetched3: host [d1 - d0] intake masks of the rank's rows (NULL = all present), as
+ * dkg_ceremony_verify_fetched: fetched1[i] == 0 makes a MISSING row, fetched3[i] == 0 an accusation by
+ * every receiver in round 4 and verdict DKG_COMPLAINT_NO_PHASE3.
+ * Outputs as the rejection-rule calls, with the rank's qualified set taken from the rule:
+ * qualified[i] = row i is not MISSING and (full variant) no complaint against i has verdict 0 (plaintext
+ * variant: no REJECT either, as dkg_ceremony_verify_fetched_proven); d_partial sums the shares of those
+ * dealers; d_dec2 / d_dec4 / d_A0 are the raw rows as before (the combine applies SKIPPED), and the
+ * decrypted shares are remembered for dkg_ceremony_shard_recon_device(d_s = NULL).
+ * d_flags: device [flag_rows] u32, flag_rows >= d1 - d0 (pass dkg_shard_rows(n, world_size), the padded
+ * block height the ranks gather; the entry point does not know world_size); rows past the rank's dealer
+ * count are zero.  bit 0: some verdict-0 round-2 complaint against the row (never set by the plaintext
+ * variant); bit 1: some round-4 complaint against it holds (verdict 0 or 5); bit 2: the row has no
+ * usable phase-3 broadcast (fetched3 == 0 or an undecodable A row).
+ * d_dissent (full variant; device [n] i32, may be NULL): the rank's partial of dissent[j] -- its dealers
+ * that receiver j rejected without a verdict-0 complaint by j against them.
+ * The complaint stage runs on the device inside the call, after the rank's checks and before the call's
+ * one synchronisation; the owned complaints' index arrays and payloads go up in one staging copy.
+ * Where P_i(j) comes from (dkg_ctx_last_complaint_eval): with dkg_ctx_set_complaint_eval(0) and the
+ * fused group-check pipeline (dkg_ctx_set_overlap on, dkg_ctx_set_verify_mode 0) the rank's pass has
+ * evaluated P^E_i(j) and P^A_i(j) for every receiver of every one of its dealers, and the complaints
+ * read those elements -- source 3, "the calling pass": no Horner walk, no second set of tables.  With
+ * protocol-order rounds or interpolation the pass does not hold both rounds' evaluations and the call
+ * falls back to dkg_complaints_verify's switch (per accused row: Horner or tables); modes 1 and 2 of
+ * dkg_ctx_set_complaint_eval force that switch's sources here too.  Source 3 exists only inside these
+ * two calls and cannot be forced: dkg_ctx_set_complaint_eval(3) stays DKG_E_ARG.  Outputs do not depend
+ * on any of this. */
+#define DKG_COMPLAINT_NOT_OWNED (-2) /* the complaint's accused is another rank's dealer */
+int dkg_ceremony_shard_verify_proven_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1, const void *d_E,
+                                            const void *d_A, const void *d_s, const void *d_s_prime,
+                                            const uint8_t *fetched1, const uint8_t *fetched3, size_t C4,
+                                            const uint32_t *accuser4, const uint32_t *accused4, const uint8_t *share4,
+                                            const uint8_t *randomness4, void *d_dec2, void *d_dec4, void *d_A0,
+                                            void *d_partial, size_t flag_rows, void *d_flags, int32_t *verdict4,
+                                            double *ms_total);
+int dkg_ceremony_shard_verify_full_proven_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1,
+                                                 const void *d_E, const void *d_A, const void *d_e1, const void *d_ct,
+                                                 const uint8_t *sk, const uint8_t *pk, const uint8_t *fetched1,
+                                                 const uint8_t *fetched3, size_t C, const uint32_t *accuser,
+                                                 const uint32_t *accused, const uint8_t *proofs, size_t C4,
+                                                 const uint32_t *accuser4, const uint32_t *accused4,
+                                                 const uint8_t *share4, const uint8_t *randomness4, void *d_dec2,
+                                                 void *d_dec4, void *d_A0, void *d_partial, size_t flag_rows,
+                                                 void *d_flags, void *d_dissent, int32_t *verdict, int32_t *verdict4,
+                                                 double *ms_total);
+/* The evaluation source of the last sharded proven call on this ctx: 3 the calling pass, 1 Horner, 2
+ * tables, 12 both of the fallback switch within one call; 0 before the first such call and after one on
+ * a rank without dealers. */
+int dkg_ctx_last_complaint_eval(const dkg_ctx *ctx);
+/* dkg_shard_combine_packed_device for the proven calls: d_flags_g device [ws][R] u32 the gathered flag
+ * words (R = dkg_shard_rows), d_dissent_g device [ws][n] i32 the gathered dissent partials (NULL with
+ * dissent == NULL).  full != 0: the qualified set = the row is not MISSING and flag bit 0 is clear
+ * (round2_device's cmask path, the functions the single-GPU drivers use); full == 0: from the rows, as
+ * dkg_shard_combine_packed_device.  reconstruct[i] = qualified[i] && bit 1.  complaints2, r2_error,
+ * r4_error keep their meaning and come from the rows; d_dec4 carries the SKIPPED rows of that qualified
+ * set.  dissent [n] (host, may be NULL): the sum of the partials.  finalise_status / recovery_index (may
+ * be NULL): the finalising parties' common outcome in the DKG_FIN_* codes as
+ * dkg_ceremony_verify_fetched_proven reports it, a dealer's usable phase-3 broadcast taken from bit 2 --
+ * OK, PHASE4_ERROR, INSUFFICIENT with the first reconstructed dealer, PANIC with the first qualified
+ * dealer without a phase-3 broadcast that nobody complained about.  A caller that sees PANIC or
+ * PHASE4_ERROR passes phase4_error = 1 to dkg_shard_finalise_device (an all-zero mpk, as the
+ * single-ceremony call returns); INSUFFICIENT is what dkg_ceremony_shard_recon_device reports as
+ * recovery_error. */
+int dkg_shard_combine_proven_device(dkg_ctx *ctx, size_t n, size_t t, size_t world_size, const void *d_pack2_g,
+                                    const void *d_pack4_g, const void *d_flags_g, const void *d_dissent_g, int full,
+                                    void *d_dec2, void *d_dec4, dkg_shard_outcome *out, int32_t *dissent,
+                                    int32_t *finalise_status, int32_t *recovery_index);
+/* dkg_ceremony_verify_fetched_proven / dkg_ceremony_verify_full_proven over the shards of a multi-device
+ * context, argument lists as there: each shard calls its sharded proven entry point on its host thread
+ * with the whole complaint lists, packs its rows, and the flag words and dissent partials join the
+ * peer-copy gather; the verdicts are merged on the host (exactly one shard owns each complaint).  Every
+ * output -- out (E, A, s, s_prime NULL, as the other dkg_multi calls), verdict, verdict4, dissent,
+ * finalise_status, recovery_index -- equals the single-context call's. */
+int dkg_multi_ceremony_verify_proven(dkg_multi *m, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                     const uint8_t *s, const uint8_t *s_prime, const uint8_t *fetched1,
+                                     const uint8_t *fetched3, size_t C4, const uint32_t *accuser4,
+                                     const uint32_t *accused4, const uint8_t *share4, const uint8_t *randomness4,
+                                     dkg_ceremony_out *out, int32_t *verdict4, int32_t *finalise_status,
+                                     int32_t *recovery_index);
+int dkg_multi_ceremony_verify_full_proven(dkg_multi *m, size_t n, size_t t, const uint8_t *E, const uint8_t *A,
+                                          const uint8_t *e1, const uint8_t *ct, const uint8_t *sk, const uint8_t *pk,
+                                          size_t C, const uint32_t *accuser, const uint32_t *accused,
+                                          const uint8_t *proofs, const uint8_t *fetched3, size_t C4,
+                                          const uint32_t *accuser4, const uint32_t *accused4, const uint8_t *share4,
+                                          const uint8_t *randomness4, dkg_ceremony_out *out, int32_t *verdict,
+                                          int32_t *dissent, int32_t *verdict4, int32_t *finalise_status,
+                                          int32_t *recovery_index);
+
 /* ---- synthetic inputs: the seeded RNG convention ----
  * dealer seed = BLAKE2b-256("dkg-amd/v1/dealer" || master[32] || u32le ceremony || u32le dealer);
  * coefficients = ChaCha20Rng(seed): hiding b_0..b_t first, then sharing a_0..a_t (committee.rs:143-146),
