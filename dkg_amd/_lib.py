@@ -50,6 +50,12 @@ class CeremonyOut(ctypes.Structure):
     ]
 
 
+class ReceiverPlan(ctypes.Structure):
+    """dkg_receiver_plan (include/dkg_amd.h)."""
+    _fields_ = [("chunk", ctypes.c_uint32), ("stages", ctypes.c_uint32), ("arity", ctypes.c_uint32 * 16),
+                ("mult", (ctypes.c_uint8 * 32) * 16)]
+
+
 class ShardOutcome(ctypes.Structure):
     _fields_ = [
         ("qualified", ctypes.c_void_p), ("complaints2", ctypes.c_void_p), ("r2_error", ctypes.c_void_p),
@@ -140,6 +146,16 @@ def lib():
     L.dkg_share_gen.argtypes = [p, sz, sz, sz, u8p, u8p, p, p, p, p]
     L.dkg_verify_pairs.argtypes = [p, sz, sz, ctypes.c_int, sz, sz, u8p, u8p, p, p]
     L.dkg_verify_receiver.argtypes = [p, sz, sz, ctypes.c_int, sz, u8p, u8p, p, p]
+    L.dkg_receiver_plan_for.argtypes = [sz, sz, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ReceiverPlan)]
+    L.dkg_receiver_plan_cost_us.argtypes = [sz, sz, ctypes.c_uint32, ctypes.POINTER(ReceiverPlan)]
+    L.dkg_receiver_plan_cost_us.restype = ctypes.c_double
+    L.dkg_receiver_plan_constants.argtypes = [ctypes.POINTER(ctypes.c_double)]
+    L.dkg_receiver_plan_constants.restype = None
+    L.dkg_ctx_set_receiver_chunk.argtypes = [p, ctypes.c_int]
+    L.dkg_ctx_last_receiver_chunk.argtypes = [p]
+    L.dkg_commitment_eval.argtypes = [p, sz, sz, sz, p, u8p, p, p]
+    L.dkg_verify_receivers.argtypes = [p, sz, sz, ctypes.c_int, sz, p, u8p, u8p, p, p, p]
+    L.dkg_party_round2.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -275,4 +291,6 @@ EXPORTED = [
     "dkg_ceremony_shard_verify_proven_device", "dkg_ceremony_shard_verify_full_proven_device",
     "dkg_ctx_last_complaint_eval", "dkg_shard_combine_proven_device",
     "dkg_multi_ceremony_verify_proven", "dkg_multi_ceremony_verify_full_proven",
+    "dkg_receiver_plan_for", "dkg_receiver_plan_cost_us", "dkg_receiver_plan_constants", "dkg_ctx_set_receiver_chunk",
+    "dkg_ctx_last_receiver_chunk", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
 ]

@@ -267,12 +267,14 @@ class Backend:
     def phase_times(self, tag="r24") -> dict:
         """Device ms of binomial / stepping / combine / check in the last ceremony's checks: tag "r24" (rounds
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
-        encryption / decryption kernels of the last full-mode ceremony).  Only recorded with
+        encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
+        commitment_eval, verify_receivers, party_round2).  Only recorded with
         set_streams(1); -1 otherwise."""
         L = _lib.lib()
         if isinstance(tag, int):
             tag = f"r{tag}"
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
+                 else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
         return {k: L.dkg_ctx_phase_ms(self._ctx, f"{tag}.{k}".encode()) for k in names}
@@ -336,6 +338,51 @@ class Backend:
         dec = ctypes.create_string_buffer(max(n, 1))
         _check(self._ctx, _lib.lib().dkg_verify_receiver(self._ctx, n, t, rnd, j, C, s_col, sp_col, dec))
         return dec.raw[:n]
+
+    # ---- one party's view (chunked evaluation, receivers.hip)
+    def set_receiver_chunk(self, chunk: int = 0):
+        """Chunk length of commitment_eval / verify_receivers / party_round2: 0 automatic (receiver_plan),
+        >= 1 forced.  Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_receiver_chunk(self._ctx, chunk))
+
+    def last_receiver_chunk(self) -> int:
+        return _lib.lib().dkg_ctx_last_receiver_chunk(self._ctx)
+
+    def commitment_eval(self, D: int, t: int, js: Sequence[int], C: bytes):
+        """(P, ok): P[m][i] = sum_k (js[m]+1)^k C_i[k] as M*D encodings, ok [D] = row i decodes (its P zero
+        otherwise)."""
+        M = len(js)
+        arr = (ctypes.c_uint32 * max(M, 1))(*js)
+        P = ctypes.create_string_buffer(max(32 * M * D, 1))
+        ok = ctypes.create_string_buffer(max(D, 1))
+        _check(self._ctx, _lib.lib().dkg_commitment_eval(self._ctx, D, t, M, arr, C, P, ok))
+        return P.raw[: 32 * M * D], ok.raw[:D]
+
+    def verify_receivers(self, n: int, t: int, rnd: int, js: Sequence[int], C: bytes, s_cols: bytes,
+                         sp_cols: Optional[bytes] = None, qualified: Optional[bytes] = None) -> bytes:
+        """verify_receiver for the indices js (0-based) in one call: s_cols / sp_cols [M][n][32], decisions
+        [M][n]; qualified [n] (round 4): 0 marks SKIPPED."""
+        M = len(js)
+        arr = (ctypes.c_uint32 * max(M, 1))(*js)
+        dec = ctypes.create_string_buffer(max(M * n, 1))
+        _check(self._ctx, _lib.lib().dkg_verify_receivers(self._ctx, n, t, rnd, M, arr, C, s_cols, sp_cols, qualified,
+                                                           dec))
+        return dec.raw[: M * n]
+
+    def party_round2(self, n: int, t: int, j: int, E: bytes, e1_col: bytes, ct_col: bytes, sk: bytes,
+                     w: Optional[bytes] = None) -> dict:
+        """Round 2 of party j in full mode: e1_col, ct_col [n][2][32] addressed to j, sk its secret key, w
+        [n][64] the proofs' nonces (None: no proofs).  Keys: s, s_prime, dec, complaints, r2_error, proofs."""
+        s = ctypes.create_string_buffer(32 * n)
+        sp = ctypes.create_string_buffer(32 * n)
+        dec = ctypes.create_string_buffer(n)
+        cnt = ctypes.c_int32(0)
+        err = ctypes.c_uint8(0)
+        prf = ctypes.create_string_buffer(192 * n) if w is not None else None
+        _check(self._ctx, _lib.lib().dkg_party_round2(self._ctx, n, t, j, E, e1_col, ct_col, sk, w, s, sp, dec,
+                                                       ctypes.byref(cnt), ctypes.byref(err), prf))
+        return {"s": s.raw, "s_prime": sp.raw, "dec": dec.raw, "complaints": cnt.value, "r2_error": err.value,
+                "proofs": prf.raw if prf is not None else None}
 
     # ---- whole ceremony
     def _ceremony_out(self, n, t, big):
@@ -990,6 +1037,27 @@ def key_comb_choice(keys: int, items_per_key: int, cached10: bool = False, cache
     """The cost rule of the sharded full calls (dkg_key_comb_choice): 1 = radix 2^10 tables, 2 = radix-16
     combs, whichever builds (unless cached) and multiplies `items_per_key` items per key faster."""
     return _lib.lib().dkg_key_comb_choice(keys, items_per_key, int(bool(cached10)), int(bool(cached16)))
+
+
+def receiver_plan(n: int, t: int, x: int, chunk: int = 0) -> dict:
+    """dkg_receiver_plan_for (host only): the chunk length and fold stages the one-party evaluation runs
+    for receiver index x (1-based).  Keys: chunk, stages, arity [stages], mult [stages] (ints),
+    cost_us (the rule's estimate)."""
+    p = _lib.ReceiverPlan()
+    L = _lib.lib()
+    rc = L.dkg_receiver_plan_for(n, t, x, chunk, ctypes.byref(p))
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "receiver_plan")
+    return {"chunk": p.chunk, "stages": p.stages, "arity": list(p.arity[: p.stages]),
+            "mult": [int.from_bytes(bytes(p.mult[s]), "little") for s in range(p.stages)],
+            "cost_us": L.dkg_receiver_plan_cost_us(n, t, x, ctypes.byref(p))}
+
+
+def receiver_plan_constants() -> dict:
+    """The rule's fitted constants (dkg_receiver_plan_constants)."""
+    c = (ctypes.c_double * 5)()
+    _lib.lib().dkg_receiver_plan_constants(c)
+    return dict(zip(("launch_us", "op_latency_us", "lane_op_us", "serial_op_latency_us", "chunked_setup_us"), c))
 
 
 def key_comb_constants() -> dict:

@@ -35,4 +35,8 @@ bool short_multipliers(const Zl& y, int K, uint8_t (*mag)[32], int8_t* sign, boo
 bool jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t* da, int8_t* db, int16_t* top,
                 int npos = 256);
 
+// receiver_plan.cpp: the NAF of a little-endian 256-bit value as +1 / -1 digit bits; returns its
+// length (the top digit is +1 at length - 1; 0 for zero), *weight (may be null) its nonzero digits.
+int naf256(const uint8_t v[32], uint32_t pos[8], uint32_t neg[8], int* weight);
+
 }  // namespace dkgh

@@ -405,4 +405,22 @@ void interp_decide(size_t D, size_t nrecv, size_t N, size_t dealer_base, size_t 
 // ok[i] &= extra[i], i < D
 void and_mask(size_t D, const uint8_t* extra, uint8_t* ok, hipStream_t stream);
 
+// ---- one party's share checks (receivers.hip): P_i(x) for a few receiver indices, chunked Horner
+// stage 1: chunks of L coefficients of the position-major table C [40][N][npad] for the Ms index slots
+// m0 .. m0 + Ms - 1 of xs (1-based indices): Q [40][Ms][G][npad], G = ceil(N / L); with G == 1 the
+// values go to R [(m0 + m) * ndealers + d][40] (point-major) instead
+void recv_chunks(size_t ndealers, size_t npad, size_t N, size_t L, const uint32_t* C, const uint32_t* xs, size_t m0,
+                 size_t Ms, uint32_t* Q, uint32_t* R, hipStream_t stream);
+// one fold stage: groups of r consecutive partials of in [40][Ms][Gin][npad] by Horner in the stage's
+// multiplier; digits + (m0 + m) * dstride: NAF +1 bits (8 words), -1 bits (8 words), length.  out
+// [40][Ms][ceil(Gin / r)][npad], or R (as recv_chunks) when one value per slot is left
+void recv_fold(size_t ndealers, size_t npad, size_t Gin, size_t r, const uint32_t* in, const uint32_t* digits,
+               size_t dstride, size_t m0, size_t Ms, uint32_t* out, uint32_t* R, hipStream_t stream);
+// dec [M][n] holds check's accept / reject of every pair; rows that do not decode, SELF (i + 1 == xs[m])
+// and SKIPPED (qualified, may be null) are applied in place
+void recv_decide(size_t M, size_t n, int round, const uint32_t* xs, const uint8_t* dok, const uint8_t* qualified,
+                 uint8_t* dec, hipStream_t stream);
+// P [M][D][8] = encodings of R [M * D][40], zero where dok[i] == 0
+void recv_encode(size_t M, size_t D, const uint32_t* R, const uint8_t* dok, uint32_t* P, hipStream_t stream);
+
 }  // namespace dkgk

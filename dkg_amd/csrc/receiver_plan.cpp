@@ -1,0 +1,145 @@
+// dkg_receiver_plan_for: how one party's evaluations P_i(x) = sum_k x^k C_i[k] are cut into chunks
+// and folded (receivers.hip runs exactly this plan).  Host only, a pure function of (n, t, x, chunk).
+#include <cstring>
+
+#include "../../include/dkg_amd.h"
+#include "host_crypto.h"
+
+namespace dkgh {
+
+// NAF of a 256-bit little-endian value: +1 / -1 digit bits in pos / neg (8 words each); returns the
+// length (0 for zero; the top digit is +1 at length - 1, which is <= 255 for a value < 2^255).
+int naf256(const uint8_t v[32], uint32_t pos[8], uint32_t neg[8], int* weight) {
+  uint32_t w[9] = {0};
+  for (int i = 0; i < 32; i++) w[i / 4] |= (uint32_t)v[i] << (8 * (i % 4));
+  memset(pos, 0, 32);
+  memset(neg, 0, 32);
+  int len = 0, wt = 0;
+  for (int i = 0; i < 257; i++) {
+    bool any = false;
+    for (int k = 0; k < 9; k++) any |= w[k] != 0;
+    if (!any) break;
+    if (w[0] & 1u) {
+      wt++;
+      if ((w[0] & 3u) == 1u) {
+        if (i < 256) pos[i / 32] |= 1u << (i % 32);
+        w[0] -= 1;  // the low bit is set: no borrow
+      } else {
+        if (i < 256) neg[i / 32] |= 1u << (i % 32);
+        for (int k = 0; k < 9 && ++w[k] == 0; k++) {}
+      }
+      len = i + 1;
+    }
+    for (int k = 0; k < 8; k++) w[k] = (w[k] >> 1) | (w[k + 1] << 31);
+    w[8] >>= 1;
+  }
+  if (weight) *weight = wt;
+  return len;
+}
+
+}  // namespace dkgh
+
+namespace {
+
+using dkgh::naf256;
+
+// doublings + additions of the signed-digit chain of multiplier m (1: none)
+int chain_ops(const uint8_t m[32]) {
+  uint32_t p[8], q[8];
+  int wt = 0;
+  const int len = naf256(m, p, q, &wt);
+  return len <= 1 ? 0 : (len - 1) + (wt - 1);
+}
+
+void u32_bytes(uint8_t out[32], uint32_t x) {
+  memset(out, 0, 32);
+  for (int i = 0; i < 4; i++) out[i] = (uint8_t)(x >> (8 * i));
+}
+
+// The plan's multipliers for a forced chunk; false if it needs more than 16 stages.
+bool fill_plan(size_t N, uint32_t x, size_t L, dkg_receiver_plan* out) {
+  memset(out, 0, sizeof *out);
+  if (L >= N) {  // one chunk: the serial walk
+    out->chunk = (uint32_t)(L > 0xffffffffu ? 0xffffffffu : L);
+    return true;
+  }
+  out->chunk = (uint32_t)L;
+  dkgh::Zl y = dkgh::zl_from_u64(1);
+  const dkgh::Zl xz = dkgh::zl_from_u64(x);
+  for (size_t k = 0; k < L; k++) y = dkgh::zl_mul(y, xz);  // x^L: the integer itself while below l
+  size_t G = (N + L - 1) / L;
+  uint32_t s = 0;
+  while (G > 1) {
+    if (s == 16) return false;
+    out->arity[s] = 2;
+    dkgh::zl_to_bytes(out->mult[s], y);
+    y = dkgh::zl_mul(y, y);
+    G = (G + 1) / 2;
+    s++;
+  }
+  out->stages = s;
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The fitted rule ("one party's checks"; profiles/receivers_time.json): a launch
+// costs RP_LAUNCH_US, a dependent point operation RP_LAT_US while the launch leaves the SIMDs
+// under-occupied, and n lanes' worth of operations RP_THR_US each once the device is full.  The serial
+// walk is k_horner, built with the product-scanning field multiplication: its dependent operation
+// costs RP_SERIAL_LAT_US.  A plan with fold stages also pays RP_SETUP_US on the host side of the call
+// (its indices and digits are uploaded).
+static const double RP_LAUNCH_US = 7.1, RP_LAT_US = 2.0, RP_THR_US = 2.2e-5, RP_SERIAL_LAT_US = 2.77,
+                    RP_SETUP_US = 1.75;
+
+void dkg_receiver_plan_constants(double c[5]) {
+  if (!c) return;
+  c[0] = RP_LAUNCH_US, c[1] = RP_LAT_US, c[2] = RP_THR_US, c[3] = RP_SERIAL_LAT_US, c[4] = RP_SETUP_US;
+}
+
+double dkg_receiver_plan_cost_us(size_t n, size_t t, uint32_t x, const dkg_receiver_plan* p) {
+  if (!p || !n || !x) return -1.0;
+  const size_t N = t + 1;
+  uint8_t xb[32];
+  u32_bytes(xb, x);
+  const double cx = chain_ops(xb) + 1, lanes = (double)((n + 63) / 64 * 64);
+  const size_t L = p->chunk < N ? p->chunk : N;
+  size_t G = (N + L - 1) / L;
+  const double lat = p->stages ? RP_LAT_US : RP_SERIAL_LAT_US;
+  double us = (p->stages ? RP_SETUP_US : 0.0) + RP_LAUNCH_US + lat * (double)(L - 1) * cx + RP_THR_US * lanes * (double)(N - G) * cx;
+  for (uint32_t s = 0; s < p->stages; s++) {
+    const size_t r = p->arity[s], Gout = (G + r - 1) / r;
+    const double cy = chain_ops(p->mult[s]) + 1;
+    us += RP_LAUNCH_US + RP_LAT_US * (double)(r - 1) * cy + RP_THR_US * lanes * (double)(G - Gout) * cy;
+    G = Gout;
+  }
+  return us;
+}
+
+int dkg_receiver_plan_for(size_t n, size_t t, uint32_t x, int chunk, dkg_receiver_plan* out) {
+  if (!out || n == 0 || x == 0 || (size_t)x > n || chunk < 0) return DKG_E_ARG;
+  const size_t N = t + 1;
+  if (chunk > 0) return fill_plan(N, x, (size_t)chunk, out) ? DKG_OK : DKG_E_ARG;
+  // automatic: the cheapest of the serial walk and the power-of-two chunks by the fitted rule
+  dkg_receiver_plan best;
+  fill_plan(N, x, N, &best);
+  double best_us = dkg_receiver_plan_cost_us(n, t, x, &best);
+  uint8_t xb[32];
+  u32_bytes(xb, x);
+  const long serial_chain = (long)(N - 1) * (chain_ops(xb) + 1);
+  for (size_t L = 2; L < N && L <= 64; L *= 2) {
+    dkg_receiver_plan p;
+    if (!fill_plan(N, x, L, &p)) continue;
+    long chain = (long)(L - 1) * (chain_ops(xb) + 1);
+    for (uint32_t k = 0; k < p.stages; k++) chain += (long)(p.arity[k] - 1) * (chain_ops(p.mult[k]) + 1);
+    if (chain > serial_chain) continue;  // a longer chain AND more work and launches never pays
+    const double us = dkg_receiver_plan_cost_us(n, t, x, &p);
+    if (us < best_us) best_us = us, best = p;
+  }
+  *out = best;
+  return DKG_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,189 @@
+// One party's share checks on gfx950: P_i(x) = sum_k x^k C_i[k] for a FEW receiver indices x and
+// all dealers i (the shared-scalar case of vartime_multiscalar_multiplication, committee.rs:287-296
+// and :532-539, as Phases<Phase1>::proceed / Phases<Phase3>::proceed run it for one party).
+// k_horner (kernels.hip) walks the t + 1 coefficients as ONE dependent chain per dealer; here the
+// polynomial is cut into G chunks of L coefficients that are walked side by side,
+//   stage 1  Q_u = sum_{k < L} x^k C[uL + k]            lane = (dealer, chunk u, receiver)
+//   stage 2  groups of r consecutive partials folded by Horner in y_s (y_0 = x^L, y_{s+1} = y_s^r),
+// so the chain is L - 1 small multiplications and one long one per fold stage.  Every multiplier is
+// the same for all dealers, hence uniform over the wave (dealers run along the wave); the long ones
+// come from the host as signed digits (dkg_receiver_plan_for).  Every addition is the complete
+// formula, so identity rows, equal operands and torsion representatives need no redo.
+// Built twice like kernels.hip (dkg_amd/Makefile): namespace dkgk, and dkgk_ilp with DKG_FE_ILP.
+#ifdef DKG_FE_ILP
+#define dkgk dkgk_ilp
+#endif
+#include "kernels.h"
+#include "points.h"
+
+namespace dkgk {
+
+namespace {
+
+// lane's cached addend in the wave's LDS slot, then y += it
+DKG_DEV void add_point_lds(ge_p3& y, const ge_p3& c, uint32_t* q) {
+  ge_cached cc;
+  ge_to_cached(cc, c);
+  lds_put_cached(q, cc);
+  ge_add_lds(y, y, q, false);
+}
+
+// y = m y for a wave-uniform small m (small_recode's chain; m = 1 is the empty chain); q clobbered
+DKG_DEV void recv_mul_small(ge_p3& y, uint32_t pos, uint32_t neg, int len, uint32_t* q) {
+  if (len <= 1) return;
+  {
+    ge_cached xc;
+    ge_to_cached(xc, y);
+    lds_put_cached(q, xc);
+  }
+#pragma unroll 1
+  for (int i = len - 2; i >= 0; i--) {
+    const uint32_t bit = 1u << i;
+    const bool nz = ((pos | neg) & bit) != 0;
+    ge_dbl_lean(y, y, nz || i == 0);
+    if (nz) ge_add_lds(y, y, q, (neg & bit) != 0, 64, i == 0);  // T only for the result
+  }
+}
+
+// y = m y for a wave-uniform multiplier of up to 255 bits: dg = NAF digits, +1 in words 0..7, -1 in
+// words 8..15, length in word 16 (top digit +1 at length - 1)
+DKG_DEV void recv_mul_long(ge_p3& y, const uint32_t* __restrict__ dg, uint32_t* q) {
+  const int len = (int)dg[16];
+  if (len <= 1) return;
+  {
+    ge_cached xc;
+    ge_to_cached(xc, y);
+    lds_put_cached(q, xc);
+  }
+#pragma unroll 1
+  for (int i = len - 2; i >= 0; i--) {
+    const uint32_t bit = 1u << (i & 31);
+    const uint32_t p = dg[i >> 5] & bit, n = dg[8 + (i >> 5)] & bit;
+    const bool nz = (p | n) != 0;
+    ge_dbl_lean(y, y, nz || i == 0);
+    if (nz) ge_add_lds(y, y, q, n != 0, 64, i == 0);
+  }
+}
+
+// final values: point-major R[m * ndealers + d] (what check and k_recv_encode read)
+DKG_DEV void recv_store(bool last, uint32_t* __restrict__ out, size_t ostride, size_t oidx, uint32_t* __restrict__ R,
+                        size_t ridx, bool live, const ge_p3& acc) {
+  if (!last) pt_store(out, ostride, oidx, acc);
+  else if (live) pt_store_aos(R, ridx, acc);
+}
+
+}  // namespace
+
+// Stage 1.  C position-major [40][N][npad]; xs[m] = receiver index (1-based) of slot m0 + blockIdx.z.
+// Q [40][Ms][G][npad] (dealers minor), or R when G == 1.
+__global__ __launch_bounds__(64, 3) void k_recv_chunks(size_t ndealers, size_t npad, size_t N, size_t L, size_t G,
+                                                       const uint32_t* __restrict__ C,
+                                                       const uint32_t* __restrict__ xs, size_t m0,
+                                                       uint32_t* __restrict__ Q, uint32_t* __restrict__ R) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* q = qs + threadIdx.x;
+  const size_t d = (size_t)blockIdx.x * 64 + threadIdx.x;  // < npad: the grid is npad / 64 wide
+  const size_t u = blockIdx.y, m = blockIdx.z;
+  const uint32_t x = xs[m0 + m];
+  uint32_t pos, neg;
+  const int len = small_recode(x, pos, neg);
+  const size_t lo = u * L, hi = lo + L < N ? lo + L : N;
+  const size_t S = N * npad;
+  ge_p3 acc, c;
+  pt_load(acc, C, S, (hi - 1) * npad + d);
+#pragma unroll 1
+  for (size_t k = hi - 1; k-- > lo;) {
+    recv_mul_small(acc, pos, neg, len, q);
+    pt_load(c, C, S, k * npad + d);
+    add_point_lds(acc, c, q);
+  }
+  recv_store(G == 1, Q, (size_t)gridDim.z * G * npad, (m * G + u) * npad + d, R, (m0 + m) * ndealers + d,
+             d < ndealers, acc);
+}
+
+// Stage 2, one fold stage: out[v] = sum_{i < r} y^i in[v r + i] over the partials that exist
+// (Gin need not be a multiple of r).  dg: the stage's digits of slot m0 + blockIdx.z (17 words, stride dstride).
+__global__ __launch_bounds__(64, 3) void k_recv_fold(size_t ndealers, size_t npad, size_t Gin, size_t r,
+                                                     const uint32_t* __restrict__ in,
+                                                     const uint32_t* __restrict__ digits, size_t dstride, size_t m0,
+                                                     uint32_t* __restrict__ out, uint32_t* __restrict__ R) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* q = qs + threadIdx.x;
+  const size_t d = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const size_t v = blockIdx.y, m = blockIdx.z, Gout = gridDim.y;
+  const uint32_t* dg = digits + (m0 + m) * dstride;
+  const size_t first = v * r, cnt = first + r <= Gin ? r : Gin - first;
+  const size_t S = (size_t)gridDim.z * Gin * npad, base = (m * Gin + first) * npad + d;
+  ge_p3 acc, c;
+  pt_load(acc, in, S, base + (cnt - 1) * npad);
+#pragma unroll 1
+  for (size_t i = cnt - 1; i-- > 0;) {
+    recv_mul_long(acc, dg, q);
+    pt_load(c, in, S, base + i * npad);
+    add_point_lds(acc, c, q);
+  }
+  recv_store(Gout == 1, out, (size_t)gridDim.z * Gout * npad, (m * Gout + v) * npad + d, R, (m0 + m) * ndealers + d,
+             d < ndealers, acc);
+}
+
+// Decisions [M][n] from the group equation's outcome eq[m * n + i] (check with an all-ones mask and no
+// self index): undecodable rows (MISSING in round 2, REJECT in round 4), SELF where i == js[m], and
+// SKIPPED for a dealer outside the qualified set (round 4, committee.rs:522), in check's order.
+__global__ __launch_bounds__(256) void k_recv_decide(size_t M, size_t n, int round, const uint32_t* __restrict__ xs,
+                                                     const uint8_t* __restrict__ dok,
+                                                     const uint8_t* __restrict__ qualified,
+                                                     uint8_t* __restrict__ dec) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= M * n) return;
+  const size_t m = p / n, i = p % n;
+  uint8_t v = dok[i] ? dec[p] : (round == 2 ? 4 : 0);
+  if (qualified && !qualified[i]) v = 3;
+  if ((uint32_t)(i + 1) == xs[m]) v = 2;
+  dec[p] = v;
+}
+
+// P [M][D][8 words] = the encodings of R [M * D][40] (point-major), zero where row i did not decode
+__global__ __launch_bounds__(256) void k_recv_encode(size_t M, size_t D, const uint32_t* __restrict__ R,
+                                                     const uint8_t* __restrict__ dok, uint32_t* __restrict__ P) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= M * D) return;
+  ge_p3 pt;
+  pt_load_aos(pt, R, p);
+  uint32_t w[8];
+  ristretto_encode(w, pt);
+  if (!dok[p % D]) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = 0;
+  }
+  st_words8(P + 8 * p, w);
+}
+
+void recv_chunks(size_t ndealers, size_t npad, size_t N, size_t L, const uint32_t* C, const uint32_t* xs, size_t m0,
+                 size_t Ms, uint32_t* Q, uint32_t* R, hipStream_t stream) {
+  if (!ndealers || !Ms || !N || !L) return;
+  const size_t G = (N + L - 1) / L;
+  hipLaunchKernelGGL(k_recv_chunks, dim3((unsigned)(npad / 64), (unsigned)G, (unsigned)Ms), dim3(64), 0, stream,
+                     ndealers, npad, N, L, G, C, xs, m0, Q, R);
+}
+
+void recv_fold(size_t ndealers, size_t npad, size_t Gin, size_t r, const uint32_t* in, const uint32_t* digits,
+               size_t dstride, size_t m0, size_t Ms, uint32_t* out, uint32_t* R, hipStream_t stream) {
+  if (!ndealers || !Ms || Gin < 2 || r < 2) return;
+  const size_t Gout = (Gin + r - 1) / r;
+  hipLaunchKernelGGL(k_recv_fold, dim3((unsigned)(npad / 64), (unsigned)Gout, (unsigned)Ms), dim3(64), 0, stream,
+                     ndealers, npad, Gin, r, in, digits, dstride, m0, out, R);
+}
+
+void recv_decide(size_t M, size_t n, int round, const uint32_t* xs, const uint8_t* dok, const uint8_t* qualified,
+                 uint8_t* dec, hipStream_t stream) {
+  if (!M || !n) return;
+  hipLaunchKernelGGL(k_recv_decide, dim3((unsigned)((M * n + 255) / 256)), dim3(256), 0, stream, M, n, round, xs, dok,
+                     qualified, dec);
+}
+
+void recv_encode(size_t M, size_t D, const uint32_t* R, const uint8_t* dok, uint32_t* P, hipStream_t stream) {
+  if (!M || !D) return;
+  hipLaunchKernelGGL(k_recv_encode, dim3((unsigned)((M * D + 255) / 256)), dim3(256), 0, stream, M, D, R, dok, P);
+}
+
+}  // namespace dkgk

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <array>
 #include <map>
 #include <memory>
 #include <string>
@@ -36,6 +37,10 @@ struct dkg_ctx {
   hipEvent_t pev[5] = {};               // phase profiling inside verify_device (nsub == 1)
   hipEvent_t hev[9] = {};               // full mode: encrypt / decrypt kernels (nsub == 1)
   hipEvent_t bpev[3] = {};              // batches by proven complaints: around the two complaint stages
+  hipEvent_t rpev[7] = {};              // one party's checks (recv.*): decrypt, decode, chunks, fold, check, prove
+  int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
+  int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
+  std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
   int hy_timed = 0;                     // hev[] hold the phases of the last serialised encrypt (1)
                                         // and / or decrypt (2) since the last collect_hybrid_phases
   static constexpr int MAX_SUB = 8;
@@ -2912,6 +2917,7 @@ int dkg_ctx_create(int device, dkg_ctx** out) {
     for (auto& e : ctx->pev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->hev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->bpev) HCK(hipEventCreate(&e));
+    for (auto& e : ctx->rpev) HCK(hipEventCreate(&e));
     for (auto& st : ctx->sub) HCK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest));
     HCK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, least));
     HCK(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
@@ -2958,6 +2964,8 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   for (auto& e : ctx->hev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->bpev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : ctx->rpev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->join)
     if (e) (void)hipEventDestroy(e);
@@ -4763,11 +4771,10 @@ int dkg_ctx_set_complaint_eval(dkg_ctx* ctx, int mode) {
   return DKG_OK;
 }
 
-int dkg_complaints_prove(dkg_ctx* ctx, size_t C, const uint8_t* sk, const uint8_t* enc, const uint8_t* w,
-                         uint8_t* proofs) {
-  return guarded(ctx, [&] {
-    if (!sk || !enc || !w || !proofs) return DKG_E_ARG;
-    if (!C) return DKG_OK;
+// ProofOfMisbehaviour::generate for C complaints from host arrays (inside a guarded call; syncs)
+static int complaints_prove_run(dkg_ctx* ctx, size_t C, const uint8_t* sk, const uint8_t* enc, const uint8_t* w,
+                                uint8_t* proofs) {
+  {
     hipStream_t st = ctx->stream;
     uint32_t* dsk = buf<uint32_t>(ctx, "cp_sk", 32 * C);
     uint32_t* denc = buf<uint32_t>(ctx, "cp_enc", 128 * C);
@@ -4805,6 +4812,329 @@ int dkg_complaints_prove(dkg_ctx* ctx, size_t C, const uint8_t* sk, const uint8_
         ctx->err = "complaints_prove: a ciphertext point does not decode";
         return DKG_E_DECODE;
       }
+    return DKG_OK;
+  }
+}
+
+int dkg_complaints_prove(dkg_ctx* ctx, size_t C, const uint8_t* sk, const uint8_t* enc, const uint8_t* w,
+                         uint8_t* proofs) {
+  return guarded(ctx, [&] {
+    if (!sk || !enc || !w || !proofs) return DKG_E_ARG;
+    if (!C) return DKG_OK;
+    return complaints_prove_run(ctx, C, sk, enc, w, proofs);
+  });
+}
+
+// ---- one party's share checks (receivers.hip): P_i(x) for a few receiver indices, chunked Horner
+int dkg_ctx_set_receiver_chunk(dkg_ctx* ctx, int chunk) {
+  if (!ctx || chunk < 0) return DKG_E_ARG;
+  ctx->receiver_chunk = chunk;
+  return DKG_OK;
+}
+
+int dkg_ctx_last_receiver_chunk(const dkg_ctx* ctx) { return ctx ? ctx->last_receiver_chunk : 0; }
+
+namespace {
+
+constexpr size_t RECV_DIG_WORDS = 20;                      // per (index, stage): 8 + 8 digit words, length
+constexpr size_t RECV_DIG_STRIDE = 16 * RECV_DIG_WORDS;    // per index
+constexpr size_t RECV_SLAB_BYTES = (size_t)256 << 20;      // chunk partials held at a time
+
+// Field multiplication of the evaluation's launches when dkg_ctx_set_field_mode leaves the choice
+// open: 1 column sums (dkgk_ilp), 0 product scanning (A/B in profiles/receivers_time.json).
+#ifndef DKG_RECV_ILP
+#define DKG_RECV_ILP 1
+#endif
+
+void recv_mark(dkg_ctx* ctx, int k) {
+  if (ctx->nsub == 1) HCK(hipEventRecord(ctx->rpev[k], ctx->stream));
+}
+
+// After a sync: recv.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); others erased.
+void recv_phase(dkg_ctx* ctx, const char* name, int a, int b) {
+  const std::string key = std::string("recv.") + name;
+  ctx->phase_ms.erase(key);
+  if (ctx->nsub != 1 || a < 0) return;
+  float ms = 0;
+  HCK(hipEventElapsedTime(&ms, ctx->rpev[a], ctx->rpev[b]));
+  ctx->phase_ms[key] = ms;
+}
+
+struct RecvEval {
+  uint32_t* R = nullptr;    // [M * D][40] point-major, slot m's values at m * D + i
+  uint8_t* dok = nullptr;   // [D] rows that decode
+  uint32_t* xs = nullptr;   // [M] device: the 1-based indices (null: not uploaded)
+  bool want_xs = true;      // in: the caller reads xs (recv_decide)
+  bool split_timed = false; // rpev[3] separates the chunk walk from the fold (one slab, one plan)
+};
+
+// Decode C [D][N][32] and evaluate every row at the M indices js[m] + 1 by the plans of
+// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks rpev[1] (start), [2] (decoded),
+// [3] (chunks, when split_timed) and [4] (evaluated).
+int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, size_t nplan, const uint8_t* C,
+              RecvEval& ev) {
+  const size_t N = t + 1, npad = pad64(D);
+  std::vector<dkg_receiver_plan> plans(M);
+  std::vector<uint32_t> hx(M), dig;
+  int last = 0;
+  bool any_stage = false;
+  auto plan_of = [&](uint32_t x, int chunk, dkg_receiver_plan& out) {
+    const std::array<size_t, 4> key = {std::max(nplan, (size_t)x), t, x, (size_t)chunk};
+    auto it = ctx->recv_plans.find(key);
+    if (it == ctx->recv_plans.end()) {
+      dkg_receiver_plan p;
+      const int rc = dkg_receiver_plan_for(key[0], t, x, chunk, &p);
+      if (rc) return rc;
+      if (ctx->recv_plans.size() >= 4096) ctx->recv_plans.clear();
+      it = ctx->recv_plans.emplace(key, p).first;
+    }
+    out = it->second;
+    return (int)DKG_OK;
+  };
+  // Several indices with the automatic choice: all take the largest of their automatic chunks (forced
+  // plans of the same function), so that the slots have one shape and share every launch -- the fold's
+  // work falls with the chunk, and such a call is bound by throughput, not by the chain.
+  int chunk = ctx->receiver_chunk;
+  if (M > 1 && chunk == 0) {
+    for (size_t m = 0; m < M; m++) {
+      dkg_receiver_plan p;
+      const int rc = plan_of(js[m] + 1, 0, p);
+      if (rc) return rc;
+      chunk = std::max(chunk, (int)std::min<size_t>(p.chunk, N));
+    }
+  }
+  for (size_t m = 0; m < M; m++) {
+    hx[m] = js[m] + 1;
+    const int rc = plan_of(hx[m], chunk, plans[m]);
+    if (rc) return rc;
+    if (plans[m].stages && dig.empty()) dig.assign(M * RECV_DIG_STRIDE, 0);
+    for (uint32_t s = 0; s < plans[m].stages; s++) {
+      uint32_t* d = &dig[m * RECV_DIG_STRIDE + s * RECV_DIG_WORDS];
+      d[16] = (uint32_t)dkgh::naf256(plans[m].mult[s], d, d + 8, nullptr);
+    }
+    any_stage |= plans[m].stages != 0;
+    last = std::max(last, (int)std::min<uint32_t>(plans[m].chunk, 0x7fffffffu));
+  }
+  ctx->last_receiver_chunk = last;
+  recv_mark(ctx, 1);
+  uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
+  h2d(ctx, Cc, C, 32 * D * N);
+  uint32_t* Cext = buf<uint32_t>(ctx, "Cext", PTB * D * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "pok", D * N);
+  ev.dok = buf<uint8_t>(ctx, "dok", D);
+  uint32_t* Cpm = buf<uint32_t>(ctx, "Cpm", PTB * N * npad);
+  dkgk::decode_points(Cc, D * N, Cext, D * N, pok, ctx->stream);
+  dkgk::dealer_ok(D, N, pok, ev.dok, ctx->stream);
+  dkgk::to_position_major(D, N, npad, Cext, Cpm, ctx->stream);
+  uint32_t* ddig = nullptr;
+  if (any_stage || ev.want_xs) {  // the serial walk of one index reads neither
+    ev.xs = buf<uint32_t>(ctx, "rv_xs", 4 * M);
+    h2d(ctx, ev.xs, hx.data(), 4 * M);
+  }
+  if (any_stage) {
+    ddig = buf<uint32_t>(ctx, "rv_dig", 4 * dig.size());
+    h2d(ctx, ddig, dig.data(), 4 * dig.size());
+  }
+  ev.R = buf<uint32_t>(ctx, "rv_R", PTB * M * D);
+  recv_mark(ctx, 2);
+  const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_RECV_ILP);
+  auto chunks = ilp ? dkgk_ilp::recv_chunks : dkgk::recv_chunks;
+  auto fold = ilp ? dkgk_ilp::recv_fold : dkgk::recv_fold;
+  size_t launches = 0;
+  for (size_t m0 = 0; m0 < M;) {
+    const dkg_receiver_plan& p = plans[m0];
+    if (p.stages == 0) {  // the serial walk: k_horner, as dkg_verify_receiver runs it
+      dkgk::horner(D, npad, N, Cpm, hx[m0], 1, ev.R + m0 * D * PT_WORDS_H, ctx->stream);
+      m0++, launches++;
+      continue;
+    }
+    const size_t L = p.chunk, G = (N + L - 1) / L;
+    size_t run = 1;  // consecutive slots with the same shape share their launches
+    while (m0 + run < M && plans[m0 + run].chunk == p.chunk && plans[m0 + run].stages == p.stages &&
+           !memcmp(plans[m0 + run].arity, p.arity, sizeof p.arity))
+      run++;
+    const size_t Ms = std::min(run, std::max<size_t>(1, RECV_SLAB_BYTES / (PTB * G * npad)));
+    const size_t G1 = (G + p.arity[0] - 1) / p.arity[0];
+    uint32_t* Q[2] = {buf<uint32_t>(ctx, "rv_q0", PTB * Ms * G * npad), buf<uint32_t>(ctx, "rv_q1", PTB * Ms * G1 * npad)};
+    for (size_t b = 0; b < run; b += Ms) {
+      const size_t ms = std::min(Ms, run - b);
+      chunks(D, npad, N, L, Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
+      if (launches == 0 && run == M && ms == run) {
+        recv_mark(ctx, 3);
+        ev.split_timed = true;
+      }
+      size_t Gin = G;
+      for (uint32_t s = 0; s < p.stages; s++) {
+        fold(D, npad, Gin, p.arity[s], Q[s & 1], ddig + s * RECV_DIG_WORDS, RECV_DIG_STRIDE, m0 + b, ms, Q[(s + 1) & 1],
+             ev.R, ctx->stream);
+        Gin = (Gin + p.arity[s] - 1) / p.arity[s];
+      }
+      if (Gin != 1) {
+        ctx->err = "receiver plan does not end in one value";
+        return DKG_E_ARG;
+      }
+      launches++;
+    }
+    m0 += run;
+  }
+  check_launch(ctx);
+  recv_mark(ctx, 4);
+  return DKG_OK;
+}
+
+void recv_eval_phases(dkg_ctx* ctx, const RecvEval& ev) {
+  recv_phase(ctx, "decode", 1, 2);
+  recv_phase(ctx, "chunks", 2, ev.split_timed ? 3 : 4);  // several slabs or plans: the whole evaluation
+  recv_phase(ctx, "fold", ev.split_timed ? 3 : -1, 4);
+}
+
+// decisions [M][n] of the evaluated slots against the share columns (device, [M][n][8])
+void recv_check(dkg_ctx* ctx, size_t n, int round, size_t M, size_t j0, const RecvEval& ev, const uint32_t* ds,
+                const uint32_t* dsp, const uint8_t* qualified, uint8_t* dec) {
+  if (M == 1) {  // one column: check's own mask and self index, as dkg_verify_receiver calls it
+    dkgk::check(n, 1, 0, j0, n, round, ds, dsp, ev.R, ctx->tab_gw, ctx->tab_hw, ev.dok, dec, ctx->stream);
+  } else {
+    uint8_t* ones = buf<uint8_t>(ctx, "rv_one", M * n);
+    HCK(hipMemsetAsync(ones, 1, M * n, ctx->stream));
+    // pair p = m * n + i as "dealer" p of one receiver; recv_base = n keeps check's self test off
+    dkgk::check(M * n, 1, 0, n, n, round, ds, dsp, ev.R, ctx->tab_gw, ctx->tab_hw, ones, dec, ctx->stream);
+  }
+  if (M > 1 || qualified) dkgk::recv_decide(M, n, round, ev.xs, ev.dok, qualified, dec, ctx->stream);
+  check_launch(ctx);
+  recv_mark(ctx, 5);
+}
+
+void recv_reset_last(dkg_ctx* ctx) {
+  ctx->last_step_flags = nullptr;  // no stepping tables
+  ctx->last_step_flag_words = 0;
+  ctx->last_bflags = nullptr;
+  ctx->last_bflag_words = 0;
+}
+
+}  // namespace
+
+int dkg_commitment_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, const uint8_t* C, uint8_t* P,
+                        uint8_t* ok) {
+  return guarded(ctx, [&] {
+    if (!D || !M) return DKG_OK;
+    if (!js || !C || !P) return DKG_E_ARG;
+    for (size_t m = 0; m < M; m++)
+      if (js[m] >= (1u << 24)) return DKG_E_ARG;
+    recv_reset_last(ctx);
+    RecvEval ev;
+    const int rc = recv_eval(ctx, D, t, M, js, D, C, ev);
+    if (rc) return rc;
+    uint32_t* Pc = buf<uint32_t>(ctx, "rv_P", 32 * M * D);
+    dkgk::recv_encode(M, D, ev.R, ev.dok, Pc, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, P, Pc, 32 * M * D);
+    if (ok) d2h(ctx, ok, ev.dok, D);
+    sync(ctx);
+    recv_eval_phases(ctx, ev);
+    recv_phase(ctx, "check", -1, 0);
+    recv_phase(ctx, "decrypt", -1, 0);
+    recv_phase(ctx, "prove", -1, 0);
+    return DKG_OK;
+  });
+}
+
+int dkg_verify_receivers(dkg_ctx* ctx, size_t n, size_t t, int round, size_t M, const uint32_t* js, const uint8_t* C,
+                         const uint8_t* s, const uint8_t* s_prime, const uint8_t* qualified, uint8_t* decision) {
+  return guarded(ctx, [&] {
+    if (round != 2 && round != 4) return DKG_E_ARG;
+    if (!M) return DKG_OK;
+    if (!n || !js || !C || !s || !decision) return DKG_E_ARG;
+    for (size_t m = 0; m < M; m++)
+      if (js[m] >= n) return DKG_E_ARG;
+    if (round == 2) {
+      int rc = need_env(ctx);
+      if (rc) return rc;
+      if (!s_prime) return DKG_E_ARG;
+    }
+    recv_reset_last(ctx);
+    RecvEval ev;
+    ev.want_xs = M > 1 || (round == 4 && qualified);
+    const int rc = recv_eval(ctx, n, t, M, js, n, C, ev);
+    if (rc) return rc;
+    uint32_t* ds = upload_scalars(ctx, "vr_s", s, M * n);
+    uint32_t* dsp = round == 2 ? upload_scalars(ctx, "vr_sp", s_prime, M * n) : nullptr;
+    const uint8_t* dq = round == 4 ? upload_mask(ctx, "rv_q", qualified, n) : nullptr;
+    uint8_t* dec = buf<uint8_t>(ctx, "vr_dec", M * n);
+    recv_check(ctx, n, round, M, js[0], ev, ds, dsp, dq, dec);
+    d2h(ctx, decision, dec, M * n);
+    sync(ctx);
+    recv_eval_phases(ctx, ev);
+    recv_phase(ctx, "check", 4, 5);
+    recv_phase(ctx, "decrypt", -1, 0);
+    recv_phase(ctx, "prove", -1, 0);
+    return DKG_OK;
+  });
+}
+
+int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* E, const uint8_t* e1, const uint8_t* ct,
+                     const uint8_t sk[32], const uint8_t* w, uint8_t* s_out, uint8_t* sp_out, uint8_t* dec,
+                     int32_t* complaints, uint8_t* r2_error, uint8_t* proofs) {
+  return guarded(ctx, [&] {
+    const int rc0 = ceremony_args(ctx, n, t, {E, e1, ct, sk, dec});
+    if (rc0) return rc0;
+    if (j >= n || (w && !proofs)) return DKG_E_ARG;
+    recv_reset_last(ctx);
+    // committee.rs:282-286: the pairs addressed to j, decrypted with sk_j (one recipient)
+    recv_mark(ctx, 0);
+    uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, 1);
+    uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 64 * n);
+    uint32_t* dct = buf<uint32_t>(ctx, "pr_ct", 64 * n);
+    h2d(ctx, de1, e1, 64 * n);
+    h2d(ctx, dct, ct, 64 * n);
+    uint32_t* ds = buf<uint32_t>(ctx, "pr_s", 32 * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "pr_sp", 32 * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "pr_iok", 2 * n);
+    uint8_t* eok = buf<uint8_t>(ctx, "pr_eok", n);
+    decrypt_device(ctx, n, 1, dsk, de1, dct, ds, dsp, iok, eok);
+    const uint32_t jj = (uint32_t)j;
+    RecvEval ev;
+    ev.want_xs = false;
+    const int rc = recv_eval(ctx, n, t, 1, &jj, n, E, ev);  // :287-296
+    if (rc) return rc;
+    dkgk::and_mask(n, eok, ev.dok, ctx->stream);  // an e1 that does not decode is missing data (:331-335)
+    uint8_t* ddec = buf<uint8_t>(ctx, "vr_dec", n);
+    recv_check(ctx, n, 2, 1, j, ev, ds, dsp, nullptr, ddec);
+    d2h(ctx, dec, ddec, n);
+    if (s_out) d2h(ctx, s_out, ds, 32 * n);
+    if (sp_out) d2h(ctx, sp_out, dsp, 32 * n);
+    sync(ctx);
+    recv_phase(ctx, "decrypt", 0, 1);
+    recv_eval_phases(ctx, ev);
+    recv_phase(ctx, "check", 4, 5);
+    recv_phase(ctx, "prove", -1, 0);
+    std::vector<size_t> rej;
+    for (size_t i = 0; i < n; i++)
+      if (dec[i] == DKG_REJECT) rej.push_back(i);
+    if (complaints) *complaints = (int32_t)rej.size();
+    if (r2_error) *r2_error = rej.size() > t ? 1 : 0;  // :340-347
+    if (w) {
+      memset(proofs, 0, 192 * n);
+      if (!rej.empty()) {  // ProofOfMisbehaviour::generate per rejected dealer (:309-322)
+        const size_t Cn = rej.size();
+        std::vector<uint8_t> ksk(32 * Cn), kenc(128 * Cn), kw(64 * Cn), kp(192 * Cn);
+        for (size_t c = 0; c < Cn; c++) {
+          const size_t i = rej[c];
+          memcpy(&ksk[32 * c], sk, 32);
+          memcpy(&kenc[128 * c], e1 + 64 * i, 32);             // e1 of the randomness
+          memcpy(&kenc[128 * c + 32], ct + 64 * i, 32);
+          memcpy(&kenc[128 * c + 64], e1 + 64 * i + 32, 32);   // e1 of the share
+          memcpy(&kenc[128 * c + 96], ct + 64 * i + 32, 32);
+          memcpy(&kw[64 * c], w + 64 * i, 64);
+        }
+        recv_mark(ctx, 5);
+        const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
+        if (rp) return rp;
+        recv_mark(ctx, 6);
+        sync(ctx);
+        recv_phase(ctx, "prove", 5, 6);
+        for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
+      }
+    }
     return DKG_OK;
   });
 }

@@ -237,6 +237,64 @@ int dkg_verify_pairs(dkg_ctx *ctx, size_t n, size_t t, int round, size_t d0, siz
 int dkg_verify_receiver(dkg_ctx *ctx, size_t n, size_t t, int round, size_t j, const uint8_t *C, const uint8_t *s,
                         const uint8_t *s_prime, uint8_t *decision);
 
+/* ---- one party's view on the whole device: chunked evaluation (receivers.hip) ----
+ * dkg_verify_receiver walks the t + 1 coefficients of every dealer as one dependent chain.  The calls
+ * below cut P_i(x) = sum_k x^k C_i[k] into ceil((t+1) / chunk) chunks that are walked side by side
+ * (Q_u = sum_{k < chunk} x^k C_i[u chunk + k]) and fold the partials in stages: stage s combines groups
+ * of arity[s] consecutive partials by Horner in mult[s].  Every multiplier is one integer for all
+ * dealers.  A multiplier may be any representative of its class mod l: the operands lie in 2E, so the
+ * results differ by an element of E[4] at most -- the same Ristretto element, encoding and decision. */
+typedef struct {
+  uint32_t chunk;        /* L >= 1; chunk >= t+1: one chunk, the serial walk (k_horner), stages == 0 */
+  uint32_t stages;       /* <= 16 */
+  uint32_t arity[16];    /* r_s >= 2: stage s folds groups of r_s consecutive partials */
+  uint8_t mult[16][32];  /* y_s, little-endian, < 2^255: y_0 = x^chunk, y_{s+1} = y_s^{r_s} (mod l) */
+} dkg_receiver_plan;
+/* The plan the runtime executes for receiver index x (1-based, = j + 1) of n parties at threshold t.
+ * chunk: 0 = the automatic choice for (n, t, x) -- the cheapest, by a fitted cost rule (chain length x
+ * latency + work / throughput + launches), of the serial walk and the chunks 2, 4, .., 64 whose chain
+ * is no longer than the serial one; >= 1 forced.  Host only, no GPU, a pure function.  DKG_E_ARG for
+ * x == 0, x > n, n == 0, chunk < 0, a NULL out, or a forced chunk that needs more than 16 stages.  It
+ * does NOT apply dkg_env_check's t < (n + 1) / 2: any t is planned. */
+int dkg_receiver_plan_for(size_t n, size_t t, uint32_t x, int chunk, dkg_receiver_plan *out);
+/* The rule's estimate (us) of the evaluation of one index under plan p, and its fitted constants
+ * c = {per launch us, per dependent point operation us, per lane and operation us, per dependent
+ * operation of the serial walk us, host-side setup of a plan with fold stages us}. */
+double dkg_receiver_plan_cost_us(size_t n, size_t t, uint32_t x, const dkg_receiver_plan *p);
+void dkg_receiver_plan_constants(double c[5]);
+/* Chunk length of the calls below: 0 (default) automatic, >= 1 forced.  Outputs do not depend on it. */
+int dkg_ctx_set_receiver_chunk(dkg_ctx *ctx, int chunk);
+/* The chunk of the last such call's plan (the largest over its indices). */
+int dkg_ctx_last_receiver_chunk(const dkg_ctx *ctx);
+/* P[m][i] = sum_k (js[m]+1)^k C_i[k], compressed; the shared-scalar case of
+ * vartime_multiscalar_multiplication (committee.rs:287-296, 532-539).  C [D][t+1][32]; js[m] < 2^24
+ * (DKG_E_ARG otherwise); ok[i] (may be NULL) = 0 and P[m][i] = 32 zero bytes where row i does not
+ * decode.  P [M][D][32].  Needs no dkg_env_init.  Phase times (dkg_ctx_phase_ms, one stream):
+ * "recv.decode" (upload, decode, transposition), "recv.chunks", "recv.fold" (-1, and recv.chunks the
+ * whole evaluation, when the indices run as several plans or slabs). */
+int dkg_commitment_eval(dkg_ctx *ctx, size_t D, size_t t, size_t M, const uint32_t *js, const uint8_t *C,
+                        uint8_t *P, uint8_t *ok);
+/* dkg_verify_receiver for M receiver indices js[] (0-based, any order, repeats allowed) in one call:
+ * s, s_prime [M][n][32] (column m = the shares addressed to js[m]); decision [M][n] with the values
+ * of dkg_verify_pairs (SELF where i == js[m], MISSING / REJECT for an undecodable row).  qualified
+ * (round 4 only, may be NULL): [n], 0 marks DKG_SKIPPED (committee.rs:522).  Phase-1/Phase-3 proceed
+ * of the parties js[] (committee.rs:273-338, 520-559).  M == 0 returns DKG_OK and touches nothing;
+ * round 2 requires dkg_env_init.  Also records "recv.check".  With M > 1 and the automatic chunk, every
+ * index runs the plan forced to the largest of the indices' automatic chunks (one shape, shared
+ * launches); dkg_ctx_last_receiver_chunk reports it. */
+int dkg_verify_receivers(dkg_ctx *ctx, size_t n, size_t t, int round, size_t M, const uint32_t *js, const uint8_t *C,
+                         const uint8_t *s, const uint8_t *s_prime, const uint8_t *qualified, uint8_t *decision);
+/* Phases<Phase1>::proceed (committee.rs:260-366) for ONE party j in full mode: decrypt the n ciphertext
+ * pairs addressed to j (e1, ct [n][2][32], w = 0 the randomness, 1 the share) with sk_j, check them
+ * against E, and, if w [n][64] is given, ProofOfMisbehaviour::generate (broadcast.rs:189-226) for every
+ * REJECT (proofs [n][192], required with w, untouched rows zero).  s_out, sp_out [n][32], complaints,
+ * r2_error may be NULL; dec [n]; *complaints = the REJECTs; *r2_error = complaints > t (:340-347).  An
+ * e1 that does not decode is missing data (MISSING, no complaint).  Requires dkg_env_init and
+ * dkg_env_check(t, n).  Also records "recv.decrypt" and "recv.prove". */
+int dkg_party_round2(dkg_ctx *ctx, size_t n, size_t t, size_t j, const uint8_t *E, const uint8_t *e1, const uint8_t *ct,
+                     const uint8_t sk[32], const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
+                     int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
+
 /* ---- whole ceremony (rounds 1-5, every party played in one process as the reference tests do,
  * committee.rs:1518-1656) in plaintext-share mode. ---- */
 typedef struct {
