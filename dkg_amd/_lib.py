@@ -154,6 +154,9 @@ def lib():
     L.dkg_ctx_set_receiver_chunk.argtypes = [p, ctypes.c_int]
     L.dkg_ctx_last_receiver_chunk.argtypes = [p]
     L.dkg_commitment_eval.argtypes = [p, sz, sz, sz, p, u8p, p, p]
+    if hasattr(L, "dkg_pair_eval_shape"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_pair_eval_shape.argtypes = [sz, ctypes.c_int] + [ctypes.POINTER(ctypes.c_uint32)] * 3
+        L.dkg_commitment_eval_pairs.argtypes = [p, sz, sz, sz, p, p, u8p, p, p]
     L.dkg_verify_receivers.argtypes = [p, sz, sz, ctypes.c_int, sz, p, u8p, u8p, p, p, p]
     L.dkg_party_round2.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -292,5 +295,5 @@ EXPORTED = [
     "dkg_ctx_last_complaint_eval", "dkg_shard_combine_proven_device",
     "dkg_multi_ceremony_verify_proven", "dkg_multi_ceremony_verify_full_proven",
     "dkg_receiver_plan_for", "dkg_receiver_plan_cost_us", "dkg_receiver_plan_constants", "dkg_ctx_set_receiver_chunk",
-    "dkg_ctx_last_receiver_chunk", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
+    "dkg_ctx_last_receiver_chunk", "dkg_pair_eval_shape", "dkg_commitment_eval_pairs", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
 ]

@@ -268,13 +268,14 @@ class Backend:
         """Device ms of binomial / stepping / combine / check in the last ceremony's checks: tag "r24" (rounds
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
         encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
-        commitment_eval, verify_receivers, party_round2).  Only recorded with
+        commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs).  Only recorded with
         set_streams(1); -1 otherwise."""
         L = _lib.lib()
         if isinstance(tag, int):
             tag = f"r{tag}"
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
+                 else ("decode", "eval") if tag == "pairs"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
         return {k: L.dkg_ctx_phase_ms(self._ctx, f"{tag}.{k}".encode()) for k in names}
@@ -342,7 +343,9 @@ class Backend:
     # ---- one party's view (chunked evaluation, receivers.hip)
     def set_receiver_chunk(self, chunk: int = 0):
         """Chunk length of commitment_eval / verify_receivers / party_round2: 0 automatic (receiver_plan),
-        >= 1 forced.  Outputs do not depend on it."""
+        >= 1 forced.  Also the chunk of the wave evaluator (commitment_eval_pairs, complaint evaluation
+        mode 4: pair_eval_shape), whose calls raise for a chunk that needs more than 64 lanes.  Outputs do
+        not depend on it."""
         _check(self._ctx, _lib.lib().dkg_ctx_set_receiver_chunk(self._ctx, chunk))
 
     def last_receiver_chunk(self) -> int:
@@ -357,6 +360,21 @@ class Backend:
         ok = ctypes.create_string_buffer(max(D, 1))
         _check(self._ctx, _lib.lib().dkg_commitment_eval(self._ctx, D, t, M, arr, C, P, ok))
         return P.raw[: 32 * M * D], ok.raw[:D]
+
+    def commitment_eval_pairs(self, D: int, t: int, rows: Sequence[int], js: Sequence[int], C: bytes):
+        """(P, ok) for the (row, index) pairs (rows[p], js[p]), any order, repeats allowed: P[p] =
+        sum_k (js[p]+1)^k C_rows[p][k] as len(rows) encodings, ok[p] = row rows[p] decodes (its P zero
+        otherwise).  One wave per pair (pair_eval_shape under set_receiver_chunk); only the distinct rows
+        named are decoded."""
+        cnt = len(rows)
+        if len(js) != cnt:
+            raise ValueError("rows and js differ in length")
+        ra = (ctypes.c_uint32 * max(cnt, 1))(*rows)
+        ja = (ctypes.c_uint32 * max(cnt, 1))(*js)
+        P = ctypes.create_string_buffer(max(32 * cnt, 1))
+        ok = ctypes.create_string_buffer(max(cnt, 1))
+        _check(self._ctx, _lib.lib().dkg_commitment_eval_pairs(self._ctx, D, t, cnt, ra, ja, C, P, ok))
+        return P.raw[: 32 * cnt], ok.raw[:cnt]
 
     def verify_receivers(self, n: int, t: int, rnd: int, js: Sequence[int], C: bytes, s_cols: bytes,
                          sp_cols: Optional[bytes] = None, qualified: Optional[bytes] = None) -> bytes:
@@ -540,8 +558,9 @@ class Backend:
 
     # ---- round-2 complaints as device batches, and the qualified set they prove (committee.rs:370-398)
     def set_complaint_eval(self, mode: int):
-        """How complaints_verify evaluates P_i(j): 0 automatic, 1 per-pair Horner, 2 difference tables.
-        Outputs do not depend on it."""
+        """How complaints_verify / complaints3_verify evaluate P_i(j): 0 automatic, 1 per-pair Horner, 2
+        difference tables, 4 one wave per (row, index) item (pair_eval_shape under set_receiver_chunk).
+        3 and anything above 4 raise.  Outputs do not depend on it."""
         _check(self._ctx, _lib.lib().dkg_ctx_set_complaint_eval(self._ctx, mode))
 
     def complaints_prove(self, sk: bytes, enc: bytes, w: bytes) -> bytes:
@@ -1051,6 +1070,16 @@ def receiver_plan(n: int, t: int, x: int, chunk: int = 0) -> dict:
     return {"chunk": p.chunk, "stages": p.stages, "arity": list(p.arity[: p.stages]),
             "mult": [int.from_bytes(bytes(p.mult[s]), "little") for s in range(p.stages)],
             "cost_us": L.dkg_receiver_plan_cost_us(n, t, x, ctypes.byref(p))}
+
+
+def pair_eval_shape(t: int, chunk: int = 0) -> dict:
+    """dkg_pair_eval_shape (host only): the shape one wave runs per (row, index) pair at threshold t.
+    Keys: chunk (L), lanes, stages.  chunk 0 automatic; raises for a forced chunk needing > 64 lanes."""
+    v = [ctypes.c_uint32() for _ in range(3)]
+    rc = _lib.lib().dkg_pair_eval_shape(t, chunk, *[ctypes.byref(x) for x in v])
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "pair_eval_shape")
+    return {"chunk": v[0].value, "lanes": v[1].value, "stages": v[2].value}
 
 
 def receiver_plan_constants() -> dict:

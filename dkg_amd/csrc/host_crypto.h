@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 namespace dkgh {
 
 void blake2b(uint8_t* out, size_t outlen, const uint8_t* in, size_t inlen);
@@ -38,5 +40,8 @@ bool jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t* da, int8_t* db
 // receiver_plan.cpp: the NAF of a little-endian 256-bit value as +1 / -1 digit bits; returns its
 // length (the top digit is +1 at length - 1; 0 for zero), *weight (may be null) its nonzero digits.
 int naf256(const uint8_t v[32], uint32_t pos[8], uint32_t neg[8], int* weight);
+// receiver_plan.cpp: the distinct values of v [count] in order of first appearance and place[p] = where
+// v[p] stands among them (the pair evaluation's distinct rows and distinct indices)
+void distinct_places(size_t count, const uint32_t* v, std::vector<uint32_t>& distinct, std::vector<uint32_t>& place);
 
 }  // namespace dkgh

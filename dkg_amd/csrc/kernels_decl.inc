@@ -422,5 +422,14 @@ void recv_decide(size_t M, size_t n, int round, const uint32_t* xs, const uint8_
                  uint8_t* dec, hipStream_t stream);
 // P [M][D][8] = encodings of R [M * D][40], zero where dok[i] == 0
 void recv_encode(size_t M, size_t D, const uint32_t* R, const uint8_t* dok, uint32_t* P, hipStream_t stream);
+// one wave per (row, index) item: item b is complaint c = list[b] (b with a null list), row crow[c] - 1 of
+// the decoded commitments Eext (element row * N + k, stride as cmp_horner), index xs[c]; the wave's lanes
+// walk G = ceil(N / L) <= 64 chunks and fold them in S = ceil(log2 G) stages (dkg_pair_eval_shape) with
+// the multipliers' records digits[slot[b]][S][17] (NAF +1 bits, -1 bits, length).  R[c][40] point-major
+void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint32_t* crow, const uint32_t* slot,
+               const uint32_t* Eext, size_t stride, size_t N, uint32_t L, uint32_t G, uint32_t S,
+               const uint32_t* digits, uint32_t* R, hipStream_t stream);
+// ok[p] = rowok[crow[p] - 1], p < cnt
+void pair_ok(size_t cnt, const uint32_t* crow, const uint8_t* rowok, uint8_t* ok, hipStream_t stream);
 
 }  // namespace dkgk

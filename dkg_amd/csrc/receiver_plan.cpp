@@ -1,6 +1,8 @@
 // dkg_receiver_plan_for: how one party's evaluations P_i(x) = sum_k x^k C_i[k] are cut into chunks
 // and folded (receivers.hip runs exactly this plan).  Host only, a pure function of (n, t, x, chunk).
 #include <cstring>
+#include <unordered_map>
+#include <vector>
 
 #include "../../include/dkg_amd.h"
 #include "host_crypto.h"
@@ -35,6 +37,22 @@ int naf256(const uint8_t v[32], uint32_t pos[8], uint32_t neg[8], int* weight) {
   }
   if (weight) *weight = wt;
   return len;
+}
+
+// The distinct values of v[0 .. count) in order of first appearance, and place[p] = the position of v[p]
+// among them: the item lists of the pair evaluation (distinct rows to decode, distinct indices to plan).
+void distinct_places(size_t count, const uint32_t* v, std::vector<uint32_t>& distinct, std::vector<uint32_t>& place) {
+  distinct.clear();
+  place.resize(count);
+  std::unordered_map<uint32_t, uint32_t> at;
+  for (size_t p = 0; p < count; p++) {
+    auto it = at.find(v[p]);
+    if (it == at.end()) {
+      it = at.emplace(v[p], (uint32_t)distinct.size()).first;
+      distinct.push_back(v[p]);
+    }
+    place[p] = it->second;
+  }
 }
 
 }  // namespace dkgh
@@ -116,6 +134,19 @@ double dkg_receiver_plan_cost_us(size_t n, size_t t, uint32_t x, const dkg_recei
     G = Gout;
   }
   return us;
+}
+
+int dkg_pair_eval_shape(size_t t, int chunk, uint32_t* L, uint32_t* lanes, uint32_t* stages) {
+  if (!L || !lanes || !stages || chunk < 0 || t >= 0xffffffffu) return DKG_E_ARG;
+  const size_t N = t + 1;
+  size_t l = chunk ? (size_t)chunk : (N + 63) / 64;
+  if (l > N) l = N;  // one lane walks the whole row
+  const size_t g = (N + l - 1) / l;
+  if (g > 64) return DKG_E_ARG;
+  uint32_t s = 0;
+  while (((size_t)1 << s) < g) s++;
+  *L = (uint32_t)l, *lanes = (uint32_t)g, *stages = s;
+  return DKG_OK;
 }
 
 int dkg_receiver_plan_for(size_t n, size_t t, uint32_t x, int chunk, dkg_receiver_plan* out) {

@@ -45,6 +45,18 @@ DKG_DEV void recv_mul_small(ge_p3& y, uint32_t pos, uint32_t neg, int len, uint3
   }
 }
 
+// the chain of recv_mul_long after its first step: q holds cached(y) of before the chain, len >= 2
+DKG_DEV void recv_chain_long(ge_p3& y, const uint32_t* __restrict__ dg, int len, const uint32_t* q) {
+#pragma unroll 1
+  for (int i = len - 2; i >= 0; i--) {
+    const uint32_t bit = 1u << (i & 31);
+    const uint32_t p = dg[i >> 5] & bit, n = dg[8 + (i >> 5)] & bit;
+    const bool nz = (p | n) != 0;
+    ge_dbl_lean(y, y, nz || i == 0);
+    if (nz) ge_add_lds(y, y, q, n != 0, 64, i == 0);
+  }
+}
+
 // y = m y for a wave-uniform multiplier of up to 255 bits: dg = NAF digits, +1 in words 0..7, -1 in
 // words 8..15, length in word 16 (top digit +1 at length - 1)
 DKG_DEV void recv_mul_long(ge_p3& y, const uint32_t* __restrict__ dg, uint32_t* q) {
@@ -55,14 +67,13 @@ DKG_DEV void recv_mul_long(ge_p3& y, const uint32_t* __restrict__ dg, uint32_t* 
     ge_to_cached(xc, y);
     lds_put_cached(q, xc);
   }
-#pragma unroll 1
-  for (int i = len - 2; i >= 0; i--) {
-    const uint32_t bit = 1u << (i & 31);
-    const uint32_t p = dg[i >> 5] & bit, n = dg[8 + (i >> 5)] & bit;
-    const bool nz = (p | n) != 0;
-    ge_dbl_lean(y, y, nz || i == 0);
-    if (nz) ge_add_lds(y, y, q, n != 0, 64, i == 0);
-  }
+  recv_chain_long(y, dg, len, q);
+}
+
+// p, or the identity (0, 1, 1, 0) where !keep
+DKG_DEV void pt_or_identity(ge_p3& p, bool keep) {
+#pragma unroll
+  for (int w = 0; w < PT_WORDS; w++) pt_word(p, w) = keep ? pt_word(p, w) : ((w == 10 || w == 20) ? 1u : 0u);
 }
 
 // final values: point-major R[m * ndealers + d] (what check and k_recv_encode read)
@@ -126,6 +137,76 @@ __global__ __launch_bounds__(64, 3) void k_recv_fold(size_t ndealers, size_t npa
              d < ndealers, acc);
 }
 
+// P_row(x) for a LIST of (row, index) items, one 64-lane workgroup per item: the index is uniform over
+// the wave, and the lanes hold G <= 64 chunks of L coefficients of that one polynomial (G = ceil(N / L),
+// S = ceil(log2 G): dkg_pair_eval_shape).  Item b: c = list[b] (b itself with a null list), row
+// crow[c] - 1 of the decoded commitments Eext (element row * N + k, as k_cmp_horner reads them), index
+// x = xs[c], digit records digits[slot[b]][S][17] of the multipliers y_s = x^(L 2^s).
+//   stage 1  lane u walks coefficients [uL, min(uL + L, N)) by Horner in x: L - 1 steps in every lane; a
+//            position past the row's end, and every position of a lane >= G, is the identity
+//   fold s   V_u = y_s V_u + V_(u - 2^s) in the lanes whose bit s is set: recv_mul_long leaves cached(V_u)
+//            of BEFORE the multiplication in the lane's LDS column, which is what lane u + 2^s adds.  The
+//            other lanes add their own column; their value is never read again.  The result migrates
+//            upward and ends in lane 2^S - 1, which alone stores it.
+// R point-major [c][40], the format of k_cmp_horner's results.
+__global__ __launch_bounds__(64, 3) void k_pair_eval(const uint32_t* __restrict__ list,
+                                                     const uint32_t* __restrict__ xs,
+                                                     const uint32_t* __restrict__ crow,
+                                                     const uint32_t* __restrict__ slot,
+                                                     const uint32_t* __restrict__ Eext, size_t stride, size_t N,
+                                                     uint32_t L, uint32_t G, uint32_t S,
+                                                     const uint32_t* __restrict__ digits, uint32_t* __restrict__ R) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  const uint32_t u = threadIdx.x;
+  uint32_t* q = qs + u;
+  const size_t b = blockIdx.x;
+  const size_t c = list ? list[b] : b;
+  const uint32_t x = xs[c];
+  const size_t row = (size_t)(crow[c] - 1) * N;
+  uint32_t pos, neg;
+  const int len = small_recode(x, pos, neg);
+  const size_t lo = (size_t)u * L;
+  ge_p3 acc, e;
+  {
+    const size_t k = lo + L - 1;
+    const bool have = u < G && k < N;
+    pt_load(acc, Eext, stride, row + (have ? k : 0));  // no lane reads past its row
+    pt_or_identity(acc, have);
+  }
+#pragma unroll 1
+  for (uint32_t i = L - 1; i-- > 0;) {
+    recv_mul_small(acc, pos, neg, len, q);
+    const size_t k = lo + i;
+    const bool have = u < G && k < N;
+    pt_load(e, Eext, stride, row + (have ? k : 0));
+    pt_or_identity(e, have);
+    add_point_lds(acc, e, q);
+  }
+#pragma unroll 1
+  for (uint32_t s = 0; s < S; s++) {
+    const uint32_t* dg = digits + ((size_t)slot[b] * S + s) * 17;
+    {  // recv_mul_long, whose first step is skipped by the empty chain (y_s = 1 at x = 1): the column
+       // is written either way, since the partner reads it
+      ge_cached cc;
+      ge_to_cached(cc, acc);
+      lds_put_cached(q, cc);
+    }
+    recv_chain_long(acc, dg, (int)dg[16], q);
+    __syncthreads();  // every column holds its lane's unmultiplied value
+    const uint32_t w = 1u << s;
+    ge_add_lds(acc, acc, (u & w) ? qs + (u - w) : q, false);
+    __syncthreads();  // the partners are read before the next stage overwrites the columns
+  }
+  if (u == (1u << S) - 1) pt_store_aos(R, c, acc);
+}
+
+// ok[p] = rowok[crow[p] - 1]: the items of k_pair_eval whose row decodes
+__global__ __launch_bounds__(256) void k_pair_ok(size_t cnt, const uint32_t* __restrict__ crow,
+                                                 const uint8_t* __restrict__ rowok, uint8_t* __restrict__ ok) {
+  const size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < cnt) ok[p] = rowok[crow[p] - 1];
+}
+
 // Decisions [M][n] from the group equation's outcome eq[m * n + i] (check with an all-ones mask and no
 // self index): undecodable rows (MISSING in round 2, REJECT in round 4), SELF where i == js[m], and
 // SKIPPED for a dealer outside the qualified set (round 4, committee.rs:522), in check's order.
@@ -172,6 +253,19 @@ void recv_fold(size_t ndealers, size_t npad, size_t Gin, size_t r, const uint32_
   const size_t Gout = (Gin + r - 1) / r;
   hipLaunchKernelGGL(k_recv_fold, dim3((unsigned)(npad / 64), (unsigned)Gout, (unsigned)Ms), dim3(64), 0, stream,
                      ndealers, npad, Gin, r, in, digits, dstride, m0, out, R);
+}
+
+void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint32_t* crow, const uint32_t* slot,
+               const uint32_t* Eext, size_t stride, size_t N, uint32_t L, uint32_t G, uint32_t S,
+               const uint32_t* digits, uint32_t* R, hipStream_t stream) {
+  if (!cnt || !N || !L || G < 1 || G > 64 || (size_t)L * G < N || (1u << S) < G) return;
+  hipLaunchKernelGGL(k_pair_eval, dim3((unsigned)cnt), dim3(64), 0, stream, list, xs, crow, slot, Eext, stride, N, L, G,
+                     S, digits, R);
+}
+
+void pair_ok(size_t cnt, const uint32_t* crow, const uint8_t* rowok, uint8_t* ok, hipStream_t stream) {
+  if (!cnt) return;
+  hipLaunchKernelGGL(k_pair_ok, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, stream, cnt, crow, rowok, ok);
 }
 
 void recv_decide(size_t M, size_t n, int round, const uint32_t* xs, const uint8_t* dok, const uint8_t* qualified,

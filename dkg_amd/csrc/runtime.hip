@@ -41,6 +41,7 @@ struct dkg_ctx {
   int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
   int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
   std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
+  std::map<std::array<size_t, 3>, std::vector<uint32_t>> pair_digits;  // k_pair_eval's [S][17] records by (t, x, L)
   int hy_timed = 0;                     // hev[] hold the phases of the last serialised encrypt (1)
                                         // and / or decrypt (2) since the last collect_hybrid_phases
   static constexpr int MAX_SUB = 8;
@@ -2160,16 +2161,73 @@ bool complaint_tables_pay(size_t n, size_t N, size_t count) {
   return tables_us < horner_us;
 }
 
+// Field multiplication of k_pair_eval when dkg_ctx_set_field_mode leaves the choice open: 1 column sums
+// (dkgk_ilp), 0 product scanning (A/B in profiles/pairs_time.json).
+#ifndef DKG_PAIR_ILP
+#define DKG_PAIR_ILP 1
+#endif
+
+// One wave per (row, index) item (receivers.hip k_pair_eval) in the shape of dkg_pair_eval_shape under
+// ctx->receiver_chunk.  Item b < cnt: c = dlist[b] (b itself with a null dlist), row dcrow[c] - 1 of Cext
+// (element row * N + k, stride), index dxs[c] = hx[b] (1-based; hx on the host, per ITEM).  The fold's
+// multipliers are dkg_receiver_plan_for's for the forced chunk L, as signed digits, one [S][17] record
+// per DISTINCT index of the call (cached on the ctx).  R[c][40].  The staging vectors `slot` and `dig`
+// are the caller's to keep until it has synchronised.
+struct PairStage {
+  std::vector<uint32_t> xs, slot, dig;
+};
+void pair_eval_launch(dkg_ctx* ctx, size_t t, size_t cnt, const uint32_t* dlist, const uint32_t* hx,
+                      const uint32_t* dxs, const uint32_t* dcrow, const uint32_t* Cext, size_t stride, uint32_t* R,
+                      PairStage& ps) {
+  if (!cnt) return;
+  const size_t N = t + 1;
+  uint32_t L, G, S;
+  if (dkg_pair_eval_shape(t, ctx->receiver_chunk, &L, &G, &S) != DKG_OK) {
+    ctx->err = "pair evaluation: the forced receiver chunk needs more than 64 lanes";
+    throw Fail{DKG_E_ARG};
+  }
+  ctx->last_receiver_chunk = (int)L;
+  dkgh::distinct_places(cnt, hx, ps.xs, ps.slot);
+  ps.dig.assign(std::max<size_t>(1, ps.xs.size() * S * 17), 0);
+  for (size_t m = 0; m < ps.xs.size() && S; m++) {
+    const uint32_t x = ps.xs[m];
+    const std::array<size_t, 3> key = {t, x, L};
+    auto it = ctx->pair_digits.find(key);
+    if (it == ctx->pair_digits.end()) {
+      dkg_receiver_plan p;
+      if (dkg_receiver_plan_for(x, t, x, (int)L, &p) != DKG_OK || p.stages != S) {
+        ctx->err = "pair evaluation: no plan for the index";
+        throw Fail{DKG_E_ARG};
+      }
+      std::vector<uint32_t> rec(S * 17, 0);
+      for (uint32_t k = 0; k < S; k++)
+        rec[k * 17 + 16] = (uint32_t)dkgh::naf256(p.mult[k], &rec[k * 17], &rec[k * 17 + 8], nullptr);
+      if (ctx->pair_digits.size() >= 65536) ctx->pair_digits.clear();
+      it = ctx->pair_digits.emplace(key, std::move(rec)).first;
+    }
+    memcpy(&ps.dig[m * S * 17], it->second.data(), 4 * S * 17);
+  }
+  uint32_t* dslot = buf<uint32_t>(ctx, "pe_slot", 4 * cnt);
+  uint32_t* ddig = buf<uint32_t>(ctx, "pe_dig", 4 * ps.dig.size());
+  h2d(ctx, dslot, ps.slot.data(), 4 * cnt);
+  h2d(ctx, ddig, ps.dig.data(), 4 * ps.dig.size());
+  const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_PAIR_ILP);
+  (ilp ? dkgk_ilp::pair_eval : dkgk::pair_eval)(cnt, dlist, dxs, dcrow, dslot, Cext, stride, N, L, G, S, ddig, R,
+                                                ctx->stream);
+}
+
 // P_row(x) = sum_k x^k C_row[k] for C (row, index) items: per row, the difference tables of that row
 // or one Horner walk per item (ctx->complaint_eval; automatic: complaint_tables_pay by the row's item
-// count).  index / row (host) and dindex / drow (device) [C]: 1-based, index within 1..n, row within
+// count).  Mode 4 sends every item to the wave evaluator (pair_eval_launch), which writes Rh in the walk's
+// place.  index / row (host) and dindex / drow (device) [C]: 1-based, index within 1..n, row within
 // 1..nrows; Cc [nrows][N][8] compressed and Cext (stride nrows * N) decoded commitments on the device.
 // An (row, index) pair listed again takes a further table row of its own, so that the table path
 // serves every item of a row it is chosen for.  Out: dridx [C] (bit 31: element of Rt, else of Rh),
 // Rh, Rt, scale as k_cv_check reads them.  Work is queued on ctx->stream; the staging vectors live
 // in `ev`, which the caller keeps until it has synchronised.
 struct ComplaintEvals {
-  std::vector<uint32_t> rows, hl, ridx;
+  std::vector<uint32_t> rows, hl, ridx, hx;
+  PairStage ps;
   const uint32_t *dridx = nullptr, *Rh = nullptr, *Rt = nullptr, *scale = nullptr;
 };
 void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, const uint32_t* index,
@@ -2210,9 +2268,15 @@ void complaint_evals(dkg_ctx* ctx, size_t n, size_t t, size_t nrows, size_t C, c
   if (!hl.empty()) {
     uint32_t* dhl = buf<uint32_t>(ctx, "cv_hl", 4 * hl.size());
     h2d(ctx, dhl, hl.data(), 4 * hl.size());
-    int nb = 1;
-    while ((n >> nb) != 0) nb++;
-    dkgk::cmp_horner(hl.size(), dhl, dindex, drow, Cext, nrows * N, N, nb, Rh, st);
+    if (ctx->complaint_eval == 4) {
+      ev.hx.resize(hl.size());
+      for (size_t k = 0; k < hl.size(); k++) ev.hx[k] = index[hl[k]];
+      pair_eval_launch(ctx, t, hl.size(), dhl, ev.hx.data(), dindex, drow, Cext, nrows * N, Rh, ev.ps);
+    } else {
+      int nb = 1;
+      while ((n >> nb) != 0) nb++;
+      dkgk::cmp_horner(hl.size(), dhl, dindex, drow, Cext, nrows * N, N, nb, Rh, st);
+    }
   }
   if (!rows.empty()) {
     const size_t D = rows.size();
@@ -3666,7 +3730,12 @@ void shard_complaints(dkg_ctx* ctx, size_t n, size_t t, size_t D, const uint32_t
     ctx->last_complaint_eval = 3;
   } else {
     const bool horner = !sp.ev2.hl.empty() || !sp.ev4.hl.empty(), tables = !sp.ev2.rows.empty() || !sp.ev4.rows.empty();
-    ctx->last_complaint_eval = horner && tables ? 12 : tables ? 2 : horner ? 1 : ctx->complaint_eval == 2 ? 2 : 1;
+    ctx->last_complaint_eval = ctx->complaint_eval == 4 ? 4
+                               : horner && tables       ? 12
+                               : tables                 ? 2
+                               : horner                 ? 1
+                               : ctx->complaint_eval == 2 ? 2
+                                                          : 1;
   }
 }
 
@@ -4766,7 +4835,7 @@ int dkg_ceremony_verify_full(dkg_ctx* ctx, size_t n, size_t t, const uint8_t* E,
 }
 
 int dkg_ctx_set_complaint_eval(dkg_ctx* ctx, int mode) {
-  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  if (!ctx || mode < 0 || mode == 3 || mode > 4) return DKG_E_ARG;  // 3: dkg_ctx_last_complaint_eval's "calling pass"
   ctx->complaint_eval = mode;
   return DKG_OK;
 }
@@ -5034,6 +5103,64 @@ int dkg_commitment_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32
     recv_phase(ctx, "check", -1, 0);
     recv_phase(ctx, "decrypt", -1, 0);
     recv_phase(ctx, "prove", -1, 0);
+    return DKG_OK;
+  });
+}
+
+int dkg_commitment_eval_pairs(dkg_ctx* ctx, size_t D, size_t t, size_t count, const uint32_t* rows, const uint32_t* js,
+                              const uint8_t* C, uint8_t* P, uint8_t* ok) {
+  return guarded(ctx, [&] {
+    if (!count) return DKG_OK;
+    if (!D || !rows || !js || !C || !P) return DKG_E_ARG;
+    for (size_t p = 0; p < count; p++)
+      if (rows[p] >= D || js[p] >= (1u << 24)) return DKG_E_ARG;
+    uint32_t L, G, S;
+    if (dkg_pair_eval_shape(t, ctx->receiver_chunk, &L, &G, &S) != DKG_OK) return DKG_E_ARG;
+    recv_reset_last(ctx);
+    const size_t N = t + 1;
+    hipStream_t st = ctx->stream;
+    std::vector<uint32_t> drows, crow, hx(count);
+    dkgh::distinct_places(count, rows, drows, crow);
+    for (size_t p = 0; p < count; p++) crow[p] += 1, hx[p] = js[p] + 1;  // 1-based, as k_cmp_horner's lists
+    const size_t Rn = drows.size();
+    recv_mark(ctx, 1);
+    // the distinct rows gathered and decoded, as the batch complaint stage does it
+    uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
+    h2d(ctx, Cc, C, 32 * D * N);
+    uint32_t* dlist = buf<uint32_t>(ctx, "pe_rows", 4 * Rn);
+    uint32_t* dcrow = buf<uint32_t>(ctx, "pe_crow", 4 * count);
+    uint32_t* dxs = buf<uint32_t>(ctx, "pe_xs", 4 * count);
+    h2d(ctx, dlist, drows.data(), 4 * Rn);
+    h2d(ctx, dcrow, crow.data(), 4 * count);
+    h2d(ctx, dxs, hx.data(), 4 * count);
+    uint32_t* rc = buf<uint32_t>(ctx, "pe_rc", 32 * Rn * N);
+    uint32_t* rext = buf<uint32_t>(ctx, "pe_ext", PTB * Rn * N);
+    uint8_t* pok = buf<uint8_t>(ctx, "pe_pok", Rn * N);
+    uint8_t* rowok = buf<uint8_t>(ctx, "pe_rowok", Rn);
+    uint8_t* iok = buf<uint8_t>(ctx, "pe_ok", count);
+    dkgk::gather_rows(Rn, N, dlist, Cc, nullptr, rc, st);
+    dkgk::decode_points(rc, Rn * N, rext, Rn * N, pok, st);
+    dkgk::dealer_ok(Rn, N, pok, rowok, st);
+    dkgk::pair_ok(count, dcrow, rowok, iok, st);
+    recv_mark(ctx, 2);
+    uint32_t* R = buf<uint32_t>(ctx, "pe_R", PTB * count);
+    PairStage ps;
+    pair_eval_launch(ctx, t, count, nullptr, hx.data(), dxs, dcrow, rext, Rn * N, R, ps);
+    recv_mark(ctx, 4);
+    uint32_t* Pc = buf<uint32_t>(ctx, "pe_P", 32 * count);
+    dkgk::recv_encode(1, count, R, iok, Pc, st);
+    check_launch(ctx);
+    d2h(ctx, P, Pc, 32 * count);
+    if (ok) d2h(ctx, ok, iok, count);
+    sync(ctx);  // the staging vectors live until here
+    for (const char* k : {"pairs.decode", "pairs.eval"}) ctx->phase_ms.erase(k);
+    if (ctx->nsub == 1) {
+      float ms = 0;
+      HCK(hipEventElapsedTime(&ms, ctx->rpev[1], ctx->rpev[2]));
+      ctx->phase_ms["pairs.decode"] = ms;
+      HCK(hipEventElapsedTime(&ms, ctx->rpev[2], ctx->rpev[4]));
+      ctx->phase_ms["pairs.eval"] = ms;
+    }
     return DKG_OK;
   });
 }

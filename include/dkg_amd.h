@@ -262,7 +262,9 @@ int dkg_receiver_plan_for(size_t n, size_t t, uint32_t x, int chunk, dkg_receive
  * operation of the serial walk us, host-side setup of a plan with fold stages us}. */
 double dkg_receiver_plan_cost_us(size_t n, size_t t, uint32_t x, const dkg_receiver_plan *p);
 void dkg_receiver_plan_constants(double c[5]);
-/* Chunk length of the calls below: 0 (default) automatic, >= 1 forced.  Outputs do not depend on it. */
+/* Chunk length of the calls below: 0 (default) automatic, >= 1 forced.  Outputs do not depend on it.  It
+ * also governs the wave evaluator (dkg_commitment_eval_pairs, dkg_ctx_set_complaint_eval(4)) as
+ * dkg_pair_eval_shape's chunk: there a forced chunk that needs more than 64 lanes is DKG_E_ARG. */
 int dkg_ctx_set_receiver_chunk(dkg_ctx *ctx, int chunk);
 /* The chunk of the last such call's plan (the largest over its indices). */
 int dkg_ctx_last_receiver_chunk(const dkg_ctx *ctx);
@@ -274,6 +276,23 @@ int dkg_ctx_last_receiver_chunk(const dkg_ctx *ctx);
  * whole evaluation, when the indices run as several plans or slabs). */
 int dkg_commitment_eval(dkg_ctx *ctx, size_t D, size_t t, size_t M, const uint32_t *js, const uint8_t *C,
                         uint8_t *P, uint8_t *ok);
+/* ---- (row, index) pairs, one wave each (receivers.hip k_pair_eval) ----
+ * The shape the pair evaluation runs for threshold t: the t + 1 coefficients of one row are cut into
+ * `lanes` <= 64 chunks of L that the 64 lanes of one wave walk side by side, and folded in `stages` =
+ * ceil(log2 lanes) in-wave stages with the multipliers of dkg_receiver_plan_for(.., chunk = L) (arity 2).
+ * chunk: 0 = automatic, L = ceil((t+1) / 64); >= 1 forced (a chunk >= t + 1 reads L = t + 1: one lane, no
+ * stage).  Host only, no GPU, a pure function.  DKG_E_ARG for a forced chunk that needs more than 64
+ * lanes, chunk < 0 or a NULL output. */
+int dkg_pair_eval_shape(size_t t, int chunk, uint32_t *L, uint32_t *lanes, uint32_t *stages);
+/* P[p] = sum_k (js[p]+1)^k C_rows[p][k], compressed: vartime_multiscalar_multiplication for a LIST of
+ * (row, index) pairs (broadcast.rs:75-86, 105-135).  C [D][t+1][32]; rows[p] < D, js[p] < 2^24 (DKG_E_ARG
+ * otherwise), any order, repeats allowed.  ok[p] (may be NULL) = 0 and P[p] = 32 zero bytes where row
+ * rows[p] does not decode.  Only the DISTINCT rows named are decoded.  count == 0: DKG_OK, nothing
+ * touched.  Needs no dkg_env_init.  dkg_ctx_set_receiver_chunk applies (dkg_pair_eval_shape's chunk; a
+ * chunk it rejects is DKG_E_ARG here); dkg_ctx_last_receiver_chunk reports the L that ran.  Phases:
+ * "pairs.decode", "pairs.eval". */
+int dkg_commitment_eval_pairs(dkg_ctx *ctx, size_t D, size_t t, size_t count, const uint32_t *rows,
+                              const uint32_t *js, const uint8_t *C, uint8_t *P, uint8_t *ok);
 /* dkg_verify_receiver for M receiver indices js[] (0-based, any order, repeats allowed) in one call:
  * s, s_prime [M][n][32] (column m = the shares addressed to js[m]); decision [M][n] with the values
  * of dkg_verify_pairs (SELF where i == js[m], MISSING / REJECT for an undecodable row).  qualified
@@ -744,8 +763,13 @@ int dkg_complaints_verify(dkg_ctx *ctx, size_t n, size_t t, size_t C, const uint
                           const uint32_t *accused, const uint8_t *pk, const uint8_t *E, const uint8_t *fetched1,
                           const uint8_t *enc, const uint8_t *proofs, int32_t *verdict, uint8_t *qualified);
 /* How dkg_complaints_verify evaluates P_i(j) = sum_k j^k E_i[k] (broadcast.rs:75-86): 0 automatic (per
- * accused dealer by its number of complaints), 1 always per-pair Horner in the exponent, 2 always the
- * difference tables of the accused rows.  Outputs do not depend on it. */
+ * accused dealer by its number of complaints, between 1 and 2), 1 always per-pair Horner in the exponent,
+ * 2 always the difference tables of the accused rows, 4 always one wave per (row, index) item
+ * (k_pair_eval: the shape of dkg_pair_eval_shape under dkg_ctx_set_receiver_chunk; a chunk that function
+ * rejects makes the complaint call return DKG_E_ARG).  dkg_complaints3_verify, the proven ceremony
+ * drivers and the sharded calls' fallback follow it too; the batch complaint stage does not.  3 is not a
+ * mode (it is dkg_ctx_last_complaint_eval's code for "the calling pass") and stays DKG_E_ARG, as does
+ * anything above 4.  Outputs do not depend on the mode. */
 int dkg_ctx_set_complaint_eval(dkg_ctx *ctx, int mode);
 /* dkg_ceremony_verify_full with the reference's rule for the qualified set (committee.rs:370-398):
  * decryption and the round-2/4 decisions run exactly as there (dec2, complaints2, r2_error keep their
@@ -912,7 +936,8 @@ int dkg_ceremony_batch_verify_full_proven(dkg_ctx *ctx, size_t B, size_t n, size
  * read those elements -- source 3, "the calling pass": no Horner walk, no second set of tables.  With
  * protocol-order rounds or interpolation the pass does not hold both rounds' evaluations and the call
  * falls back to dkg_complaints_verify's switch (per accused row: Horner or tables); modes 1 and 2 of
- * dkg_ctx_set_complaint_eval force that switch's sources here too.  Source 3 exists only inside these
+ * dkg_ctx_set_complaint_eval force that switch's sources here too, and mode 4 sends the fallback's items
+ * to the wave evaluator.  Source 3 exists only inside these
  * two calls and cannot be forced: dkg_ctx_set_complaint_eval(3) stays DKG_E_ARG.  Outputs do not depend
  * on any of this. */
 #define DKG_COMPLAINT_NOT_OWNED (-2) /* the complaint's accused is another rank's dealer */
@@ -934,8 +959,8 @@ int dkg_ceremony_shard_verify_full_proven_device(dkg_ctx *ctx, size_t n, size_t 
                                                  void *d_flags, void *d_dissent, int32_t *verdict, int32_t *verdict4,
                                                  double *ms_total);
 /* The evaluation source of the last sharded proven call on this ctx: 3 the calling pass, 1 Horner, 2
- * tables, 12 both of the fallback switch within one call; 0 before the first such call and after one on
- * a rank without dealers. */
+ * tables, 12 both of the fallback switch within one call, 4 the wave evaluator (the fallback under
+ * dkg_ctx_set_complaint_eval(4)); 0 before the first such call and after one on a rank without dealers. */
 int dkg_ctx_last_complaint_eval(const dkg_ctx *ctx);
 /* dkg_shard_combine_packed_device for the proven calls: d_flags_g device [ws][R] u32 the gathered flag
  * words (R = dkg_shard_rows), d_dissent_g device [ws][n] i32 the gathered dissent partials (NULL with
