@@ -237,6 +237,14 @@ def lib():
     L.dkg_shard_combine_packed_device.argtypes = [p, sz, sz, sz, p, p, p, p, ctypes.POINTER(ShardOutcome)]
     L.dkg_fixed_base_windows.argtypes = []
     L.dkg_key_comb_windows.argtypes = []
+    if hasattr(L, "dkg_comb_geometry"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_ctx_set_comb_build.argtypes = [p, ctypes.c_int]
+        L.dkg_ctx_last_comb_build.argtypes = [p]
+        L.dkg_ctx_last_comb_build_ms.argtypes = [p]
+        L.dkg_ctx_last_comb_build_ms.restype = ctypes.c_double
+        L.dkg_comb_geometry.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+        L.dkg_comb_entries.argtypes = [p, ctypes.c_int, u8p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, p]
     L.dkg_packed_row_words.argtypes = [sz]
     L.dkg_packed_row_words.restype = sz
     L.dkg_decisions_pack_device.argtypes = [p, sz, sz, sz, sz, p, p]
@@ -295,5 +303,6 @@ EXPORTED = [
     "dkg_ctx_last_complaint_eval", "dkg_shard_combine_proven_device",
     "dkg_multi_ceremony_verify_proven", "dkg_multi_ceremony_verify_full_proven",
     "dkg_receiver_plan_for", "dkg_receiver_plan_cost_us", "dkg_receiver_plan_constants", "dkg_ctx_set_receiver_chunk",
+    "dkg_ctx_set_comb_build", "dkg_ctx_last_comb_build", "dkg_ctx_last_comb_build_ms", "dkg_comb_geometry", "dkg_comb_entries",
     "dkg_ctx_last_receiver_chunk", "dkg_pair_eval_shape", "dkg_commitment_eval_pairs", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
 ]

@@ -765,6 +765,32 @@ class Backend:
         """The kind (1 or 2) the last single-ceremony encryption used."""
         return _lib.lib().dkg_ctx_last_key_comb(self._ctx)
 
+    def set_comb_build(self, mode: int):
+        """Builder of the radix-2^BITS comb tables (dkg_ctx_set_comb_build): 0 automatic, 1 one thread per
+        entry, 2 chained.  Governs every comb built afterwards and drops the cached caller-base and member-key
+        combs.  Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_comb_build(self._ctx, mode))
+
+    def last_comb_build(self) -> int:
+        """The builder (1 or 2) the last comb build ran; 0 before the first."""
+        return _lib.lib().dkg_ctx_last_comb_build(self._ctx)
+
+    def last_comb_build_ms(self) -> float:
+        """Device time of the last comb build, ms."""
+        return _lib.lib().dkg_ctx_last_comb_build_ms(self._ctx)
+
+    def comb_entries(self, kind: int, base: Optional[bytes], window: int, first: int, count: int) -> bytes:
+        """dkg_comb_entries: a fresh build of the comb of `base` (None = the generator) with the current
+        builder; entries d = first + 1 .. first + count of `window` as count x 96 bytes, the canonical
+        encodings of y + x, y - x, 2dxy."""
+        out = ctypes.create_string_buffer(max(96 * count, 1))
+        b = None if base is None else bytes(base)
+        if b is not None and len(b) != 32:
+            raise ValueError("base must be 32 bytes")
+        _check(self._ctx, _lib.lib().dkg_comb_entries(self._ctx, kind, b, window, first, count,
+                                                      ctypes.cast(out, ctypes.c_void_p)))
+        return out.raw[:96 * count]
+
     def ceremony_shard_recon_device(self, n, t, d0, d1, qualified, reconstruct, d_s: Optional[int], d_terms: int,
                                     r2_error=None, r4_error=None) -> bool:
         """After the exchange: replace the terms of this rank's reconstructed dealers by g * a_i0
@@ -1056,6 +1082,17 @@ def key_comb_choice(keys: int, items_per_key: int, cached10: bool = False, cache
     """The cost rule of the sharded full calls (dkg_key_comb_choice): 1 = radix 2^10 tables, 2 = radix-16
     combs, whichever builds (unless cached) and multiplies `items_per_key` items per key faster."""
     return _lib.lib().dkg_key_comb_choice(keys, items_per_key, int(bool(cached10)), int(bool(cached16)))
+
+
+def comb_geometry(kind: int) -> dict:
+    """dkg_comb_geometry (host only): kind 0 the shared bases' comb, kind 1 the member keys'.  Keys: bits,
+    windows, entries (per window), chunk (consecutive entries per thread of the chained builder)."""
+    b, w = ctypes.c_int(), ctypes.c_int()
+    e, c = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = _lib.lib().dkg_comb_geometry(kind, ctypes.byref(b), ctypes.byref(w), ctypes.byref(e), ctypes.byref(c))
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "comb_geometry")
+    return {"bits": b.value, "windows": w.value, "entries": e.value, "chunk": c.value}
 
 
 def receiver_plan(n: int, t: int, x: int, chunk: int = 0) -> dict:

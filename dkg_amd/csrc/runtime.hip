@@ -19,6 +19,7 @@
 #include "host_crypto.h"
 #include "kernels.h"
 #include "kernels_ilp.h"
+#include "comb_build.h"
 
 struct dkg_ctx {
   int device = 0;
@@ -63,6 +64,10 @@ struct dkg_ctx {
   int last_key_comb = 0;                // the kind the last encrypt_device used (0: none yet)
   uint8_t fb_base[32] = {0};            // dkg_fixed_base_batch: the caller base whose comb sits in fb_tabw
   bool fb_valid = false;
+  int comb_build = 0;                   // radix-2^BITS comb builder: 0 automatic (comb_build_auto), 1 one
+                                        // thread per entry (k_build_combw), 2 chained (comb_build.hip)
+  int last_comb_build = 0;              // the builder the last build ran (0: none yet)
+  hipEvent_t cb_ev[2] = {};             // around that build's launches
   int binom_mode = 0;                   // binomial: 0 per-wave Horner loops (k_binom_wave) for
                                         // tables of many column groups, else one launch per step
                                         // with lane pairs (k_binom_pair) for the steps under one
@@ -245,6 +250,33 @@ int guarded(dkg_ctx* ctx, F&& f) {
   }
 }
 
+// The builder behind automatic mode, per kind (0 the shared bases' radix, 1 the member keys'): chained
+// where it measured at least twice as fast as one thread per entry (profiles/comb_build_time.json,
+// DESIGN.md section 4).
+#ifndef DKG_COMBW_BUILD_AUTO
+#define DKG_COMBW_BUILD_AUTO 2
+#endif
+#ifndef DKG_KEY_COMB_BUILD_AUTO
+#define DKG_KEY_COMB_BUILD_AUTO 2
+#endif
+int comb_build_auto(int kind) { return kind == 0 ? DKG_COMBW_BUILD_AUTO : DKG_KEY_COMB_BUILD_AUTO; }
+
+// The radix-2^BITS combs of the decoded points ext[.., e0 + c], c < count, into tab (kind 0: COMBW_WORDS
+// words each, kind 1: key_comb_words()), by the ctx's builder; events around the launches
+// (dkg_ctx_last_comb_build_ms).
+void build_combs(dkg_ctx* ctx, int kind, const uint32_t* ext, size_t stride, size_t e0, uint32_t* tab,
+                 hipStream_t st, size_t count) {
+  const int mode = ctx->comb_build ? ctx->comb_build : comb_build_auto(kind);
+  uint32_t* wbase =
+      mode == 2 ? buf<uint32_t>(ctx, "cb.wbase", 4 * dkgk::comb_chain_scratch_words(kind, count)) : nullptr;
+  HCK(hipEventRecord(ctx->cb_ev[0], st));
+  if (mode == 2) dkgk::build_comb_chained(kind, ext, stride, e0, tab, wbase, st, count);
+  else if (kind == 0) dkgk::build_combw(ext, stride, e0, tab, st, count);
+  else dkgk::build_key_combs(ext, stride, e0, tab, st, count);
+  HCK(hipEventRecord(ctx->cb_ev[1], st));
+  ctx->last_comb_build = mode;
+}
+
 // Decode one 32-byte point and build its comb table into `tab`.
 // Comb tables of one point: radix-16 (LDS kernels; may be null) and radix-2^11 (may be null).
 void comb_for_point(dkg_ctx* ctx, const uint8_t p[32], uint32_t* tab, bool* ok, uint32_t* tab8 = nullptr) {
@@ -254,7 +286,7 @@ void comb_for_point(dkg_ctx* ctx, const uint8_t p[32], uint32_t* tab, bool* ok, 
   h2d(ctx, comp, p, 32);
   dkgk::decode_points(comp, 1, ext, 1, okd, ctx->stream);
   if (tab) dkgk::build_comb(ext, 1, 0, tab, ctx->stream);
-  if (tab8) dkgk::build_combw(ext, 1, 0, tab8, ctx->stream);
+  if (tab8) build_combs(ctx, 0, ext, 1, 0, tab8, ctx->stream, 1);
   check_launch(ctx);
   uint8_t v = 0;
   d2h(ctx, &v, okd, 1);
@@ -1869,7 +1901,7 @@ const uint8_t* encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* 
     held.clear();  // invalid until this build is queued
     dkgk::decode_points(pkc, n, pk_ext, n, pk_ok, st);
     // one comb per recipient key: r * pk_q is fixed-base
-    if (kind == 1) dkgk::build_key_combs(pk_ext, n, 0, tabs, st, n);
+    if (kind == 1) build_combs(ctx, 1, pk_ext, n, 0, tabs, st, n);
     else dkgk::benc_tab(n, pk_ext, n, tabs, st);
     if (pk_host) held.assign(pk_host, pk_host + 32 * n);
   }
@@ -2982,6 +3014,7 @@ int dkg_ctx_create(int device, dkg_ctx** out) {
     for (auto& e : ctx->hev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->bpev) HCK(hipEventCreate(&e));
     for (auto& e : ctx->rpev) HCK(hipEventCreate(&e));
+    for (auto& e : ctx->cb_ev) HCK(hipEventCreate(&e));
     for (auto& st : ctx->sub) HCK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest));
     HCK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, least));
     HCK(hipEventCreateWithFlags(&ctx->side_fork, hipEventDisableTiming));
@@ -3030,6 +3063,8 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   for (auto& e : ctx->bpev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->rpev)
+    if (e) (void)hipEventDestroy(e);
+  for (auto& e : ctx->cb_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->join)
     if (e) (void)hipEventDestroy(e);
@@ -4397,6 +4432,71 @@ int dkg_ctx_set_key_comb(dkg_ctx* ctx, int mode) {
   return DKG_OK;
 }
 int dkg_ctx_last_key_comb(const dkg_ctx* ctx) { return ctx ? ctx->last_key_comb : 0; }
+
+int dkg_ctx_set_comb_build(dkg_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  ctx->comb_build = mode;
+  // tables of the other builder must not pass for this one's: the caller base's comb and the member
+  // keys' radix-2^BITS combs are rebuilt at their next use
+  ctx->fb_valid = false;
+  ctx->key_tabs_pk.clear();
+  return DKG_OK;
+}
+int dkg_ctx_last_comb_build(const dkg_ctx* ctx) { return ctx ? ctx->last_comb_build : 0; }
+double dkg_ctx_last_comb_build_ms(const dkg_ctx* ctx) {
+  if (!ctx || !ctx->last_comb_build) return 0.0;
+  float ms = 0;
+  if (hipEventSynchronize(ctx->cb_ev[1]) != hipSuccess) return 0.0;
+  if (hipEventElapsedTime(&ms, ctx->cb_ev[0], ctx->cb_ev[1]) != hipSuccess) return 0.0;
+  return ms;
+}
+
+int dkg_comb_geometry(int kind, int* bits, int* windows, uint32_t* entries, uint32_t* chunk) {
+  return dkgk::comb_geometry(kind, bits, windows, entries, chunk) ? DKG_OK : DKG_E_ARG;
+}
+
+int dkg_comb_entries(dkg_ctx* ctx, int kind, const uint8_t base[32], int window, uint32_t first, uint32_t count,
+                     uint8_t* out) {
+  return guarded(ctx, [&] {
+    int windows = 0;
+    uint32_t entries = 0;
+    if (!dkgk::comb_geometry(kind, nullptr, &windows, &entries, nullptr)) return DKG_E_ARG;
+    if (window < 0 || window >= windows || first > entries || count > entries - first) {
+      ctx->err = "comb_entries: window or range outside the comb's geometry";
+      return DKG_E_ARG;
+    }
+    if (count == 0) return DKG_OK;
+    if (!out) return DKG_E_ARG;
+    uint32_t* comp = buf<uint32_t>(ctx, "comb_in", 32);
+    uint32_t* ext = buf<uint32_t>(ctx, "comb_ext", PTB);
+    uint8_t* okd = buf<uint8_t>(ctx, "comb_ok", 1);
+    h2d(ctx, comp, base ? base : BASEPOINT, 32);
+    dkgk::decode_points(comp, 1, ext, 1, okd, ctx->stream);
+    check_launch(ctx);
+    uint8_t v = 0;
+    d2h(ctx, &v, okd, 1);
+    sync(ctx);
+    if (!v) {
+      ctx->err = "comb_entries: base point failed to decode";
+      return DKG_E_DECODE;
+    }
+    // always a fresh build: kind 0 into the caller base's buffer (470 MB; its cached comb is given up)
+    uint32_t* tab;
+    if (kind == 0) {
+      tab = buf<uint32_t>(ctx, "fb_tabw", COMBW_BYTES);
+      ctx->fb_valid = false;
+    } else {
+      tab = buf<uint32_t>(ctx, "ce.tab", 4 * dkgk::key_comb_words());
+    }
+    build_combs(ctx, kind, ext, 1, 0, tab, ctx->stream, 1);
+    uint32_t* ob = buf<uint32_t>(ctx, "ce.out", (size_t)96 * count);
+    dkgk::comb_entries_bytes(kind, tab, window, first, count, ob, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, out, ob, (size_t)96 * count);
+    sync(ctx);
+    return DKG_OK;
+  });
+}
 
 // Which comb of the recipient keys serves K = pk_q r for `keys` keys with items_per_key items each (a
 // shard of D dealers: 2 D): the smaller of build (unless that kind's tables are cached) + multiplication.

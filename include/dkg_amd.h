@@ -497,6 +497,36 @@ size_t dkg_packed_row_words(size_t n);
 int dkg_fixed_base_windows(void);
 /* The same for the member keys' combs (full mode's K = pk_q r, radix 2^DKG_KEY_COMB_BITS). */
 int dkg_key_comb_windows(void);
+/* How the radix-2^BITS comb tables are built (the g and h combs of dkg_ctx_create / dkg_env_init, a
+ * caller base's comb in dkg_fixed_base_batch, the member keys' radix-2^DKG_KEY_COMB_BITS combs of full
+ * mode): 1 = one thread per entry (its own doublings, multiple and inversion), 2 = chained (one
+ * doubling chain per base for the windows' bases, then each thread walks a chunk of consecutive
+ * entries by mixed additions and inverts the chunk's Z together), 0 (default) = automatic: chained for
+ * both radices (DESIGN.md section 4 has the measured ratios).  Governs every comb built after the call
+ * and drops the cached caller-base comb and the cached member-key combs, so their next use rebuilds
+ * them.  The generator's comb of dkg_ctx_create is built under automatic.  The tables' canonical
+ * contents (dkg_comb_entries) and every output computed from them do not depend on the builder.
+ * DKG_E_ARG for any other mode. */
+int dkg_ctx_set_comb_build(dkg_ctx *ctx, int mode);
+/* The builder (1 or 2) the last comb build on this ctx ran; 0 before the first. */
+int dkg_ctx_last_comb_build(const dkg_ctx *ctx);
+/* Device time of that build in ms (events around its launches; waits for it to finish). */
+double dkg_ctx_last_comb_build_ms(const dkg_ctx *ctx);
+/* The geometry of a comb kind (a host function, no ctx, no GPU): kind 0 = the shared bases' comb
+ * (radix 2^DKG_COMBW_BITS), kind 1 = the member keys' comb (radix 2^DKG_KEY_COMB_BITS).  *bits the
+ * radix' exponent, *windows = 256 / bits + 1, *entries = 2^(bits - 1) per window, *chunk the
+ * consecutive entries one thread of the chained builder owns.  Outputs may be NULL.  DKG_E_ARG for
+ * any other kind. */
+int dkg_comb_geometry(int kind, int *bits, int *windows, uint32_t *entries, uint32_t *chunk);
+/* Builds the comb of `base` (32-byte encoding; NULL = the generator) with the ctx's current builder --
+ * always a fresh build: no cached table is read and none is kept (a kind-0 build takes the caller
+ * base's buffer of dkg_fixed_base_batch, whose cached comb is dropped) -- and writes entries
+ * d = first + 1 .. first + count of `window`, entry d = d * 2^(bits * window) * base, as out
+ * [count][96]: the canonical little-endian encodings of y + x, y - x and 2 d_curve x y of the affine
+ * point.  DKG_E_DECODE for a base that does not decode, DKG_E_ARG for a kind, window or range outside
+ * the geometry; count == 0 returns DKG_OK and touches nothing. */
+int dkg_comb_entries(dkg_ctx *ctx, int kind, const uint8_t base[32], int window, uint32_t first, uint32_t count,
+                     uint8_t *out);
 /* d_dec device [nvalid][n] raw rows of dealers d0 .. d0+nvalid-1 (dkg_ceremony_shard_device's
  * output) -> d_packed device [rows][dkg_packed_row_words(n)] u32, rows past nvalid zero (the padded
  * rank block, rows = dkg_shard_rows).  DKG_E_ARG if a row holds values the encoding cannot carry

@@ -413,6 +413,19 @@ def affine_pair(p0, p1, where="affine_pairs", scaled=False):
     return out
 
 
+def comb_chain_entry(p, bw, where="comb_chain"):
+    """comb_build.hip k_comb_chain: one step of the walk P_d = P_(d-1) + B_w (ge_madd, B_w a comb entry),
+    the running product of the chunk's Z, 1 / Z_k = (the inverse of the product) x (a prefix product),
+    and k_build_combw's closing sequence (comb_entry_put): the entry the consumers read."""
+    X, Y, Z, T = ge_madd(p, bw, where)
+    run = fe_mul(Z, Z, where)                   # run * Z
+    zi = fe_mul(run, run, where)                # fe_invert's output (a product of tight values) * a prefix
+    run = fe_mul(run, Z, where)
+    x, y = fe_mul(X, zi, where), fe_mul(Y, zi, where)
+    return (fe_carry(fe_add(y, x, where), where), fe_carry(fe_sub(y, x, where), where),
+            fe_mul(fe_mul(x, y, where), D2, where))
+
+
 def ge_to_cached_ded(p):
     X, Y, Z, T = p
     return (fe_add(Y, X, "to_cached_ded"), fe_sub(Y, X, "to_cached_ded"), fe_add(Z, Z, "to_cached_ded"),
@@ -596,6 +609,7 @@ def run():
         aff = (fe_carry(fe_add(tight, tight)), fe_carry(fe_sub(tight, tight)), fe_mul(fe_mul(tight, tight), D2))
         outs += [ge_madd(pt, comb8_entry(*aff), "comb8 madd"), ge_madd(pt, aff, "ge_msub", minus=True)]
         outs += [ge_madd_signed(pt, affine_addend(pt)), ge_add_ded(pt, ge_to_cached_ded(pt))]
+        outs += [ge_madd(pt, comb_chain_entry(pt, aff), "comb_chain madd")]
         outs += [ge_madd_signed(pt, q, "ge_madd_signed(affine_pairs)") for q in affine_pair(pt, pt)]
         # the stepping's scaled state: entered by ge_to_scaled, then closed under ge_add_sc_lds; its
         # records feed the scaled normalisations, whose slots are addends like the proper ones'

@@ -143,7 +143,7 @@ def lagrange_at_zero(ys, xs):
 
 
 # ---------------- the ceremony (plaintext-share mode) ----------------
-def ceremony(n, t, master, ceremony_id=0, faults=None, with_coeffs=True, transport=None):
+def ceremony(n, t, master, ceremony_id=0, faults=None, with_coeffs=True, transport=None, ck=CK_BYTES):
     """Returns a dict of inputs/outputs.  faults: list of dicts
        {"kind": "E_identity", "dealer": i} (committee.rs:1127-1128 style),
        {"kind": "share_flip", "dealer": i, "receiver": j}   s_ij += 1,
@@ -154,7 +154,7 @@ def ceremony(n, t, master, ceremony_id=0, faults=None, with_coeffs=True, transpo
        Dealers / receivers are 1-based as in the reference."""
     faults = faults or []
     assert t < (n + 1) // 2, "Environment::init asserts threshold < (nr_members + 1) / 2"
-    h = hash_to_group(CK_BYTES)
+    h = hash_to_group(ck)
     g = gmul_base(1)
     A, B, E, Apub, S, SP = [], [], [], [], [], []
     for i in range(n):
@@ -252,7 +252,7 @@ def ceremony(n, t, master, ceremony_id=0, faults=None, with_coeffs=True, transpo
         # property of the honest run (committee.rs:1633-1647): mpk == g * sum of qualified secrets
         assert mpk == gmul_base(sum(A[i][0] for i in range(n) if qualified[i])) or not exact
     out = {
-        "n": n, "t": t, "ceremony": ceremony_id, "master_seed": hx(master), "ck_bytes": hx(CK_BYTES),
+        "n": n, "t": t, "ceremony": ceremony_id, "master_seed": hx(master), "ck_bytes": hx(ck),
         "h": hx(h), "faults": faults,
         "E": "".join(hx(p) for e in Ew for p in e),
         "A": "".join(hx(p) for e in Aw for p in e),
@@ -791,6 +791,10 @@ def main():
             {"kind": "share_flip", "dealer": d, "receiver": j} for d in range(1, 5) for j in range(5, last + 1)] + [
             {"kind": "A_generator", "dealer": 16}])
     files["spot_n4096_t2047.json"] = spot(4096, 2047, m, [5, 3000], [0, 1500, 4095])
+    # n = 8: a ceremony under a commitment key of its own (h and its comb differ from every other
+    # fixture's) and a full-mode ceremony with its own member keys (tests/test_gpu_comb_build.py)
+    files["ceremony_n8_t3_ck.json"] = ceremony(8, 3, m, ceremony_id=9, ck=b"A commitment key of this ceremony's own.")
+    files["full_n8_t3.json"] = full_ceremony(8, 3, m, ceremony_id=10)
     only = set(sys.argv[1].split(",")) if len(sys.argv) > 1 else None
     files = {k: v for k, v in files.items() if only is None or k in only}
     for obj in files.values():
