@@ -651,47 +651,39 @@ class Backend:
         _check(self._ctx, _lib.lib().dkg_dealer_coeffs_device(self._ctx, master, ceremony0, B, d0, D, t, vp(d_a),
                                                                vp(d_b)))
 
-    def ceremony_shard_device(self, n, t, d0, d1, d_a, d_b, d_dec2, d_dec4, d_A0, d_partial) -> float:
+    # ---- one rank of a dealer-sharded ceremony: rounds 2-5 of its dealers [d0, d1).  The d_* are device
+    # pointers (e.g. torch tensor .data_ptr())
+    def _shard_call(self, fn, n, t, d0, d1, args) -> float:
+        """One sharded entry point, fn(ctx, n, t, d0, d1, *args, &ms_total): the call's device time in ms."""
         ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_device(self._ctx, n, t, d0, d1, vp(d_a), vp(d_b),
-                                                                vp(d_dec2), vp(d_dec4), vp(d_A0),
-                                                                vp(d_partial), ctypes.byref(ms)))
+        _check(self._ctx, fn(self._ctx, n, t, d0, d1, *args, ctypes.byref(ms)))
         return ms.value
+
+    def ceremony_shard_device(self, n, t, d0, d1, d_a, d_b, d_dec2, d_dec4, d_A0, d_partial) -> float:
+        return self._shard_call(_lib.lib().dkg_ceremony_shard_device, n, t, d0, d1,
+                                (d_a, d_b, d_dec2, d_dec4, d_A0, d_partial))
 
     def ceremony_shard_verify_device(self, n, t, d0, d1, d_E, d_A, d_s, d_sp, d_dec2, d_dec4, d_A0,
                                      d_partial) -> float:
         """Rounds 2-5 of this rank's dealers [d0, d1) on received broadcasts (device pointers)."""
-        ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_device(
-            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_s), vp(d_sp), vp(d_dec2), vp(d_dec4), vp(d_A0),
-            vp(d_partial), ctypes.byref(ms)))
-        return ms.value
+        return self._shard_call(_lib.lib().dkg_ceremony_shard_verify_device, n, t, d0, d1,
+                                (d_E, d_A, d_s, d_sp, d_dec2, d_dec4, d_A0, d_partial))
 
     def ceremony_shard_full_device(self, n, t, d0, d1, d_a, d_b, d_r, sk: bytes, pk: bytes, d_dec2, d_dec4, d_A0,
                                    d_partial, d_e1: Optional[int] = None, d_ct: Optional[int] = None) -> float:
         """ceremony_shard_device in full (encrypted-share) mode: this rank's dealers' shares encrypted to
         the n member keys (d_r: device [D][n][2][32] randomness; sk, pk host [n][32]), decrypted by all n
         receivers, and checked.  d_e1 / d_ct (device [D][n][2][32], optional) receive the ciphertexts."""
-        ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_full_device(
-            self._ctx, n, t, d0, d1, vp(d_a), vp(d_b), vp(d_r), sk, pk, vp(d_e1), vp(d_ct), vp(d_dec2), vp(d_dec4),
-            vp(d_A0), vp(d_partial), ctypes.byref(ms)))
-        return ms.value
+        return self._shard_call(_lib.lib().dkg_ceremony_shard_full_device, n, t, d0, d1,
+                                (d_a, d_b, d_r, sk, pk, d_e1, d_ct, d_dec2, d_dec4, d_A0, d_partial))
 
     def ceremony_shard_verify_full_device(self, n, t, d0, d1, d_E, d_A, d_e1, d_ct, sk: bytes, d_dec2, d_dec4, d_A0,
                                           d_partial) -> float:
         """ceremony_shard_verify_device on received ciphertexts d_e1, d_ct (device [D][n][2][32])."""
-        ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_full_device(
-            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_e1), vp(d_ct), sk, vp(d_dec2), vp(d_dec4), vp(d_A0),
-            vp(d_partial), ctypes.byref(ms)))
-        return ms.value
+        return self._shard_call(_lib.lib().dkg_ceremony_shard_verify_full_device, n, t, d0, d1,
+                                (d_E, d_A, d_e1, d_ct, sk, d_dec2, d_dec4, d_A0, d_partial))
 
-    # ---- the sharded calls that decide by the proven complaints (each rank verifies those against its own dealers)
+    # the sharded calls that decide by the proven complaints (each rank verifies those against its own dealers)
     def ceremony_shard_verify_proven_device(self, n, t, d0, d1, d_E, d_A, d_s, d_sp, accusers4: Sequence[int],
                                             accused4: Sequence[int], share4: bytes, randomness4: bytes, d_dec2, d_dec4,
                                             d_A0, d_partial, flag_rows: int, d_flags, fetched1: Optional[bytes] = None,
@@ -702,13 +694,11 @@ class Backend:
         (flag_rows = shard_rows(n, world_size)); fetched1 / fetched3: the rank's rows' intake masks."""
         C4 = len(accusers4)
         res4 = _carray(ctypes.c_int32, C4)
-        ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_proven_device(
-            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_s), vp(d_sp), _opt(fetched1), _opt(fetched3), C4,
-            _carray(ctypes.c_uint32, C4, accusers4), _carray(ctypes.c_uint32, C4, accused4), share4, randomness4,
-            vp(d_dec2), vp(d_dec4), vp(d_A0), vp(d_partial), flag_rows, vp(d_flags), res4, ctypes.byref(ms)))
-        return ms.value, list(res4)[:C4]
+        ms = self._shard_call(_lib.lib().dkg_ceremony_shard_verify_proven_device, n, t, d0, d1, (
+            d_E, d_A, d_s, d_sp, _opt(fetched1), _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, d_dec2, d_dec4, d_A0, d_partial, flag_rows,
+            d_flags, res4))
+        return ms, list(res4)[:C4]
 
     def ceremony_shard_verify_full_proven_device(self, n, t, d0, d1, d_E, d_A, d_e1, d_ct, sk: bytes, pk: bytes,
                                                  accusers: Sequence[int], accused: Sequence[int], proofs: bytes,
@@ -720,15 +710,12 @@ class Backend:
         (ms, verdict, verdict4).  d_dissent: device [n] i32, the rank's dissent partial (optional)."""
         C, C4 = len(accusers), len(accusers4)
         res, res4 = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4)
-        ms = ctypes.c_double()
-        vp = ctypes.c_void_p
-        _check(self._ctx, _lib.lib().dkg_ceremony_shard_verify_full_proven_device(
-            self._ctx, n, t, d0, d1, vp(d_E), vp(d_A), vp(d_e1), vp(d_ct), sk, pk, _opt(fetched1), _opt(fetched3), C,
-            _carray(ctypes.c_uint32, C, accusers), _carray(ctypes.c_uint32, C, accused), proofs, C4,
-            _carray(ctypes.c_uint32, C4, accusers4), _carray(ctypes.c_uint32, C4, accused4), share4, randomness4,
-            vp(d_dec2), vp(d_dec4), vp(d_A0), vp(d_partial), flag_rows, vp(d_flags), vp(d_dissent), res, res4,
-            ctypes.byref(ms)))
-        return ms.value, list(res)[:C], list(res4)[:C4]
+        ms = self._shard_call(_lib.lib().dkg_ceremony_shard_verify_full_proven_device, n, t, d0, d1, (
+            d_E, d_A, d_e1, d_ct, sk, pk, _opt(fetched1), _opt(fetched3), C, _carray(ctypes.c_uint32, C, accusers),
+            _carray(ctypes.c_uint32, C, accused), proofs, C4, _carray(ctypes.c_uint32, C4, accusers4),
+            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, d_dec2, d_dec4, d_A0, d_partial, flag_rows,
+            d_flags, d_dissent, res, res4))
+        return ms, list(res)[:C], list(res4)[:C4]
 
     def last_complaint_eval(self) -> int:
         """Where the last sharded proven call took P_i(j) from: 3 its own pass, 1 Horner, 2 tables, 12 both."""
@@ -952,44 +939,38 @@ class MultiBackend:
             setattr(r, k, bufs[k].raw)
         return r
 
-    def ceremony(self, a: bytes, b: bytes, n: int, t: int) -> CeremonyResult:
+    def _ceremony_call(self, fn, n, t, args, tail=()) -> CeremonyResult:
+        """One multi-device entry point, fn(m, n, t, *args, out, *tail), as a CeremonyResult."""
         o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_run(self._m, n, t, a, b, ctypes.byref(o)))
+        self._check(fn(self._m, n, t, *args, ctypes.byref(o), *tail))
         return self._result(n, t, o, bufs)
+
+    def _pointers(self, per_shard):
+        return (ctypes.c_void_p * len(self.devices))(*per_shard)
+
+    def ceremony(self, a: bytes, b: bytes, n: int, t: int) -> CeremonyResult:
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_run, n, t, (a, b))
 
     def ceremony_device(self, d_as, d_bs, n: int, t: int) -> CeremonyResult:
         """d_as[i], d_bs[i]: device pointers on devices[i] to shard i's dealers' coefficients."""
-        k = len(self.devices)
-        pa = (ctypes.c_void_p * k)(*d_as)
-        pb = (ctypes.c_void_p * k)(*d_bs)
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_run_device(self._m, n, t, pa, pb, ctypes.byref(o)))
-        return self._result(n, t, o, bufs)
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_run_device, n, t,
+                                   (self._pointers(d_as), self._pointers(d_bs)))
 
     def ceremony_verify(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, n: int, t: int) -> CeremonyResult:
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_verify(self._m, n, t, E, A, s, s_prime, ctypes.byref(o)))
-        return self._result(n, t, o, bufs)
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_verify, n, t, (E, A, s, s_prime))
 
     # ---- full (encrypted-share) mode: each shard encrypts, decrypts and checks its dealers' rows
     def ceremony_full(self, a: bytes, b: bytes, r: bytes, sk: bytes, pk: bytes, n: int, t: int) -> CeremonyResult:
         """r: host [n][n][2][32] encryption randomness (enc_randomness); sk, pk: member_keys."""
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_run_full(self._m, n, t, a, b, r, sk, pk, ctypes.byref(o)))
-        return self._result(n, t, o, bufs)
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_run_full, n, t, (a, b, r, sk, pk))
 
     def ceremony_full_device(self, d_as, d_bs, d_rs, sk: bytes, pk: bytes, n: int, t: int) -> CeremonyResult:
         """d_as[i], d_bs[i], d_rs[i]: device pointers on devices[i] to shard i's coefficients and randomness."""
-        k = len(self.devices)
-        pa, pb, pr = ((ctypes.c_void_p * k)(*x) for x in (d_as, d_bs, d_rs))
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_run_full_device(self._m, n, t, pa, pb, pr, sk, pk, ctypes.byref(o)))
-        return self._result(n, t, o, bufs)
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_run_full_device, n, t,
+                                   (self._pointers(d_as), self._pointers(d_bs), self._pointers(d_rs), sk, pk))
 
     def ceremony_verify_full(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, n: int, t: int) -> CeremonyResult:
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_verify_full(self._m, n, t, E, A, e1, ct, sk, ctypes.byref(o)))
-        return self._result(n, t, o, bufs)
+        return self._ceremony_call(_lib.lib().dkg_multi_ceremony_verify_full, n, t, (E, A, e1, ct, sk))
 
     # ---- the proven-complaint rule: each shard verifies the complaints against its own dealers
     def ceremony_verify_proven(self, E: bytes, A: bytes, s: bytes, s_prime: bytes, fetched1: Optional[bytes],
@@ -999,12 +980,12 @@ class MultiBackend:
         C4 = len(accusers4)
         res4 = _carray(ctypes.c_int32, C4)
         st, ri = ctypes.c_int32(), ctypes.c_int32()
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_verify_proven(
-            self._m, n, t, E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
-            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, ctypes.byref(o), res4, ctypes.byref(st),
-            ctypes.byref(ri)))
-        return ProvenResult(self._result(n, t, o, bufs), list(res4)[:C4], st.value, ri.value)
+        r = self._ceremony_call(
+            _lib.lib().dkg_multi_ceremony_verify_proven, n, t,
+            (E, A, s, s_prime, _opt(fetched1), _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+             _carray(ctypes.c_uint32, C4, accused4), share4, randomness4),
+            tail=(res4, ctypes.byref(st), ctypes.byref(ri)))
+        return ProvenResult(r, list(res4)[:C4], st.value, ri.value)
 
     def ceremony_verify_full_proven(self, E: bytes, A: bytes, e1: bytes, ct: bytes, sk: bytes, pk: bytes,
                                     accusers: Sequence[int], accused: Sequence[int], proofs: bytes,
@@ -1015,14 +996,13 @@ class MultiBackend:
         C, C4 = len(accusers), len(accusers4)
         res, res4, dis = _carray(ctypes.c_int32, C), _carray(ctypes.c_int32, C4), _carray(ctypes.c_int32, n)
         st, ri = ctypes.c_int32(), ctypes.c_int32()
-        o, bufs = self._out(n, t)
-        self._check(_lib.lib().dkg_multi_ceremony_verify_full_proven(
-            self._m, n, t, E, A, e1, ct, sk, pk, C, _carray(ctypes.c_uint32, C, accusers),
-            _carray(ctypes.c_uint32, C, accused), proofs, _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
-            _carray(ctypes.c_uint32, C4, accused4), share4, randomness4, ctypes.byref(o), res, dis, res4,
-            ctypes.byref(st), ctypes.byref(ri)))
-        return ProvenResult(self._result(n, t, o, bufs), list(res4)[:C4], st.value, ri.value, list(res)[:C],
-                            list(dis)[:n])
+        r = self._ceremony_call(
+            _lib.lib().dkg_multi_ceremony_verify_full_proven, n, t,
+            (E, A, e1, ct, sk, pk, C, _carray(ctypes.c_uint32, C, accusers), _carray(ctypes.c_uint32, C, accused),
+             proofs, _opt(fetched3), C4, _carray(ctypes.c_uint32, C4, accusers4),
+             _carray(ctypes.c_uint32, C4, accused4), share4, randomness4),
+            tail=(res, dis, res4, ctypes.byref(st), ctypes.byref(ri)))
+        return ProvenResult(r, list(res4)[:C4], st.value, ri.value, list(res)[:C], list(dis)[:n])
 
 
 @dataclass

@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <thread>
@@ -405,179 +406,6 @@ int dkg_multi_env_init(dkg_multi* m, size_t threshold, size_t nr_members, const 
   });
 }
 
-int dkg_multi_ceremony_run_device(dkg_multi* m, size_t n, size_t t, const void* const* d_a, const void* const* d_b,
-                                  dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!d_a || !d_b) return DKG_E_ARG;
-    const double t0 = now_ms();
-    std::vector<double> sh(m->ws(), 0);
-    rc = for_shards(m, [&](int i) {
-      size_t a, b;
-      range(m, n, i, &a, &b);
-      shard_outputs(m, n, i, b - a);
-      return dkg_ceremony_shard_device(m->ctx[i], n, t, a, b, d_a[i], d_b[i], m->dec2[i].p, m->dec4[i].p,
-                                       m->A0[i].p, m->part[i].p, &sh[i]);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    return finish(m, n, t, out, t0);
-  });
-}
-
-int dkg_multi_ceremony_run(dkg_multi* m, size_t n, size_t t, const uint8_t* a, const uint8_t* b,
-                           dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!a || !b) return DKG_E_ARG;
-    const size_t N = t + 1;
-    std::vector<const void*> pa(m->ws()), pb(m->ws());
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t bytes = 32 * N * (d1 - d0);
-      pa[i] = m->in_a[i].get(m->dev[i], bytes);
-      pb[i] = m->in_b[i].get(m->dev[i], bytes);
-      MCK(hipMemcpy((void*)pa[i], a + 32 * N * d0, bytes, hipMemcpyHostToDevice));
-      MCK(hipMemcpy((void*)pb[i], b + 32 * N * d0, bytes, hipMemcpyHostToDevice));
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    return dkg_multi_ceremony_run_device(m, n, t, pa.data(), pb.data(), out);
-  });
-}
-
-int dkg_multi_ceremony_verify(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* s,
-                              const uint8_t* s_prime, dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!E || !A || !s || !s_prime) return DKG_E_ARG;
-    const size_t N = t + 1;
-    double t0 = 0;
-    std::vector<double> sh(m->ws(), 0);
-    // uploads first (every shard), then the timed region
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t D = d1 - d0;
-      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_s[i].get(m->dev[i], 32 * n * D), s + 32 * n * d0, 32 * n * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_sp[i].get(m->dev[i], 32 * n * D), s_prime + 32 * n * d0, 32 * n * D,
-                    hipMemcpyHostToDevice));
-      shard_outputs(m, n, i, D);
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    t0 = now_ms();
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      return dkg_ceremony_shard_verify_device(m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_s[i].p,
-                                              m->in_sp[i].p, m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p,
-                                              &sh[i]);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    return finish(m, n, t, out, t0);
-  });
-}
-
-int dkg_multi_ceremony_run_full_device(dkg_multi* m, size_t n, size_t t, const void* const* d_a, const void* const* d_b,
-                                       const void* const* d_r, const uint8_t* sk, const uint8_t* pk,
-                                       dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!d_a || !d_b || !d_r || !sk || !pk) {
-      m->err = "bad arguments: d_a, d_b, d_r, sk and pk must be non-NULL";
-      return DKG_E_ARG;
-    }
-    const double t0 = now_ms();
-    std::vector<double> sh(m->ws(), 0);
-    rc = for_shards(m, [&](int i) {
-      size_t a, b;
-      range(m, n, i, &a, &b);
-      shard_outputs(m, n, i, b - a);
-      return dkg_ceremony_shard_full_device(m->ctx[i], n, t, a, b, d_a[i], d_b[i], d_r[i], sk, pk, nullptr, nullptr,
-                                            m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, &sh[i]);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    return finish(m, n, t, out, t0);
-  });
-}
-
-int dkg_multi_ceremony_run_full(dkg_multi* m, size_t n, size_t t, const uint8_t* a, const uint8_t* b,
-                                const uint8_t* r, const uint8_t* sk, const uint8_t* pk, dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!a || !b || !r || !sk || !pk) {
-      m->err = "bad arguments: a, b, r, sk and pk must be non-NULL";
-      return DKG_E_ARG;
-    }
-    const size_t N = t + 1;
-    std::vector<const void*> pa(m->ws()), pb(m->ws()), pr(m->ws());
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t bytes = 32 * N * (d1 - d0), rbytes = 64 * n * (d1 - d0);
-      pa[i] = m->in_a[i].get(m->dev[i], bytes);
-      pb[i] = m->in_b[i].get(m->dev[i], bytes);
-      pr[i] = m->in_r[i].get(m->dev[i], rbytes);
-      MCK(hipMemcpy((void*)pa[i], a + 32 * N * d0, bytes, hipMemcpyHostToDevice));
-      MCK(hipMemcpy((void*)pb[i], b + 32 * N * d0, bytes, hipMemcpyHostToDevice));
-      MCK(hipMemcpy((void*)pr[i], r + 64 * n * d0, rbytes, hipMemcpyHostToDevice));
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    return dkg_multi_ceremony_run_full_device(m, n, t, pa.data(), pb.data(), pr.data(), sk, pk, out);
-  });
-}
-
-int dkg_multi_ceremony_verify_full(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
-                                   const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
-  return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!E || !A || !e1 || !ct || !sk) {
-      m->err = "bad arguments: E, A, e1, ct and sk must be non-NULL";
-      return DKG_E_ARG;
-    }
-    const size_t N = t + 1;
-    double t0 = 0;
-    std::vector<double> sh(m->ws(), 0);
-    // uploads first (every shard), then the timed region
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t D = d1 - d0;
-      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_e1[i].get(m->dev[i], 64 * n * D), e1 + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_ct[i].get(m->dev[i], 64 * n * D), ct + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
-      shard_outputs(m, n, i, D);
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    t0 = now_ms();
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      return dkg_ceremony_shard_verify_full_device(m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_e1[i].p,
-                                                   m->in_ct[i].p, sk, m->dec2[i].p, m->dec4[i].p, m->A0[i].p,
-                                                   m->part[i].p, &sh[i]);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    return finish(m, n, t, out, t0);
-  });
-}
-
 }  // extern "C"
 
 namespace {
@@ -625,9 +453,159 @@ int pack_shard(dkg_multi* m, size_t n, int i, size_t R, size_t d0, size_t D) {
   return dkg_decisions_pack_device(m->ctx[i], R, D, n, d0, m->dec4[i].p, m->pk4[i].p);
 }
 
+// One ceremony for the shards, as the pointers of the C ABI (null = absent), in the manner of the
+// library's ShardInput: the dealers' coefficients (a, b: generate mode) as whole host arrays or as
+// per-shard device pointers, or the received broadcasts on the host; full mode is sk != nullptr and the
+// proven rule follows the presence of `lists`.
+struct MultiInput {
+  const uint8_t *a = nullptr, *b = nullptr, *r = nullptr;              // host [n][..], sliced by dealer, or
+  const void *const *d_a = nullptr, *const *d_b = nullptr, *const *d_r = nullptr;  //   [ws] device pointers
+  const uint8_t *E = nullptr, *A = nullptr;                            // the received commitments
+  const uint8_t *s = nullptr, *s_prime = nullptr;                      // plaintext shares, or
+  const uint8_t *e1 = nullptr, *ct = nullptr;                          //   ciphertexts
+  const uint8_t *sk = nullptr, *pk = nullptr;                          // the members' keys (full mode)
+  const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;              // intake masks [n]
+  const ProvenLists* lists = nullptr;
+  const ProvenOut* pv = nullptr;  // with `lists`: the common outcome's destinations
+};
+
+// Every dkg_multi_ceremony_* entry point: the uploads (every shard), then the timed region -- the shards'
+// calls on their own threads and the steps after them.  `required`: the entry point's pointers that must
+// not be null.
+int multi_ceremony(dkg_multi* m, size_t n, size_t t, const MultiInput& in, dkg_ceremony_out* out,
+                   std::initializer_list<const void*> required) {
+  int rc = check_args(m, n, t, out);
+  if (rc != DKG_OK) return rc;
+  for (const void* p : required)
+    if (!p) {
+      m->err = "bad arguments: a required input pointer is NULL";
+      return DKG_E_ARG;
+    }
+  const ProvenLists none;
+  const ProvenLists& c = in.lists ? *in.lists : none;
+  if ((rc = proven_lists_ok(m, c)) != DKG_OK) return rc;
+  const int ws = m->ws();
+  const size_t N = t + 1, R = dkg_shard_rows(n, ws);
+  const bool gen = in.a || in.d_a, full = in.sk != nullptr;
+  // what goes up per shard: its dealers' slice of each host array that is present
+  struct Upload {
+    const uint8_t* host;
+    size_t per_dealer;
+    std::vector<DevBuf>& to;
+  };
+  const Upload uploads[] = {{in.a, 32 * N, m->in_a},  {in.b, 32 * N, m->in_b},        {in.r, 64 * n, m->in_r},
+                            {in.E, 32 * N, m->in_a},  {in.A, 32 * N, m->in_b},        {in.s, 32 * n, m->in_s},
+                            {in.s_prime, 32 * n, m->in_sp}, {in.e1, 64 * n, m->in_e1}, {in.ct, 64 * n, m->in_ct}};
+  rc = for_shards(m, [&](int i) {
+    size_t d0, d1;
+    range(m, n, i, &d0, &d1);
+    const size_t D = d1 - d0;
+    for (const Upload& u : uploads)
+      if (u.host)
+        MCK(hipMemcpy(u.to[i].get(m->dev[i], u.per_dealer * D), u.host + u.per_dealer * d0, u.per_dealer * D,
+                      hipMemcpyHostToDevice));
+    shard_outputs(m, n, i, D);
+    if (in.lists) proven_outputs(m, n, i, R);
+    return DKG_OK;
+  });
+  if (rc != DKG_OK) return rc;
+  const double t0 = now_ms();
+  std::vector<double> sh(ws, 0);
+  std::vector<std::vector<int32_t>> v2(ws, std::vector<int32_t>(c.C ? c.C : 1));
+  std::vector<std::vector<int32_t>> v4(ws, std::vector<int32_t>(c.C4 ? c.C4 : 1));
+  rc = for_shards(m, [&](int i) {
+    size_t d0, d1;
+    range(m, n, i, &d0, &d1);
+    dkg_ctx* ctx = m->ctx[i];
+    // the coefficients or the commitments, and the randomness: the caller's device arrays or the uploads
+    const void *pa = in.d_a ? in.d_a[i] : m->in_a[i].p, *pb = in.d_b ? in.d_b[i] : m->in_b[i].p;
+    const void* pr = in.d_r ? in.d_r[i] : m->in_r[i].p;
+    void *dec2 = m->dec2[i].p, *dec4 = m->dec4[i].p, *A0 = m->A0[i].p, *part = m->part[i].p;
+    const uint8_t *f1 = in.fetched1 ? in.fetched1 + d0 : nullptr, *f3 = in.fetched3 ? in.fetched3 + d0 : nullptr;
+    if (gen)
+      return full ? dkg_ceremony_shard_full_device(ctx, n, t, d0, d1, pa, pb, pr, in.sk, in.pk, nullptr, nullptr, dec2,
+                                                   dec4, A0, part, &sh[i])
+                  : dkg_ceremony_shard_device(ctx, n, t, d0, d1, pa, pb, dec2, dec4, A0, part, &sh[i]);
+    if (!in.lists)
+      return full ? dkg_ceremony_shard_verify_full_device(ctx, n, t, d0, d1, pa, pb, m->in_e1[i].p, m->in_ct[i].p,
+                                                          in.sk, dec2, dec4, A0, part, &sh[i])
+                  : dkg_ceremony_shard_verify_device(ctx, n, t, d0, d1, pa, pb, m->in_s[i].p, m->in_sp[i].p, dec2,
+                                                     dec4, A0, part, &sh[i]);
+    const int r =
+        full ? dkg_ceremony_shard_verify_full_proven_device(
+                   ctx, n, t, d0, d1, pa, pb, m->in_e1[i].p, m->in_ct[i].p, in.sk, in.pk, f1, f3, c.C, c.accuser,
+                   c.accused, c.proofs, c.C4, c.accuser4, c.accused4, c.share4, c.randomness4, dec2, dec4, A0, part, R,
+                   m->flags[i].p, m->dis[i].p, v2[i].data(), v4[i].data(), &sh[i])
+             : dkg_ceremony_shard_verify_proven_device(ctx, n, t, d0, d1, pa, pb, m->in_s[i].p, m->in_sp[i].p, f1, f3,
+                                                       c.C4, c.accuser4, c.accused4, c.share4, c.randomness4, dec2,
+                                                       dec4, A0, part, R, m->flags[i].p, v4[i].data(), &sh[i]);
+    return r != DKG_OK ? r : pack_shard(m, n, i, R, d0, d1 - d0);
+  });
+  if (rc != DKG_OK) return rc;
+  record_shards(m, sh);
+  merge_verdicts(c.C, v2, c.verdict);
+  merge_verdicts(c.C4, v4, c.verdict4);
+  return finish(m, n, t, out, t0, in.lists ? in.pv : nullptr);
+}
+
 }  // namespace
 
 extern "C" {
+
+int dkg_multi_ceremony_run_device(dkg_multi* m, size_t n, size_t t, const void* const* d_a, const void* const* d_b,
+                                  dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.d_a = d_a, in.d_b = d_b;
+    return multi_ceremony(m, n, t, in, out, {d_a, d_b});
+  });
+}
+
+int dkg_multi_ceremony_run(dkg_multi* m, size_t n, size_t t, const uint8_t* a, const uint8_t* b,
+                           dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.a = a, in.b = b;
+    return multi_ceremony(m, n, t, in, out, {a, b});
+  });
+}
+
+int dkg_multi_ceremony_verify(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A, const uint8_t* s,
+                              const uint8_t* s_prime, dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime;
+    return multi_ceremony(m, n, t, in, out, {E, A, s, s_prime});
+  });
+}
+
+int dkg_multi_ceremony_run_full_device(dkg_multi* m, size_t n, size_t t, const void* const* d_a, const void* const* d_b,
+                                       const void* const* d_r, const uint8_t* sk, const uint8_t* pk,
+                                       dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.d_a = d_a, in.d_b = d_b, in.d_r = d_r, in.sk = sk, in.pk = pk;
+    return multi_ceremony(m, n, t, in, out, {d_a, d_b, d_r, sk, pk});
+  });
+}
+
+int dkg_multi_ceremony_run_full(dkg_multi* m, size_t n, size_t t, const uint8_t* a, const uint8_t* b,
+                                const uint8_t* r, const uint8_t* sk, const uint8_t* pk, dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.a = a, in.b = b, in.r = r, in.sk = sk, in.pk = pk;
+    return multi_ceremony(m, n, t, in, out, {a, b, r, sk, pk});
+  });
+}
+
+int dkg_multi_ceremony_verify_full(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
+                                   const uint8_t* e1, const uint8_t* ct, const uint8_t* sk, dkg_ceremony_out* out) {
+  return guarded_multi(m, [&] {
+    MultiInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk;
+    return multi_ceremony(m, n, t, in, out, {E, A, e1, ct, sk});
+  });
+}
 
 int dkg_multi_ceremony_verify_proven(dkg_multi* m, size_t n, size_t t, const uint8_t* E, const uint8_t* A,
                                      const uint8_t* s, const uint8_t* s_prime, const uint8_t* fetched1,
@@ -636,45 +614,14 @@ int dkg_multi_ceremony_verify_proven(dkg_multi* m, size_t n, size_t t, const uin
                                      dkg_ceremony_out* out, int32_t* verdict4, int32_t* finalise_status,
                                      int32_t* recovery_index) {
   return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!E || !A || !s || !s_prime) return DKG_E_ARG;
     ProvenLists c;
     c.C4 = C4, c.accuser4 = accuser4, c.accused4 = accused4, c.share4 = share4, c.randomness4 = randomness4;
     c.verdict4 = verdict4;
-    if ((rc = proven_lists_ok(m, c)) != DKG_OK) return rc;
-    const size_t N = t + 1, R = dkg_shard_rows(n, m->ws());
-    std::vector<double> sh(m->ws(), 0);
-    std::vector<std::vector<int32_t>> v4(m->ws(), std::vector<int32_t>(C4 ? C4 : 1));
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t D = d1 - d0;
-      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_s[i].get(m->dev[i], 32 * n * D), s + 32 * n * d0, 32 * n * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_sp[i].get(m->dev[i], 32 * n * D), s_prime + 32 * n * d0, 32 * n * D,
-                    hipMemcpyHostToDevice));
-      shard_outputs(m, n, i, D);
-      proven_outputs(m, n, i, R);
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    const double t0 = now_ms();
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      int r = dkg_ceremony_shard_verify_proven_device(
-          m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_s[i].p, m->in_sp[i].p,
-          fetched1 ? fetched1 + d0 : nullptr, fetched3 ? fetched3 + d0 : nullptr, C4, accuser4, accused4, share4,
-          randomness4, m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, R, m->flags[i].p, v4[i].data(), &sh[i]);
-      return r != DKG_OK ? r : pack_shard(m, n, i, R, d0, d1 - d0);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    merge_verdicts(C4, v4, verdict4);
     const ProvenOut pv{false, nullptr, finalise_status, recovery_index};
-    return finish(m, n, t, out, t0, &pv);
+    MultiInput in;
+    in.E = E, in.A = A, in.s = s, in.s_prime = s_prime, in.fetched1 = fetched1, in.fetched3 = fetched3;
+    in.lists = &c, in.pv = &pv;
+    return multi_ceremony(m, n, t, in, out, {E, A, s, s_prime});
   });
 }
 
@@ -687,51 +634,15 @@ int dkg_multi_ceremony_verify_full_proven(dkg_multi* m, size_t n, size_t t, cons
                                           int32_t* dissent, int32_t* verdict4, int32_t* finalise_status,
                                           int32_t* recovery_index) {
   return guarded_multi(m, [&] {
-    int rc = check_args(m, n, t, out);
-    if (rc != DKG_OK) return rc;
-    if (!E || !A || !e1 || !ct || !sk || !pk) {
-      m->err = "bad arguments: E, A, e1, ct, sk and pk must be non-NULL";
-      return DKG_E_ARG;
-    }
     ProvenLists c;
     c.C = C, c.accuser = accuser, c.accused = accused, c.proofs = proofs, c.verdict = verdict;
     c.C4 = C4, c.accuser4 = accuser4, c.accused4 = accused4, c.share4 = share4, c.randomness4 = randomness4;
     c.verdict4 = verdict4;
-    if ((rc = proven_lists_ok(m, c)) != DKG_OK) return rc;
-    const size_t N = t + 1, R = dkg_shard_rows(n, m->ws());
-    std::vector<double> sh(m->ws(), 0);
-    std::vector<std::vector<int32_t>> v2(m->ws(), std::vector<int32_t>(C ? C : 1));
-    std::vector<std::vector<int32_t>> v4(m->ws(), std::vector<int32_t>(C4 ? C4 : 1));
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      const size_t D = d1 - d0;
-      MCK(hipMemcpy(m->in_a[i].get(m->dev[i], 32 * N * D), E + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_b[i].get(m->dev[i], 32 * N * D), A + 32 * N * d0, 32 * N * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_e1[i].get(m->dev[i], 64 * n * D), e1 + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
-      MCK(hipMemcpy(m->in_ct[i].get(m->dev[i], 64 * n * D), ct + 64 * n * d0, 64 * n * D, hipMemcpyHostToDevice));
-      shard_outputs(m, n, i, D);
-      proven_outputs(m, n, i, R);
-      return DKG_OK;
-    });
-    if (rc != DKG_OK) return rc;
-    const double t0 = now_ms();
-    rc = for_shards(m, [&](int i) {
-      size_t d0, d1;
-      range(m, n, i, &d0, &d1);
-      int r = dkg_ceremony_shard_verify_full_proven_device(
-          m->ctx[i], n, t, d0, d1, m->in_a[i].p, m->in_b[i].p, m->in_e1[i].p, m->in_ct[i].p, sk, pk, nullptr,
-          fetched3 ? fetched3 + d0 : nullptr, C, accuser, accused, proofs, C4, accuser4, accused4, share4, randomness4,
-          m->dec2[i].p, m->dec4[i].p, m->A0[i].p, m->part[i].p, R, m->flags[i].p, m->dis[i].p, v2[i].data(),
-          v4[i].data(), &sh[i]);
-      return r != DKG_OK ? r : pack_shard(m, n, i, R, d0, d1 - d0);
-    });
-    if (rc != DKG_OK) return rc;
-    record_shards(m, sh);
-    merge_verdicts(C, v2, verdict);
-    merge_verdicts(C4, v4, verdict4);
     const ProvenOut pv{true, dissent, finalise_status, recovery_index};
-    return finish(m, n, t, out, t0, &pv);
+    MultiInput in;
+    in.E = E, in.A = A, in.e1 = e1, in.ct = ct, in.sk = sk, in.pk = pk, in.fetched3 = fetched3;
+    in.lists = &c, in.pv = &pv;
+    return multi_ceremony(m, n, t, in, out, {E, A, e1, ct, sk, pk});
   });
 }
 

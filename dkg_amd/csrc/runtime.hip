@@ -10,6 +10,7 @@
 #include <array>
 #include <map>
 #include <memory>
+#include <optional>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -3783,20 +3784,45 @@ void shard_proven_verdicts(const ShardProven& sp) {
   for (size_t k = 0; k < sp.own4.size(); k++) sp.verdict4[sp.own4[k]] = sp.hver4[k];
 }
 
-// Rounds 2-5 of one rank of a dealer-sharded ceremony on its dealers [d0, d0+D): E/A compressed
-// [D][N][32], s/sp canonical [D][n][32] on the device -> decision rows, master-key terms, partial
-// final shares (layouts of dkg_ceremony_shard_device).  e_ok (may be null; [D] on the device): 0 = the
-// dealer's round-1 data is missing, as receivers_rounds takes RoundMasks::e_ok -- full mode's decode mask
-// of the dealer's ciphertexts: a MISSING row in round 2.
+// One rank's call of a dealer-sharded ceremony on its dealers [d0, d1), as the pointers of the C ABI
+// (null = absent; device pointers unless marked host), in the manner of CeremonyInput.  Generate mode is
+// a != nullptr, full mode is sk != nullptr, and the proven rule follows the presence of `proven`, not
+// C > 0.  Layouts as dkg_ceremony_shard_device documents them.
+struct ShardInput {
+  const void *a = nullptr, *b = nullptr;        // the dealers' coefficients (generate), or
+  const void *E = nullptr, *A = nullptr;        //   the received commitments
+  const void *s = nullptr, *s_prime = nullptr;  // the received plaintext shares, or
+  const void *e1 = nullptr, *ct = nullptr;      //   the received ciphertexts, or
+  const void* r = nullptr;                      //   the encryption randomness (generate, full mode)
+  void *e1_out = nullptr, *ct_out = nullptr;    //     and where its ciphertexts go (optional)
+  const uint8_t *sk = nullptr, *pk = nullptr;   // host: the members' keys (full mode)
+  ShardProven* proven = nullptr;                // the complaint lists, the intake masks, flags and verdicts
+  void *dec2 = nullptr, *dec4 = nullptr, *A0 = nullptr, *partial = nullptr;
+  double* ms_total = nullptr;
+};
+
+// What the share stage of shard_ceremony hands the rounds: E/A compressed [D][N][32], s/sp canonical
+// [D][n][32] on the device, and e_ok (may be null; [D] on the device): 0 = the dealer's round-1 data is
+// missing, as receivers_rounds takes RoundMasks::e_ok -- the phase-1 intake mask, in full mode joined
+// with the decode mask of the dealer's ciphertexts: a MISSING row in round 2.
+struct ShardRows {
+  const uint32_t *E, *A, *s, *s_prime;
+  const uint8_t* e_ok;
+};
+
+// Rounds 2-5 of one rank of a dealer-sharded ceremony on its dealers [d0, d0+D) -> decision rows,
+// master-key terms, partial final shares.
 //
-// sp (may be null): the rank decides by the PROVEN complaints against its own dealers (ShardProven,
+// in.proven (may be null): the rank decides by the PROVEN complaints against its own dealers (ShardProven,
 // shard_complaints) -- the stage follows the checks on the stream and gives the qualified mask of the
-// partial sums; a_ok as verify_rounds takes it (the intake mask of the phase-3 broadcasts); e1c / ctc the
-// rank's ciphertexts [D][n][2][8] (full mode: the pairs the round-2 complaints are verified against).
-void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uint32_t* Ec, const uint32_t* Ac,
-                const uint32_t* ds, const uint32_t* dsp, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
-                const uint8_t* e_ok = nullptr, ShardProven* sp = nullptr, const uint8_t* a_ok = nullptr,
-                const uint32_t* e1c = nullptr, const uint32_t* ctc = nullptr) {
+// partial sums; its df3 goes to verify_rounds as a_ok (the intake mask of the phase-3 broadcasts); in.e1 /
+// in.ct are the rank's ciphertexts [D][n][2][8] (full mode: the pairs the round-2 complaints are verified
+// against).
+void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const ShardInput& in, const ShardRows& rows) {
+  const uint32_t *Ec = rows.E, *Ac = rows.A, *ds = rows.s, *dsp = rows.s_prime;
+  void *d_dec2 = in.dec2, *d_dec4 = in.dec4, *d_A0 = in.A0, *d_partial = in.partial;
+  ShardProven* sp = in.proven;
+  const uint8_t *e_ok = rows.e_ok, *a_ok = sp ? sp->df3 : nullptr;
   const size_t N = t + 1;
   if (!D) {
     HCK(hipMemsetAsync(d_partial, 0, 32 * n, ctx->stream));
@@ -3834,7 +3860,9 @@ void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uin
   ctx->shares_pending = false;
   // the proven rule: this sits inside the caller's with_binom_ded body, so a rerun with the complete
   // formula reruns the stage on the rerun's tables
-  if (sp) shard_complaints(ctx, n, t, D, Ec, Ac, e1c, ctc, (const uint8_t*)d_dec2, rej, qm, *sp);
+  if (sp)
+    shard_complaints(ctx, n, t, D, Ec, Ac, (const uint32_t*)in.e1, (const uint32_t*)in.ct, (const uint8_t*)d_dec2, rej,
+                     qm, *sp);
   // A dealer accused in round 4 (committee.rs:660-670) has its term replaced after the exchange,
   // once the final parties are known (dkg_ceremony_shard_recon_device): its shares stay here.
   ctx->shard_s = ds;
@@ -3844,168 +3872,166 @@ void shard_rows(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t D, const uin
   dkgk::sum_shares(D, n, ds, qm, (uint32_t*)d_partial, ctx->stream);  // partial of :454-462
 }
 
+// The argument prologue of the six dkg_ceremony_shard_*_device entry points; nothing is queued before it
+// returns.  `keys`: the host keys the entry point's mode takes (their absence cannot be told from the
+// plaintext mode's).  d_partial is written even for a rank without dealers; with dealers the mode's inputs
+// and the other three outputs are required.
+int shard_args(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const ShardInput& in,
+               std::initializer_list<const void*> keys) {
+  const int rc = ceremony_args(ctx, n, t, {in.partial});
+  if (rc) return rc;
+  if (d1 < d0 || d1 > n) return DKG_E_ARG;
+  for (const void* k : keys)
+    if (!k) return DKG_E_ARG;
+  const size_t D = d1 - d0;
+  if (D) {
+    const bool inputs = in.a      ? in.b && (!in.sk || in.r)
+                        : in.sk   ? in.E && in.A && in.e1 && in.ct
+                                  : in.E && in.A && in.s && in.s_prime;
+    if (!inputs || !in.dec2 || !in.dec4 || !in.A0) return DKG_E_ARG;
+  }
+  if (const ShardProven* sp = in.proven) {
+    if (sp->flag_rows < D || (sp->flag_rows && !sp->d_flags)) return DKG_E_ARG;
+    if (!complaint_args_ok(n, sp->C2, sp->accuser2, sp->accused2, {sp->proofs, sp->verdict2}) ||
+        !complaint_args_ok(n, sp->C4, sp->accuser4, sp->accused4, {sp->share4, sp->randomness4, sp->verdict4}))
+      return DKG_E_ARG;
+  }
+  return DKG_OK;
+}
+
+// Every dkg_ceremony_shard_*_device entry point: one rank's rounds on its dealers [d0, d1).  The timed
+// region (ev[0]..ev[1], ms_total) starts after the key uploads and covers the proven staging upload, the
+// share stage and the rounds.
+//
+// Full mode: items, decode masks, MISSING rows and decrypted shares are per dealer, so the hybrid stage
+// is shard-local: D dealers' items to all n keys.  With chunk streams it runs on the side stream beside
+// the check pipeline's binomial, stepping and recombination, which read no share; the checks wait for
+// the decrypted shares (shares_pending / wait_shares), and the ciphertexts' decode mask joins the dealer
+// mask there.  Serialised runs (nsub == 1) record the full.* phases.
+int shard_ceremony(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const ShardInput& in) {
+  const size_t D = d1 - d0, N = t + 1, items = 2 * D * n;
+  const bool gen = in.a != nullptr, full = in.sk != nullptr;
+  ShardProven* sp = in.proven;
+  const uint32_t *dsk = nullptr, *dpk = nullptr;
+  if (full) dsk = upload_scalars(ctx, "fm_sk", in.sk, n);
+  if (full && gen) {
+    uint32_t* p = buf<uint32_t>(ctx, "fm_pk", 32 * n);
+    h2d(ctx, p, in.pk, 32 * n);
+    dpk = p;
+  }
+  HCK(hipEventRecord(ctx->ev[0], ctx->stream));
+  if (sp) {  // before the side stream forks: it reads the intake mask
+    sp->full = full, sp->pk = in.pk;
+    shard_proven_upload(ctx, n, d0, D, *sp);
+  }
+  // the shares the rounds read: generated, received (Scalar::from_bytes semantics: bit 255 cleared,
+  // reduced, as upload_scalars) or decrypted
+  uint32_t* ds = buf<uint32_t>(ctx, "sh_s", 32 * D * n);
+  uint32_t* dsp = buf<uint32_t>(ctx, "sh_sp", 32 * D * n);
+  ShardRows rows{(const uint32_t*)in.E, (const uint32_t*)in.A, ds, dsp, sp ? sp->df1 : nullptr};
+  // what runs beside the checks on the side stream (one-stream runs: back to back): the generated shares'
+  // evaluation, and in full mode the hybrid stage under the fused group check
+  const bool side = ctx->nsub > 1 && (!full || ctx->verify_mode == 0);
+  hipStream_t hy = side ? ctx->side : ctx->stream;
+  SharesScope pending(ctx);  // on an exception the home stream still waits for the side stream's work
+  std::optional<ExtScope> ext;
+  const uint32_t *e1 = (const uint32_t*)in.e1, *ct = (const uint32_t*)in.ct;
+  if (gen) {
+    uint32_t* Ec = buf<uint32_t>(ctx, "sh_E", 32 * D * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "sh_A", 32 * D * N);
+    // full mode: the dealers' plaintext shares stay apart from what the receivers decrypt
+    uint32_t* gs = full ? buf<uint32_t>(ctx, "shg_s", 32 * D * n) : ds;
+    uint32_t* gsp = full ? buf<uint32_t>(ctx, "shg_sp", 32 * D * n) : dsp;
+    if (D) round1_device(ctx, D, n, t, (const uint32_t*)in.a, (const uint32_t*)in.b, Ec, Ac, gs, gsp, false, side);
+    if (D && full) {
+      uint32_t* o1 = in.e1_out ? (uint32_t*)in.e1_out : buf<uint32_t>(ctx, "shf_e1", 32 * items);
+      uint32_t* oc = in.ct_out ? (uint32_t*)in.ct_out : buf<uint32_t>(ctx, "shf_ct", 32 * items);
+      encrypt_device(ctx, D, n, dpk, gs, gsp, (const uint32_t*)in.r, o1, oc, hy, in.pk, true);  // committee.rs:169-172
+      e1 = o1, ct = oc;
+    }
+    ext.emplace(ctx, D, N);
+    rows.E = Ec, rows.A = Ac;
+  } else if (D && !full) {
+    dkgk::reduce_scalars(D * n, (const uint32_t*)in.s, ds, ctx->stream);
+    dkgk::reduce_scalars(D * n, (const uint32_t*)in.s_prime, dsp, ctx->stream);
+  }
+  if (full) {
+    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
+    rows.e_ok = eok;
+    if (D) {
+      if (side && !gen) {  // round1_device forked the side stream already
+        HCK(hipEventRecord(ctx->side_fork, ctx->stream));
+        HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
+      }
+      decrypt_device(ctx, D, n, dsk, e1, ct, ds, dsp, iok, eok, hy);  // committee.rs:282-286
+      if (sp && sp->df1) dkgk::and_mask(D, sp->df1, eok, hy);  // an absent phase-1 broadcast: a MISSING row as well
+      if (side) {
+        HCK(hipEventRecord(ctx->shares_done, ctx->side));
+        ctx->shares_pending = true;
+      }
+    }
+  }
+  with_binom_ded(ctx, [&] {
+    shard_rows(ctx, n, t, d0, D, in, rows);
+    check_launch(ctx);
+    HCK(hipEventRecord(ctx->ev[1], ctx->stream));
+    binom_mark_copy(ctx);
+    sync(ctx);
+  });
+  collect_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
+  if (full) collect_hybrid_phases(ctx);
+  if (sp) shard_proven_verdicts(*sp);
+  if (in.ms_total) *in.ms_total = ev_ms(ctx, 0, 1);
+  return DKG_OK;
+}
+
+int shard_call(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const ShardInput& in,
+               std::initializer_list<const void*> keys = {}) {
+  return guarded(ctx, [&] {
+    const int rc = shard_args(ctx, n, t, d0, d1, in, keys);
+    return rc ? rc : shard_ceremony(ctx, n, t, d0, d1, in);
+  });
+}
+
 extern "C" {
 
 int dkg_ceremony_shard_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_a,
                               const void* d_b, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
                               double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n) return DKG_E_ARG;
-    const size_t D = d1 - d0, N = t + 1;
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* Ec = buf<uint32_t>(ctx, "sh_E", 32 * D * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "sh_A", 32 * D * N);
-    uint32_t* ds = buf<uint32_t>(ctx, "sh_s", 32 * D * n);
-    uint32_t* dsp = buf<uint32_t>(ctx, "sh_sp", 32 * D * n);
-    // the shares on the side stream beside the checks, which wait for them (one-stream runs: back to back);
-    // on an exception the home stream still waits for them before the state is dropped
-    SharesScope pending(ctx);
-    if (D) round1_device(ctx, D, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false, ctx->nsub > 1);
-    ExtScope ext(ctx, D, N);
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, Ec, Ac, ds, dsp, d_dec2, d_dec4, d_A0, d_partial);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardInput in;
+  in.a = d_a, in.b = d_b;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in);
 }
 
 int dkg_ceremony_shard_verify_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_E,
                                      const void* d_A, const void* d_s, const void* d_s_prime, void* d_dec2,
                                      void* d_dec4, void* d_A0, void* d_partial, double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n) return DKG_E_ARG;
-    const size_t D = d1 - d0;
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    // received shares: Scalar::from_bytes semantics (bit 255 cleared, reduced), as upload_scalars
-    uint32_t* ds = buf<uint32_t>(ctx, "shv_s", 32 * D * n);
-    uint32_t* dsp = buf<uint32_t>(ctx, "shv_sp", 32 * D * n);
-    if (D) {
-      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s, ds, ctx->stream);
-      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s_prime, dsp, ctx->stream);
-    }
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, ds, dsp, d_dec2, d_dec4, d_A0,
-                 d_partial);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardInput in;
+  in.E = d_E, in.A = d_A, in.s = d_s, in.s_prime = d_s_prime;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in);
 }
 
-// Full mode of the two calls above (dkg_ceremony_run_full_device / dkg_ceremony_verify_full on rows
-// [d0, d1)).  Items, decode masks, MISSING rows and decrypted shares are per dealer, so the hybrid stage
-// is shard-local: D dealers' items to all n keys.  With chunk streams it runs on the side stream beside
-// the check pipeline's binomial, stepping and recombination, which read no share; the checks wait for
-// the decrypted shares (shares_pending / wait_shares), and the ciphertexts' decode mask joins the dealer
-// mask there.  Serialised runs (nsub == 1) record the full.* phases.
+// Full mode of the two calls above (dkg_ceremony_run_full_device / dkg_ceremony_verify_full on rows [d0, d1))
 int dkg_ceremony_shard_full_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_a,
                                    const void* d_b, const void* d_r, const uint8_t* sk, const uint8_t* pk, void* d_e1,
                                    void* d_ct, void* d_dec2, void* d_dec4, void* d_A0, void* d_partial,
                                    double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk || !pk) return DKG_E_ARG;
-    const size_t D = d1 - d0, N = t + 1, items = 2 * D * n;
-    if (D && (!d_a || !d_b || !d_r)) return DKG_E_ARG;
-    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
-    uint32_t* dpk = buf<uint32_t>(ctx, "fm_pk", 32 * n);
-    h2d(ctx, dpk, pk, 32 * n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* Ec = buf<uint32_t>(ctx, "sh_E", 32 * D * N);
-    uint32_t* Ac = buf<uint32_t>(ctx, "sh_A", 32 * D * N);
-    uint32_t* ds = buf<uint32_t>(ctx, "sh_s", 32 * D * n);     // the dealers' plaintext shares
-    uint32_t* dsp = buf<uint32_t>(ctx, "sh_sp", 32 * D * n);
-    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);    // what the receivers decrypt
-    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
-    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
-    hipStream_t hy = side ? ctx->side : ctx->stream;
-    SharesScope pending(ctx);  // on an exception the home stream still waits for the side stream's work
-    if (D) {
-      round1_device(ctx, D, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, Ec, Ac, ds, dsp, false, side);
-      uint32_t* e1 = d_e1 ? (uint32_t*)d_e1 : buf<uint32_t>(ctx, "shf_e1", 32 * items);
-      uint32_t* ct = d_ct ? (uint32_t*)d_ct : buf<uint32_t>(ctx, "shf_ct", 32 * items);
-      encrypt_device(ctx, D, n, dpk, ds, dsp, (const uint32_t*)d_r, e1, ct, hy, pk, true);  // committee.rs:169-172
-      decrypt_device(ctx, D, n, dsk, e1, ct, rs, rsp, iok, eok, hy);                        // committee.rs:282-286
-      if (side) {
-        HCK(hipEventRecord(ctx->shares_done, ctx->side));
-        ctx->shares_pending = true;
-      }
-    }
-    ExtScope ext(ctx, D, N);
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, Ec, Ac, rs, rsp, d_dec2, d_dec4, d_A0, d_partial, eok);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);
-    collect_hybrid_phases(ctx);
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardInput in;
+  in.a = d_a, in.b = d_b, in.r = d_r, in.e1_out = d_e1, in.ct_out = d_ct, in.sk = sk, in.pk = pk;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in, {sk, pk});
 }
 
 int dkg_ceremony_shard_verify_full_device(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const void* d_E,
                                           const void* d_A, const void* d_e1, const void* d_ct, const uint8_t* sk,
                                           void* d_dec2, void* d_dec4, void* d_A0, void* d_partial, double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk) return DKG_E_ARG;
-    const size_t D = d1 - d0, items = 2 * D * n;
-    if (D && (!d_E || !d_A || !d_e1 || !d_ct)) return DKG_E_ARG;
-    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);
-    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
-    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
-    SharesScope pending(ctx);
-    if (D) {
-      if (side) {
-        HCK(hipEventRecord(ctx->side_fork, ctx->stream));
-        HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
-      }
-      decrypt_device(ctx, D, n, dsk, (const uint32_t*)d_e1, (const uint32_t*)d_ct, rs, rsp, iok, eok,
-                     side ? ctx->side : ctx->stream);
-      if (side) {
-        HCK(hipEventRecord(ctx->shares_done, ctx->side));
-        ctx->shares_pending = true;
-      }
-    }
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, rs, rsp, d_dec2, d_dec4, d_A0,
-                 d_partial, eok);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);
-    collect_hybrid_phases(ctx);  // decryption phases only
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardInput in;
+  in.E = d_E, in.A = d_A, in.e1 = d_e1, in.ct = d_ct, in.sk = sk;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in, {sk});
 }
 
 // dkg_ceremony_shard_verify_device with the reference's rule for the reconstructable set, as
@@ -4017,39 +4043,14 @@ int dkg_ceremony_shard_verify_proven_device(dkg_ctx* ctx, size_t n, size_t t, si
                                             const uint8_t* randomness4, void* d_dec2, void* d_dec4, void* d_A0,
                                             void* d_partial, size_t flag_rows, void* d_flags, int32_t* verdict4,
                                             double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !d_partial) return DKG_E_ARG;
-    const size_t D = d1 - d0;
-    if (D && (!d_E || !d_A || !d_s || !d_s_prime || !d_dec2 || !d_dec4 || !d_A0)) return DKG_E_ARG;
-    if (flag_rows < D || (flag_rows && !d_flags)) return DKG_E_ARG;
-    if (!complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4})) return DKG_E_ARG;
-    ShardProven sp;
-    sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
-    sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
-    sp.flag_rows = flag_rows, sp.d_flags = d_flags;
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    shard_proven_upload(ctx, n, d0, D, sp);
-    uint32_t* ds = buf<uint32_t>(ctx, "shv_s", 32 * D * n);
-    uint32_t* dsp = buf<uint32_t>(ctx, "shv_sp", 32 * D * n);
-    if (D) {
-      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s, ds, ctx->stream);
-      dkgk::reduce_scalars(D * n, (const uint32_t*)d_s_prime, dsp, ctx->stream);
-    }
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, ds, dsp, d_dec2, d_dec4, d_A0,
-                 d_partial, sp.df1, &sp, sp.df3);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);
-    shard_proven_verdicts(sp);
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardProven sp;
+  sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
+  sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
+  sp.flag_rows = flag_rows, sp.d_flags = d_flags;
+  ShardInput in;
+  in.E = d_E, in.A = d_A, in.s = d_s, in.s_prime = d_s_prime, in.proven = &sp;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in);
 }
 
 // dkg_ceremony_shard_verify_full_device with both rounds decided by the proven complaints, as
@@ -4064,58 +4065,15 @@ int dkg_ceremony_shard_verify_full_proven_device(dkg_ctx* ctx, size_t n, size_t 
                                                  void* d_dec4, void* d_A0, void* d_partial, size_t flag_rows,
                                                  void* d_flags, void* d_dissent, int32_t* verdict, int32_t* verdict4,
                                                  double* ms_total) {
-  return guarded(ctx, [&] {
-    int rc = need_env(ctx);
-    if (rc) return rc;
-    if (dkg_env_check(t, n) != DKG_OK || d1 < d0 || d1 > n || !sk || !pk || !d_partial) return DKG_E_ARG;
-    const size_t D = d1 - d0, items = 2 * D * n;
-    if (D && (!d_E || !d_A || !d_e1 || !d_ct || !d_dec2 || !d_dec4 || !d_A0)) return DKG_E_ARG;
-    if (flag_rows < D || (flag_rows && !d_flags)) return DKG_E_ARG;
-    if (!complaint_args_ok(n, C, accuser, accused, {proofs, verdict}) ||
-        !complaint_args_ok(n, C4, accuser4, accused4, {share4, randomness4, verdict4}))
-      return DKG_E_ARG;
-    ShardProven sp;
-    sp.full = true, sp.pk = pk;
-    sp.C2 = C, sp.accuser2 = accuser, sp.accused2 = accused, sp.proofs = proofs, sp.verdict2 = verdict;
-    sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
-    sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
-    sp.flag_rows = flag_rows, sp.d_flags = d_flags, sp.d_dissent = d_dissent;
-    uint32_t* dsk = upload_scalars(ctx, "fm_sk", sk, n);
-    HCK(hipEventRecord(ctx->ev[0], ctx->stream));
-    shard_proven_upload(ctx, n, d0, D, sp);  // before the side stream forks: it reads the intake mask
-    uint32_t* rs = buf<uint32_t>(ctx, "shf_s", 32 * D * n);
-    uint32_t* rsp = buf<uint32_t>(ctx, "shf_sp", 32 * D * n);
-    uint8_t* iok = buf<uint8_t>(ctx, "shf_iok", items);
-    uint8_t* eok = buf<uint8_t>(ctx, "shf_eok", D);
-    const bool side = ctx->nsub > 1 && ctx->verify_mode == 0;
-    SharesScope pending(ctx);
-    if (D) {
-      if (side) {
-        HCK(hipEventRecord(ctx->side_fork, ctx->stream));
-        HCK(hipStreamWaitEvent(ctx->side, ctx->side_fork, 0));
-      }
-      hipStream_t hy = side ? ctx->side : ctx->stream;
-      decrypt_device(ctx, D, n, dsk, (const uint32_t*)d_e1, (const uint32_t*)d_ct, rs, rsp, iok, eok, hy);
-      if (sp.df1) dkgk::and_mask(D, sp.df1, eok, hy);  // an absent phase-1 broadcast: a MISSING row as well
-      if (side) {
-        HCK(hipEventRecord(ctx->shares_done, ctx->side));
-        ctx->shares_pending = true;
-      }
-    }
-    with_binom_ded(ctx, [&] {
-      shard_rows(ctx, n, t, d0, D, (const uint32_t*)d_E, (const uint32_t*)d_A, rs, rsp, d_dec2, d_dec4, d_A0,
-                 d_partial, eok, &sp, sp.df3, (const uint32_t*)d_e1, (const uint32_t*)d_ct);
-      check_launch(ctx);
-      HCK(hipEventRecord(ctx->ev[1], ctx->stream));
-      binom_mark_copy(ctx);
-      sync(ctx);
-    });
-    collect_phases(ctx);
-    collect_hybrid_phases(ctx);  // decryption phases only
-    shard_proven_verdicts(sp);
-    if (ms_total) *ms_total = ev_ms(ctx, 0, 1);
-    return DKG_OK;
-  });
+  ShardProven sp;
+  sp.C2 = C, sp.accuser2 = accuser, sp.accused2 = accused, sp.proofs = proofs, sp.verdict2 = verdict;
+  sp.C4 = C4, sp.accuser4 = accuser4, sp.accused4 = accused4, sp.share4 = share4, sp.randomness4 = randomness4;
+  sp.fetched1 = fetched1, sp.fetched3 = fetched3, sp.verdict4 = verdict4;
+  sp.flag_rows = flag_rows, sp.d_flags = d_flags, sp.d_dissent = d_dissent;
+  ShardInput in;
+  in.E = d_E, in.A = d_A, in.e1 = d_e1, in.ct = d_ct, in.sk = sk, in.pk = pk, in.proven = &sp;
+  in.dec2 = d_dec2, in.dec4 = d_dec4, in.A0 = d_A0, in.partial = d_partial, in.ms_total = ms_total;
+  return shard_call(ctx, n, t, d0, d1, in, {sk, pk});
 }
 
 int dkg_ctx_last_complaint_eval(const dkg_ctx* ctx) { return ctx ? ctx->last_complaint_eval : 0; }

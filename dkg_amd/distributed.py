@@ -130,6 +130,7 @@ class ShardedCeremony:
             self.g_dec4 = torch.empty(self.ws * R * self.W1, **i32)
         else:
             self.dec2, self.dec4 = self.send[:S2], self.send[S2:2 * S2]
+            self.p2 = self.p4 = None  # the library writes the raw rows straight into the block
             self.g_dec2 = torch.empty(self.ws * R * n, **u8)
             self.g_dec4 = torch.empty(self.ws * R * n, **u8)
         self.g_all = torch.empty(self.ws * self.S, **u8)
@@ -195,22 +196,6 @@ class ShardedCeremony:
         self.g_flags = torch.empty(ws * R, **i32)
         self.g_dis = torch.empty(ws * n, **i32)
 
-    def exchange_proven(self):
-        """exchange() for the proven runs' block: also the gathered flag words [ws][R] and dissent
-        partials [ws][n]."""
-        self._pack(self.dec2, self.pp2)
-        self._pack(self.dec4, self.pp4)
-        self._all_gather(self.g_allp, self.p_send)
-        S2, R, ws, S, n, u8 = self.S2, self.R, self.ws, self.S, self.n, self.torch.uint8
-        g = self.g_allp.view(ws, self.SP)
-        self.g_dec2.view(u8).view(ws, S2).copy_(g[:, :S2])
-        self.g_dec4.view(u8).view(ws, S2).copy_(g[:, S2:2 * S2])
-        self.g_A0.view(ws, R * 32).copy_(g[:, 2 * S2:2 * S2 + R * 32])
-        self.g_part.view(ws, n * 32).copy_(g[:, 2 * S2 + R * 32:S])
-        self.g_flags.view(u8).view(ws, 4 * R).copy_(g[:, S:S + 4 * R])
-        self.g_dis.view(u8).view(ws, 4 * n).copy_(g[:, S + 4 * R:])
-        return self.g_dec2, self.g_dec4, self.g_A0, self.g_part, self.g_flags, self.g_dis
-
     def _merge_verdicts(self, v):
         """One all_reduce(MAX) over the ranks' verdict arrays: COMPLAINT_NOT_OWNED is below every real code
         and exactly one rank owns each complaint.  Staged through the host under gloo, as _all_gather."""
@@ -233,7 +218,7 @@ class ShardedCeremony:
             self.n, self.t, self.d0, self.d1, d_E, d_A, d_s, d_sp, accusers4, accused4, share4, randomness4,
             self.dec2.data_ptr(), self.dec4.data_ptr(), self.pA0.data_ptr(), self.ppart.data_ptr(), self.R,
             self.pflags.data_ptr(), fetched1=fetched1, fetched3=fetched3)
-        return self._finish_proven(ms, finalise, False, [], v4, d_s)
+        return self._finish(ms, finalise, d_s, proven=(False, [], v4))
 
     def run_verify_full_proven(self, d_E: int, d_A: int, d_e1: int, d_ct: int, sk: bytes, pk: bytes, accusers,
                                accused, proofs: bytes, accusers4, accused4, share4: bytes, randomness4: bytes,
@@ -249,64 +234,35 @@ class ShardedCeremony:
             accused4, share4, randomness4, self.dec2.data_ptr(), self.dec4.data_ptr(), self.pA0.data_ptr(),
             self.ppart.data_ptr(), self.R, self.pflags.data_ptr(), self.pdis.data_ptr(), fetched1=fetched1,
             fetched3=fetched3)
-        return self._finish_proven(ms, finalise, True, v, v4, None)
+        return self._finish(ms, finalise, None, proven=(True, v, v4))
 
-    def _finish_proven(self, ms: float, finalise: bool, full: bool, v, v4, d_s: Optional[int]) -> ShardResult:
-        from ._lib import FIN_PANIC, FIN_PHASE4_ERROR
-
-        n, t, ws = self.n, self.t, self.ws
-        self._last_proven = True
-        steps = {}
-        c0 = time.perf_counter()
-        self.exchange_proven()
-        verdict, verdict4 = self._merge_verdicts(v), self._merge_verdicts(v4)
-        self._fence()
-        c1 = time.perf_counter()
-        steps["exchange"] = (c1 - c0) * 1e3
-        o, dissent, status, index = self.be.shard_combine_proven_device(
-            n, t, ws, self.g_dec2.data_ptr(), self.g_dec4.data_ptr(), self.g_flags.data_ptr(),
-            self.g_dis.data_ptr() if full else None, full, self.c_dec2.data_ptr(), self.c_dec4.data_ptr())
-        dec = Decisions(self.c_dec2.view(n, n), self.c_dec4.view(n, n), np.array(o.qualified, dtype=np.uint8),
-                        np.array(o.complaints2, dtype=np.int32), np.array(o.r2_error, dtype=np.uint8),
-                        np.array(o.reconstruct, dtype=np.uint8), np.array(o.r4_error, dtype=np.uint8),
-                        o.phase4_error)
-        extra = dict(verdict=verdict if full else None, verdict4=verdict4, dissent=dissent, finalise_status=status,
-                     recovery_index=index)
-        c2 = time.perf_counter()
-        steps["combine"] = (c2 - c1) * 1e3
-        if not finalise:
-            return ShardResult(dec, None, None, None, ms, steps, **extra)
-        # nobody finalises after a Phase4 failure, and a panic of every party's finalise leaves no mpk
-        no_mpk = status in (FIN_PHASE4_ERROR, FIN_PANIC)
-        if dec.reconstruct.any() and not no_mpk:
-            no_mpk = self.be.ceremony_shard_recon_device(n, t, self.d0, self.d1, dec.qualified, dec.reconstruct, d_s,
-                                                         self.pA0.data_ptr(), dec.r2_error, dec.r4_error)
-            if not no_mpk:
-                self._all_gather(self.g_A0, self.pA0)
-                self._fence()
-        c3 = time.perf_counter()
-        steps["recon"] = (c3 - c2) * 1e3
-        mpk = self.be.shard_finalise_device(n, t, ws, self.g_A0.data_ptr(), self.g_part.data_ptr(), dec.qualified,
-                                            no_mpk, self.fs.data_ptr(), self.pub.data_ptr())
-        fs, pub = self.fs.clone(), self.pub.clone()
-        steps["finalise"] = (time.perf_counter() - c3) * 1e3
-        return ShardResult(dec, fs, pub, None if no_mpk else mpk, ms, steps, **extra)
+    def _exchange(self, send, g_all, p2, p4, tail=()):
+        """All-gather every rank's send block (one collective), then split the gathered [ws][len(send)]
+        blocks on the device into g_dec2, g_dec4, g_A0, g_part and `tail`'s (tensor, bytes per rank)."""
+        if self.packed:
+            self._pack(self.dec2, p2)
+            self._pack(self.dec4, p4)
+        self._all_gather(g_all, send)
+        ws, u8 = self.ws, self.torch.uint8
+        g = g_all.view(ws, -1)
+        parts = [(self.g_dec2, self.S2), (self.g_dec4, self.S2), (self.g_A0, self.R * 32), (self.g_part, self.n * 32)]
+        at = 0
+        for dst, size in parts + list(tail):
+            dst.view(u8).view(ws, size).copy_(g[:, at:at + size])
+            at += size
+        return tuple(dst for dst, _ in parts + list(tail))
 
     def exchange(self):
-        """All-gather every rank's send block (one collective), then split the gathered [ws][S] blocks
-        on the device into the decision rows (round 2, round 4; packed bitmaps [ws][R][W+1] or bytes
-        [ws][R][n]), the master-key terms [ws][R][32] and the partial final shares [ws][n][32]."""
-        if self.packed:
-            self._pack(self.dec2, self.p2)
-            self._pack(self.dec4, self.p4)
-        self._all_gather(self.g_all, self.send)
-        S2, R, ws = self.S2, self.R, self.ws
-        g = self.g_all.view(ws, self.S)
-        self.g_dec2.view(self.torch.uint8).view(ws, S2).copy_(g[:, :S2])
-        self.g_dec4.view(self.torch.uint8).view(ws, S2).copy_(g[:, S2:2 * S2])
-        self.g_A0.view(ws, R * 32).copy_(g[:, 2 * S2:2 * S2 + R * 32])
-        self.g_part.view(ws, self.n * 32).copy_(g[:, 2 * S2 + R * 32:])
-        return self.g_dec2, self.g_dec4, self.g_A0, self.g_part
+        """The exchange of the send block: the decision rows (round 2, round 4; packed bitmaps
+        [ws][R][W+1] or bytes [ws][R][n]), the master-key terms [ws][R][32] and the partial final shares
+        [ws][n][32]."""
+        return self._exchange(self.send, self.g_all, self.p2, self.p4)
+
+    def exchange_proven(self):
+        """exchange() for the proven runs' block: also the gathered flag words [ws][R] and dissent
+        partials [ws][n]."""
+        return self._exchange(self.p_send, self.g_allp, self.pp2, self.pp4,
+                              ((self.g_flags, 4 * self.R), (self.g_dis, 4 * self.n)))
 
     def run(self, d_a: int, d_b: int, finalise: bool = True) -> ShardResult:
         """Share gen + rounds 2/4 for this rank's dealers (device pointers d_a, d_b to its [D][t+1][32]
@@ -347,18 +303,38 @@ class ShardedCeremony:
                                                        self.A0.data_ptr(), self.part.data_ptr())
         return self._finish(ms, finalise, None)
 
-    def _finish(self, ms: float, finalise: bool, d_s: Optional[int] = None) -> ShardResult:
+    def _finish(self, ms: float, finalise: bool, d_s: Optional[int] = None, proven=None) -> ShardResult:
+        """The steps after the shard call.  proven: a proven run's (full, verdict, verdict4) -- this rank's
+        verdict arrays -- whose block also carries the flag words and dissent partials."""
+        from ._lib import FIN_PANIC, FIN_PHASE4_ERROR
+
         n, t, ws = self.n, self.t, self.ws
-        self._last_proven = False
-        steps = {}
+        self._last_proven = proven is not None
+        A0 = self.A0 if proven is None else self.pA0  # this rank's terms in the block that was sent
+        steps, extra = {}, {}
         c0 = time.perf_counter()
-        self.exchange()
+        if proven is None:
+            self.exchange()
+        else:
+            full, v, v4 = proven
+            self.exchange_proven()
+            verdict, verdict4 = self._merge_verdicts(v), self._merge_verdicts(v4)
         self._fence()
         c1 = time.perf_counter()
         steps["exchange"] = (c1 - c0) * 1e3
-        o = self.be.shard_combine_device(n, t, ws, self.g_dec2.data_ptr(), self.g_dec4.data_ptr(),
-                                         self.c_dec2.data_ptr(), self.c_dec4.data_ptr(), packed=self.packed,
-                                         arrays=True)
+        if proven is None:
+            o = self.be.shard_combine_device(n, t, ws, self.g_dec2.data_ptr(), self.g_dec4.data_ptr(),
+                                             self.c_dec2.data_ptr(), self.c_dec4.data_ptr(), packed=self.packed,
+                                             arrays=True)
+            no_mpk = o.phase4_error
+        else:
+            o, dissent, status, index = self.be.shard_combine_proven_device(
+                n, t, ws, self.g_dec2.data_ptr(), self.g_dec4.data_ptr(), self.g_flags.data_ptr(),
+                self.g_dis.data_ptr() if full else None, full, self.c_dec2.data_ptr(), self.c_dec4.data_ptr())
+            extra = dict(verdict=verdict if full else None, verdict4=verdict4, dissent=dissent,
+                         finalise_status=status, recovery_index=index)
+            # nobody finalises after a Phase4 failure, and a panic of every party's finalise leaves no mpk
+            no_mpk = status in (FIN_PHASE4_ERROR, FIN_PANIC)
         dec = Decisions(self.c_dec2.view(n, n), self.c_dec4.view(n, n), np.array(o.qualified, dtype=np.uint8),
                         np.array(o.complaints2, dtype=np.int32), np.array(o.r2_error, dtype=np.uint8),
                         np.array(o.reconstruct, dtype=np.uint8), np.array(o.r4_error, dtype=np.uint8),
@@ -366,17 +342,16 @@ class ShardedCeremony:
         c2 = time.perf_counter()
         steps["combine"] = (c2 - c1) * 1e3
         if not finalise:
-            return ShardResult(dec, None, None, None, ms, steps)
-        no_mpk = dec.phase4_error
-        if dec.reconstruct.any() and not dec.phase4_error:
+            return ShardResult(dec, None, None, None, ms, steps, **extra)
+        if dec.reconstruct.any() and not no_mpk:
             # a dealer accused in round 4 (committee.rs:660-670) enters mpk as g * a_i0 over the
             # disclosing final parties' shares (:747-789): the owning rank replaces its term and the
             # terms are gathered again (the interpolation points depend on every rank's rows).  Fewer
             # than t disclosing parties: nobody recovers (:779-781), the same verdict on every rank.
             no_mpk = self.be.ceremony_shard_recon_device(n, t, self.d0, self.d1, dec.qualified, dec.reconstruct, d_s,
-                                                         self.A0.data_ptr(), dec.r2_error, dec.r4_error)
+                                                         A0.data_ptr(), dec.r2_error, dec.r4_error)
             if not no_mpk:
-                self._all_gather(self.g_A0, self.A0)
+                self._all_gather(self.g_A0, A0)
                 self._fence()
         c3 = time.perf_counter()
         steps["recon"] = (c3 - c2) * 1e3
@@ -385,4 +360,4 @@ class ShardedCeremony:
         # device copies of this run's shares (the buffers are reused), read back only when asked for
         fs, pub = self.fs.clone(), self.pub.clone()
         steps["finalise"] = (time.perf_counter() - c3) * 1e3
-        return ShardResult(dec, fs, pub, None if no_mpk else mpk, ms, steps)
+        return ShardResult(dec, fs, pub, None if no_mpk else mpk, ms, steps, **extra)

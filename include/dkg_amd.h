@@ -379,7 +379,10 @@ int dkg_ceremony_run_device(dkg_ctx *ctx, size_t n, size_t t, const void *d_a, c
  * gets g * a_i0 after the exchange, dkg_ceremony_shard_recon_device, because the interpolation
  * points -- the final parties -- depend on every rank's rows; then mpk = sum of the qualified
  * dealers' terms); d_partial [n][32] = sum over this rank's QUALIFIED dealers of s_ij (qualification
- * of a dealer is decided by its own round-2 row, so it needs no exchange). */
+ * of a dealer is decided by its own round-2 row, so it needs no exchange).
+ * Arguments, here and in the five dkg_ceremony_shard_*_device calls below: d_partial (written even for a
+ * rank without dealers, d0 == d1) and the host keys a call takes are always required; with d0 < d1 so are
+ * its device inputs and d_dec2, d_dec4, d_A0.  A null one is DKG_E_ARG, before anything is queued. */
 int dkg_ceremony_shard_device(dkg_ctx *ctx, size_t n, size_t t, size_t d0, size_t d1, const void *d_a,
                               const void *d_b, void *d_dec2, void *d_dec4, void *d_A0, void *d_partial,
                               double *ms_total);

@@ -3,7 +3,8 @@ dealer-sharded ceremony end to end through dkg_amd.distributed.ShardedCeremony.r
 run_verify_proven on GPU 0 -- ranks sharing the GPU over gloo, or one rank over RCCL
 (DKG_DIST_BACKEND=nccl), as tests/dist_worker.py.  Every rank passes the WHOLE complaint lists and
 uploads only its dealers' rows.  Rank 0 writes the combined outputs as JSON to argv[1], keyed
-"full:<scenario>" / "plain:<scenario>" (tests/test_gpu_shard_proven.py full_scenarios, plain_scenarios)."""
+"full:<scenario>" / "plain:<scenario>" (tests/test_gpu_shard_proven.py full_scenarios, plain_scenarios); with
+argv[2] = "mixed", the runs of mixed() under "mixed" instead."""
 import json
 import os
 import sys
@@ -30,7 +31,33 @@ def proven_summary(res, sc):
     return d
 
 
-def main(out_path):
+def mixed(be, dev, rank, ws, put):
+    """Rejection-rule and proven runs alternating on ONE ShardedCeremony, each also on an object of its own
+    (argv[2] = "mixed"): [[kind, summary on the shared object, summary on the fresh one]]."""
+    cer = faulted_ceremony(golden)
+    cer["s"], cer["s_prime"] = cer.pop("shares")
+    n, t = cer["n"], cer["t"]
+    N = t + 1
+    be.env_init(t, n)
+    d0, d1 = dealer_range(rank, ws, n)
+    ins = [put(cer[k][w * d0:w * d1]) for k, w in (("E", 32 * N), ("A", 32 * N), ("e1", 64 * n), ("ct", 64 * n),
+                                                   ("s", 32 * n), ("s_prime", 32 * n))]  # alive until the return
+    E, A, e1, ct, s, sp = (x.data_ptr() for x in ins)
+    c2, c4 = lists2(cer["c2"]), lists4(cer["c4"])
+    runs = {"rejection_full": lambda sc: sc.run_verify_full(E, A, e1, ct, cer["sk"]),
+            "proven_full": lambda sc: sc.run_verify_full_proven(E, A, e1, ct, cer["sk"], cer["pk"], *c2, *c4),
+            "rejection_plain": lambda sc: sc.run_verify(E, A, s, sp),
+            "proven_plain": lambda sc: sc.run_verify_proven(E, A, s, sp, *c4)}
+    one = ShardedCeremony(be, dist, n, t, dev)
+    out = []
+    for kind in ("rejection_full", "proven_full", "rejection_full", "rejection_plain", "proven_plain",
+                 "rejection_plain", "proven_full"):
+        fresh = ShardedCeremony(be, dist, n, t, dev)
+        out.append([kind, proven_summary(runs[kind](one), one), proven_summary(runs[kind](fresh), fresh)])
+    return out
+
+
+def main(out_path, mode=None):
     rank = int(os.environ["RANK"])
     backend = os.environ.get("DKG_DIST_BACKEND", "gloo")
     dev = torch.device("cuda", 0)
@@ -42,6 +69,16 @@ def main(out_path):
     ws = dist.get_world_size()
     be = dkg_amd.Backend(0)
     put = lambda x: torch.frombuffer(bytearray(x or b"\0"), dtype=torch.uint8).to(dev)  # noqa: E731
+    out = {"mixed": mixed(be, dev, rank, ws, put)} if mode == "mixed" else scenarios(be, dev, rank, ws, put)
+    dist.barrier()
+    if rank == 0:
+        with open(out_path, "w") as f:
+            json.dump(out, f)
+    be.close()
+    dist.destroy_process_group()
+
+
+def scenarios(be, dev, rank, ws, put):
     out = {}
     cer = faulted_ceremony(golden)
     cer["s"], cer["s_prime"] = cer.pop("shares")
@@ -77,13 +114,8 @@ def main(out_path):
         out["raw_rows"] = "accepted"
     except ValueError:
         out["raw_rows"] = "ValueError"
-    dist.barrier()
-    if rank == 0:
-        with open(out_path, "w") as f:
-            json.dump(out, f)
-    be.close()
-    dist.destroy_process_group()
+    return out
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(*sys.argv[1:3])

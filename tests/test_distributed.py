@@ -250,6 +250,116 @@ class OracleBackend:
         return FR.gsum([terms[32 * i:32 * i + 32] for i in range(n) if qualified[i]])
 
 
+class OracleProvenBackend(OracleBackend):
+    """OracleBackend with the proven run's two entry points for a ceremony WITHOUT complaints (the double
+    verifies none): the rank's rows and partial sums as the rejection rule gives them, zero flag words, and
+    the combine by the flag-word model of tests/test_shard_proven.py."""
+
+    def ceremony_shard_verify_proven_device(self, n, t, d0, d1, dE, dA, ds, dsp, accusers4, accused4, share4,
+                                            randomness4, o2, o4, oA, op, flag_rows, d_flags, fetched1=None,
+                                            fetched3=None):
+        assert not len(accusers4) and fetched1 is None and fetched3 is None
+        self.ceremony_shard_verify_device(n, t, d0, d1, dE, dA, ds, dsp, o2, o4, oA, op)
+        self._wr(d_flags, bytes(4 * flag_rows))
+        return 0.0, []
+
+    def shard_combine_proven_device(self, n, t, ws, d_pack2_g, d_pack4_g, d_flags_g, d_dissent_g=None, full=True,
+                                    d_dec2=None, d_dec4=None):
+        from dkg_amd.api import ShardOutcome
+        from tests import combine_ref as CR
+        from tests.test_shard_proven import flag_outcome
+        R = CR.rows_per_rank(ws, n)
+        sz = 4 * ws * R * CR.packed_words(n)
+        g2, g4 = (CR.unpack_ranks(np.frombuffer(self._rd(d, sz), dtype=np.uint32), ws, n).reshape(n, n).tolist()
+                  for d in (d_pack2_g, d_pack4_g))
+        flags = bytes(CR.compact(np.frombuffer(self._rd(d_flags_g, 4 * ws * R), dtype=np.uint8), ws, n, 4))
+        o = flag_outcome(n, t, g2, g4, np.frombuffer(flags, dtype=np.int32).tolist(), full)
+        self._wr(d_dec2, bytes(x for row in g2 for x in row))
+        self._wr(d_dec4, bytes(x for row in o["dec4"] for x in row))
+        out = ShardOutcome(o["qualified"], o["complaints2"], o["r2_error"], o["reconstruct"], o["r4_error"],
+                           o["n_qualified"], bool(o["phase4_error"]))
+        return out, None, o["finalise_status"], o["recovery_index"]
+
+
+def _alternate_main(rank, ws, port, names, errq):
+    import torch
+    import torch.distributed as dist
+
+    from dkg_amd._lib import FIN_OK
+    from dkg_amd.distributed import ShardedCeremony, dealer_range
+
+    try:
+        dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=ws)
+        for name in names:
+            with open(os.path.join(ROOT, "tests", "golden", name)) as f:
+                c = json.load(f)
+            n, t = c["n"], c["t"]
+            N = t + 1
+            d0, d1 = dealer_range(rank, ws, n)
+            H = bytes.fromhex
+            put = lambda x: torch.frombuffer(bytearray(x or b"\0"), dtype=torch.uint8)  # noqa: E731
+            ins = [put(H(c[k])[w * d0:w * d1]) for k, w in (("E", 32 * N), ("A", 32 * N), ("s", 32 * n),
+                                                            ("s_prime", 32 * n))]
+            ptrs = [x.data_ptr() for x in ins]
+            new = lambda: ShardedCeremony(OracleProvenBackend(H(c["h"])), dist, n, t, torch.device("cpu"))  # noqa: E731
+            run = lambda sc, proven: (sc.run_verify_proven(*ptrs, [], [], b"", b"") if proven  # noqa: E731
+                                      else sc.run_verify(*ptrs))
+            key = lambda r: (r.decisions.dec2.reshape(-1).tolist(), r.decisions.dec4.reshape(-1).tolist(),  # noqa: E731
+                             r.decisions.qualified.tolist(), r.decisions.reconstruct.tolist(),
+                             r.decisions.complaints2.tolist(), r.decisions.r2_error.tolist(),
+                             r.decisions.r4_error.tolist(), bool(r.decisions.phase4_error), r.final_share,
+                             r.public_share, r.mpk, r.verdict, r.verdict4, r.dissent, r.finalise_status,
+                             r.recovery_index)
+            one = new()
+            S = one.exchange_bytes(proven=False)
+            for proven in (False, True, False, True):
+                got, want = run(one, proven), run(new(), proven)
+                assert key(got) == key(want), (name, proven)
+                assert one.exchange_bytes() == (S + 4 * one.R + 4 * n if proven else S), (name, proven)
+                d = got.decisions
+                assert d.qualified.tolist() == c["qualified"], name  # round 2 keeps the rejection rule
+                assert got.final_share.hex() == c["final_share"], name
+                if proven:  # no complaint holds: nobody is reconstructed
+                    assert (got.verdict, got.verdict4, got.dissent) == (None, [], None)
+                    assert not d.reconstruct.any() and got.finalise_status == FIN_OK and got.mpk is not None
+                else:
+                    assert got.verdict4 is None and got.finalise_status is None
+                    assert d.reconstruct.tolist() == c["reconstruct"], name
+                    assert (got.mpk.hex() if got.mpk else "00" * 32) == c["mpk"], name
+        dist.barrier()
+        dist.destroy_process_group()
+    except BaseException as e:
+        errq.put(f"rank {rank}: {type(e).__name__}: {e}")
+        raise
+
+
+@pytest.mark.parametrize("ws", [2, 3])
+def test_sharded_rules_alternate_on_one_object_gloo(ws):
+    """A rejection-rule run, a proven run, and both again on ONE ShardedCeremony over gloo with the oracle
+    standing in for the GPU: the one _finish and the one block-splitting routine serve both kinds, each run
+    equals the same run on a fresh object, and exchange_bytes() reports the kind of the run just made
+    (fault_a_generator: a round-4 reconstruction under the rejection rule, none under the proven rule
+    without complaints; fault_share_flip: a disqualified dealer)."""
+    ctx = mp.get_context("spawn")
+    errq = ctx.Queue()
+    port = _free_port()
+    names = ["fault_a_generator_n10_t4.json", "fault_share_flip_n10_t4.json"]
+    procs = [ctx.Process(target=_alternate_main, args=(r, ws, port, names, errq)) for r in range(ws)]
+    for p in procs:
+        p.start()
+    for p in procs:
+        p.join(timeout=240)
+    alive = [p for p in procs if p.is_alive()]
+    for p in alive:
+        p.kill()
+    errs = []
+    while not errq.empty():
+        errs.append(errq.get())
+    assert not alive, "rank hung"
+    assert not errs, errs
+    assert all(p.exitcode == 0 for p in procs), [p.exitcode for p in procs]
+
+
 def _run_verify_main(rank, ws, port, names, errq):
     import torch
     import torch.distributed as dist

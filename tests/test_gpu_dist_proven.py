@@ -85,6 +85,30 @@ def references(golden):
     return want
 
 
+def test_rules_alternate_on_one_object(tmp_path, references):
+    """Three ranks over gloo (dealers 3, 3, 4): rejection-rule and proven runs alternating on ONE
+    ShardedCeremony -- one _finish and one block-splitting routine serve both -- each equal to the same run
+    on an object of its own, with exchange_bytes() reporting the kind of the run just made."""
+    out = tmp_path / "dist_mixed.json"
+    _spawn(3, "gloo", [str(out), "mixed"])
+    runs = json.loads(out.read_text())["mixed"]
+    assert [k for k, _, _ in runs] == ["rejection_full", "proven_full", "rejection_full", "rejection_plain",
+                                       "proven_plain", "rejection_plain", "proven_full"]
+    n = 10
+    R = shard_rows(n, 3)
+    S = 2 * 4 * R * packed_row_words(n) + 32 * R + 32 * n
+    for kind, one, fresh in runs:
+        assert one == fresh, kind
+        proven = kind.startswith("proven")
+        assert one["exchange_bytes"] == (S + 4 * R + 4 * n if proven else S) and one["plain_bytes"] == S, kind
+        assert (one["verdict4"] is not None) == proven and (one["verdict"] is not None) == (kind == "proven_full")
+    for k, v in references["full:honest"].items():
+        assert runs[1][1][k] == v and runs[6][1][k] == v, k
+    for k, v in references["rejection"].items():
+        assert runs[0][1][k] == v and runs[2][1][k] == v, k
+    assert runs[3][1] == runs[5][1]
+
+
 @pytest.mark.parametrize("ws,backend", [(2, "gloo"), (3, "gloo"), (1, "nccl")])
 def test_sharded_proven_processes(tmp_path, references, ws, backend):
     out = tmp_path / "dist_proven.json"

@@ -672,6 +672,153 @@ def test_multi_backend_plain(be, mb, golden, name):
     assert rc == DKG_E_ARG  # complaints without a verdict array
 
 
+# ---------------------------------------------------------------- 6c. the six shard entry points, one driver
+OUTS = ["dec2", "dec4", "A0", "partial"]
+# kind -> (entry point, its arguments after d1 in order, the device pointers it requires of a rank with
+# dealers).  d_partial, the host keys it takes and d_flags (flag_rows > 0) are required of every rank.
+SIX = {
+    "gen": ("dkg_ceremony_shard_device", ["a", "b"] + OUTS, ["a", "b"]),
+    "verify": ("dkg_ceremony_shard_verify_device", ["E", "A", "s", "sp"] + OUTS, ["E", "A", "s", "sp"]),
+    "gen_full": ("dkg_ceremony_shard_full_device", ["a", "b", "r", "sk", "pk", "e1_out", "ct_out"] + OUTS,
+                 ["a", "b", "r"]),
+    "verify_full": ("dkg_ceremony_shard_verify_full_device", ["E", "A", "e1", "ct", "sk"] + OUTS,
+                    ["E", "A", "e1", "ct"]),
+    "verify_proven": ("dkg_ceremony_shard_verify_proven_device",
+                      ["E", "A", "s", "sp", "f1", "f3", "C4", "acc4", "acd4", "sh4", "rn4"] + OUTS +
+                      ["flag_rows", "flags", "v4"], ["E", "A", "s", "sp"]),
+    "verify_full_proven": ("dkg_ceremony_shard_verify_full_proven_device",
+                           ["E", "A", "e1", "ct", "sk", "pk", "f1", "f3", "C", "acc", "acd", "proofs", "C4", "acc4",
+                            "acd4", "sh4", "rn4"] + OUTS + ["flag_rows", "flags", "dissent", "v2", "v4"],
+                           ["E", "A", "e1", "ct"]),
+}
+ALWAYS = ["partial", "sk", "pk", "flags"]
+
+
+def six_call(b, kind, cer, seeds, d0, d1, R, null=None):
+    """One of the six entry points through the C ABI on dealers [d0, d1) of the faulted ceremony `cer` (the
+    received broadcasts and complaint lists) or of `seeds` (full_n10_t4.json: the generate modes), with
+    argument `null` passed as NULL.  Every output buffer is poisoned first.  -> (rc, {output: bytes / list})."""
+    import torch
+
+    n, t = cer["n"], cer["t"]
+    N, D = t + 1, d1 - d0
+    fn, order, _ = SIX[kind]
+    u8 = dict(dtype=torch.uint8, device="cuda:0")
+    gen = kind.startswith("gen")
+    a, b_ = dkg_amd.dealer_coefficients(H(seeds["master_seed"]), seeds["ceremony"], d0, D, t) if D else (b"", b"")
+    host = dict(a=a, b=b_, r=H(seeds["enc_r"])[64 * n * d0:64 * n * d1], E=cer["E"][32 * N * d0:32 * N * d1],
+                A=cer["A"][32 * N * d0:32 * N * d1], s=cer["s"][32 * n * d0:32 * n * d1],
+                sp=cer["s_prime"][32 * n * d0:32 * n * d1], e1=cer["e1"][64 * n * d0:64 * n * d1],
+                ct=cer["ct"][64 * n * d0:64 * n * d1])
+    ins = {k: _dev(v) for k, v in host.items() if k in order}
+    size = dict(dec2=D * n, dec4=D * n, A0=32 * D, partial=32 * n, e1_out=64 * D * n, ct_out=64 * D * n,
+                flags=4 * R, dissent=4 * n)
+    outs = {k: torch.full((max(v, 16),), 0xEE, **u8) for k, v in size.items() if k in order}
+    a2, d2, pr = lists2(cer["c2"])
+    a4, d4, s4, r4 = lists4(cer["c4"])
+    v2, v4 = (ctypes.c_int32 * len(a2))(*[9] * len(a2)), (ctypes.c_int32 * len(a4))(*[9] * len(a4))
+    args = {k: ctypes.c_void_p(v.data_ptr()) for k, v in (ins | outs).items()}
+    args.update(sk=H(seeds["member_sk"]) if gen else cer["sk"], pk=H(seeds["member_pk"]) if gen else cer["pk"], f1=None,
+                f3=None, C=len(a2), acc=u32s(a2), acd=u32s(d2), proofs=pr, C4=len(a4), acc4=u32s(a4), acd4=u32s(d4),
+                sh4=s4, rn4=r4, flag_rows=R, v2=v2, v4=v4)
+    if null is not None:
+        assert null in order
+        args[null] = None
+    rc = getattr(_lib.lib(), fn)(b.ctx, n, t, d0, d1, *(args[k] for k in order), None)
+    got = {k: _host(v)[:size[k]] for k, v in outs.items()}
+    if "v4" in order:
+        got["v4"] = list(v4)
+    if "v2" in order:
+        got["v2"] = list(v2)
+    return rc, got
+
+
+@pytest.fixture(scope="module")
+def six_fresh(faulted, golden):
+    """(kind, d0, d1, R) -> the call's outputs on a context of its own, computed once."""
+    seeds = golden("full_n10_t4.json")
+    memo = {}
+
+    def get(kind, d0, d1, R):
+        key = (kind, d0, d1, R)
+        if key not in memo:
+            b = dkg_amd.Backend(0)
+            try:
+                b.env_init(faulted["t"], faulted["n"], CK)
+                rc, memo[key] = six_call(b, kind, faulted, seeds, d0, d1, R)
+                assert rc == DKG_OK, key
+            finally:
+                b.close()
+        return memo[key]
+
+    return get
+
+
+def six_sequence():
+    """(kind, ws, rank): a 3-dealer rank, then all 10 dealers (the merged buffers grow), the 3-dealer rank
+    again (they are reused), the last ranks of two and of three (5 and 4 dealers), and a rank without dealers."""
+    kinds = list(SIX)
+    seq = [(k, 3, 1) for k in kinds] + [(k, 1, 0) for k in kinds] + [(k, 3, 0) for k in kinds]
+    seq += [(k, 2, 1) for k in kinds[::2]] + [(k, 3, 2) for k in kinds[1::2]] + [(k, 3, None) for k in kinds]
+    return seq
+
+
+@pytest.mark.parametrize("order", ["forward", "reverse"])
+def test_six_entry_points_share_one_context(faulted, golden, six_fresh, order):
+    """The six entry points one after another on ONE context, in one order and in the reverse one: every
+    output (rows, terms, partial sums, flags, dissent, verdicts, ciphertexts) is what the same call gives
+    on a fresh context, whatever the calls before it left in the context's buffers."""
+    n, t = faulted["n"], faulted["t"]
+    assert [shard_range(n, 3, r) for r in range(3)] == [(0, 3), (3, 6), (6, 10)]
+    seeds = golden("full_n10_t4.json")
+    seq = six_sequence()
+    b = dkg_amd.Backend(0)
+    try:
+        b.env_init(t, n, CK)
+        for kind, ws, r in seq if order == "forward" else seq[::-1]:
+            d0, d1 = (4, 4) if r is None else shard_range(n, ws, r)
+            R = shard_rows(n, ws)
+            rc, got = six_call(b, kind, faulted, seeds, d0, d1, R)
+            assert rc == DKG_OK, (kind, ws, r)
+            assert got == six_fresh(kind, d0, d1, R), (kind, ws, r)
+            if r is None:
+                assert got["partial"] == bytes(32 * n)
+    finally:
+        b.close()
+    # the generated ciphertexts are the fixture's rows, the received ones' verdicts the single context's
+    g = six_fresh("gen_full", 3, 6, 4)
+    assert (g["e1_out"].hex(), g["ct_out"].hex()) == (seeds["e1"][128 * n * 3:128 * n * 6],
+                                                      seeds["ct"][128 * n * 3:128 * n * 6])
+    assert six_fresh("verify_full_proven", 0, 10, 10)["v2"] == [0, 0, 0, 2, 1]
+
+
+@pytest.mark.parametrize("kind", list(SIX))
+def test_six_entry_points_required_pointers(faulted, golden, six_fresh, kind):
+    """One argument rule for the six: with dealers, each required pointer NULL in turn is DKG_E_ARG and the
+    context then serves the good call with unchanged outputs; a rank without dealers (d0 == d1) takes the
+    same NULLs, except d_partial (written even then), the host keys and d_flags."""
+    n, t = faulted["n"], faulted["t"]
+    seeds = golden("full_n10_t4.json")
+    _, order, inputs = SIX[kind]
+    always = [k for k in ALWAYS if k in order]
+    b = dkg_amd.Backend(0)
+    try:
+        b.env_init(t, n, CK)
+        for null in inputs + ["dec2", "dec4", "A0"] + always:
+            assert six_call(b, kind, faulted, seeds, 6, 10, 4, null)[0] == DKG_E_ARG, null
+        rc, got = six_call(b, kind, faulted, seeds, 6, 10, 4)
+        assert rc == DKG_OK and got == six_fresh(kind, 6, 10, 4)
+        empty = six_fresh(kind, 4, 4, 4)
+        for null in inputs + ["dec2", "dec4", "A0"]:
+            rc, got = six_call(b, kind, faulted, seeds, 4, 4, 4, null)
+            assert rc == DKG_OK and got == empty, null
+        for null in always:
+            assert six_call(b, kind, faulted, seeds, 4, 4, 4, null)[0] == DKG_E_ARG, null
+        assert six_call(b, kind, faulted, seeds, 6, 10, 4)[1] == six_fresh(kind, 6, 10, 4)
+    finally:
+        b.close()
+
+
 # ---------------------------------------------------------------- 7. the headline shape, once
 def test_rank0_of_8_at_n1024_matches_single_context(be, ranks):
     """n = 1024, t = 511, rank 0 of 8 (128 dealers, two column groups), one complaint of each round per
