@@ -159,6 +159,11 @@ def lib():
         L.dkg_commitment_eval_pairs.argtypes = [p, sz, sz, sz, p, p, u8p, p, p]
     L.dkg_verify_receivers.argtypes = [p, sz, sz, ctypes.c_int, sz, p, u8p, u8p, p, p, p]
     L.dkg_party_round2.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
+    if hasattr(L, "dkg_seat_pack"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_seat_pack.argtypes = [sz, sz, p] + [ctypes.POINTER(ctypes.c_uint32)] * 3 + [p, p, ctypes.POINTER(ctypes.c_uint32)]
+        L.dkg_commitment_eval_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, p, p]
+        L.dkg_verify_seats.argtypes = [p, sz, sz, sz, ctypes.c_int, sz, p, p, u8p, u8p, p, p, p]
+        L.dkg_party_round2_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -305,4 +310,5 @@ EXPORTED = [
     "dkg_receiver_plan_for", "dkg_receiver_plan_cost_us", "dkg_receiver_plan_constants", "dkg_ctx_set_receiver_chunk",
     "dkg_ctx_set_comb_build", "dkg_ctx_last_comb_build", "dkg_ctx_last_comb_build_ms", "dkg_comb_geometry", "dkg_comb_entries",
     "dkg_ctx_last_receiver_chunk", "dkg_pair_eval_shape", "dkg_commitment_eval_pairs", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
+    "dkg_seat_pack", "dkg_commitment_eval_seats", "dkg_verify_seats", "dkg_party_round2_seats",
 ]

@@ -268,14 +268,15 @@ class Backend:
         """Device ms of binomial / stepping / combine / check in the last ceremony's checks: tag "r24" (rounds
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
         encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
-        commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs).  Only recorded with
-        set_streams(1); -1 otherwise."""
+        commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs), "seats" (the last
+        commitment_eval_seats, verify_seats, party_round2_seats).  Only recorded with set_streams(1); -1 otherwise."""
         L = _lib.lib()
         if isinstance(tag, int):
             tag = f"r{tag}"
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("decode", "eval") if tag == "pairs"
+                 else ("decrypt", "decode", "eval", "check", "prove") if tag == "seats"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
         return {k: L.dkg_ctx_phase_ms(self._ctx, f"{tag}.{k}".encode()) for k in names}
@@ -401,6 +402,52 @@ class Backend:
                                                        ctypes.byref(cnt), ctypes.byref(err), prf))
         return {"s": s.raw, "s_prime": sp.raw, "dec": dec.raw, "complaints": cnt.value, "r2_error": err.value,
                 "proofs": prf.raw if prf is not None else None}
+
+    # ---- hosted seats: one operator's party index in each of many ceremonies (k_seat_horner)
+    @staticmethod
+    def _seat_arrays(cer, js):
+        S = len(cer)
+        if len(js) != S:
+            raise ValueError("cer and js differ in length")
+        return S, (ctypes.c_uint32 * max(S, 1))(*cer), (ctypes.c_uint32 * max(S, 1))(*js)
+
+    def commitment_eval_seats(self, B: int, n: int, t: int, cer: Sequence[int], js: Sequence[int], C: bytes):
+        """(P, ok) for the seats (cer[p], js[p]) of B ceremonies of (n, t), C [B*n][t+1][32]: P[p][i] =
+        sum_k (js[p]+1)^k C_{cer[p], i}[k] as S*n encodings, ok [S][n] = the row decodes (its P zero
+        otherwise).  commitment_eval per seat in one call; only the ceremonies named are decoded."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        P = ctypes.create_string_buffer(max(32 * S * n, 1))
+        ok = ctypes.create_string_buffer(max(S * n, 1))
+        _check(self._ctx, _lib.lib().dkg_commitment_eval_seats(self._ctx, B, n, t, S, ca, ja, C, P, ok))
+        return P.raw[: 32 * S * n], ok.raw[: S * n]
+
+    def verify_seats(self, B: int, n: int, t: int, rnd: int, cer: Sequence[int], js: Sequence[int], C: bytes,
+                     s_cols: bytes, sp_cols: Optional[bytes] = None, qualified: Optional[bytes] = None) -> bytes:
+        """verify_receivers with one index per seat, all seats in one call: s_cols / sp_cols [S][n][32],
+        decisions [S][n]; qualified [B][n] (round 4): 0 marks SKIPPED for that ceremony's seats."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        dec = ctypes.create_string_buffer(max(S * n, 1))
+        _check(self._ctx, _lib.lib().dkg_verify_seats(self._ctx, B, n, t, rnd, S, ca, ja, C, s_cols, sp_cols, qualified,
+                                                       dec))
+        return dec.raw[: S * n]
+
+    def party_round2_seats(self, B: int, n: int, t: int, cer: Sequence[int], js: Sequence[int], E: bytes,
+                           e1_cols: bytes, ct_cols: bytes, sks: bytes, w: Optional[bytes] = None) -> dict:
+        """party_round2 for every seat in one call: e1_cols, ct_cols [S][n][2][32], sks [S][32], w [S][n][64]
+        (None: no proofs).  Keys: s, s_prime [S][n][32], dec [S][n], complaints [S], r2_error [S], proofs
+        [S][n][192] or None."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        s = ctypes.create_string_buffer(max(32 * S * n, 1))
+        sp = ctypes.create_string_buffer(max(32 * S * n, 1))
+        dec = ctypes.create_string_buffer(max(S * n, 1))
+        cnt = (ctypes.c_int32 * max(S, 1))()
+        err = ctypes.create_string_buffer(max(S, 1))
+        prf = ctypes.create_string_buffer(max(192 * S * n, 1)) if w is not None else None
+        _check(self._ctx, _lib.lib().dkg_party_round2_seats(self._ctx, B, n, t, S, ca, ja, E, e1_cols, ct_cols, sks, w,
+                                                             s, sp, dec, cnt, err, prf))
+        return {"s": s.raw[: 32 * S * n], "s_prime": sp.raw[: 32 * S * n], "dec": dec.raw[: S * n],
+                "complaints": list(cnt[:S]), "r2_error": list(err.raw[:S]),
+                "proofs": prf.raw[: 192 * S * n] if prf is not None else None}
 
     # ---- whole ceremony
     def _ceremony_out(self, n, t, big):
@@ -1097,6 +1144,22 @@ def pair_eval_shape(t: int, chunk: int = 0) -> dict:
     if rc != _lib.DKG_OK:
         raise _lib.DkgError(rc, "pair_eval_shape")
     return {"chunk": v[0].value, "lanes": v[1].value, "stages": v[2].value}
+
+
+def seat_pack(n: int, js: Sequence[int]) -> dict:
+    """dkg_seat_pack (host only): how the seats with party indices js (0-based) of ceremonies of n parties
+    share the waves of the seats calls.  Keys: width, per_wave, tiles, wave_of [S], slot_of [S], waves."""
+    S = len(js)
+    ja = (ctypes.c_uint32 * max(S, 1))(*js)
+    wave_of = (ctypes.c_uint32 * max(S, 1))()
+    slot_of = (ctypes.c_uint32 * max(S, 1))()
+    v = [ctypes.c_uint32() for _ in range(4)]
+    rc = _lib.lib().dkg_seat_pack(n, S, ja, ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(v[2]), wave_of, slot_of,
+                                  ctypes.byref(v[3]))
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "seat_pack")
+    return {"width": v[0].value, "per_wave": v[1].value, "tiles": v[2].value, "wave_of": list(wave_of[:S]),
+            "slot_of": list(slot_of[:S]), "waves": v[3].value}
 
 
 def receiver_plan_constants() -> dict:

@@ -44,4 +44,17 @@ int naf256(const uint8_t v[32], uint32_t pos[8], uint32_t neg[8], int* weight);
 // v[p] stands among them (the pair evaluation's distinct rows and distinct indices)
 void distinct_places(size_t count, const uint32_t* v, std::vector<uint32_t>& distinct, std::vector<uint32_t>& place);
 
+// seat_pack.cpp: what one seats call uploads for k_seat_horner, from dkg_seat_pack's placement.  Wave v
+// evaluates at x = wave_desc[2v] the dealers wave_desc[2v + 1] * 64 + i, i < width, of the seats
+// wave_seat[v * per_wave + slot] (SEAT_NONE: an empty slot); seat p's commitments are ceremony slot
+// seat_col[p] among the distinct ceremonies `cers` (order of first appearance), the only ones decoded.
+constexpr uint32_t SEAT_NONE = 0xffffffffu;
+struct SeatPlan {
+  uint32_t width = 0, per_wave = 0, tiles = 0, waves = 0;
+  std::vector<uint32_t> cers, seat_col, seat_x, wave_desc, wave_seat;
+  size_t live_lanes = 0;  // S n of the 64 waves lanes
+};
+// DKG_E_ARG for cer[p] >= B, 2^32 - 1 seats or more, and whatever dkg_seat_pack rejects
+int seat_plan(size_t B, size_t n, size_t S, const uint32_t* cer, const uint32_t* js, SeatPlan& out);
+
 }  // namespace dkgh

@@ -193,12 +193,12 @@ DKG_DEV int w4_recode(const uint32_t* __restrict__ sk8, int8_t* dig, int16_t* nz
 // (key = c*n + q, w, lane group lg) with lg fastest, its lanes the dealers lg*64 .. of ceremony c; the
 // scalar is wave-uniform.  The chain is k_dec_mul_w4's (hybrid.hip): each lane's odd multiples R, 3R,
 // 5R, 7R in the global table T (one 40-KB slot per wave of the launch, blockIdx.x), the next addend
-// copied into the wave's LDS slot by LDS-DMA during the doublings before it.
-__global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_bdec_mul_w4(size_t n, size_t LG, size_t wv0,
-                                                                      const uint32_t* __restrict__ sk,
-                                                                      const uint32_t* __restrict__ R_ext,
-                                                                      uint32_t* __restrict__ K_ext, size_t count,
-                                                                      uint32_t* __restrict__ T) {
+// copied into the wave's LDS slot by LDS-DMA during the doublings before it.  SEATS: the item index has
+// no recipient axis (k_seat_dec_mul_w4 below); nothing else differs.
+template <bool SEATS>
+DKG_DEV void bdec_w4_wave(size_t n, size_t LG, size_t wv0, const uint32_t* __restrict__ sk,
+                          const uint32_t* __restrict__ R_ext, uint32_t* __restrict__ K_ext, size_t count,
+                          uint32_t* __restrict__ T) {
   __shared__ uint32_t qs[PT_WORDS * 64];
   __shared__ int16_t nzb[96];  // bits of the nonzero digits, top first
   __shared__ int8_t nzd[96];   // their digits
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_bdec_mul_w4(size_t n, 
   const size_t c = key / n, q = key % n;
   const size_t i = lg * 64 + threadIdx.x;
   const bool live = i < n;
-  const size_t idx = ((c * n + (live ? i : 0)) * n + q) * 2 + w;
+  const size_t idx = SEATS ? (key * n + (live ? i : 0)) * 2 + w : ((c * n + (live ? i : 0)) * n + q) * 2 + w;
   uint32_t* tb = T + (size_t)blockIdx.x * (4 * PT_WORDS * 64);
   if (threadIdx.x == 0) nnz_s = w4_recode(sk + 8 * key, dig, nzb, nzd);
   // the lane's table of odd multiples
@@ -264,6 +264,24 @@ __global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_bdec_mul_w4(size_t n, 
   if (live) pt_store(K_ext, count, idx, x);
 }
 
+__global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_bdec_mul_w4(size_t n, size_t LG, size_t wv0,
+                                                                      const uint32_t* __restrict__ sk,
+                                                                      const uint32_t* __restrict__ R_ext,
+                                                                      uint32_t* __restrict__ K_ext, size_t count,
+                                                                      uint32_t* __restrict__ T) {
+  bdec_w4_wave<false>(n, LG, wv0, sk, R_ext, K_ext, count, T);
+}
+
+// The same chain for the seats of one operator: key p = seat p's secret key, its items the n pairs
+// addressed to it, item (p * n + i) * 2 + w (no recipient axis: the rows-per-key split of k_benc_mul).
+__global__ __launch_bounds__(64, DKG_DEC_W4_WAVES) void k_seat_dec_mul_w4(size_t n, size_t LG, size_t wv0,
+                                                                          const uint32_t* __restrict__ sk,
+                                                                          const uint32_t* __restrict__ R_ext,
+                                                                          uint32_t* __restrict__ K_ext, size_t count,
+                                                                          uint32_t* __restrict__ T) {
+  bdec_w4_wave<true>(n, LG, wv0, sk, R_ext, K_ext, count, T);
+}
+
 // waves of one bdec_mul call, and the words of its odd-multiples table (slices of <= DEC_TAB_WAVES)
 static size_t bdec_waves(size_t keys, size_t n) { return keys * 2 * ((n + 63) / 64); }
 
@@ -279,6 +297,15 @@ void bdec_mul(size_t keys, size_t n, const uint32_t* sk, const uint32_t* R_ext, 
   const size_t waves = bdec_waves(keys, n);
   for (size_t wv0 = 0; wv0 < waves; wv0 += DEC_TAB_WAVES)
     hipLaunchKernelGGL(k_bdec_mul_w4, dim3((unsigned)std::min(DEC_TAB_WAVES, waves - wv0)), dim3(64), 0, stream, n,
+                       (n + 63) / 64, wv0, sk, R_ext, K_ext, count, table);
+}
+
+void seat_dec_mul(size_t seats, size_t n, const uint32_t* sk, const uint32_t* R_ext, uint32_t* K_ext, size_t count,
+                  uint32_t* table, hipStream_t stream) {
+  if (!seats || !n) return;
+  const size_t waves = bdec_waves(seats, n);
+  for (size_t wv0 = 0; wv0 < waves; wv0 += DEC_TAB_WAVES)
+    hipLaunchKernelGGL(k_seat_dec_mul_w4, dim3((unsigned)std::min(DEC_TAB_WAVES, waves - wv0)), dim3(64), 0, stream, n,
                        (n + 63) / 64, wv0, sk, R_ext, K_ext, count, table);
 }
 

@@ -310,6 +310,10 @@ size_t bdec_mul_table_words(size_t keys, size_t n);
 size_t bdec_launch_waves();  // waves per launch (the table's slots): larger calls run as slices
 void bdec_mul(size_t keys, size_t n, const uint32_t* sk, const uint32_t* R_ext, uint32_t* K_ext, size_t count,
               uint32_t* table, hipStream_t stream);
+// the same for `seats` keys with n items pairs each and no recipient axis: K = sk_p * R for the items
+// (p * n + i) * 2 + w; table: bdec_mul_table_words(seats, n) words
+void seat_dec_mul(size_t seats, size_t n, const uint32_t* sk, const uint32_t* R_ext, uint32_t* K_ext, size_t count,
+                  uint32_t* table, hipStream_t stream);
 
 // ---- round-2 complaints, complaints.hip (broadcast.rs:50-99, 189-283)
 // out[k] = sa[k] P (joint = false, width-2 windows) or sa[k] P + sb[k] Q (Straus), P / Q = elements
@@ -429,6 +433,18 @@ void recv_encode(size_t M, size_t D, const uint32_t* R, const uint8_t* dok, uint
 void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint32_t* crow, const uint32_t* slot,
                const uint32_t* Eext, size_t stride, size_t N, uint32_t L, uint32_t G, uint32_t S,
                const uint32_t* digits, uint32_t* R, hipStream_t stream);
+// ---- seats (ceremony, party) of one operator: dkg_seat_pack's waves, one workgroup each (k_seat_horner).
+// Wave v evaluates at x = wdesc[2v] the dealers wdesc[2v + 1] * 64 + i, i < width (a power of two <= 64),
+// of the 64 / width seats wseat[v * (64 / width) + slot] (0xffffffff: empty); seat p reads columns
+// scol[p] * n + dealer of the position-major table C [40][N][cols].  R [seat * n + dealer][40] point-major
+void seat_horner(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, const uint32_t* wdesc,
+                 const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* R, hipStream_t stream);
+// sok [S][n] = dok[scol[p] * n + i] and extra [S][n] (may be null)
+void seat_ok(size_t S, size_t n, const uint32_t* scol, const uint8_t* dok, const uint8_t* extra, uint8_t* sok,
+             hipStream_t stream);
+// recv_decide per seat: party sx[p] - 1 of ceremony scer[p]; sok [S][n]; qualified [B][n] (may be null)
+void seat_decide(size_t S, size_t n, int round, const uint32_t* sx, const uint32_t* scer, const uint8_t* sok,
+                 const uint8_t* qualified, uint8_t* dec, hipStream_t stream);
 // ok[p] = rowok[crow[p] - 1], p < cnt
 void pair_ok(size_t cnt, const uint32_t* crow, const uint8_t* rowok, uint8_t* ok, hipStream_t stream);
 

@@ -9,6 +9,8 @@
 // the same for all dealers, hence uniform over the wave (dealers run along the wave); the long ones
 // come from the host as signed digits (dkg_receiver_plan_for).  Every addition is the complete
 // formula, so identity rows, equal operands and torsion representatives need no redo.
+// k_pair_eval gives one wave to one (row, index) pair; k_seat_horner walks the seats (ceremony, party) of
+// one operator serially, seats of equal x side by side in a wave (dkg_seat_pack).
 // Built twice like kernels.hip (dkg_amd/Makefile): namespace dkgk, and dkgk_ilp with DKG_FE_ILP.
 #ifdef DKG_FE_ILP
 #define dkgk dkgk_ilp
@@ -200,6 +202,70 @@ __global__ __launch_bounds__(64, 3) void k_pair_eval(const uint32_t* __restrict_
   if (u == (1u << S) - 1) pt_store_aos(R, c, acc);
 }
 
+// P_i(x) for the SEATS (ceremony, party) of one operator, one 64-lane workgroup per wave of dkg_seat_pack's
+// placement.  Every polynomial of a seat is evaluated at the seat's x = j + 1, and the host packs only
+// seats of equal x into one wave, so the multiplier is wave-uniform as in k_recv_chunks: the serial walk
+// acc = x acc + C[k] over the N coefficients, no fold.  Wave v: x = wdesc[2v], dealer tile wdesc[2v + 1];
+// lane l = slot W + i (W = 1 << wshift) is dealer d = tile 64 + i of seat wseat[v (64 / W) + slot], whose
+// commitments are columns scol[seat] n + d of the position-major table C [40][N][cols] over the decoded
+// ceremonies.  A lane with d >= n or in an empty slot (SEAT_NONE) walks column 0 and stores nothing.
+// R point-major [seat n + d][40].
+__global__ __launch_bounds__(64, 3) void k_seat_horner(size_t n, size_t N, size_t cols, uint32_t wshift,
+                                                       const uint32_t* __restrict__ wdesc,
+                                                       const uint32_t* __restrict__ wseat,
+                                                       const uint32_t* __restrict__ scol,
+                                                       const uint32_t* __restrict__ C, uint32_t* __restrict__ R) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* q = qs + threadIdx.x;
+  const size_t v = blockIdx.x;
+  const uint32_t x = wdesc[2 * v], tile = wdesc[2 * v + 1];
+  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
+  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
+  const size_t d = (size_t)tile * 64 + i;
+  const bool live = seat != 0xffffffffu && d < n;
+  size_t col = 0;
+  if (live) col = (size_t)scol[seat] * n + d;
+  uint32_t pos, neg;
+  const int len = small_recode(x, pos, neg);
+  const size_t S = N * cols;
+  ge_p3 acc, c;
+  pt_load(acc, C, S, (N - 1) * cols + col);
+#pragma unroll 1
+  for (size_t k = N - 1; k-- > 0;) {
+    recv_mul_small(acc, pos, neg, len, q);
+    pt_load(c, C, S, k * cols + col);
+    add_point_lds(acc, c, q);
+  }
+  if (live) pt_store_aos(R, (size_t)seat * n + d, acc);
+}
+
+// sok[p n + i] = dok[scol[p] n + i] (and extra[p n + i], may be null): dealer i's data decodes for seat p
+__global__ __launch_bounds__(256) void k_seat_ok(size_t S, size_t n, const uint32_t* __restrict__ scol,
+                                                 const uint8_t* __restrict__ dok, const uint8_t* __restrict__ extra,
+                                                 uint8_t* __restrict__ sok) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S * n) return;
+  const size_t p = e / n, i = e % n;
+  sok[e] = dok[(size_t)scol[p] * n + i] && (!extra || extra[e]);
+}
+
+// k_recv_decide for seats: dec [S][n] holds the group equation's outcome; seat p = party sx[p] - 1 of
+// ceremony scer[p], whose qualified set is qualified[scer[p] n ..] (may be null).  The same order:
+// undecodable data (sok), then SKIPPED, then SELF.
+__global__ __launch_bounds__(256) void k_seat_decide(size_t S, size_t n, int round, const uint32_t* __restrict__ sx,
+                                                     const uint32_t* __restrict__ scer,
+                                                     const uint8_t* __restrict__ sok,
+                                                     const uint8_t* __restrict__ qualified,
+                                                     uint8_t* __restrict__ dec) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= S * n) return;
+  const size_t p = e / n, i = e % n;
+  uint8_t v = sok[e] ? dec[e] : (round == 2 ? 4 : 0);
+  if (qualified && !qualified[(size_t)scer[p] * n + i]) v = 3;
+  if ((uint32_t)(i + 1) == sx[p]) v = 2;
+  dec[e] = v;
+}
+
 // ok[p] = rowok[crow[p] - 1]: the items of k_pair_eval whose row decodes
 __global__ __launch_bounds__(256) void k_pair_ok(size_t cnt, const uint32_t* __restrict__ crow,
                                                  const uint8_t* __restrict__ rowok, uint8_t* __restrict__ ok) {
@@ -261,6 +327,29 @@ void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint3
   if (!cnt || !N || !L || G < 1 || G > 64 || (size_t)L * G < N || (1u << S) < G) return;
   hipLaunchKernelGGL(k_pair_eval, dim3((unsigned)cnt), dim3(64), 0, stream, list, xs, crow, slot, Eext, stride, N, L, G,
                      S, digits, R);
+}
+
+void seat_horner(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, const uint32_t* wdesc,
+                 const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* R, hipStream_t stream) {
+  uint32_t wshift = 0;
+  while ((1u << wshift) < width) wshift++;
+  if (!waves || !n || !N || (1u << wshift) != width || width > 64 || cols < n) return;
+  hipLaunchKernelGGL(k_seat_horner, dim3((unsigned)waves), dim3(64), 0, stream, n, N, cols, wshift, wdesc, wseat, scol,
+                     C, R);
+}
+
+void seat_ok(size_t S, size_t n, const uint32_t* scol, const uint8_t* dok, const uint8_t* extra, uint8_t* sok,
+             hipStream_t stream) {
+  if (!S || !n) return;
+  hipLaunchKernelGGL(k_seat_ok, dim3((unsigned)((S * n + 255) / 256)), dim3(256), 0, stream, S, n, scol, dok, extra,
+                     sok);
+}
+
+void seat_decide(size_t S, size_t n, int round, const uint32_t* sx, const uint32_t* scer, const uint8_t* sok,
+                 const uint8_t* qualified, uint8_t* dec, hipStream_t stream) {
+  if (!S || !n) return;
+  hipLaunchKernelGGL(k_seat_decide, dim3((unsigned)((S * n + 255) / 256)), dim3(256), 0, stream, S, n, round, sx, scer,
+                     sok, qualified, dec);
 }
 
 void pair_ok(size_t cnt, const uint32_t* crow, const uint8_t* rowok, uint8_t* ok, hipStream_t stream) {

@@ -5324,6 +5324,237 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
   });
 }
 
+// ---- hosted seats: one operator's share checks across many ceremonies (receivers.hip k_seat_horner)
+// Field multiplication of k_seat_horner when dkg_ctx_set_field_mode leaves the choice open: 1 column sums
+// (dkgk_ilp), 0 product scanning (A/B in profiles/seats_time.json).
+#ifndef DKG_SEAT_ILP
+#define DKG_SEAT_ILP 1
+#endif
+
+namespace {
+
+// After a sync: seats.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); a < 0: not run
+void seat_phase(dkg_ctx* ctx, const char* name, int a, int b) {
+  const std::string key = std::string("seats.") + name;
+  ctx->phase_ms.erase(key);
+  if (ctx->nsub != 1 || a < 0) return;
+  float ms = 0;
+  HCK(hipEventElapsedTime(&ms, ctx->rpev[a], ctx->rpev[b]));
+  ctx->phase_ms[key] = ms;
+}
+
+struct SeatEval {
+  dkgh::SeatPlan plan;         // host staging of the descriptors: lives until the caller has synchronised
+  std::vector<uint32_t> rows;  // dealer rows of the distinct ceremonies
+  uint32_t* R = nullptr;       // [S * n][40] point-major
+  uint8_t* sok = nullptr;      // [S][n] dealer i's data decodes for seat p
+  uint32_t* sx = nullptr;      // [S] device: the seats' 1-based indices
+  uint32_t* scer = nullptr;    // [S] device: the seats' ceremonies
+};
+
+// Decode the distinct ceremonies the seats name (C [B * n][N][32]) and evaluate dealer i of seat p's
+// ceremony at js[p] + 1 by dkg_seat_pack's waves.  extra (device [S][n], may be null) is ANDed into sok.
+// Marks rpev[1] (start), [2] (decoded), [3] (evaluated).
+int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer, const uint32_t* js,
+               const uint8_t* C, const uint8_t* extra, SeatEval& ev) {
+  if (B > 0xffffffffu / n) return DKG_E_ARG;  // dealer rows are 32-bit
+  const int rc = dkgh::seat_plan(B, n, S, cer, js, ev.plan);
+  if (rc) return rc;
+  const dkgh::SeatPlan& pl = ev.plan;
+  const size_t N = t + 1, Bd = pl.cers.size(), D = Bd * n, cols = pad64(D);
+  ev.rows.resize(D);
+  for (size_t c = 0; c < Bd; c++)
+    for (size_t i = 0; i < n; i++) ev.rows[c * n + i] = (uint32_t)(pl.cers[c] * n + i);
+  hipStream_t st = ctx->stream;
+  recv_mark(ctx, 1);
+  uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * B * n * N);
+  h2d(ctx, Cc, C, 32 * B * n * N);
+  uint32_t* drows = buf<uint32_t>(ctx, "st_rows", 4 * D);
+  uint32_t* dscol = buf<uint32_t>(ctx, "st_scol", 4 * S);
+  uint32_t* dwdesc = buf<uint32_t>(ctx, "st_wdesc", 4 * pl.wave_desc.size());
+  uint32_t* dwseat = buf<uint32_t>(ctx, "st_wseat", 4 * pl.wave_seat.size());
+  ev.sx = buf<uint32_t>(ctx, "st_sx", 4 * S);
+  ev.scer = buf<uint32_t>(ctx, "st_scer", 4 * S);
+  h2d(ctx, drows, ev.rows.data(), 4 * D);
+  h2d(ctx, dscol, pl.seat_col.data(), 4 * S);
+  h2d(ctx, dwdesc, pl.wave_desc.data(), 4 * pl.wave_desc.size());
+  h2d(ctx, dwseat, pl.wave_seat.data(), 4 * pl.wave_seat.size());
+  h2d(ctx, ev.sx, pl.seat_x.data(), 4 * S);
+  h2d(ctx, ev.scer, cer, 4 * S);
+  // only the ceremonies named are gathered and decoded, as the pair evaluation does with its rows
+  uint32_t* gc = buf<uint32_t>(ctx, "st_rc", 32 * D * N);
+  uint32_t* Cext = buf<uint32_t>(ctx, "Cext", PTB * D * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "pok", D * N);
+  uint8_t* dok = buf<uint8_t>(ctx, "dok", D);
+  uint32_t* Cpm = buf<uint32_t>(ctx, "Cpm", PTB * N * cols);
+  ev.sok = buf<uint8_t>(ctx, "st_sok", S * n);
+  ev.R = buf<uint32_t>(ctx, "rv_R", PTB * S * n);
+  dkgk::gather_rows(D, N, drows, Cc, nullptr, gc, st);
+  dkgk::decode_points(gc, D * N, Cext, D * N, pok, st);
+  dkgk::dealer_ok(D, N, pok, dok, st);
+  dkgk::to_position_major(D, N, cols, Cext, Cpm, st);
+  dkgk::seat_ok(S, n, dscol, dok, extra, ev.sok, st);
+  recv_mark(ctx, 2);
+  const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_SEAT_ILP);
+  (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, Cpm, ev.R, st);
+  check_launch(ctx);
+  recv_mark(ctx, 3);
+  return DKG_OK;
+}
+
+// decisions [S][n] of the evaluated seats against their share columns (device, [S][n][8]); marks rpev[4]
+void seats_check(dkg_ctx* ctx, size_t n, int round, size_t S, const SeatEval& ev, const uint32_t* ds,
+                 const uint32_t* dsp, const uint8_t* qualified, uint8_t* dec) {
+  // pair p * n + i as "dealer" of one receiver, as recv_check; recv_base = n keeps check's self test off
+  dkgk::check(S * n, 1, 0, n, n, round, ds, dsp, ev.R, ctx->tab_gw, ctx->tab_hw, ev.sok, dec, ctx->stream);
+  dkgk::seat_decide(S, n, round, ev.sx, ev.scer, ev.sok, qualified, dec, ctx->stream);
+  check_launch(ctx);
+  recv_mark(ctx, 4);
+}
+
+}  // namespace
+
+int dkg_commitment_eval_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer,
+                              const uint32_t* js, const uint8_t* C, uint8_t* P, uint8_t* ok) {
+  return guarded(ctx, [&] {
+    if (!S) return DKG_OK;
+    if (!B || !n || !cer || !js || !C || !P) return DKG_E_ARG;
+    recv_reset_last(ctx);
+    SeatEval ev;
+    const int rc = seats_eval(ctx, B, n, t, S, cer, js, C, nullptr, ev);
+    if (rc) return rc;
+    uint32_t* Pc = buf<uint32_t>(ctx, "rv_P", 32 * S * n);
+    dkgk::recv_encode(1, S * n, ev.R, ev.sok, Pc, ctx->stream);  // one flag per (seat, dealer)
+    check_launch(ctx);
+    d2h(ctx, P, Pc, 32 * S * n);
+    if (ok) d2h(ctx, ok, ev.sok, S * n);
+    sync(ctx);
+    seat_phase(ctx, "decrypt", -1, 0);
+    seat_phase(ctx, "decode", 1, 2);
+    seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "check", -1, 0);
+    seat_phase(ctx, "prove", -1, 0);
+    return DKG_OK;
+  });
+}
+
+int dkg_verify_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, int round, size_t S, const uint32_t* cer,
+                     const uint32_t* js, const uint8_t* C, const uint8_t* s, const uint8_t* s_prime,
+                     const uint8_t* qualified, uint8_t* decision) {
+  return guarded(ctx, [&] {
+    if (round != 2 && round != 4) return DKG_E_ARG;
+    if (!S) return DKG_OK;
+    if (!B || !n || !cer || !js || !C || !s || !decision) return DKG_E_ARG;
+    if (round == 2) {
+      int rc = need_env(ctx);
+      if (rc) return rc;
+      if (!s_prime) return DKG_E_ARG;
+    }
+    recv_reset_last(ctx);
+    SeatEval ev;
+    const int rc = seats_eval(ctx, B, n, t, S, cer, js, C, nullptr, ev);
+    if (rc) return rc;
+    uint32_t* ds = upload_scalars(ctx, "vr_s", s, S * n);
+    uint32_t* dsp = round == 2 ? upload_scalars(ctx, "vr_sp", s_prime, S * n) : nullptr;
+    const uint8_t* dq = round == 4 ? upload_mask(ctx, "rv_q", qualified, B * n) : nullptr;
+    uint8_t* dec = buf<uint8_t>(ctx, "vr_dec", S * n);
+    seats_check(ctx, n, round, S, ev, ds, dsp, dq, dec);
+    d2h(ctx, decision, dec, S * n);
+    sync(ctx);
+    seat_phase(ctx, "decrypt", -1, 0);
+    seat_phase(ctx, "decode", 1, 2);
+    seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "check", 3, 4);
+    seat_phase(ctx, "prove", -1, 0);
+    return DKG_OK;
+  });
+}
+
+int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer,
+                           const uint32_t* js, const uint8_t* E, const uint8_t* e1, const uint8_t* ct,
+                           const uint8_t* sk, const uint8_t* w, uint8_t* s_out, uint8_t* sp_out, uint8_t* dec,
+                           int32_t* complaints, uint8_t* r2_error, uint8_t* proofs) {
+  return guarded(ctx, [&] {
+    if (!S) return DKG_OK;
+    const int rc0 = ceremony_args(ctx, n, t, {E, e1, ct, sk, dec, cer, js});
+    if (rc0) return rc0;
+    if (!B || (w && !proofs)) return DKG_E_ARG;
+    for (size_t p = 0; p < S; p++)
+      if (cer[p] >= B || js[p] >= n) return DKG_E_ARG;  // before any launch
+    recv_reset_last(ctx);
+    hipStream_t st = ctx->stream;
+    // committee.rs:282-286 for every seat: the n pairs addressed to seat p, decrypted with sk_p -- one wave
+    // per (seat key, w, 64 dealers), the scalar wave-uniform (k_bdec_mul_w4's chain, seat-addressed)
+    recv_mark(ctx, 0);
+    const size_t items = 2 * S * n;
+    uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, S);
+    uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 32 * items);
+    uint32_t* dct = buf<uint32_t>(ctx, "pr_ct", 32 * items);
+    h2d(ctx, de1, e1, 32 * items);
+    h2d(ctx, dct, ct, 32 * items);
+    uint32_t* ds = buf<uint32_t>(ctx, "pr_s", 32 * S * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "pr_sp", 32 * S * n);
+    uint8_t* iok = buf<uint8_t>(ctx, "pr_iok", items);
+    uint8_t* eok = buf<uint8_t>(ctx, "pr_eok", S * n);
+    uint32_t* R = buf<uint32_t>(ctx, "hy.R", PTB * items);
+    uint32_t* K = buf<uint32_t>(ctx, "hy.K", PTB * items);
+    uint32_t* Kc = buf<uint32_t>(ctx, "hy.Kc", 32 * items);
+    uint32_t* T = buf<uint32_t>(ctx, "bf.dec_tab", 4 * dkgk::bdec_mul_table_words(S, n));
+    dkgk::decode_points(de1, items, R, items, iok, st);
+    dkgk::seat_dec_mul(S, n, dsk, R, K, items, T, st);
+    dkgk::encode_points(K, items, items, Kc, st);
+    dkgk::sym_xor(S, n, Kc, true, dct, ds, dsp, st);
+    dkgk::dealer_ok(S * n, 2, iok, eok, st);  // an e1 that does not decode is missing data (:331-335)
+    check_launch(ctx);
+    SeatEval ev;
+    const int rc = seats_eval(ctx, B, n, t, S, cer, js, E, eok, ev);  // :287-296
+    if (rc) return rc;
+    uint8_t* ddec = buf<uint8_t>(ctx, "vr_dec", S * n);
+    seats_check(ctx, n, 2, S, ev, ds, dsp, nullptr, ddec);
+    d2h(ctx, dec, ddec, S * n);
+    if (s_out) d2h(ctx, s_out, ds, 32 * S * n);
+    if (sp_out) d2h(ctx, sp_out, dsp, 32 * S * n);
+    sync(ctx);
+    seat_phase(ctx, "decrypt", 0, 1);
+    seat_phase(ctx, "decode", 1, 2);
+    seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "check", 3, 4);
+    seat_phase(ctx, "prove", -1, 0);
+    std::vector<size_t> rej;  // (seat, dealer) pairs p * n + i
+    for (size_t p = 0; p < S; p++) {
+      size_t cnt = 0;
+      for (size_t i = 0; i < n; i++)
+        if (dec[p * n + i] == DKG_REJECT) rej.push_back(p * n + i), cnt++;
+      if (complaints) complaints[p] = (int32_t)cnt;
+      if (r2_error) r2_error[p] = cnt > t ? 1 : 0;  // :340-347
+    }
+    if (w) {
+      memset(proofs, 0, 192 * S * n);
+      if (!rej.empty()) {  // ProofOfMisbehaviour::generate per rejected dealer (:309-322), all seats in one run
+        const size_t Cn = rej.size();
+        std::vector<uint8_t> ksk(32 * Cn), kenc(128 * Cn), kw(64 * Cn), kp(192 * Cn);
+        for (size_t c = 0; c < Cn; c++) {
+          const size_t e = rej[c];
+          memcpy(&ksk[32 * c], sk + 32 * (e / n), 32);
+          memcpy(&kenc[128 * c], e1 + 64 * e, 32);             // e1 of the randomness
+          memcpy(&kenc[128 * c + 32], ct + 64 * e, 32);
+          memcpy(&kenc[128 * c + 64], e1 + 64 * e + 32, 32);   // e1 of the share
+          memcpy(&kenc[128 * c + 96], ct + 64 * e + 32, 32);
+          memcpy(&kw[64 * c], w + 64 * e, 64);
+        }
+        recv_mark(ctx, 5);
+        const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
+        if (rp) return rp;
+        recv_mark(ctx, 6);
+        sync(ctx);
+        seat_phase(ctx, "prove", 5, 6);
+        for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
+      }
+    }
+    return DKG_OK;
+  });
+}
+
 int dkg_complaints_verify(dkg_ctx* ctx, size_t n, size_t t, size_t C, const uint32_t* accuser, const uint32_t* accused,
                           const uint8_t* pk, const uint8_t* E, const uint8_t* fetched1, const uint8_t* enc,
                           const uint8_t* proofs, int32_t* verdict, uint8_t* qualified) {

@@ -314,6 +314,52 @@ int dkg_party_round2(dkg_ctx *ctx, size_t n, size_t t, size_t j, const uint8_t *
                      const uint8_t sk[32], const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
                      int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
 
+/* ---- hosted seats: one operator's share checks across many ceremonies (receivers.hip k_seat_horner,
+ * DESIGN.md section 4) ----
+ * A seat is (ceremony c, party j): an operator that holds one party index in each of many ceremonies of
+ * one (n, t) runs Phases<Phase1>::proceed and Phases<Phase3>::proceed (committee.rs:260-366, 508-580) for
+ * its own index in each.  Every polynomial of a seat is evaluated at x = j + 1, so seats of equal x share
+ * a wave with a wave-uniform multiplier.  dkg_seat_pack is that placement, a pure host function that the
+ * calls below execute as returned: seats are grouped by x ascending, keep caller order inside a group and
+ * fill waves of per_wave slots (a group's last wave may be partly filled; a wave never holds two x); a
+ * seat with n > 64 takes `tiles` consecutive waves of 64 dealers.  width W = 64 for n >= 64, else the
+ * power of two >= n; per_wave = 64 / W; tiles = ceil(n / 64); wave_of [S] the first wave of seat p,
+ * slot_of [S] its slot (< per_wave), *waves the total.  Lane slot * W + i of wave wave_of[p] + tile is
+ * dealer tile * 64 + i of seat p, live where that is < n.  DKG_E_ARG for n == 0, js[p] >= n, a NULL js or
+ * output with S > 0, or more than 2^32 - 1 waves; S == 0: DKG_OK, *waves = 0 (width, per_wave and tiles
+ * are written whenever they are given). */
+int dkg_seat_pack(size_t n, size_t S, const uint32_t *js, uint32_t *width, uint32_t *per_wave, uint32_t *tiles,
+                  uint32_t *wave_of, uint32_t *slot_of, uint32_t *waves);
+/* The three calls share: B ceremonies of (n, t); seat p is party js[p] < n of ceremony cer[p] < B
+ * (DKG_E_ARG otherwise), any order, several seats per ceremony and repeats allowed; C (E, A) is
+ * [B * n][t+1][32] as in the batch calls, row c * n + i dealer i of ceremony c.  Only the DISTINCT
+ * ceremonies named are decoded; rows of other ceremonies are never interpreted.  S == 0 returns DKG_OK and
+ * touches nothing.  dkg_ctx_set_field_mode selects the kernel copy.  Phase times (dkg_ctx_phase_ms, one
+ * stream): "seats.decrypt", "seats.decode" (upload, gather, decode, transposition), "seats.eval",
+ * "seats.check", "seats.prove"; a phase the call did not run reads -1.
+ *
+ * dkg_commitment_eval with M = 1 per seat (committee.rs:287-296, 532-539): P[p][i] = sum_k (js[p]+1)^k
+ * C_{cer[p], i}[k], compressed, [S][n][32]; ok [S][n] (may be NULL) = 0 and P = 32 zero bytes where the
+ * row does not decode.  Needs no dkg_env_init. */
+int dkg_commitment_eval_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t *cer,
+                              const uint32_t *js, const uint8_t *C, uint8_t *P, uint8_t *ok);
+/* dkg_verify_receivers with M = 1 per seat (committee.rs:273-338, 520-559): s, s_prime [S][n][32] = the
+ * shares addressed to seat p; decision [S][n]; qualified (round 4 only, may be NULL) [B][n], 0 marks
+ * DKG_SKIPPED for the seats of that ceremony (:522).  Undecodable row: MISSING (round 2) / REJECT
+ * (round 4), then SKIPPED, then SELF.  Round 2 requires dkg_env_init. */
+int dkg_verify_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, int round, size_t S, const uint32_t *cer,
+                     const uint32_t *js, const uint8_t *C, const uint8_t *s, const uint8_t *s_prime,
+                     const uint8_t *qualified, uint8_t *decision);
+/* dkg_party_round2 per seat (Phases<Phase1>::proceed in full mode, committee.rs:260-366): e1, ct
+ * [S][n][2][32] = the pairs addressed to seat p, sk [S][32] its keys, w [S][n][64] or NULL; s_out, sp_out
+ * [S][n][32], complaints [S], r2_error [S] (may be NULL); dec [S][n]; proofs [S][n][192] (required with
+ * w, untouched rows zero).  One decryption launch set for all seats; the REJECTs of all seats are proven
+ * in one run.  Requires dkg_env_init and dkg_env_check(t, n). */
+int dkg_party_round2_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t *cer,
+                           const uint32_t *js, const uint8_t *E, const uint8_t *e1, const uint8_t *ct,
+                           const uint8_t *sk, const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
+                           int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
+
 /* ---- whole ceremony (rounds 1-5, every party played in one process as the reference tests do,
  * committee.rs:1518-1656) in plaintext-share mode. ---- */
 typedef struct {
