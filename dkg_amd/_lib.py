@@ -164,6 +164,13 @@ def lib():
         L.dkg_commitment_eval_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, p, p]
         L.dkg_verify_seats.argtypes = [p, sz, sz, sz, ctypes.c_int, sz, p, p, u8p, u8p, p, p, p]
         L.dkg_party_round2_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
+    if hasattr(L, "dkg_finalise_seats"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_complaints_verify_ceremonies.argtypes = [p, sz, sz, sz, sz, p, p, p, u8p, u8p, u8p, u8p, u8p, p, p]
+        L.dkg_complaints3_verify_ceremonies.argtypes = [p, sz, sz, sz, sz, p, p, p, u8p, u8p, u8p, u8p, u8p, u8p, p, p]
+        L.dkg_party_round3_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, p, p]
+        L.dkg_finalise_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, p, u8p,
+                                         p, p, p]
+        L.dkg_seat_finalise_status.argtypes = [sz, sz, sz, u8p, u8p, u8p, p, ctypes.c_int, ctypes.c_int, p]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -311,4 +318,6 @@ EXPORTED = [
     "dkg_ctx_set_comb_build", "dkg_ctx_last_comb_build", "dkg_ctx_last_comb_build_ms", "dkg_comb_geometry", "dkg_comb_entries",
     "dkg_ctx_last_receiver_chunk", "dkg_pair_eval_shape", "dkg_commitment_eval_pairs", "dkg_commitment_eval", "dkg_verify_receivers", "dkg_party_round2",
     "dkg_seat_pack", "dkg_commitment_eval_seats", "dkg_verify_seats", "dkg_party_round2_seats",
+    "dkg_complaints_verify_ceremonies", "dkg_complaints3_verify_ceremonies", "dkg_party_round3_seats", "dkg_finalise_seats",
+    "dkg_seat_finalise_status",
 ]

@@ -269,14 +269,14 @@ class Backend:
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
         encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
         commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs), "seats" (the last
-        commitment_eval_seats, verify_seats, party_round2_seats).  Only recorded with set_streams(1); -1 otherwise."""
+        commitment_eval_seats, verify_seats, party_round2_seats; lagrange / mpk: the last finalise_seats).  Only recorded with set_streams(1); -1 otherwise."""
         L = _lib.lib()
         if isinstance(tag, int):
             tag = f"r{tag}"
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("decode", "eval") if tag == "pairs"
-                 else ("decrypt", "decode", "eval", "check", "prove") if tag == "seats"
+                 else ("decrypt", "decode", "eval", "check", "prove", "lagrange", "mpk") if tag == "seats"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
         return {k: L.dkg_ctx_phase_ms(self._ctx, f"{tag}.{k}".encode()) for k in names}
@@ -448,6 +448,79 @@ class Backend:
         return {"s": s.raw[: 32 * S * n], "s_prime": sp.raw[: 32 * S * n], "dec": dec.raw[: S * n],
                 "complaints": list(cnt[:S]), "r2_error": list(err.raw[:S]),
                 "proofs": prf.raw[: 192 * S * n] if prf is not None else None}
+
+    # ---- hosted seats through rounds 3-5 (k_seat_lagrange; the batch's complaint kernels)
+    def complaints_verify_ceremonies(self, B: int, n: int, t: int, ceremony: Sequence[int], accusers: Sequence[int],
+                                     accused: Sequence[int], pk: bytes, E: bytes, enc: bytes, proofs: bytes,
+                                     fetched1: Optional[bytes] = None, want_qualified: bool = True):
+        """complaints_verify for the complaints of B ceremonies in one call: (verdicts [C], qualified [B*n] or
+        None).  ceremony 0-based, accusers / accused 1-based; pk [B][n][32], E [B*n][t+1][32], enc [C][128]."""
+        C = len(ceremony)
+        if len(accusers) != C or len(accused) != C:
+            raise ValueError("ceremony, accusers and accused differ in length")
+        res = _carray(ctypes.c_int32, C)
+        q = ctypes.create_string_buffer(max(B * n, 1)) if want_qualified else None
+        _check(self._ctx, _lib.lib().dkg_complaints_verify_ceremonies(
+            self._ctx, B, n, t, C, _carray(ctypes.c_uint32, C, ceremony), _carray(ctypes.c_uint32, C, accusers),
+            _carray(ctypes.c_uint32, C, accused), pk, E, None if fetched1 is None else bytes(fetched1), enc, proofs,
+            res, q))
+        return list(res)[:C], (list(q.raw[:B * n]) if q is not None else None)
+
+    def complaints3_verify_ceremonies(self, B: int, n: int, t: int, ceremony: Sequence[int], accusers: Sequence[int],
+                                      accused: Sequence[int], share: bytes, randomness: bytes, E: bytes, A: bytes,
+                                      qualified: Optional[bytes] = None, fetched3: Optional[bytes] = None):
+        """complaints3_verify for the round-4 complaints of B ceremonies in one call: (verdicts [C],
+        reconstruct [B*n]).  qualified / fetched3 [B*n] (None = all 1)."""
+        C = len(ceremony)
+        if len(accusers) != C or len(accused) != C:
+            raise ValueError("ceremony, accusers and accused differ in length")
+        res = _carray(ctypes.c_int32, C)
+        rec = ctypes.create_string_buffer(max(B * n, 1))
+        _check(self._ctx, _lib.lib().dkg_complaints3_verify_ceremonies(
+            self._ctx, B, n, t, C, _carray(ctypes.c_uint32, C, ceremony), _carray(ctypes.c_uint32, C, accusers),
+            _carray(ctypes.c_uint32, C, accused), share, randomness, E, A,
+            None if qualified is None else bytes(qualified), None if fetched3 is None else bytes(fetched3), res, rec))
+        return list(res)[:C], list(rec.raw[:B * n])
+
+    def party_round3_seats(self, B: int, n: int, t: int, cer: Sequence[int], js: Sequence[int], qualified: bytes,
+                           s_cols: bytes, public: bool = True):
+        """Phases<Phase2>::proceed per seat: (final_share, public_share), [S][32] each (public_share None
+        without `public`); qualified [B][n], s_cols [S][n][32]."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        fs = ctypes.create_string_buffer(max(32 * S, 1))
+        ps = ctypes.create_string_buffer(max(32 * S, 1)) if public else None
+        _check(self._ctx, _lib.lib().dkg_party_round3_seats(self._ctx, B, n, t, S, ca, ja, bytes(qualified), s_cols,
+                                                             fs, ps))
+        return fs.raw[: 32 * S], (ps.raw[: 32 * S] if ps is not None else None)
+
+    def finalise_seats(self, B: int, n: int, t: int, cer: Sequence[int], js: Sequence[int], qualified: bytes,
+                       reconstruct: bytes, A0: bytes, s_cols: bytes, disclosures=(), fetched3: Optional[bytes] = None,
+                       r2_error=None, r4_error=None) -> "PartyFinalise":
+        """Phases<Phase5>::finalise per seat (dkg_finalise_seats).  qualified, reconstruct [B][n]; A0 [B*n][32];
+        s_cols [S][n][32] the seats' own columns; disclosures: (ceremony, sender, dealer, share) with sender /
+        dealer 1-based, or a 4-tuple (ceremonies, senders, dealers, share bytes) of flat arrays; r2_error /
+        r4_error [S] the seats' own.  PartyFinalise with one entry per seat."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        if isinstance(disclosures, tuple) and len(disclosures) == 4 and isinstance(disclosures[3], (bytes, bytearray)):
+            dc, dsnd, dd, dsh = disclosures
+            dsh = bytes(dsh)
+        else:
+            disclosures = list(disclosures)
+            dc, dsnd, dd = ([d[k] for d in disclosures] for k in range(3))
+            dsh = b"".join(d[3] for d in disclosures)
+        D5 = len(dc)
+        if len(dsnd) != D5 or len(dd) != D5 or len(dsh) != 32 * D5:
+            raise ValueError("the disclosure arrays differ in length")
+        mask = lambda x: None if x is None else bytes(bytearray(x))  # noqa: E731
+        mpk = ctypes.create_string_buffer(32 * max(S, 1))
+        st = _carray(ctypes.c_int32, S)
+        ri = _carray(ctypes.c_int32, S)
+        arr = lambda v: _carray(ctypes.c_uint32, D5, v) if D5 else None  # noqa: E731
+        _check(self._ctx, _lib.lib().dkg_finalise_seats(
+            self._ctx, B, n, t, S, ca, ja, mask(qualified), mask(reconstruct), mask(fetched3), mask(r2_error),
+            mask(r4_error), A0, s_cols, D5, arr(dc), arr(dsnd), arr(dd), dsh if D5 else None, mpk, st, ri))
+        m = mpk.raw
+        return PartyFinalise([m[32 * p:32 * p + 32] for p in range(S)], list(st)[:S], list(ri)[:S])
 
     # ---- whole ceremony
     def _ceremony_out(self, n, t, big):
@@ -1160,6 +1233,38 @@ def seat_pack(n: int, js: Sequence[int]) -> dict:
         raise _lib.DkgError(rc, "seat_pack")
     return {"width": v[0].value, "per_wave": v[1].value, "tiles": v[2].value, "wave_of": list(wave_of[:S]),
             "slot_of": list(slot_of[:S]), "waves": v[3].value}
+
+
+def seat_finalise_status(n: int, t: int, p: int, qualified, reconstruct, points: Sequence[int], a_present=None,
+                         r2_error: bool = False, r4_error: bool = False):
+    """dkg_seat_finalise_status (host only): (status, recovery_index) of seat p (0-based) from what it holds:
+    qualified, reconstruct [n]; points[i] = the points held for dealer i (its own included); a_present [n]
+    (None = all): dealer i's A_i0 was fetched and decodes.  The rule finalise_seats executes per seat."""
+    mask = lambda x: None if x is None else bytes(bytearray(x))  # noqa: E731
+    idx = ctypes.c_int32(-1)
+    rc = _lib.lib().dkg_seat_finalise_status(n, t, p, mask(qualified), mask(reconstruct), mask(a_present),
+                                             (ctypes.c_uint32 * max(n, 1))(*points), int(bool(r2_error)),
+                                             int(bool(r4_error)), ctypes.byref(idx))
+    if rc < 0:
+        raise _lib.DkgError(rc, "seat_finalise_status")
+    return rc, idx.value
+
+
+def seat_disclosures(qualified, reconstruct, s_col: bytes, t: Optional[int] = None):
+    """What Phases<Phase4>::proceed (committee.rs:625-688) leaves a seat to broadcast (host only): (shares,
+    phase4_error).  shares[i] = the seat's share of dealer i (32 bytes of s_col [n][32]) for the reconstructed
+    dealers and None for the others -- BroadcastPhase5's Vec<Option<share>> -- or None as a whole with
+    phase4_error, when the party broadcasts nothing (:673-677).  phase4_error needs the threshold t; without
+    it it reads None and the shares are returned unconditionally."""
+    n = len(qualified)
+    if len(reconstruct) != n or len(s_col) != 32 * n:
+        raise ValueError("qualified, reconstruct and s_col differ in length")
+    if any(r and not q for q, r in zip(qualified, reconstruct)):
+        raise ValueError("only qualified members are reconstructed (committee.rs:639)")
+    err = None if t is None else sum(map(bool, qualified)) - sum(map(bool, reconstruct)) <= t
+    if err:
+        return None, True
+    return [s_col[32 * i:32 * i + 32] if reconstruct[i] else None for i in range(n)], err
 
 
 def receiver_plan_constants() -> dict:

@@ -14,6 +14,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/dkg_amd.h"
@@ -21,6 +22,7 @@
 #include "kernels.h"
 #include "kernels_ilp.h"
 #include "comb_build.h"
+#include "seat_finalise.h"
 
 struct dkg_ctx {
   int device = 0;
@@ -2618,6 +2620,64 @@ struct BatchDevice {
   const uint8_t *fetched1 = nullptr, *fetched3 = nullptr;
 };
 
+// The two complaint stages on GATHERED rows, shared by a batch (batch_complaints gathers on the device from
+// its own uploads) and by the hosted operator's calls (complaints_ceremonies gathers on the host): queued
+// on ctx->stream, no synchronisation, a launch count that depends on nothing.  Always the per-complaint
+// Horner walk (k_cmp_horner).  Device index arrays [C] as ComplaintIndex names them, seq = 0, 1, 2, ..
+// Round 4 (k_c3_*): rc [2 R][N][8] the accused dealers' E rows, then their A rows; share / randomness
+// host [C][32]; qualified / fetched3 (device, may be null) by dealer row drow; dver [C] out.
+void complaints4_rows(dkg_ctx* ctx, size_t n, size_t t, size_t C4, size_t R4, const uint32_t* rc, const uint32_t* x4,
+                      const uint32_t* crow4, const uint32_t* drow4, const uint32_t* seq, const uint8_t* share,
+                      const uint8_t* randomness, const uint8_t* qualified, const uint8_t* fetched3, int32_t* dver4) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  int nb = 1;
+  while ((n >> nb) != 0) nb++;
+  uint32_t* rext = buf<uint32_t>(ctx, "bp.rows4_ext", PTB * 2 * R4 * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "bp.rows4_pok", 2 * R4 * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows4_ok", 2 * R4);
+  dkgk::decode_points(rc, 2 * R4 * N, rext, 2 * R4 * N, pok, st);
+  dkgk::dealer_ok(2 * R4, N, pok, rowok, st);
+  uint32_t* dsh = buf<uint32_t>(ctx, "bp.share", 32 * C4);
+  uint32_t* drn = buf<uint32_t>(ctx, "bp.rand", 32 * C4);
+  h2d(ctx, dsh, share, 32 * C4);
+  h2d(ctx, drn, randomness, 32 * C4);
+  uint32_t* sr = buf<uint32_t>(ctx, "bp.sr", 32 * 2 * C4);
+  uint32_t* acc2 = buf<uint32_t>(ctx, "bp.acc2", 4 * 2 * C4);
+  uint32_t* acd2 = buf<uint32_t>(ctx, "bp.acd2", 4 * 2 * C4);
+  dkgk::c3_prep(C4, R4, x4, crow4, dsh, drn, sr, acc2, acd2, st);
+  uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh4", PTB * 2 * C4);
+  dkgk::cmp_horner(2 * C4, seq, acc2, acd2, rext, 2 * R4 * N, N, nb, Rh, st);
+  uint8_t* eq = buf<uint8_t>(ctx, "bp.eq4", 2 * C4);
+  dkgk::c3_check(C4, x4, sr, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
+  dkgk::c3_final(C4, R4, crow4, drow4, rowok, qualified, fetched3, eq, dver4, st);
+}
+// Round 2 (k_cv_*): rc [R][N][8] the accused dealers' E rows; dpk the stacked member keys, party2 the
+// accusers' 1-based rows of it; denc [C][128] (device) the pairs the accused sent; proofs host [C][192];
+// fetched (device, may be null) [R] by the commitment row's place; dver [C] out.
+void complaints2_rows(dkg_ctx* ctx, size_t n, size_t t, size_t C2, size_t R2, const uint32_t* rc, const uint32_t* x2,
+                      const uint32_t* party2, const uint32_t* crow2, const uint32_t* seq, const uint32_t* dpk,
+                      const uint32_t* denc, const uint8_t* proofs, const uint8_t* fetched, int32_t* dver2) {
+  const size_t N = t + 1;
+  hipStream_t st = ctx->stream;
+  int nb = 1;
+  while ((n >> nb) != 0) nb++;
+  uint32_t* rext = buf<uint32_t>(ctx, "bp.rows2_ext", PTB * R2 * N);
+  uint8_t* pok = buf<uint8_t>(ctx, "bp.rows2_pok", R2 * N);
+  uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows2_ok", R2);
+  dkgk::decode_points(rc, R2 * N, rext, R2 * N, pok, st);
+  dkgk::dealer_ok(R2, N, pok, rowok, st);
+  uint32_t* dprf = buf<uint32_t>(ctx, "bp.proofs", 192 * C2);
+  h2d(ctx, dprf, proofs, 192 * C2);
+  // the party rows stand where one ceremony has the accusers, the commitment rows where it has the accused
+  const Announcements an = complaint_announcements(ctx, C2, party2, dpk, denc, dprf, st);
+  uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh2", PTB * C2);
+  dkgk::cmp_horner(C2, seq, x2, crow2, rext, R2 * N, N, nb, Rh, st);
+  uint8_t* eq = buf<uint8_t>(ctx, "bp.eq2", 2 * C2);
+  dkgk::cv_check(C2, x2, an.p12, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
+  dkgk::cv_final(C2, party2, crow2, dpk, denc, dprf, an.a1c, an.a2c, an.ppok, rowok, fetched, eq, dver2, st);
+}
+
 // Both complaint stages of a batch, queued on ctx->stream after the batch's uploads and before its
 // rounds; no host synchronisation, host work O(C), a launch count that does not depend on B and no
 // copy per row, ceremony or complaint.  Round 4 first, as verify_ceremony.  c2 comes with full mode
@@ -2628,8 +2688,6 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
                       const BatchComplaints4& c4, BatchProven& bp) {
   const size_t N = t + 1, V = B * n, C2 = c2 ? c2->C : 0, C4 = c4.C;
   hipStream_t st = ctx->stream;
-  int nb = 1;
-  while ((n >> nb) != 0) nb++;
   const ComplaintIndex i4 = complaint_index(n, C4, c4.ceremony, c4.accuser, c4.accused);
   const ComplaintIndex i2 = c2 ? complaint_index(n, C2, c2->ceremony, c2->accuser, c2->accused) : ComplaintIndex{};
   const size_t R4 = i4.rows.size(), R2 = i2.rows.size(), iota = std::max(2 * C4, C2);
@@ -2663,26 +2721,10 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
   HCK(hipMemsetAsync(proven4, 0, V, st));
   if (C4) {
     uint32_t* rc = buf<uint32_t>(ctx, "bp.rows4", 32 * 2 * R4 * N);
-    uint32_t* rext = buf<uint32_t>(ctx, "bp.rows4_ext", PTB * 2 * R4 * N);
-    uint8_t* pok = buf<uint8_t>(ctx, "bp.rows4_pok", 2 * R4 * N);
-    uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows4_ok", 2 * R4);
     dkgk::gather_rows(R4, N, rows4, dev.E, dev.A, rc, st);
-    dkgk::decode_points(rc, 2 * R4 * N, rext, 2 * R4 * N, pok, st);
-    dkgk::dealer_ok(2 * R4, N, pok, rowok, st);
-    uint32_t* dsh = buf<uint32_t>(ctx, "bp.share", 32 * C4);
-    uint32_t* drn = buf<uint32_t>(ctx, "bp.rand", 32 * C4);
-    h2d(ctx, dsh, c4.share, 32 * C4);
-    h2d(ctx, drn, c4.randomness, 32 * C4);
-    uint32_t* sr = buf<uint32_t>(ctx, "bp.sr", 32 * 2 * C4);
-    uint32_t* acc2 = buf<uint32_t>(ctx, "bp.acc2", 4 * 2 * C4);
-    uint32_t* acd2 = buf<uint32_t>(ctx, "bp.acd2", 4 * 2 * C4);
-    dkgk::c3_prep(C4, R4, x4, crow4, dsh, drn, sr, acc2, acd2, st);
-    uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh4", PTB * 2 * C4);
-    dkgk::cmp_horner(2 * C4, seq, acc2, acd2, rext, 2 * R4 * N, N, nb, Rh, st);
-    uint8_t* eq = buf<uint8_t>(ctx, "bp.eq4", 2 * C4);
-    dkgk::c3_check(C4, x4, sr, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
     // the qualified set is applied on the host (IGNORED, batch_proven_outcome), as verify_ceremony does
-    dkgk::c3_final(C4, R4, crow4, drow4, rowok, nullptr, dev.fetched3, eq, dver4, st);
+    complaints4_rows(ctx, n, t, C4, R4, rc, x4, crow4, drow4, seq, c4.share, c4.randomness, nullptr, dev.fetched3,
+                     dver4);
   }
   HCK(hipEventRecord(ctx->bpev[1], st));
   // ---- round 2 (k_cv_*): the E rows of the accused dealers, the ciphertext pairs from the batch's own
@@ -2697,25 +2739,12 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
   }
   if (C2) {
     uint32_t* rc = buf<uint32_t>(ctx, "bp.rows2", 32 * R2 * N);
-    uint32_t* rext = buf<uint32_t>(ctx, "bp.rows2_ext", PTB * R2 * N);
-    uint8_t* pok = buf<uint8_t>(ctx, "bp.rows2_pok", R2 * N);
-    uint8_t* rowok = buf<uint8_t>(ctx, "bp.rows2_ok", R2);
     dkgk::gather_rows(R2, N, rows2, dev.E, nullptr, rc, st);
-    dkgk::decode_points(rc, R2 * N, rext, R2 * N, pok, st);
-    dkgk::dealer_ok(R2, N, pok, rowok, st);
     uint32_t* dpk = buf<uint32_t>(ctx, "bp.pk", 32 * V);
-    uint32_t* dprf = buf<uint32_t>(ctx, "bp.proofs", 192 * C2);
     uint32_t* denc = buf<uint32_t>(ctx, "bp.enc", 128 * C2);
     h2d(ctx, dpk, c2->pk, 32 * V);
-    h2d(ctx, dprf, c2->proofs, 192 * C2);
     dkgk::gather_enc(C2, n, drow2, x2, dev.e1, dev.ct, denc, st);
-    // the party rows stand where one ceremony has the accusers, the commitment rows where it has the accused
-    const Announcements an = complaint_announcements(ctx, C2, party2, dpk, denc, dprf, st);
-    uint32_t* Rh = buf<uint32_t>(ctx, "bp.Rh2", PTB * C2);
-    dkgk::cmp_horner(C2, seq, x2, crow2, rext, R2 * N, N, nb, Rh, st);
-    uint8_t* eq = buf<uint8_t>(ctx, "bp.eq2", 2 * C2);
-    dkgk::cv_check(C2, x2, an.p12, seq, Rh, nullptr, nullptr, ctx->tab_gw, ctx->tab_hw, eq, st);
-    dkgk::cv_final(C2, party2, crow2, dpk, denc, dprf, an.a1c, an.a2c, an.ppok, rowok, nullptr, eq, dver2, st);
+    complaints2_rows(ctx, n, t, C2, R2, rc, x2, party2, crow2, seq, dpk, denc, c2->proofs, nullptr, dver2);
   }
   // ---- the verdicts as the rounds' masks
   dkgk::proven_masks(C2, n, drow2, x2, dver2, C4, drow4, dver4, cmask, pair, proven4, st);
@@ -5550,6 +5579,340 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
         seat_phase(ctx, "prove", 5, 6);
         for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
       }
+    }
+    return DKG_OK;
+  });
+}
+
+// ---- hosted seats through rounds 3-5 (seat_finalise.hip)
+namespace {
+
+// The index arrays of one *_ceremonies call in one upload: x | party | crow | drow | 0, 1, 2, ..
+struct CeremonyComplaintIndex {
+  ComplaintIndex ix;
+  std::vector<uint32_t> host;
+  const uint32_t *x = nullptr, *party = nullptr, *crow = nullptr, *drow = nullptr, *seq = nullptr;
+};
+void upload_complaint_index(dkg_ctx* ctx, size_t n, size_t C, size_t items, const uint32_t* ceremony,
+                            const uint32_t* accuser, const uint32_t* accused, CeremonyComplaintIndex& ci) {
+  ci.ix = complaint_index(n, C, ceremony, accuser, accused);
+  ci.host.resize(4 * C + items * C);
+  memcpy(&ci.host[0], accuser, 4 * C);
+  memcpy(&ci.host[C], ci.ix.party.data(), 4 * C);
+  memcpy(&ci.host[2 * C], ci.ix.crow.data(), 4 * C);
+  memcpy(&ci.host[3 * C], ci.ix.drow.data(), 4 * C);
+  for (size_t k = 0; k < items * C; k++) ci.host[4 * C + k] = (uint32_t)k;
+  uint32_t* d = buf<uint32_t>(ctx, "sc.idx", 4 * ci.host.size());
+  h2d(ctx, d, ci.host.data(), 4 * ci.host.size());
+  ci.x = d, ci.party = d + C, ci.crow = d + 2 * C, ci.drow = d + 3 * C, ci.seq = d + 4 * C;
+}
+
+// rows `rows` (0-based dealer rows) of src [..][N][32] behind one another into out
+void gather_rows_host(const std::vector<uint32_t>& rows, size_t N, const uint8_t* src, uint8_t* out) {
+  for (size_t r = 0; r < rows.size(); r++) memcpy(out + 32 * N * r, src + 32 * N * (size_t)rows[r], 32 * N);
+}
+
+}  // namespace
+
+int dkg_complaints_verify_ceremonies(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t C, const uint32_t* ceremony,
+                                     const uint32_t* accuser, const uint32_t* accused, const uint8_t* pk,
+                                     const uint8_t* E, const uint8_t* fetched1, const uint8_t* enc,
+                                     const uint8_t* proofs, int32_t* verdict, uint8_t* qualified) {
+  return guarded(ctx, [&] {
+    if (!B) return DKG_OK;
+    const int rc0 = ceremony_args(ctx, n, t, {pk, E});
+    if (rc0) return rc0;
+    if (B > 0xffffffffu / n) return DKG_E_ARG;  // dealer rows are 32-bit
+    if (!batch_complaint_args_ok(B, n, C, ceremony, accuser, accused, {enc, proofs, verdict})) return DKG_E_ARG;
+    const size_t N = t + 1, V = B * n;
+    hipStream_t st = ctx->stream;
+    CeremonyComplaintIndex ci;  // the staging vectors live until the sync
+    std::vector<uint8_t> hrows, hfet;
+    int32_t* dver = nullptr;
+    if (C) {
+      upload_complaint_index(ctx, n, C, 1, ceremony, accuser, accused, ci);
+      const size_t R = ci.ix.rows.size();
+      hrows.resize(32 * R * N);
+      gather_rows_host(ci.ix.rows, N, E, hrows.data());
+      uint32_t* rc = buf<uint32_t>(ctx, "bp.rows2", 32 * R * N);
+      h2d(ctx, rc, hrows.data(), 32 * R * N);
+      const uint8_t* dfet = nullptr;
+      if (fetched1) {  // by the commitment row's place, as k_cv_final reads it
+        hfet.resize(R);
+        for (size_t r = 0; r < R; r++) hfet[r] = fetched1[ci.ix.rows[r]];
+        dfet = upload_mask(ctx, "sc.fetched1", hfet.data(), R);
+      }
+      uint32_t* dpk = buf<uint32_t>(ctx, "bp.pk", 32 * V);
+      uint32_t* denc = buf<uint32_t>(ctx, "bp.enc", 128 * C);
+      h2d(ctx, dpk, pk, 32 * V);
+      h2d(ctx, denc, enc, 128 * C);
+      dver = buf<int32_t>(ctx, "bp.verdict2", 4 * C);
+      complaints2_rows(ctx, n, t, C, R, rc, ci.x, ci.party, ci.crow, ci.seq, dpk, denc, proofs, dfet, dver);
+      check_launch(ctx);
+      d2h(ctx, verdict, dver, 4 * C);
+    }
+    std::vector<uint8_t> rowok;
+    if (qualified) {
+      // the "row decodes" term needs every row: decoded for its validity only, in slabs of bounded size
+      rowok.resize(V);
+      const size_t slab = std::max<size_t>(1, ((size_t)1 << 18) / N);
+      uint32_t* Ec = buf<uint32_t>(ctx, "sc.E", 32 * std::min(slab, V) * N);
+      uint32_t* Eext = buf<uint32_t>(ctx, "sc.Eext", PTB * std::min(slab, V) * N);
+      uint8_t* pok = buf<uint8_t>(ctx, "sc.pok", std::min(slab, V) * N);
+      uint8_t* dok = buf<uint8_t>(ctx, "sc.rowok", V);
+      for (size_t r0 = 0; r0 < V; r0 += slab) {
+        const size_t rn = std::min(slab, V - r0);
+        h2d(ctx, Ec, E + 32 * N * r0, 32 * N * rn);
+        dkgk::decode_points(Ec, rn * N, Eext, rn * N, pok, st);
+        dkgk::dealer_ok(rn, N, pok, dok + r0, st);
+      }
+      check_launch(ctx);
+      d2h(ctx, rowok.data(), dok, V);
+    }
+    sync(ctx);
+    if (qualified) {
+      for (size_t i = 0; i < V; i++) qualified[i] = rowok[i] && (!fetched1 || fetched1[i]);
+      for (size_t c = 0; c < C; c++)
+        if (verdict[c] == 0) qualified[(size_t)ceremony[c] * n + accused[c] - 1] = 0;  // committee.rs:381-394
+    }
+    return DKG_OK;
+  });
+}
+
+int dkg_complaints3_verify_ceremonies(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t C, const uint32_t* ceremony,
+                                      const uint32_t* accuser, const uint32_t* accused, const uint8_t* share,
+                                      const uint8_t* randomness, const uint8_t* E, const uint8_t* A,
+                                      const uint8_t* qualified, const uint8_t* fetched3, int32_t* verdict,
+                                      uint8_t* reconstruct) {
+  return guarded(ctx, [&] {
+    if (!B) return DKG_OK;
+    const int rc0 = ceremony_args(ctx, n, t, {E, A});
+    if (rc0) return rc0;
+    if (B > 0xffffffffu / n) return DKG_E_ARG;
+    if (!batch_complaint_args_ok(B, n, C, ceremony, accuser, accused, {share, randomness, verdict})) return DKG_E_ARG;
+    const size_t N = t + 1, V = B * n;
+    if (reconstruct) memset(reconstruct, 0, V);
+    if (!C) return DKG_OK;
+    CeremonyComplaintIndex ci;  // the staging vectors live until the sync
+    upload_complaint_index(ctx, n, C, 2, ceremony, accuser, accused, ci);
+    const size_t R = ci.ix.rows.size();
+    std::vector<uint8_t> hrows(32 * 2 * R * N);  // the accused dealers' E rows, then their A rows
+    gather_rows_host(ci.ix.rows, N, E, hrows.data());
+    gather_rows_host(ci.ix.rows, N, A, hrows.data() + 32 * R * N);
+    uint32_t* rc = buf<uint32_t>(ctx, "bp.rows4", 32 * 2 * R * N);
+    h2d(ctx, rc, hrows.data(), 32 * 2 * R * N);
+    const uint8_t* dq = upload_mask(ctx, "sc.qualified", qualified, V);
+    const uint8_t* df3 = upload_mask(ctx, "sc.fetched3", fetched3, V);
+    int32_t* dver = buf<int32_t>(ctx, "bp.verdict4", 4 * C);
+    complaints4_rows(ctx, n, t, C, R, rc, ci.x, ci.crow, ci.drow, ci.seq, share, randomness, dq, df3, dver);
+    check_launch(ctx);
+    d2h(ctx, verdict, dver, 4 * C);
+    sync(ctx);
+    if (reconstruct)
+      for (size_t c = 0; c < C; c++)  // committee.rs:643, :664-669
+        if (verdict[c] == 0 || verdict[c] == DKG_COMPLAINT_NO_PHASE3)
+          reconstruct[(size_t)ceremony[c] * n + accused[c] - 1] = 1;
+    return DKG_OK;
+  });
+}
+
+int dkg_party_round3_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer,
+                           const uint32_t* js, const uint8_t* qualified, const uint8_t* s, uint8_t* final_share,
+                           uint8_t* public_share) {
+  (void)t;
+  return guarded(ctx, [&] {
+    if (!S) return DKG_OK;
+    if (!B || !n || !cer || !js || !qualified || !s || !final_share) return DKG_E_ARG;
+    if (B > 0xffffffffu / n || S >= 0xffffffffu) return DKG_E_ARG;
+    for (size_t p = 0; p < S; p++)
+      if (cer[p] >= B || js[p] >= n) return DKG_E_ARG;  // before any launch
+    hipStream_t st = ctx->stream;
+    const uint8_t* dq = upload_mask(ctx, "sr.q", qualified, B * n);
+    uint32_t* dcer = buf<uint32_t>(ctx, "sr.cer", 4 * S);
+    h2d(ctx, dcer, cer, 4 * S);
+    const uint32_t* ds = upload_scalars(ctx, "sr.s", s, S * n);
+    uint32_t* fs = buf<uint32_t>(ctx, "sr.fs", 32 * S);
+    dkgk::seat_share_sum(S, n, dcer, dq, ds, fs, st);  // committee.rs:453-461
+    d2h(ctx, final_share, fs, 32 * S);
+    if (public_share) {  // :462-467
+      uint32_t* ge = buf<uint32_t>(ctx, "sr.ge", PTB * S);
+      uint32_t* oc = buf<uint32_t>(ctx, "sr.out", 32 * S);
+      dkgk::fixed_base(S, fs, ctx->tab_gw, ge, st);
+      dkgk::encode_points(ge, S, S, oc, st);
+      d2h(ctx, public_share, oc, 32 * S);
+    }
+    check_launch(ctx);
+    sync(ctx);
+    return DKG_OK;
+  });
+}
+
+int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer, const uint32_t* js,
+                       const uint8_t* qualified, const uint8_t* reconstruct, const uint8_t* fetched3,
+                       const uint8_t* r2_error, const uint8_t* r4_error, const uint8_t* A0, const uint8_t* s,
+                       size_t D5, const uint32_t* d_ceremony, const uint32_t* d_sender, const uint32_t* d_dealer,
+                       const uint8_t* d_share, uint8_t* mpk, int32_t* status, int32_t* recovery_index) {
+  return guarded(ctx, [&] {
+    if (!S) return DKG_OK;
+    if (!B || !n || !cer || !js || !qualified || !reconstruct || !A0 || !s || !mpk || !status) return DKG_E_ARG;
+    if (D5 && (!d_ceremony || !d_sender || !d_dealer || !d_share)) return DKG_E_ARG;
+    // party indices are multipliers below 2^24 on the device; rows, seats and list places are 32-bit
+    if (n >= ((size_t)1 << 24) || B > 0xffffffffu / n || S >= 0xffffffffu || D5 >= 0xffffffffu) return DKG_E_ARG;
+    for (size_t p = 0; p < S; p++)
+      if (cer[p] >= B || js[p] >= n) return DKG_E_ARG;
+    for (size_t d = 0; d < D5; d++)
+      if (d_ceremony[d] >= B || d_sender[d] < 1 || d_sender[d] > n || d_dealer[d] < 1 || d_dealer[d] > n)
+        return DKG_E_ARG;
+    constexpr uint32_t NONE = dkgk::SEAT_ROW_NONE;
+    // the ceremonies named, and per ceremony its final parties and one record per reconstructed dealer
+    std::vector<uint32_t> cers, slot;
+    dkgh::distinct_places(S, cer, cers, slot);
+    const size_t Bd = cers.size(), D = Bd * n;
+    std::unordered_map<uint32_t, uint32_t> slot_of;
+    slot_of.reserve(2 * Bd);
+    std::vector<uint8_t> fin(D);
+    std::vector<uint32_t> rec(D, NONE), rptr(Bd + 1, 0), rdeal;
+    for (size_t c = 0; c < Bd; c++) {
+      slot_of[cers[c]] = (uint32_t)c;
+      const uint8_t *q = qualified + (size_t)cers[c] * n, *r = reconstruct + (size_t)cers[c] * n;
+      for (size_t i = 0; i < n; i++) {
+        if (r[i] && !q[i]) {
+          ctx->err = "finalise: only qualified members should be reconstructed (committee.rs:746-747 panics)";
+          return DKG_E_ARG;
+        }
+        fin[c * n + i] = q[i] && !r[i];  // :733-739
+        if (r[i]) {
+          rec[c * n + i] = (uint32_t)rdeal.size();
+          rdeal.push_back((uint32_t)i);
+        }
+      }
+      rptr[c + 1] = (uint32_t)rdeal.size();
+    }
+    const size_t K = rdeal.size();
+    // the disclosures the reference's loop reads (:763-775), in CSR form per record
+    auto key = [&](uint32_t g, uint32_t sender0, uint32_t dealer0) { return ((uint64_t)g * n + sender0) * n + dealer0; };
+    std::unordered_set<uint64_t> seen;
+    seen.reserve(2 * D5);
+    std::vector<uint32_t> dptr(K + 1, 0), keep(D5, NONE);
+    for (size_t d = 0; d < D5; d++) {
+      if (!seen.insert(key(d_ceremony[d], d_sender[d] - 1, d_dealer[d] - 1)).second) {
+        ctx->err = "finalise: a (ceremony, sender, dealer) disclosure is listed twice";
+        return DKG_E_ARG;
+      }
+      const auto it = slot_of.find(d_ceremony[d]);
+      if (it == slot_of.end()) continue;  // a ceremony no seat names
+      const size_t c = it->second;
+      const uint32_t k = rec[c * n + d_dealer[d] - 1];
+      if (k == NONE || !fin[c * n + d_sender[d] - 1]) continue;
+      keep[d] = k;
+      dptr[k + 1]++;
+    }
+    size_t longest = 0;
+    for (size_t k = 0; k < K; k++) {
+      longest = std::max<size_t>(longest, dptr[k + 1]);
+      dptr[k + 1] += dptr[k];
+    }
+    if (longest + 1 > dkgk::SEAT_LAGRANGE_MAX_POINTS) {
+      ctx->err = "finalise: more disclosures for one dealer than the interpolation stages";
+      return DKG_E_ARG;
+    }
+    const size_t kept = dptr[K];
+    std::vector<uint32_t> dx(std::max<size_t>(1, kept)), fill(dptr.begin(), dptr.end() - 1);
+    std::vector<uint8_t> hy(32 * std::max<size_t>(1, kept));
+    for (size_t d = 0; d < D5; d++) {
+      if (keep[d] == NONE) continue;
+      const size_t at = fill[keep[d]]++;
+      dx[at] = d_sender[d];
+      memcpy(&hy[32 * at], d_share + 32 * d, 32);
+    }
+    // dkg_seat_finalise_status per seat; a_ok (null at first: by fetched3 alone) [D] = A0 decodes
+    std::vector<uint32_t> pts(n);
+    std::vector<uint8_t> apres(n);
+    auto seat_status = [&](size_t p, const uint8_t* a_ok, int32_t* index) {
+      const size_t c = slot[p], g = cers[c];
+      std::fill(pts.begin(), pts.end(), 0u);
+      for (uint32_t k = rptr[c]; k < rptr[c + 1]; k++) {
+        const bool self = fin[c * n + js[p]] && seen.count(key((uint32_t)g, js[p], rdeal[k]));
+        pts[rdeal[k]] = 1 + (dptr[k + 1] - dptr[k]) - (self ? 1 : 0);  // the seat uses its own share (:754-761)
+      }
+      for (size_t i = 0; i < n; i++) apres[i] = (!fetched3 || fetched3[g * n + i]) && (!a_ok || a_ok[c * n + i]);
+      return dkg_seat_finalise_status(n, t, js[p], qualified + g * n, reconstruct + g * n, apres.data(), pts.data(),
+                                      r2_error && r2_error[p], r4_error && r4_error[p], index);
+    };
+    std::vector<uint8_t> skip(S);
+    std::vector<uint32_t> sx(S), own(S, NONE);
+    for (size_t p = 0; p < S; p++) {
+      int32_t index;
+      skip[p] = seat_status(p, nullptr, &index) != DKG_FIN_OK;
+      sx[p] = js[p] + 1;
+      if (!qualified[(size_t)cer[p] * n + js[p]]) own[p] = (uint32_t)(slot[p] * n + js[p]);  // its own A_p0 (:190)
+    }
+    hipStream_t st = ctx->stream;
+    // ---- the interpolations, one workgroup per seat
+    uint32_t* dslot = buf<uint32_t>(ctx, "sf.slot", 4 * S);
+    uint32_t* dsx = buf<uint32_t>(ctx, "sf.sx", 4 * S);
+    uint32_t* down = buf<uint32_t>(ctx, "sf.own", 4 * S);
+    uint8_t* dskip = buf<uint8_t>(ctx, "sf.skip", S);
+    uint32_t* drptr = buf<uint32_t>(ctx, "sf.rptr", 4 * (Bd + 1));
+    uint32_t* drdeal = buf<uint32_t>(ctx, "sf.rdeal", 4 * K);
+    uint32_t* ddptr = buf<uint32_t>(ctx, "sf.dptr", 4 * (K + 1));
+    uint32_t* ddx = buf<uint32_t>(ctx, "sf.dx", 4 * dx.size());
+    h2d(ctx, dslot, slot.data(), 4 * S);
+    h2d(ctx, dsx, sx.data(), 4 * S);
+    h2d(ctx, down, own.data(), 4 * S);
+    h2d(ctx, dskip, skip.data(), S);
+    h2d(ctx, drptr, rptr.data(), 4 * (Bd + 1));
+    h2d(ctx, drdeal, rdeal.data(), 4 * K);
+    h2d(ctx, ddptr, dptr.data(), 4 * (K + 1));
+    h2d(ctx, ddx, dx.data(), 4 * dx.size());
+    const uint32_t* ds = upload_scalars(ctx, "sf.s", s, S * n);
+    const uint32_t* dy = upload_scalars(ctx, "sf.dy", hy.data(), hy.size() / 32);
+    uint32_t* sigma = buf<uint32_t>(ctx, "sf.sigma", 32 * S);
+    recv_mark(ctx, 0);
+    dkgk::seat_lagrange(S, n, dslot, dsx, dskip, drptr, drdeal, ddptr, ddx, dy, ds, longest + 1, sigma, st);
+    recv_mark(ctx, 1);
+    // ---- mpk_p = sum of the A_i0 it adds + g sigma_p (:789-795): only the named ceremonies' rows
+    std::vector<uint8_t> ha0(32 * D);
+    for (size_t c = 0; c < Bd; c++) memcpy(&ha0[32 * c * n], A0 + 32 * (size_t)cers[c] * n, 32 * n);
+    uint32_t* a0c = buf<uint32_t>(ctx, "sf.a0c", 32 * D);
+    uint32_t* a0e = buf<uint32_t>(ctx, "sf.a0e", PTB * D);
+    uint8_t* a0ok = buf<uint8_t>(ctx, "sf.a0ok", D);
+    uint8_t* fm = buf<uint8_t>(ctx, "sf.fin", D);
+    uint32_t* H = buf<uint32_t>(ctx, "sf.H", PTB * Bd);
+    uint32_t* Hs = buf<uint32_t>(ctx, "sf.Hs", PTB * S);
+    uint32_t* ownp = buf<uint32_t>(ctx, "sf.ownp", PTB * S);
+    uint32_t* ge = buf<uint32_t>(ctx, "sf.ge", PTB * S);
+    uint32_t* oc = buf<uint32_t>(ctx, "sf.out", 32 * S);
+    h2d(ctx, a0c, ha0.data(), 32 * D);
+    h2d(ctx, fm, fin.data(), D);
+    dkgk::decode_points(a0c, D, a0e, D, a0ok, st);
+    dkgk::sum_points(n, a0e, D, fm, H, Bd, 0, st, Bd);
+    dkgk::seat_gather_points(S, dslot, H, Bd, Hs, S, st);
+    dkgk::fill_identity(S, ownp, st);
+    dkgk::seat_gather_points(S, down, a0e, D, ownp, S, st);
+    dkgk::add_points(S, Hs, ownp, S, Hs, st);
+    dkgk::fixed_base(S, sigma, ctx->tab_gw, ge, st);
+    dkgk::add_points(S, ge, Hs, S, ge, st);
+    dkgk::encode_points(ge, S, S, oc, st);
+    recv_mark(ctx, 2);
+    check_launch(ctx);
+    std::vector<uint8_t> okh(D), outh(32 * S);
+    d2h(ctx, okh.data(), a0ok, D);
+    d2h(ctx, outh.data(), oc, 32 * S);
+    sync(ctx);
+    seat_phase(ctx, "lagrange", 0, 1);
+    seat_phase(ctx, "mpk", 1, 2);
+    memset(mpk, 0, 32 * S);
+    for (size_t p = 0; p < S; p++) {
+      int32_t index = -1;
+      status[p] = seat_status(p, okh.data(), &index);
+      if (recovery_index) recovery_index[p] = index;
+      if (status[p] != DKG_FIN_OK) continue;
+      if (own[p] != NONE && !okh[own[p]]) {
+        ctx->err = "finalise: a disqualified seat's own A_0 commitment does not decode";
+        return DKG_E_DECODE;
+      }
+      memcpy(mpk + 32 * p, &outh[32 * p], 32);
     }
     return DKG_OK;
   });

@@ -46,6 +46,39 @@ extern "C" int dkg_seat_pack(size_t n, size_t S, const uint32_t* js, uint32_t* w
   return DKG_OK;
 }
 
+// The outcome of Phases<Phase5>::finalise for one seat (committee.rs:726-805) from what the seat holds:
+// pure host code, the rule dkg_finalise_seats executes for every seat.
+extern "C" int dkg_seat_finalise_status(size_t n, size_t t, size_t p, const uint8_t* qualified,
+                                        const uint8_t* reconstruct, const uint8_t* a_present, const uint32_t* points,
+                                        int r2_error, int r4_error, int32_t* recovery_index) {
+  if (recovery_index) *recovery_index = -1;
+  if (!n || p >= n || !qualified || !reconstruct || !points) return DKG_E_ARG;
+  size_t nq = 0, nr = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (reconstruct[i] && !qualified[i]) return DKG_E_ARG;  // :746-747 panics
+    nq += qualified[i] != 0;
+    nr += reconstruct[i] != 0;
+  }
+  if (r2_error) return DKG_FIN_R2_ERROR;          // :340-347
+  if (r4_error) return DKG_FIN_R4_ERROR;          // :567-569
+  if (nq - nr <= t) return DKG_FIN_PHASE4_ERROR;  // :673-677
+  for (size_t i = 0; i < n; i++) {                // index order, the first failure wins (:745-797)
+    int status = DKG_FIN_OK;
+    if (reconstruct[i]) {
+      if (points[i] < t) status = DKG_FIN_INSUFFICIENT;  // :779-781 (threshold, not t + 1)
+    } else if (!qualified[i]) {
+      if (i != p) status = DKG_FIN_PANIC;  // :791-794; a disqualified seat adds its own A_p0 (:190)
+    } else if (a_present && !a_present[i]) {
+      status = DKG_FIN_PANIC;  // never stored (:527-530), as dkg_ceremony_verify_fetched_proven
+    }
+    if (status != DKG_FIN_OK) {
+      if (recovery_index) *recovery_index = (int32_t)i;
+      return status;
+    }
+  }
+  return DKG_FIN_OK;
+}
+
 namespace dkgh {
 
 int seat_plan(size_t B, size_t n, size_t S, const uint32_t* cer, const uint32_t* js, SeatPlan& out) {

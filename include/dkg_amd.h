@@ -360,6 +360,87 @@ int dkg_party_round2_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S,
                            const uint8_t *sk, const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
                            int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
 
+/* ---- hosted seats through rounds 3-5 (seat_finalise.hip) ----
+ * What an operator's seats do after their share checks, without one call per ceremony and without data
+ * an operator never holds (the n x n share matrix, the other parties' keys).  All calls take B ceremonies
+ * of one (n, t) with rows laid out as above (row c * n + i = dealer i of ceremony c) and seats as above.
+ * S == 0 (the complaint calls: B == 0) returns DKG_OK and touches nothing; a count of 0 allows NULL list
+ * arrays; an index outside its range or a missing required pointer is DKG_E_ARG.
+ *
+ * Phases<Phase2>::compute_qualified_set (committee.rs:370-398, broadcast.rs:50-99) for the broadcast
+ * complaints of MANY ceremonies: flat arrays as dkg_ceremony_batch_verify_full_proven takes them
+ * (ceremony[c] 0-based < B, accuser / accused 1-based; ceremonies interleaved, duplicates allowed; verdicts
+ * in input order), but enc [C][128] comes from the caller as in dkg_complaints_verify -- no ceremony is
+ * replayed.  pk [B][n][32], E [B*n][t+1][32], fetched1 [B*n] (NULL = all present).  verdict [C] and
+ * qualified [B][n] (may be NULL) equal what dkg_complaints_verify returns for ceremony g on g's slices and
+ * g's own complaints in their relative order: DKG_COMPLAINT_IGNORED, -1, 1, 2, 0 in its precedence.  A
+ * ceremony without a complaint is qualified except for missing or undecodable rows.  Only the DISTINCT
+ * accused rows of E are uploaded and decoded for the checks; the other rows are decoded (for the "row
+ * decodes" term) only when qualified is requested.  The launch count of the checks does not depend on
+ * B, and P_i(j) is always one Horner walk per complaint: dkg_ctx_set_complaint_eval does not apply.
+ * Requires dkg_env_init (h). */
+int dkg_complaints_verify_ceremonies(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t C, const uint32_t *ceremony,
+                                     const uint32_t *accuser, const uint32_t *accused, const uint8_t *pk,
+                                     const uint8_t *E, const uint8_t *fetched1, const uint8_t *enc,
+                                     const uint8_t *proofs, int32_t *verdict, uint8_t *qualified);
+/* Phases<Phase4>::proceed's loop (committee.rs:636-670, broadcast.rs:104-144) for the round-4 complaints of
+ * many ceremonies, the same flat arrays; share, randomness [C][32]; E, A [B*n][t+1][32]; qualified,
+ * fetched3 [B*n] (NULL = all 1).  verdict [C] and reconstruct [B][n] (may be NULL; all 0 for a ceremony
+ * without a complaint) equal dkg_complaints3_verify's for ceremony g: DKG_COMPLAINT_IGNORED,
+ * DKG_COMPLAINT_NO_PHASE3, -1, 3, 2, 0 in its precedence.  Only the distinct accused rows of E and A are
+ * uploaded and decoded; always the per-complaint Horner walk (dkg_ctx_set_complaint_eval does not
+ * apply).  Requires dkg_env_init (h). */
+int dkg_complaints3_verify_ceremonies(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t C, const uint32_t *ceremony,
+                                      const uint32_t *accuser, const uint32_t *accused, const uint8_t *share,
+                                      const uint8_t *randomness, const uint8_t *E, const uint8_t *A,
+                                      const uint8_t *qualified, const uint8_t *fetched3, int32_t *verdict,
+                                      uint8_t *reconstruct);
+/* Phases<Phase2>::proceed per seat (committee.rs:453-467): qualified [B][n] the round-2 qualified sets,
+ * s [S][n][32] the shares addressed to seat p (read reduced mod l, as everywhere).  final_share[p] = the
+ * sum over the dealers i with qualified[cer[p]][i] of s[p][i], the seat's own dealer row included as in
+ * the reference; public_share[p] (may be NULL) = g final_share[p].  [S][32] each.  The reference's guard
+ * at :443 compares qualified_set.len(), which is always n, so it cannot fire under dkg_env_check: there is
+ * no error output.  One launch set for all seats.  Needs no dkg_env_init. */
+int dkg_party_round3_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t *cer,
+                           const uint32_t *js, const uint8_t *qualified, const uint8_t *s, uint8_t *final_share,
+                           uint8_t *public_share);
+/* Phases<Phase5>::finalise per seat (committee.rs:726-805).  qualified, reconstruct [B][n]; fetched3 [B*n]
+ * (NULL = all present); r2_error, r4_error [S] (NULL = none): the SEAT's own Phase1 / Phase3 outcomes;
+ * A0 [B*n][32] the dealers' A_i0; s [S][n][32] the seat's own column.  The D5 disclosures are the flat
+ * form of the BroadcastPhase5 messages the operator fetched (a Vec<Option<share>> per dealer, so a sender
+ * may disclose for some dealers only): entry d = sender d_sender[d] of ceremony d_ceremony[d] disclosed
+ * dealer d_dealer[d]'s share d_share[d] (sender, dealer 1-based; shares read reduced mod l).
+ * Seat p: R2_ERROR, R4_ERROR, then PHASE4_ERROR (qualified - reconstruct <= t in its ceremony, :673-677);
+ * then the dealers in index order, the first failure wins (:745-797).  A reconstructed dealer i is
+ * interpolated at zero through the seat's own (js[p] + 1, s[p][i]) and every listed disclosure for (its
+ * ceremony, i) by a sender q != js[p] + 1 that is a final party (qualified and not reconstructed, :765);
+ * fewer than t points: DKG_FIN_INSUFFICIENT with index i (exactly t interpolate, as the reference).  A
+ * dealer that is not reconstructed adds A0[i] if it is qualified or the seat itself; DKG_FIN_PANIC with
+ * index i if it is disqualified and not the seat, and also if it is qualified but fetched3[i] == 0 or its
+ * A0 does not decode (the rule of dkg_ceremony_verify_fetched_proven, not a whole-call DKG_E_DECODE).
+ * mpk[p] = the sum of those A0 + g (the sum of the recovered secrets), 32 zero bytes unless status[p] ==
+ * DKG_FIN_OK; recovery_index[p] (may be NULL) = -1 unless INSUFFICIENT or PANIC.
+ * Entries the reference's loop never reads are ignored: a sender that is not a final party, a dealer that
+ * is not reconstructed, the seat's own sender.  A ceremony no seat names is never interpreted.
+ * DKG_E_ARG: a duplicate (ceremony, sender, dealer), an index outside its range, reconstruct without
+ * qualified in a named ceremony (:746-747 panics).  DKG_E_DECODE only for the own A0 of a disqualified
+ * seat that finalises.  The status of every seat is dkg_seat_finalise_status's.  One 64-lane workgroup
+ * per seat interpolates (k_seat_lagrange); host work O(S n + D5).  Phase times "seats.lagrange" and
+ * "seats.mpk" (one stream).  Needs no dkg_env_init. */
+int dkg_finalise_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t *cer, const uint32_t *js,
+                       const uint8_t *qualified, const uint8_t *reconstruct, const uint8_t *fetched3,
+                       const uint8_t *r2_error, const uint8_t *r4_error, const uint8_t *A0, const uint8_t *s,
+                       size_t D5, const uint32_t *d_ceremony, const uint32_t *d_sender, const uint32_t *d_dealer,
+                       const uint8_t *d_share, uint8_t *mpk, int32_t *status, int32_t *recovery_index);
+/* The status rule of dkg_finalise_seats for ONE seat p (0-based) as a pure host function (no GPU, no
+ * context): qualified, reconstruct [n]; a_present [n] (NULL = all): dealer i's A_i0 was fetched and
+ * decodes; points [n]: the points the seat holds for dealer i (its own included; read for reconstructed
+ * dealers only); r2_error, r4_error the seat's own.  Returns the DKG_FIN_* code, *recovery_index (may be
+ * NULL) as above; DKG_E_ARG for n == 0, p >= n, a NULL required pointer or reconstruct without qualified. */
+int dkg_seat_finalise_status(size_t n, size_t t, size_t p, const uint8_t *qualified, const uint8_t *reconstruct,
+                             const uint8_t *a_present, const uint32_t *points, int r2_error, int r4_error,
+                             int32_t *recovery_index);
+
 /* ---- whole ceremony (rounds 1-5, every party played in one process as the reference tests do,
  * committee.rs:1518-1656) in plaintext-share mode. ---- */
 typedef struct {
