@@ -171,6 +171,11 @@ def lib():
         L.dkg_finalise_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, u8p, u8p, u8p, sz, p, p, p, u8p,
                                          p, p, p]
         L.dkg_seat_finalise_status.argtypes = [sz, sz, sz, u8p, u8p, u8p, p, ctypes.c_int, ctypes.c_int, p]
+    if hasattr(L, "dkg_party_round1_seats"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_party_round1_seats.argtypes = [p, sz, sz, sz, sz, p, p, u8p, u8p, u8p, u8p, p, p, p, p, p, p, p]
+        L.dkg_ctx_set_seat_deal.argtypes = [p, ctypes.c_int]
+        L.dkg_ctx_last_seat_deal.argtypes = [p]
+        L.dkg_seat_enc_digits.argtypes = [p, p, ctypes.POINTER(ctypes.c_int)]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -320,4 +325,5 @@ EXPORTED = [
     "dkg_seat_pack", "dkg_commitment_eval_seats", "dkg_verify_seats", "dkg_party_round2_seats",
     "dkg_complaints_verify_ceremonies", "dkg_complaints3_verify_ceremonies", "dkg_party_round3_seats", "dkg_finalise_seats",
     "dkg_seat_finalise_status",
+    "dkg_party_round1_seats", "dkg_ctx_set_seat_deal", "dkg_ctx_last_seat_deal", "dkg_seat_enc_digits",
 ]

@@ -269,14 +269,16 @@ class Backend:
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
         encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
         commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs), "seats" (the last
-        commitment_eval_seats, verify_seats, party_round2_seats; lagrange / mpk: the last finalise_seats).  Only recorded with set_streams(1); -1 otherwise."""
+        commitment_eval_seats, verify_seats, party_round2_seats; lagrange / mpk: the last finalise_seats; commit /
+        deal_*: the last party_round1_seats).  Only recorded with set_streams(1); -1 otherwise."""
         L = _lib.lib()
         if isinstance(tag, int):
             tag = f"r{tag}"
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("decode", "eval") if tag == "pairs"
-                 else ("decrypt", "decode", "eval", "check", "prove", "lagrange", "mpk") if tag == "seats"
+                 else ("decrypt", "decode", "eval", "check", "prove", "lagrange", "mpk", "commit", "deal_e1", "deal_mul",
+                       "deal_encode", "deal_sym") if tag == "seats"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
         return {k: L.dkg_ctx_phase_ms(self._ctx, f"{tag}.{k}".encode()) for k in names}
@@ -448,6 +450,34 @@ class Backend:
         return {"s": s.raw[: 32 * S * n], "s_prime": sp.raw[: 32 * S * n], "dec": dec.raw[: S * n],
                 "complaints": list(cnt[:S]), "r2_error": list(err.raw[:S]),
                 "proofs": prf.raw[: 192 * S * n] if prf is not None else None}
+
+    # ---- hosted seats deal round 1 (k_seat_enc_mul)
+    def party_round1_seats(self, B: int, n: int, t: int, cer: Sequence[int], js: Sequence[int], a: bytes, b: bytes,
+                           r: bytes, pk: bytes) -> dict:
+        """Phases<Initialise>::init for every seat in one call: a, b [S][t+1][32] the seats' coefficients, r
+        [S][n][2][32] their encryption randomness (w = 0 for s', 1 for s), pk [B][n][32] the ceremonies' sorted
+        member keys.  Keys: E, A [S][t+1][32]; e1, ct [S][n][2][32]; s, s_prime [S][n][32]; own [S][2][32] =
+        (s', s) at js[p].  Row p equals share_gen(D = 1) + encrypt_shares(D = 1) of seat p."""
+        S, ca, ja = self._seat_arrays(cer, js)
+        N = t + 1
+        E, A = (ctypes.create_string_buffer(max(32 * S * N, 1)) for _ in range(2))
+        e1, ct = (ctypes.create_string_buffer(max(64 * S * n, 1)) for _ in range(2))
+        s, sp = (ctypes.create_string_buffer(max(32 * S * n, 1)) for _ in range(2))
+        own = ctypes.create_string_buffer(max(64 * S, 1))
+        _check(self._ctx, _lib.lib().dkg_party_round1_seats(self._ctx, B, n, t, S, ca, ja, a, b, r, pk, E, A, e1, ct, s,
+                                                             sp, own))
+        return {"E": E.raw[: 32 * S * N], "A": A.raw[: 32 * S * N], "e1": e1.raw[: 64 * S * n],
+                "ct": ct.raw[: 64 * S * n], "s": s.raw[: 32 * S * n], "s_prime": sp.raw[: 32 * S * n],
+                "own": own.raw[: 64 * S]}
+
+    def set_seat_deal(self, mode: int):
+        """K = pk_q r of party_round1_seats: 0 (default) automatic, 1 a radix-16 comb per key slot, 2 the joint
+        radix-4 chain of both scalars.  Outputs do not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_seat_deal(self._ctx, mode))
+
+    def last_seat_deal(self) -> int:
+        """The route (1 or 2) the last party_round1_seats ran; 0 before the first."""
+        return _lib.lib().dkg_ctx_last_seat_deal(self._ctx)
 
     # ---- hosted seats through rounds 3-5 (k_seat_lagrange; the batch's complaint kernels)
     def complaints_verify_ceremonies(self, B: int, n: int, t: int, ceremony: Sequence[int], accusers: Sequence[int],
@@ -1233,6 +1263,19 @@ def seat_pack(n: int, js: Sequence[int]) -> dict:
         raise _lib.DkgError(rc, "seat_pack")
     return {"width": v[0].value, "per_wave": v[1].value, "tiles": v[2].value, "wave_of": list(wave_of[:S]),
             "slot_of": list(slot_of[:S]), "waves": v[3].value}
+
+
+def seat_enc_digits(k: int) -> List[int]:
+    """dkg_seat_enc_digits (host only): the signed radix-4 digits, window 0 first, that party_round1_seats'
+    joint chain walks for the scalar k < 2^255, as the kernel's own routine computes them."""
+    if k < 0 or k >= 1 << 256:
+        raise _lib.DkgError(_lib.DKG_E_ARG, "seat_enc_digits")
+    d = (ctypes.c_int8 * 128)()
+    w = ctypes.c_int(0)
+    rc = _lib.lib().dkg_seat_enc_digits(k.to_bytes(32, "little"), d, ctypes.byref(w))
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "seat_enc_digits")
+    return list(d[: w.value])
 
 
 def seat_finalise_status(n: int, t: int, p: int, qualified, reconstruct, points: Sequence[int], a_present=None,

@@ -320,6 +320,18 @@ def _hybrid_items(n: int, p1: Phase1Intake) -> Tuple[bytes, bytes]:
     return bytes(e1), bytes(ct)
 
 
+def seat_phase1(n: int, E_p: bytes, e1_p: bytes, ct_p: bytes) -> BroadcastPhase1:
+    """The BroadcastPhase1 of one dealing seat from its row of Backend.party_round1_seats: E_p [t+1][32],
+    e1_p, ct_p [n][2][32] (w = 0 the randomness, 1 the share).  Full-mode EncryptedShares with
+    recipient_index q + 1 (committee.rs:164-178), share = e1 || ct of w = 1, randomness = that of w = 0: the
+    inverse of _hybrid_items on row p, the layout intake_phase1 reads."""
+    if len(E_p) % 32 or len(e1_p) != 64 * n or len(ct_p) != 64 * n:
+        raise ValueError("E_p [t+1][32] and e1_p, ct_p [n][2][32] expected")
+    item = lambda q, w: e1_p[32 * (2 * q + w):32 * (2 * q + w + 1)] + ct_p[32 * (2 * q + w):32 * (2 * q + w + 1)]  # noqa: E731
+    return BroadcastPhase1([E_p[k:k + 32] for k in range(0, len(E_p), 32)],
+                           [EncryptedShares(q + 1, item(q, 1), item(q, 0)) for q in range(n)])
+
+
 def verify_broadcasts_proven(be, n: int, t: int, phase1: Sequence[Optional[BroadcastPhase1]],
                              phase3: Sequence[Optional[BroadcastPhase3]],
                              phase4: Sequence[Optional[BroadcastPhase4]],

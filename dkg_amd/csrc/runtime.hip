@@ -23,6 +23,7 @@
 #include "kernels_ilp.h"
 #include "comb_build.h"
 #include "seat_finalise.h"
+#include "seat_deal.h"
 
 struct dkg_ctx {
   int device = 0;
@@ -65,6 +66,9 @@ struct dkg_ctx {
   int key_comb = 0;                     // K = pk_q r: 0 radix 2^DKG_KEY_COMB_BITS, except that the sharded
                                         // full calls choose by dkg_key_comb_choice; 1 / 2 force a kind
   int last_key_comb = 0;                // the kind the last encrypt_device used (0: none yet)
+  int seat_deal = 0;                    // K = pk r of dkg_party_round1_seats: 0 automatic (DKG_SEAT_DEAL_AUTO), 1
+                                        // radix-16 combs per key slot, 2 the joint chain (seat_deal.hip)
+  int last_seat_deal = 0;               // the route the last such call ran (0: none yet)
   uint8_t fb_base[32] = {0};            // dkg_fixed_base_batch: the caller base whose comb sits in fb_tabw
   bool fb_valid = false;
   int comb_build = 0;                   // radix-2^BITS comb builder: 0 automatic (comb_build_auto), 1 one
@@ -3228,6 +3232,17 @@ int dkg_jsf_digits(const uint8_t a[32], const uint8_t b[32], int8_t da[256], int
   if (!a || !b || !da || !db || !top) return DKG_E_ARG;
   return dkgh::jsf_digits(a, b, da, db, top) ? DKG_OK : DKG_E_ARG;
 }
+int dkg_seat_enc_digits(const uint8_t k[32], int8_t digits[128], int* windows) {
+  if (!k || !digits || !windows || (k[31] & 0x80)) return DKG_E_ARG;
+  uint32_t w[8];
+  for (int i = 0; i < 8; i++)
+    w[i] = (uint32_t)k[4 * i] | (uint32_t)k[4 * i + 1] << 8 | (uint32_t)k[4 * i + 2] << 16 | (uint32_t)k[4 * i + 3] << 24;
+  int carry = 0;
+  for (int win = 0; win < dkgk::SEAT_ENC_WINDOWS; win++)  // the kernel's loop (k_seat_enc_mul)
+    digits[win] = (int8_t)dkgk::seat_enc_digit(dkgk::seat_enc_bits(w[win >> 4], win), win, carry);
+  *windows = dkgk::SEAT_ENC_WINDOWS;
+  return DKG_OK;
+}
 int dkg_split_digits(size_t n, size_t L, int pieces, int mode, int8_t* digits, int16_t* top) {
   if (!n || !L || pieces < 2 || pieces > (int)SHORT_MAX || mode < 0 || mode > 3 || mode == 1 || !digits || !top)
     return DKG_E_ARG;
@@ -4420,6 +4435,13 @@ int dkg_ctx_set_key_comb(dkg_ctx* ctx, int mode) {
 }
 int dkg_ctx_last_key_comb(const dkg_ctx* ctx) { return ctx ? ctx->last_key_comb : 0; }
 
+int dkg_ctx_set_seat_deal(dkg_ctx* ctx, int mode) {
+  if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
+  ctx->seat_deal = mode;
+  return DKG_OK;
+}
+int dkg_ctx_last_seat_deal(const dkg_ctx* ctx) { return ctx ? ctx->last_seat_deal : 0; }
+
 int dkg_ctx_set_comb_build(dkg_ctx* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
   ctx->comb_build = mode;
@@ -5580,6 +5602,165 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
         for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
       }
     }
+    return DKG_OK;
+  });
+}
+
+// ---- hosted seats deal round 1 (seat_deal.hip)
+// K = pk r of a dealing seat when dkg_ctx_set_seat_deal leaves the choice open: 2 the joint chain, 1 the
+// radix-16 combs per key slot (profiles/seat_deal_time.json).
+#ifndef DKG_SEAT_DEAL_AUTO
+#define DKG_SEAT_DEAL_AUTO 2
+#endif
+
+namespace {
+
+enum { SD_COMMIT, SD_E1, SD_MUL, SD_ENCODE, SD_SYM, SD_PHASES };
+const char* const SD_NAMES[SD_PHASES] = {"commit", "deal_e1", "deal_mul", "deal_encode", "deal_sym"};
+
+// After a sync: seats.<SD_NAMES> = the summed device times of the call's marks over all chunks (bf_mark's
+// segments); a phase without a mark reads -1.
+void collect_seat_deal_phases(dkg_ctx* ctx) {
+  double ms[SD_PHASES] = {};
+  bool seen[SD_PHASES] = {};
+  for (size_t k = 1; k < ctx->bf_marks.size(); k++) {
+    const int ph = ctx->bf_marks[k].first;
+    if (ph < 0) continue;
+    float v = 0;
+    HCK(hipEventElapsedTime(&v, ctx->bf_marks[k - 1].second, ctx->bf_marks[k].second));
+    ms[ph] += v;
+    seen[ph] = true;
+  }
+  for (int i = 0; i < SD_PHASES; i++) {
+    const std::string name = std::string("seats.") + SD_NAMES[i];
+    if (seen[i]) ctx->phase_ms[name] = ms[i];
+    else ctx->phase_ms.erase(name);
+  }
+  ctx->bf_marks.clear();
+}
+
+// Seats per chunk of the hybrid stage: the extended-form R and K, the K encodings and, on the comb route,
+// the per-slot key copies, their gather index and their radix-16 combs within BFULL_SCRATCH_BYTES;
+// dkg_ctx_set_batch_full_chunk forces a count (of seats, here).
+size_t seat_deal_chunk(const dkg_ctx* ctx, size_t S, size_t n, int mode) {
+  size_t per = 2 * n * (2 * PTB + 32);
+  if (mode == 1) per += n * (PTB + 4 + 4 * dkgk::benc_tab_words());
+  const size_t c = ctx->bfull_chunk ? ctx->bfull_chunk : std::max<size_t>(1, BFULL_SCRATCH_BYTES / per);
+  return std::min(c, S);
+}
+
+}  // namespace
+
+int dkg_party_round1_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer,
+                           const uint32_t* js, const uint8_t* a, const uint8_t* b, const uint8_t* r,
+                           const uint8_t* pk, uint8_t* E, uint8_t* A, uint8_t* e1, uint8_t* ct, uint8_t* s_out,
+                           uint8_t* sp_out, uint8_t* own) {
+  return guarded(ctx, [&] {
+    if (!S) return DKG_OK;
+    const int rc0 = ceremony_args(ctx, n, t, {cer, js, a, b, r, pk, E, A, e1, ct});
+    if (rc0) return rc0;
+    if (!B || B > 0xffffffffu / n || S > 0xffffffffu / (2 * n)) return DKG_E_ARG;  // keys and items are 32-bit
+    for (size_t p = 0; p < S; p++)
+      if (cer[p] >= B || js[p] >= n) return DKG_E_ARG;  // before any launch
+    const int mode = ctx->seat_deal ? ctx->seat_deal : DKG_SEAT_DEAL_AUTO;
+    ctx->last_seat_deal = mode;
+    hipStream_t st = ctx->stream;
+    const size_t N = t + 1;
+    // the distinct ceremonies named, in order of first mention: only their keys are uploaded and decoded
+    std::vector<uint32_t> cers, kbase(S);
+    {
+      std::map<uint32_t, uint32_t> slot_of;
+      for (size_t p = 0; p < S; p++) {
+        auto it = slot_of.find(cer[p]);
+        if (it == slot_of.end()) {
+          it = slot_of.emplace(cer[p], (uint32_t)cers.size()).first;
+          cers.push_back(cer[p]);
+        }
+        kbase[p] = it->second * (uint32_t)n;
+      }
+    }
+    const size_t Ck = cers.size() * n;
+    std::vector<uint8_t> pkh(32 * Ck);
+    for (size_t c = 0; c < cers.size(); c++) memcpy(&pkh[32 * c * n], pk + 32 * (size_t)cers[c] * n, 32 * n);
+    uint32_t* dpk = buf<uint32_t>(ctx, "sd_pk", 32 * Ck);
+    uint32_t* pk_ext = buf<uint32_t>(ctx, "sd_pk_ext", PTB * Ck);
+    uint8_t* pk_ok = buf<uint8_t>(ctx, "sd_pk_ok", Ck);
+    uint32_t* dkbase = buf<uint32_t>(ctx, "sd_kbase", 4 * S);
+    h2d(ctx, dpk, pkh.data(), 32 * Ck);
+    h2d(ctx, dkbase, kbase.data(), 4 * S);
+    uint32_t* da = upload_scalars(ctx, "sd_a", a, S * N);
+    uint32_t* db = upload_scalars(ctx, "sd_b", b, S * N);
+    uint32_t* dr = upload_scalars(ctx, "sd_r", r, 2 * S * n);
+    uint32_t* Ec = buf<uint32_t>(ctx, "sd_E", 32 * S * N);
+    uint32_t* Ac = buf<uint32_t>(ctx, "sd_A", 32 * S * N);
+    uint32_t* ds = buf<uint32_t>(ctx, "sd_s", 32 * S * n);
+    uint32_t* dsp = buf<uint32_t>(ctx, "sd_sp", 32 * S * n);
+    uint32_t* de1 = buf<uint32_t>(ctx, "sd_e1", 64 * S * n);
+    uint32_t* dct = buf<uint32_t>(ctx, "sd_ct", 64 * S * n);
+    dkgk::decode_points(dpk, Ck, pk_ext, Ck, pk_ok, st);
+    bf_reset(ctx);
+    auto mark = [&](int phase) {  // phase times are recorded on one stream only, as the seats calls do
+      if (ctx->nsub == 1) bf_mark(ctx, st, phase);
+    };
+    mark(-1);
+    round1_device(ctx, S, n, t, da, db, Ec, Ac, ds, dsp);  // committee.rs:141-167 with D = S dealers
+    mark(SD_COMMIT);
+    // :164-178 per seat: items (p, q, w) at (p * n + q) * 2 + w, in chunks of seats
+    const size_t chunk = seat_deal_chunk(ctx, S, n, mode);
+    const size_t mslots = chunk * n, mi = 2 * mslots;
+    uint32_t* R = buf<uint32_t>(ctx, "bf.R", PTB * mi);
+    uint32_t* K = buf<uint32_t>(ctx, "bf.K", PTB * mi);
+    uint32_t* Kc = buf<uint32_t>(ctx, "bf.Kc", 32 * mi);
+    uint32_t *idx = nullptr, *pks = nullptr, *tab = nullptr;
+    if (mode == 1) {
+      idx = buf<uint32_t>(ctx, "sd_idx", 4 * mslots);
+      pks = buf<uint32_t>(ctx, "bf.pk_ext", PTB * mslots);
+      tab = buf<uint32_t>(ctx, "bf.tab", 4 * dkgk::benc_tab_words() * mslots);
+    }
+    for (size_t p0 = 0; p0 < S; p0 += chunk) {
+      const size_t Sc = std::min(chunk, S - p0), slots = Sc * n, items = 2 * slots;
+      const size_t q0 = p0 * n, i0 = 2 * q0;  // first (seat, recipient) slot / item
+      dkgk::fixed_base(items, dr + 8 * i0, ctx->tab_gw, R, st);  // e1 = G::generator() * r  (elgamal.rs:141)
+      mark(SD_E1);
+      if (mode == 1) {  // a comb per key slot: k_benc_tab, then k_benc_mul with one dealer row per key
+        dkgk::seat_key_index(slots, n, dkbase + p0, idx, st);
+        dkgk::seat_gather_points(slots, idx, pk_ext, Ck, pks, slots, st);
+        dkgk::benc_tab(slots, pks, slots, tab, st);
+        dkgk::benc_mul(slots, n, 1, dr + 8 * i0, tab, K, items, st);
+      } else {          // key = pk * r  (elgamal.rs:138-140), both products of a slot on one lane
+        dkgk::seat_enc_mul(slots, n, dkbase + p0, dr + 8 * i0, pk_ext, Ck, K, items, st);
+      }
+      mark(SD_MUL);
+      dkgk::encode_points(R, items, items, de1 + 8 * i0, st);
+      dkgk::encode_points(K, items, items, Kc, st);
+      mark(SD_ENCODE);
+      dkgk::sym_xor(Sc, n, Kc, false, dct + 8 * i0, ds + 8 * q0, dsp + 8 * q0, st);
+      mark(SD_SYM);
+    }
+    check_launch(ctx);
+    std::vector<uint8_t> okh(Ck), sh, sph;
+    d2h(ctx, okh.data(), pk_ok, Ck);
+    d2h(ctx, E, Ec, 32 * S * N);
+    d2h(ctx, A, Ac, 32 * S * N);
+    d2h(ctx, e1, de1, 64 * S * n);
+    d2h(ctx, ct, dct, 64 * S * n);
+    if (own && !s_out) sh.resize(32 * S * n), s_out = sh.data();
+    if (own && !sp_out) sph.resize(32 * S * n), sp_out = sph.data();
+    if (s_out) d2h(ctx, s_out, ds, 32 * S * n);
+    if (sp_out) d2h(ctx, sp_out, dsp, 32 * S * n);
+    sync(ctx);
+    collect_seat_deal_phases(ctx);
+    for (size_t k = 0; k < Ck; k++)
+      if (!okh[k]) {
+        ctx->err = "party_round1_seats: the key of recipient " + std::to_string(k % n) + " of ceremony " +
+                   std::to_string(cers[k / n]) + " does not decode";
+        return DKG_E_DECODE;
+      }
+    if (own)  // what init keeps as decrypted_shares[my - 1] (:179-185): the dealer's own (s', s)
+      for (size_t p = 0; p < S; p++) {
+        memcpy(own + 64 * p, sp_out + 32 * (p * n + js[p]), 32);
+        memcpy(own + 64 * p + 32, s_out + 32 * (p * n + js[p]), 32);
+      }
     return DKG_OK;
   });
 }

@@ -360,6 +360,48 @@ int dkg_party_round2_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S,
                            const uint8_t *sk, const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
                            int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
 
+/* ---- hosted seats deal round 1 (seat_deal.hip) ----
+ * Phases<Initialise>::init (committee.rs:124-216) for every seat of an operator in one call: seat p, party
+ * js[p] of ceremony cer[p] (the seats calls' rules above), commits to its two polynomials a[p], b[p]
+ * ([S][t+1][32] sharing / hiding coefficients), evaluates the n shares and randomness values and
+ * hybrid-encrypts both to ALL n members of its ceremony, itself included (:164-178), under r
+ * ([S][n][2][32], w = 0 the randomness s', 1 the share s; read reduced mod l).  pk [B][n][32] the sorted
+ * member keys per ceremony.  Output row p equals, byte for byte, dkg_share_gen(D = 1) on (a[p], b[p])
+ * followed by dkg_encrypt_shares(D = 1) to pk[cer[p]] with r[p]: E, A [S][t+1][32]; e1, ct [S][n][2][32]
+ * (the EncryptedShares of BroadcastPhase1); s_out, sp_out [S][n][32] (may be NULL); own [S][2][32] (may be
+ * NULL) = (s', s) at js[p], what init keeps as decrypted_shares[my - 1] (:179-185).
+ * Only the DISTINCT ceremonies named are decoded: a key set no seat names is never interpreted.  A key of
+ * a named ceremony that does not decode: DKG_E_DECODE, dkg_ctx_last_error names the ceremony and the
+ * recipient, the outputs are unspecified.  S == 0 returns DKG_OK and touches nothing.  Requires
+ * dkg_env_init (h) and dkg_env_check(t, n); DKG_E_ARG for B == 0, an index out of range or a NULL required
+ * pointer.  One stream: k_commit / k_share_eval with D = S, then per chunk of seats e1 = g r on the shared
+ * comb, K = pk r (below), the item-indexed encode and k_sym_xor.  The chunk keeps the hybrid stage's
+ * scratch within 2 GiB; dkg_ctx_set_batch_full_chunk forces it, counted in SEATS here; outputs do not
+ * depend on it.  Phase times (dkg_ctx_phase_ms; summed over the chunks): "seats.commit",
+ * "seats.deal_e1", "seats.deal_mul", "seats.deal_encode", "seats.deal_sym"; a phase that did not run
+ * reads -1.  Host pointers only: there is no device-pointer variant and no shard form. */
+int dkg_party_round1_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t *cer,
+                           const uint32_t *js, const uint8_t *a, const uint8_t *b, const uint8_t *r,
+                           const uint8_t *pk, uint8_t *E, uint8_t *A, uint8_t *e1, uint8_t *ct, uint8_t *s_out,
+                           uint8_t *sp_out, uint8_t *own);
+/* How dkg_party_round1_seats computes K = pk_q r (elgamal.rs:138-140).  A dealing seat uses each recipient
+ * key for exactly two items, so: 2 = the joint chain (k_seat_enc_mul): one lane per (seat, recipient)
+ * walks the signed radix-4 digits of both scalars right to left over M = 4^w pk -- 2 doublings and 2
+ * complete additions per window, no table; 1 = a signed radix-16 comb per key slot, k_benc_tab and
+ * k_benc_mul with one dealer row per key as the batches run them (80 KiB per slot, in chunks): the
+ * yardstick and an independent cross-check; 0 (default) = automatic, by profiles/seat_deal_time.json.
+ * Outputs do not depend on it.  dkg_ctx_set_field_mode does not apply to either.  DKG_E_ARG for any other
+ * mode. */
+int dkg_ctx_set_seat_deal(dkg_ctx *ctx, int mode);
+/* The route (1 or 2) the last dkg_party_round1_seats ran; 0 before the first. */
+int dkg_ctx_last_seat_deal(const dkg_ctx *ctx);
+/* The joint chain's recoding of one scalar, exactly as k_seat_enc_mul computes it (one routine serves
+ * both): signed radix-4 digits, sum_w digits[w] 4^w = k, *windows = 128 always; digits[w] in
+ * {-2, -1, 0, 1} below the top window, which keeps its value plus the carry in {0, 1, 2} ({0, 1} for
+ * k < 2^254, every canonical scalar among them).  DKG_E_ARG for k >= 2^255 or a NULL pointer.  Host-only,
+ * a pure function. */
+int dkg_seat_enc_digits(const uint8_t k[32], int8_t digits[128], int *windows);
+
 /* ---- hosted seats through rounds 3-5 (seat_finalise.hip) ----
  * What an operator's seats do after their share checks, without one call per ceremony and without data
  * an operator never holds (the n x n share matrix, the other parties' keys).  All calls take B ceremonies
