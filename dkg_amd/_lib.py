@@ -133,6 +133,10 @@ def lib():
     L.dkg_split_multipliers.argtypes = [sz, sz, ctypes.c_int, p, p]
     if hasattr(L, "dkg_zero_tests"):  # a test aid: absent from an older library loaded through DKG_AMD_LIB
         L.dkg_zero_tests.argtypes = [p, sz, p, p]
+    if hasattr(L, "dkg_fe_ops"):  # test aids, likewise
+        L.dkg_fe_ops.argtypes = [p, ctypes.c_int, ctypes.c_int, sz, p, p]
+    if hasattr(L, "dkg_sc_ops"):
+        L.dkg_sc_ops.argtypes = [p, ctypes.c_int, sz, p, p]
     L.dkg_jsf_digits.argtypes = [p, p, p, p, p]
     L.dkg_split_digits.argtypes = [sz, sz, ctypes.c_int, ctypes.c_int, p, p]
     L.dkg_ctx_phase_ms.argtypes = [p, ctypes.c_char_p]
@@ -295,7 +299,7 @@ EXPORTED = [
     "dkg_env_check", "dkg_msm_batch", "dkg_fixed_base_batch", "dkg_poly_eval_batch",
     "dkg_points_valid_batch", "dkg_share_gen", "dkg_verify_pairs", "dkg_verify_receiver",
     "dkg_ctx_set_split", "dkg_ctx_set_stepping", "dkg_ctx_set_field_mode", "dkg_ctx_set_binomial", "dkg_ctx_set_check", "dkg_ctx_last_split", "dkg_ctx_last_split_len", "dkg_ctx_set_verify_mode", "dkg_ctx_fallback_rows", "dkg_split_model_ms", "dkg_split_len",
-    "dkg_ctx_set_combine", "dkg_ctx_last_combine", "dkg_ctx_last_binomial", "dkg_ctx_set_addends", "dkg_ctx_set_stepping_formula", "dkg_ctx_stepping_redos", "dkg_zero_tests", "dkg_stepping_lane_map", "dkg_ctx_binomial_reruns", "dkg_ctx_binomial_wave_redos", "dkg_split_multipliers", "dkg_jsf_digits", "dkg_split_digits",
+    "dkg_ctx_set_combine", "dkg_ctx_last_combine", "dkg_ctx_last_binomial", "dkg_ctx_set_addends", "dkg_ctx_set_stepping_formula", "dkg_ctx_stepping_redos", "dkg_zero_tests", "dkg_fe_ops", "dkg_sc_ops", "dkg_stepping_lane_map", "dkg_ctx_binomial_reruns", "dkg_ctx_binomial_wave_redos", "dkg_split_multipliers", "dkg_jsf_digits", "dkg_split_digits",
     "dkg_ctx_clock_probe", "dkg_device_pci_bus_id",
     "dkg_ceremony_run", "dkg_ceremony_verify", "dkg_ceremony_verify_fetched", "dkg_ceremony_run_device", "dkg_ceremony_shard_device",
     "dkg_ceremony_shard_verify_device",

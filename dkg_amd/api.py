@@ -217,6 +217,41 @@ class Backend:
         _check(self._ctx, _lib.lib().dkg_zero_tests(self._ctx, count, arr, out))
         return [tuple(out.raw[3 * i:3 * i + 3]) for i in range(count)]
 
+    # words per operand tuple (in, out) of dkg_fe_ops / dkg_sc_ops, by op (include/dkg_amd.h)
+    FE_OPS = {"mul": (0, 20, 10), "sq": (1, 10, 10), "mul2": (2, 40, 20), "sq2": (3, 20, 20),
+              "mul_small": (4, 11, 10), "carry": (5, 10, 10), "add": (6, 20, 10), "sub": (7, 20, 10),
+              "neg": (8, 10, 10), "dbl": (9, 10, 10), "invert": (10, 10, 10), "pow22523": (11, 10, 10),
+              "tobytes": (12, 10, 10), "frombytes": (13, 8, 10), "abs": (14, 10, 10)}
+    SC_OPS = {"reduce9": (0, 9, 8), "reduce256": (1, 8, 8), "reduce512": (2, 16, 8), "add": (3, 16, 8),
+              "sub": (4, 16, 8), "neg": (5, 8, 8), "mul_small_add": (6, 17, 8), "horner2": (7, 25, 8),
+              "lazy": (8, 20, 18), "mont_mul": (9, 16, 8), "mul": (10, 16, 8), "mont_inv": (11, 8, 8),
+              "radix16": (12, 8, 16)}
+
+    @staticmethod
+    def _word_ops(table, op, tuples):
+        code, win, wout = table[op]
+        count = len(tuples)
+        flat = [w for tup in tuples for w in tup]
+        if len(flat) != win * count:
+            raise ValueError(f"{op}: every operand tuple takes {win} words")
+        arr = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+        out = (ctypes.c_uint32 * max(wout * count, 1))()
+        return code, count, wout, arr, out
+
+    def fe_ops(self, flavour: int, op: str, tuples) -> list:
+        """Test aid (dkg_fe_ops): the field primitive `op` (a key of FE_OPS) on each tuple of raw 32-bit
+        limb words, in flavour 1 (product scanning) or 2 (column sums); one list of output words per tuple."""
+        code, count, wout, arr, out = self._word_ops(self.FE_OPS, op, tuples)
+        _check(self._ctx, _lib.lib().dkg_fe_ops(self._ctx, flavour, code, count, arr, out))
+        return [list(out[wout * i:wout * (i + 1)]) for i in range(count)]
+
+    def sc_ops(self, op: str, tuples) -> list:
+        """Test aid (dkg_sc_ops): the scalar primitive `op` (a key of SC_OPS) on each tuple of 32-bit
+        words; one list of output words per tuple."""
+        code, count, wout, arr, out = self._word_ops(self.SC_OPS, op, tuples)
+        _check(self._ctx, _lib.lib().dkg_sc_ops(self._ctx, code, count, arr, out))
+        return [list(out[wout * i:wout * (i + 1)]) for i in range(count)]
+
     def binomial_reruns(self) -> int:
         """1 when the last ceremony / shard call reran its verification with the complete formula
         (a dedicated addition of the per-step binomial met an exceptional pair), else 0."""

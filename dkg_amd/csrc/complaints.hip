@@ -26,21 +26,6 @@ namespace {
 __device__ const uint32_t CMP_G[8] = {0x0aaef2e2u, 0x714ebc6au, 0x61a984a8u, 0x5f5100c5u,
                                       0x6a0be358u, 0x8ddd82a5u, 0x4559a6b6u, 0x762d8de0u};
 
-// r = -a mod l (a canonical)
-DKG_DEV void sc_neg(sc& r, const sc& a) {
-  uint32_t nz = 0;
-  int64_t b = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    nz |= a.v[i];
-    const int64_t d = (int64_t)sc_const::L[i] - (int64_t)a.v[i] + b;
-    r.v[i] = (uint32_t)d;
-    b = d >> 32;
-  }
-#pragma unroll
-  for (int i = 0; i < 8; i++) r.v[i] = nz ? r.v[i] : 0u;
-}
-
 // Scalar::from_bytes_mod_order_wide of a 64-byte hash: lo + hi 2^256 mod l
 DKG_DEV void sc_wide(sc& r, const uint64_t (&h)[8]) {
   uint32_t lo[8], hi[8];

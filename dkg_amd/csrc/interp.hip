@@ -19,22 +19,6 @@
 
 namespace dkgk {
 
-DKG_DEV void sc_sub(sc& r, const sc& a, const sc& b) {  // a - b mod l, a, b < l
-  uint32_t w[9];
-  int64_t acc = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    acc += (int64_t)a.v[i] - b.v[i];
-    w[i] = (uint32_t)acc;
-    acc >>= 32;
-  }
-  sc t;
-#pragma unroll
-  for (int i = 0; i < 8; i++) t.v[i] = w[i];
-  sc_add_l_if(t, acc < 0);
-  r = t;
-}
-
 DKG_DEV bool sc_eq(const sc& a, const sc& b) {
   uint32_t d = 0;
 #pragma unroll

@@ -1011,6 +1011,185 @@ void zero_tests(size_t count, const uint32_t* limbs, uint8_t* out, hipStream_t s
   hipLaunchKernelGGL(k_zero_tests, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, count, limbs, out);
 }
 
+// Test aid: one primitive of fe25519.h on caller-supplied limbs, one operand tuple per lane, in the
+// flavour this translation unit compiles.  Raw limb words in and out (FE_OP_* of kernels_decl.inc give
+// the tuple layouts); the operands come from memory, so nothing is folded at compile time.
+DKG_DEV void fe_ld_raw(fe& r, const uint32_t* __restrict__ p) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) r.v[i] = p[i];
+}
+DKG_DEV void fe_st_raw(uint32_t* __restrict__ p, const fe& a) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) p[i] = a.v[i];
+}
+template <int OP>
+__global__ __launch_bounds__(64) void k_fe_ops(size_t count, size_t win, size_t wout, const uint32_t* __restrict__ in,
+                                               uint32_t* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (e >= count) return;
+  const uint32_t* x = in + e * win;
+  uint32_t* y = out + e * wout;
+  fe a, b, c, d, r, s;
+  if (OP == FE_OP_FROMBYTES) {
+    uint32_t w[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) w[i] = x[i];
+    fe_frombytes32(r, w);
+    fe_st_raw(y, r);
+    return;
+  }
+  fe_ld_raw(a, x);
+  if (OP == FE_OP_MUL || OP == FE_OP_MUL2 || OP == FE_OP_SQ2 || OP == FE_OP_ADD || OP == FE_OP_SUB) fe_ld_raw(b, x + 10);
+  if (OP == FE_OP_MUL2) {
+    fe_ld_raw(c, x + 20);
+    fe_ld_raw(d, x + 30);
+  }
+  if (OP == FE_OP_MUL) fe_mul(r, a, b);
+  if (OP == FE_OP_SQ) fe_sq(r, a);
+  if (OP == FE_OP_MUL2) fe_mul2(r, a, b, s, c, d);
+  if (OP == FE_OP_SQ2) fe_sq2(r, a, s, b);
+  if (OP == FE_OP_MUL_SMALL) fe_mul_small(r, a, x[10]);
+  if (OP == FE_OP_CARRY) fe_carry(r, a);
+  if (OP == FE_OP_ADD) fe_add(r, a, b);
+  if (OP == FE_OP_SUB) fe_sub(r, a, b);
+  if (OP == FE_OP_NEG) fe_neg(r, a);
+  if (OP == FE_OP_DBL) fe_dbl(r, a);
+  if (OP == FE_OP_INVERT) fe_invert(r, a);
+  if (OP == FE_OP_POW22523) fe_pow22523(r, a);
+  if (OP == FE_OP_ABS) fe_abs(r, a);
+  if (OP == FE_OP_TOBYTES) {
+    uint32_t w[8];
+    fe_tobytes32(w, a);
+#pragma unroll
+    for (int i = 0; i < 8; i++) y[i] = w[i];
+    y[8] = fe_isneg(a);
+    y[9] = fe_iszero(a) ? 1u : 0u;
+    return;
+  }
+  fe_st_raw(y, r);
+  if (OP == FE_OP_MUL2 || OP == FE_OP_SQ2) fe_st_raw(y + 10, s);
+}
+
+bool fe_ops_shape(int op, size_t* win, size_t* wout) {
+  static const uint8_t shape[FE_OP_COUNT][2] = {{20, 10}, {10, 10}, {40, 20}, {20, 20}, {11, 10}, {10, 10}, {20, 10}, {20, 10},
+                                                {10, 10}, {10, 10}, {10, 10}, {10, 10}, {10, 10}, {8, 10},  {10, 10}};
+  if (op < 0 || op >= FE_OP_COUNT) return false;
+  *win = shape[op][0];
+  *wout = shape[op][1];
+  return true;
+}
+
+template <int OP>
+static void fe_ops_launch(int op, size_t count, size_t win, size_t wout, const uint32_t* in, uint32_t* out,
+                          hipStream_t stream) {
+  if (op == OP)
+    hipLaunchKernelGGL(k_fe_ops<OP>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, count, win, wout, in, out);
+  if constexpr (OP + 1 < FE_OP_COUNT) fe_ops_launch<OP + 1>(op, count, win, wout, in, out, stream);
+}
+void fe_ops(int op, size_t count, const uint32_t* in, uint32_t* out, hipStream_t stream) {
+  size_t win, wout;
+  if (!count || !fe_ops_shape(op, &win, &wout)) return;
+  fe_ops_launch<0>(op, count, win, wout, in, out, stream);
+}
+
+#ifndef DKG_FE_ILP  // the scalars have one flavour: only the dkgk copy carries their aid
+// Test aid: one primitive of sc25519.h per lane on caller-supplied words (SC_OP_* of kernels_decl.inc).
+template <int OP>
+__global__ __launch_bounds__(64) void k_sc_ops(size_t count, size_t win, size_t wout, const uint32_t* __restrict__ in,
+                                               uint32_t* __restrict__ out) {
+  const size_t e = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (e >= count) return;
+  const uint32_t* x = in + e * win;
+  uint32_t* y = out + e * wout;
+  sc a, b, c, r;
+#pragma unroll
+  for (int i = 0; i < 8; i++) a.v[i] = x[i];
+  if (OP == SC_OP_REDUCE9) {
+    uint32_t w[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) w[i] = x[i];
+    sc_reduce9(r, w);
+  }
+  if (OP == SC_OP_REDUCE256) sc_reduce256(r, a.v);
+  if (OP == SC_OP_REDUCE512) {
+    uint32_t w[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) w[i] = x[i];
+    sc_reduce512(r, w);
+  }
+  if (OP == SC_OP_ADD || OP == SC_OP_SUB || OP == SC_OP_MONT_MUL || OP == SC_OP_MUL) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) b.v[i] = x[8 + i];
+  }
+  if (OP == SC_OP_ADD) sc_add(r, a, b);
+  if (OP == SC_OP_SUB) sc_sub(r, a, b);
+  if (OP == SC_OP_NEG) sc_neg(r, a);
+  if (OP == SC_OP_MONT_MUL) sc_mont_mul(r, a, b);
+  if (OP == SC_OP_MUL) sc_mul(r, a, b);
+  if (OP == SC_OP_MONT_INV) sc_mont_inv(r, a);
+  if (OP == SC_OP_MUL_SMALL_ADD || OP == SC_OP_HORNER2) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) b.v[i] = x[9 + i];
+  }
+  if (OP == SC_OP_MUL_SMALL_ADD) sc_mul_small_add(r, a, x[8], b);
+  if (OP == SC_OP_HORNER2) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) c.v[i] = x[17 + i];
+    sc_horner2(r, a, x[8], b, c);
+  }
+  if (OP == SC_OP_LAZY) {  // state [10], steps (<= SC_LAZY_STEPS, checked by the caller), x, coefficient [8]
+    uint32_t v[10];
+#pragma unroll
+    for (int i = 0; i < 10; i++) v[i] = x[i];
+    const uint32_t steps = x[10], pt = x[11];
+#pragma unroll
+    for (int i = 0; i < 8; i++) c.v[i] = x[12 + i];
+#pragma unroll 1
+    for (uint32_t k = 0; k < steps; k++) sc_lazy_step(v, pt, c);
+    sc_lazy_fold(v);
+    sc_lazy_final(r, v);
+#pragma unroll
+    for (int i = 0; i < 10; i++) y[i] = v[i];
+    y += 10;
+  }
+  if (OP == SC_OP_RADIX16) {  // 64 signed digits, four to a word (byte k of word i = digit 4 i + k)
+    int8_t dg[64];
+    sc_radix16(dg, a);
+#pragma unroll
+    for (int i = 0; i < 16; i++)
+      y[i] = (uint32_t)(uint8_t)dg[4 * i] | ((uint32_t)(uint8_t)dg[4 * i + 1] << 8) |
+             ((uint32_t)(uint8_t)dg[4 * i + 2] << 16) | ((uint32_t)(uint8_t)dg[4 * i + 3] << 24);
+    return;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) y[i] = r.v[i];
+}
+
+bool sc_ops_shape(int op, size_t* win, size_t* wout) {
+  static const uint8_t shape[SC_OP_COUNT][2] = {{9, 8},  {8, 8},  {16, 8},  {16, 8}, {16, 8}, {8, 8}, {17, 8},
+                                                {25, 8}, {20, 18}, {16, 8}, {16, 8}, {8, 8},  {8, 16}};
+  if (op < 0 || op >= SC_OP_COUNT) return false;
+  *win = shape[op][0];
+  *wout = shape[op][1];
+  return true;
+}
+
+uint32_t sc_ops_lazy_steps() { return SC_LAZY_STEPS; }
+
+template <int OP>
+static void sc_ops_launch(int op, size_t count, size_t win, size_t wout, const uint32_t* in, uint32_t* out,
+                          hipStream_t stream) {
+  if (op == OP)
+    hipLaunchKernelGGL(k_sc_ops<OP>, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, stream, count, win, wout, in, out);
+  if constexpr (OP + 1 < SC_OP_COUNT) sc_ops_launch<OP + 1>(op, count, win, wout, in, out, stream);
+}
+void sc_ops(int op, size_t count, const uint32_t* in, uint32_t* out, hipStream_t stream) {
+  size_t win, wout;
+  if (!count || !sc_ops_shape(op, &win, &wout)) return;
+  sc_ops_launch<0>(op, count, win, wout, in, out, stream);
+}
+#endif  // !DKG_FE_ILP
+
 // The stepping's store of one evaluation: the point-major record, and Z once more in a dense 40-B
 // record when the affine normalisation reads only Z in its first pass (Rz)
 DKG_DEV void step_store_r(uint32_t* __restrict__ R, uint32_t* __restrict__ Rz, size_t e, const ge_p3& D) {

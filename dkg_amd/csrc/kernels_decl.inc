@@ -133,6 +133,29 @@ double stepping_waves_per_simd(size_t cols, size_t N, size_t pieces, size_t last
 size_t stepping_flag_words(size_t ndealers, size_t pieces);
 // test aid (dkg_zero_tests): out[count][3] = fe_maybe_zero, fe_tight_zero, fe_zero_guard of limbs[count][10]
 void zero_tests(size_t count, const uint32_t* limbs, uint8_t* out, hipStream_t stream);
+// test aid (dkg_fe_ops): one fe25519.h primitive per lane, in this copy's flavour of the products.  in
+// [count][win] and out [count][wout] raw 32-bit words (fe_ops_shape; false for an unknown op): ten limbs
+// per element, operands in the primitive's argument order.  MUL2 (fa, ga, fb, gb) and SQ2 (fa, fb) return
+// both results; MUL_SMALL takes the limbs and k; TOBYTES returns the 8 words, fe_isneg, fe_iszero;
+// FROMBYTES takes 8 words.
+enum {
+  FE_OP_MUL, FE_OP_SQ, FE_OP_MUL2, FE_OP_SQ2, FE_OP_MUL_SMALL, FE_OP_CARRY, FE_OP_ADD, FE_OP_SUB, FE_OP_NEG,
+  FE_OP_DBL, FE_OP_INVERT, FE_OP_POW22523, FE_OP_TOBYTES, FE_OP_FROMBYTES, FE_OP_ABS, FE_OP_COUNT
+};
+bool fe_ops_shape(int op, size_t* win, size_t* wout);
+void fe_ops(int op, size_t count, const uint32_t* in, uint32_t* out, hipStream_t stream);
+// test aid (dkg_sc_ops; the product-scanning copy only): one sc25519.h primitive per lane on 32-bit
+// words.  REDUCE9 / REDUCE256 / REDUCE512 take 9 / 8 / 16 words; MUL_SMALL_ADD (a, x, c); HORNER2 (a, x,
+// c1, c0); LAZY takes (state [10], steps <= SC_LAZY_STEPS, x, coefficient [8]), runs the steps and
+// sc_lazy_fold, and returns the folded state [10] and sc_lazy_final [8]; RADIX16 returns the 64 signed
+// digits as bytes, four to a word.
+enum {
+  SC_OP_REDUCE9, SC_OP_REDUCE256, SC_OP_REDUCE512, SC_OP_ADD, SC_OP_SUB, SC_OP_NEG, SC_OP_MUL_SMALL_ADD,
+  SC_OP_HORNER2, SC_OP_LAZY, SC_OP_MONT_MUL, SC_OP_MUL, SC_OP_MONT_INV, SC_OP_RADIX16, SC_OP_COUNT
+};
+bool sc_ops_shape(int op, size_t* win, size_t* wout);
+uint32_t sc_ops_lazy_steps();  // SC_LAZY_STEPS of sc25519.h
+void sc_ops(int op, size_t count, const uint32_t* in, uint32_t* out, hipStream_t stream);
 // Rz (may be null): also a dense copy of every stored point's Z, 10 words per point at the index of
 // R (read by affine_pieces).
 // col0, dreal, gw: column c (0-based within this call) is global table column col0 + c of dealer

@@ -3433,6 +3433,46 @@ int dkg_zero_tests(dkg_ctx* ctx, size_t count, const uint32_t* limbs, uint8_t* o
   });
 }
 
+int dkg_fe_ops(dkg_ctx* ctx, int flavour, int op, size_t count, const uint32_t* in, uint32_t* out) {
+  return guarded(ctx, [&] {
+    size_t win, wout;
+    if ((flavour != 1 && flavour != 2) || !dkgk::fe_ops_shape(op, &win, &wout)) return DKG_E_ARG;
+    if (count == 0) return DKG_OK;
+    if (!in || !out) return DKG_E_ARG;
+    uint32_t* di = buf<uint32_t>(ctx, "fo_in", 4 * win * count);
+    uint32_t* od = buf<uint32_t>(ctx, "fo_out", 4 * wout * count);
+    h2d(ctx, di, in, 4 * win * count);
+    (flavour == 2 ? dkgk_ilp::fe_ops : dkgk::fe_ops)(op, count, di, od, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, out, od, 4 * wout * count);
+    sync(ctx);
+    return DKG_OK;
+  });
+}
+
+int dkg_sc_ops(dkg_ctx* ctx, int op, size_t count, const uint32_t* in, uint32_t* out) {
+  return guarded(ctx, [&] {
+    size_t win, wout;
+    if (!dkgk::sc_ops_shape(op, &win, &wout)) return DKG_E_ARG;
+    if (count == 0) return DKG_OK;
+    if (!in || !out) return DKG_E_ARG;
+    if (op == dkgk::SC_OP_LAZY)
+      for (size_t e = 0; e < count; e++)
+        if (in[e * win + 10] > dkgk::sc_ops_lazy_steps()) {
+          ctx->err = "sc_ops: more lazy steps than SC_LAZY_STEPS";
+          return DKG_E_ARG;
+        }
+    uint32_t* di = buf<uint32_t>(ctx, "so_in", 4 * win * count);
+    uint32_t* od = buf<uint32_t>(ctx, "so_out", 4 * wout * count);
+    h2d(ctx, di, in, 4 * win * count);
+    dkgk::sc_ops(op, count, di, od, ctx->stream);
+    check_launch(ctx);
+    d2h(ctx, out, od, 4 * wout * count);
+    sync(ctx);
+    return DKG_OK;
+  });
+}
+
 int dkg_points_valid_batch(dkg_ctx* ctx, size_t count, const uint8_t* points, uint8_t* ok) {
   return guarded(ctx, [&] {
     if (count == 0) return DKG_OK;

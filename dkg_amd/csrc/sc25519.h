@@ -183,6 +183,36 @@ DKG_DEV void sc_add(sc& r, const sc& a, const sc& b) {
   sc_reduce9(r, w);
 }
 
+DKG_DEV void sc_sub(sc& r, const sc& a, const sc& b) {  // a - b mod l, a, b < l
+  uint32_t w[9];
+  int64_t acc = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    acc += (int64_t)a.v[i] - b.v[i];
+    w[i] = (uint32_t)acc;
+    acc >>= 32;
+  }
+  sc t;
+#pragma unroll
+  for (int i = 0; i < 8; i++) t.v[i] = w[i];
+  sc_add_l_if(t, acc < 0);
+  r = t;
+}
+
+// r = -a mod l for a < l
+DKG_DEV void sc_neg(sc& r, const sc& a) {
+  uint32_t nz = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) nz |= a.v[i];
+  int64_t b = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int64_t d = (int64_t)sc_const::L[i] - (int64_t)a.v[i] + b;
+    r.v[i] = nz ? (uint32_t)d : 0u;
+    b = d >> 32;
+  }
+}
+
 // Reduce any 256-bit value (e.g. a `from_bits` input, groups.rs:29-36) to canonical form.
 DKG_DEV void sc_reduce256(sc& r, const uint32_t (&x)[8]) {
   uint32_t w[9];
@@ -243,6 +273,35 @@ DKG_DEV void sc_mul(sc& r, const sc& a, const sc& b) {
   for (int i = 0; i < 8; i++) rr.v[i] = sc_const::RR[i];
   sc_mont_mul(ab, a, b);    // a b / R
   sc_mont_mul(r, ab, rr);   // a b
+}
+
+// r = a^(l - 2) R for a != 0 given as a R (R = 2^256): the inverse in Montgomery form.  l - 2 =
+// 2^252 + 0x14def9dea2f79cd65812631a5cf5d3eb: the top bit starts the chain, 252 squarings follow.
+DKG_DEV void sc_mont_inv(sc& r, const sc am) {  // by value: r may be the same object
+  const uint32_t e[4] = {0x5cf5d3ebu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu};
+  r = am;
+#pragma unroll 1
+  for (int bit = 251; bit >= 0; bit--) {
+    sc_mont_mul(r, r, r);
+    if (bit < 128 && ((e[bit >> 5] >> (bit & 31)) & 1u)) sc_mont_mul(r, r, am);  // wave-uniform
+  }
+}
+
+// 512-bit little-endian value (16 words) mod l: lo + hi * 2^256 = lo + MontMul(hi, R^2).
+__device__ inline void sc_reduce512(sc& r, const uint32_t (&w)[16]) {
+  uint32_t lo[8], hi[8];
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    lo[i] = w[i];
+    hi[i] = w[8 + i];
+  }
+  sc a, b, rr;
+  sc_reduce256(a, lo);
+  sc_reduce256(b, hi);
+#pragma unroll
+  for (int i = 0; i < 8; i++) rr.v[i] = sc_const::RR[i];
+  sc_mont_mul(b, b, rr);  // hi * 2^256 mod l
+  sc_add(r, a, b);
 }
 
 // Signed radix-16 recoding (64 digits in [-8, 8)), as dalek Scalar::to_radix_16; s < 2^255.

@@ -31,20 +31,6 @@ DKG_DEV void sc_st(uint32_t* __restrict__ p, const sc& s) {
   q[1] = make_uint4(s.v[4], s.v[5], s.v[6], s.v[7]);
 }
 
-// r = -a mod l for a < l
-DKG_DEV void sc_neg(sc& r, const sc& a) {
-  uint32_t nz = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) nz |= a.v[i];
-  int64_t b = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    const int64_t d = (int64_t)sc_const::L[i] - (int64_t)a.v[i] + b;
-    r.v[i] = nz ? (uint32_t)d : 0u;
-    b = d >> 32;
-  }
-}
-
 // The sum of acc over the wave's 64 lanes, valid in lane 0 (the upper lanes hold partial sums).
 DKG_DEV void sc_wave_sum(sc& acc) {
 #pragma unroll 1
@@ -53,18 +39,6 @@ DKG_DEV void sc_wave_sum(sc& acc) {
 #pragma unroll
     for (int w = 0; w < 8; w++) o.v[w] = (uint32_t)__shfl_down((int)acc.v[w], off, 64);
     sc_add(acc, acc, o);
-  }
-}
-
-// r = a^(l - 2) R for a != 0 given as a R (R = 2^256): the inverse in Montgomery form.  l - 2 =
-// 2^252 + 0x14def9dea2f79cd65812631a5cf5d3eb: the top bit starts the chain, 252 squarings follow.
-DKG_DEV void sc_mont_inv(sc& r, const sc am) {  // by value: r may be the same object
-  const uint32_t e[4] = {0x5cf5d3ebu, 0x5812631au, 0xa2f79cd6u, 0x14def9deu};
-  r = am;
-#pragma unroll 1
-  for (int bit = 251; bit >= 0; bit--) {
-    sc_mont_mul(r, r, r);
-    if (bit < 128 && ((e[bit >> 5] >> (bit & 31)) & 1u)) sc_mont_mul(r, r, am);  // wave-uniform
   }
 }
 

@@ -13,23 +13,6 @@ namespace dkgk {
 
 using namespace sym;
 
-// 512-bit little-endian value (16 words) mod l: lo + hi * 2^256 = lo + MontMul(hi, R^2).
-__device__ void sc_reduce512(sc& r, const uint32_t (&w)[16]) {
-  uint32_t lo[8], hi[8];
-#pragma unroll
-  for (int i = 0; i < 8; i++) {
-    lo[i] = w[i];
-    hi[i] = w[8 + i];
-  }
-  sc a, b, rr;
-  sc_reduce256(a, lo);
-  sc_reduce256(b, hi);
-#pragma unroll
-  for (int i = 0; i < 8; i++) rr.v[i] = sc_const::RR[i];
-  sc_mont_mul(b, b, rr);  // hi * 2^256 mod l
-  sc_add(r, a, b);
-}
-
 // Row r = ceremony (c0 + r / D) dealer (d0 + r % D): seed words [rows][8].
 __global__ __launch_bounds__(256) void k_dealer_seeds(size_t rows, size_t D, size_t d0, uint32_t c0,
                                                       const uint32_t* __restrict__ master, uint32_t* __restrict__ seeds) {

@@ -143,6 +143,31 @@ long long dkg_ctx_stepping_redos(dkg_ctx *ctx);
  * (fe_tight_zero), and the filtered guard the dedicated additions use (fe_zero_guard), each 0 or 1.
  * The guard equals the full test on every input. */
 int dkg_zero_tests(dkg_ctx *ctx, size_t count, const uint32_t *limbs, uint8_t *out);
+/* Test aid: one field primitive (fe25519.h) on count operand tuples of raw 32-bit limb words, one tuple
+ * per lane; results are limbs too, so their bounds can be checked.  flavour as dkg_ctx_set_field_mode:
+ * 1 product scanning, 2 column sums.  op, with the words per tuple in -> out (an element is ten limbs):
+ *   0 fe_mul (f, g) 20 -> 10          1 fe_sq 10 -> 10
+ *   2 fe_mul2 (fa, ga, fb, gb) 40 -> 20 (ra, rb)      3 fe_sq2 (fa, fb) 20 -> 20
+ *   4 fe_mul_small (a, k < 2^12) 11 -> 10             5 fe_carry 10 -> 10
+ *   6 fe_add (a, b) 20 -> 10          7 fe_sub (a, b) 20 -> 10
+ *   8 fe_neg 10 -> 10                 9 fe_dbl 10 -> 10
+ *  10 fe_invert 10 -> 10             11 fe_pow22523 10 -> 10
+ *  12 fe_tobytes32 10 -> 10: the 8 words, fe_isneg, fe_iszero
+ *  13 fe_frombytes32 8 -> 10         14 fe_abs 10 -> 10
+ * The operands must lie in the primitive's documented range.  DKG_E_ARG for an unknown op or flavour;
+ * count == 0 touches nothing. */
+int dkg_fe_ops(dkg_ctx *ctx, int flavour, int op, size_t count, const uint32_t *in, uint32_t *out);
+/* Test aid: one scalar primitive (sc25519.h) on count operand tuples of 32-bit little-endian words, one
+ * per lane (a scalar is 8 words).  op, with the words per tuple in -> out:
+ *   0 sc_reduce9 9 -> 8               1 sc_reduce256 8 -> 8           2 sc_reduce512 16 -> 8
+ *   3 sc_add (a, b) 16 -> 8           4 sc_sub (a, b) 16 -> 8         5 sc_neg 8 -> 8
+ *   6 sc_mul_small_add (a, x, c) 17 -> 8              7 sc_horner2 (a, x, c1, c0) 25 -> 8
+ *   8 the lazy accumulator (state [10], steps <= 5, x, coefficient [8]) 20 -> 18: `steps` calls of
+ *     sc_lazy_step, then sc_lazy_fold; the folded state [10] and sc_lazy_final [8]
+ *   9 sc_mont_mul (a, b) 16 -> 8     10 sc_mul (a, b) 16 -> 8        11 sc_mont_inv 8 -> 8
+ *  12 sc_radix16 8 -> 16: the 64 signed digits as bytes, four to a word
+ * DKG_E_ARG for an unknown op or too many lazy steps; count == 0 touches nothing. */
+int dkg_sc_ops(dkg_ctx *ctx, int op, size_t count, const uint32_t *in, uint32_t *out);
 /* The stepping's banded lane map ("Dead positions"): a `lanes`-lane workgroup
  * made of slots of `nseg` segments, `seg_len` lanes each except a slot's last (`last_len`).  Returns
  * the band width B (wave w holds positions [wB, (w+1)B) of every segment) and fills out[0..2] with

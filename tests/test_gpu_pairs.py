@@ -134,6 +134,36 @@ def test_lengths_around_the_wave(be, golden, N):
         assert P[32 * p:32 * p + 32] == exp[32 * p:32 * p + 32], pairs[p]
 
 
+# ---------------------------------------------------------------- both copies of k_pair_eval
+def test_field_modes(be, golden):
+    """k_pair_eval is compiled with both field multiplications and the runtime picks one per launch: the
+    product-scanning copy (dkg_ctx_set_field_mode 1) and the column-sum copy (2) give the bytes of the
+    default, at N = 65 (one past a wave) and on the n = 16 ceremony's shuffled pairs with a forced chunk."""
+    sp = golden("spot_n256_t127.json")
+    cat = b"".join(H(d["E"]) for d in sp["dealers"])
+    N = 65
+    C65 = cat[:32 * N] + cat[32 * (256 - N):]
+    pairs65 = [(i, x - 1) for x in (1, 4096, 1 << 24) for i in range(2)]
+    c = golden("ceremony_n16_t7.json")
+    n, t = c["n"], c["t"]
+    CE = H(c["E"])
+    rng = random.Random(16)
+    pairs = [(i, j) for i in range(n) for j in range(n)]
+    rng.shuffle(pairs)
+    exp65, exp = expect(C65, N, pairs65, {}), expect(CE, t + 1, pairs, {})
+    try:
+        for mode in (0, 1, 2):
+            be.set_field_mode(mode)
+            be.set_receiver_chunk(0)
+            assert run(be, 2, N - 1, pairs65, C65) == (exp65, b"\x01" * len(pairs65)), mode
+            for chunk in (0, 3):
+                be.set_receiver_chunk(chunk)
+                assert run(be, n, t, pairs, CE) == (exp, b"\x01" * len(pairs)), (mode, chunk)
+    finally:
+        be.set_field_mode(0)
+        be.set_receiver_chunk(0)
+
+
 # ---------------------------------------------------------------- order, slots, arguments
 def test_order_independence(be, golden):
     """The same pairs permuted give the permuted outputs: an item's slot among the call's distinct indices

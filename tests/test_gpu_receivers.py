@@ -167,6 +167,38 @@ def test_shapes(be, n, t, js, chunks):
     shaped_case(be, n, t, js, chunks)
 
 
+# ---------------------------------------------------------------- both copies of k_recv_chunks / k_recv_fold
+def test_field_modes(be, golden):
+    """The chunk and fold kernels are compiled with both field multiplications and the runtime picks one
+    per call: the product-scanning copies (dkg_ctx_set_field_mode 1) and the column-sum copies (2) give
+    the bytes of the default, on the n = 10 fixture's columns (one chunk, and three chunks with a fold)
+    and on a shape with a ragged dealer group and five chunks."""
+    c = golden("ceremony_n10_t4.json")
+    n, t = c["n"], c["t"]
+    js = list(range(n))
+    E, A = H(c["E"]), H(c["A"])
+    s, sp = columns(H(c["s"]), n, js), columns(H(c["s_prime"]), n, js)
+    qual = bytes(1 if q else 0 for q in c["qualified"])
+    exp2, exp4 = col_str(c["dec2"], n, js), col_str(c["dec4"], n, js)
+    points = {}
+    try:
+        for mode in (0, 1, 2):
+            be.set_field_mode(mode)
+            be.env_init(t, n, CK)
+            for chunk in (0, 2):
+                be.set_receiver_chunk(chunk)
+                assert dec_str(be.verify_receivers(n, t, 2, js, E, s, sp)) == exp2, (mode, chunk)
+                assert dec_str(be.verify_receivers(n, t, 4, js, A, s, None, qual)) == exp4, (mode, chunk)
+                # the evaluated points themselves: mode 0 (first) is the default's bytes
+                got = be.commitment_eval(n, t, js, E)
+                assert got == points.setdefault(chunk, got), (mode, chunk)
+            if mode:
+                shaped_case(be, 70, 34, [69, 3, 34, 3], (8,))
+    finally:
+        be.set_field_mode(0)
+        be.set_receiver_chunk(0)
+
+
 def test_wide_index_short_polynomial(be):
     """(4096, 3): multipliers of 12-13 bits, N smaller than any useful chunk."""
     shaped_case(be, 4096, 3, [4094, 4095, 2730], (0, 2))
