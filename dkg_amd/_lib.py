@@ -180,6 +180,13 @@ def lib():
         L.dkg_ctx_set_seat_deal.argtypes = [p, ctypes.c_int]
         L.dkg_ctx_last_seat_deal.argtypes = [p]
         L.dkg_seat_enc_digits.argtypes = [p, p, ctypes.POINTER(ctypes.c_int)]
+    if hasattr(L, "dkg_seat_eval_shape"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_seat_eval_shape.argtypes = [sz, sz, sz, ctypes.c_uint32, ctypes.c_int] + [ctypes.POINTER(ctypes.c_uint32)] * 3 + [
+            ctypes.POINTER(ctypes.c_uint64)]
+        L.dkg_seat_eval_constants.argtypes = [ctypes.POINTER(ctypes.c_double)]
+        L.dkg_seat_eval_constants.restype = None
+        L.dkg_ctx_set_seat_eval.argtypes = [p, ctypes.c_int, ctypes.c_int]
+        L.dkg_ctx_last_seat_eval.argtypes = [p, ctypes.POINTER(ctypes.c_int)]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -330,4 +337,5 @@ EXPORTED = [
     "dkg_complaints_verify_ceremonies", "dkg_complaints3_verify_ceremonies", "dkg_party_round3_seats", "dkg_finalise_seats",
     "dkg_seat_finalise_status",
     "dkg_party_round1_seats", "dkg_ctx_set_seat_deal", "dkg_ctx_last_seat_deal", "dkg_seat_enc_digits",
+    "dkg_seat_eval_shape", "dkg_seat_eval_constants", "dkg_ctx_set_seat_eval", "dkg_ctx_last_seat_eval",
 ]

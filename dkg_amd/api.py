@@ -312,7 +312,7 @@ class Backend:
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("decode", "eval") if tag == "pairs"
-                 else ("decrypt", "decode", "eval", "check", "prove", "lagrange", "mpk", "commit", "deal_e1", "deal_mul",
+                 else ("decrypt", "decode", "eval", "fold", "check", "prove", "lagrange", "mpk", "commit", "deal_e1", "deal_mul",
                        "deal_encode", "deal_sym") if tag == "seats"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
                  if tag == "full" else ("binomial", "stepping", "combine", "check"))
@@ -513,6 +513,19 @@ class Backend:
     def last_seat_deal(self) -> int:
         """The route (1 or 2) the last party_round1_seats ran; 0 before the first."""
         return _lib.lib().dkg_ctx_last_seat_deal(self._ctx)
+
+    def set_seat_eval(self, mode: int = 0, chunk: int = 0):
+        """The evaluation of commitment_eval_seats / verify_seats / party_round2_seats: 0 (default) automatic
+        by seat_eval_shape's rule, 1 the serial walk, 2 chunked with seat_eval_shape(.., chunk) (chunk 0: the
+        rule's; a shape of one chunk runs the serial walk).  chunk must be 0 outside mode 2.  Outputs do not
+        depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_seat_eval(self._ctx, mode, chunk))
+
+    def last_seat_eval(self) -> tuple:
+        """(route, L) of the last seats call: route 1 serial (L = t + 1) or 2 chunked; (0, 0) before the first."""
+        c = ctypes.c_int(0)
+        mode = _lib.lib().dkg_ctx_last_seat_eval(self._ctx, ctypes.byref(c))
+        return mode, c.value
 
     # ---- hosted seats through rounds 3-5 (k_seat_lagrange; the batch's complaint kernels)
     def complaints_verify_ceremonies(self, B: int, n: int, t: int, ceremony: Sequence[int], accusers: Sequence[int],
@@ -1298,6 +1311,23 @@ def seat_pack(n: int, js: Sequence[int]) -> dict:
         raise _lib.DkgError(rc, "seat_pack")
     return {"width": v[0].value, "per_wave": v[1].value, "tiles": v[2].value, "wave_of": list(wave_of[:S]),
             "slot_of": list(slot_of[:S]), "waves": v[3].value}
+
+
+def seat_eval_shape(n: int, t: int, waves: int, x_max: int, chunk: int = 0) -> dict:
+    """dkg_seat_eval_shape (host only): the shape the seats calls evaluate `waves` waves of seat_pack in, the
+    largest index being x_max (1-based).  Keys: chunk (L), chunks (G), stages, scratch_bytes, constants (the
+    rule's: dkg_seat_eval_constants).  chunk 0 automatic; chunks == 1 is the serial walk."""
+    v = [ctypes.c_uint32() for _ in range(3)]
+    sb = ctypes.c_uint64()
+    L = _lib.lib()
+    rc = L.dkg_seat_eval_shape(n, t, waves, x_max, chunk, *[ctypes.byref(x) for x in v], ctypes.byref(sb))
+    if rc != _lib.DKG_OK:
+        raise _lib.DkgError(rc, "seat_eval_shape")
+    c = (ctypes.c_double * 6)()
+    L.dkg_seat_eval_constants(c)
+    return {"chunk": v[0].value, "chunks": v[1].value, "stages": v[2].value, "scratch_bytes": sb.value,
+            "constants": dict(zip(("launch_us", "op_latency_us", "lane_op_us", "serial_op_latency_us",
+                                   "chunked_setup_us", "margin"), c))}
 
 
 def seat_enc_digits(k: int) -> List[int]:

@@ -462,6 +462,16 @@ void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint3
 // scol[p] * n + dealer of the position-major table C [40][N][cols].  R [seat * n + dealer][40] point-major
 void seat_horner(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, const uint32_t* wdesc,
                  const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* R, hipStream_t stream);
+// The same evaluation cut into G = ceil(N / L) chunks of L coefficients (k_seat_chunks, grid (waves, G))
+// and folded in ceil(log2 G) stages of arity 2 (k_seat_fold, one launch per stage).  Q, in, out hold
+// partials lanes-minor, [40][chunks][64 * waves]; nothing is launched for G > 65535.  seat_fold: wave v
+// multiplies by the 17-word digit record digits[xslot[v] * dstride ..] (y = x^(L 2^stage), as recv_fold's
+// records); the stage with Gin <= 2 stores the live lanes to R as seat_horner does, the others to out.
+void seat_chunks(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, size_t L, const uint32_t* wdesc,
+                 const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* Q, hipStream_t stream);
+void seat_fold(size_t waves, size_t n, uint32_t width, size_t Gin, const uint32_t* wdesc, const uint32_t* wseat,
+               const uint32_t* xslot, const uint32_t* digits, size_t dstride, const uint32_t* in, uint32_t* out,
+               uint32_t* R, hipStream_t stream);
 // sok [S][n] = dok[scol[p] * n + i] and extra [S][n] (may be null)
 void seat_ok(size_t S, size_t n, const uint32_t* scol, const uint8_t* dok, const uint8_t* extra, uint8_t* sok,
              hipStream_t stream);

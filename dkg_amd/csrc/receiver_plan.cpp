@@ -1,5 +1,6 @@
 // dkg_receiver_plan_for: how one party's evaluations P_i(x) = sum_k x^k C_i[k] are cut into chunks
 // and folded (receivers.hip runs exactly this plan).  Host only, a pure function of (n, t, x, chunk).
+#include <algorithm>
 #include <cstring>
 #include <unordered_map>
 #include <vector>
@@ -170,6 +171,66 @@ int dkg_receiver_plan_for(size_t n, size_t t, uint32_t x, int chunk, dkg_receive
     if (us < best_us) best_us = us, best = p;
   }
   *out = best;
+  return DKG_OK;
+}
+
+// The seats' rule ("seats of large committees"; profiles/seat_chunks_time.json), in
+// the form of dkg_receiver_plan_cost_us with 64 * waves lanes: a launch costs SE_LAUNCH_US, a dependent
+// point operation of k_seat_chunks / k_seat_fold SE_LAT_US, one of k_seat_horner SE_SERIAL_LAT_US, a
+// lane's operation SE_THR_US once the device is full, and a chunked call SE_SETUP_US for its digit
+// records, its scratch and the upload.  The rule's estimates miss the record's device times by up to a
+// quarter, so a chunked shape is taken only where its estimate is below SE_MARGIN times the serial one.
+static const double SE_LAUNCH_US = 7.1, SE_LAT_US = 1.5, SE_THR_US = 2.6e-5, SE_SERIAL_LAT_US = 1.95,
+                    SE_SETUP_US = 25.0, SE_MARGIN = 0.8;
+static const uint64_t SE_SCRATCH_MAX = (uint64_t)1 << 30;
+
+void dkg_seat_eval_constants(double c[6]) {
+  if (!c) return;
+  c[0] = SE_LAUNCH_US, c[1] = SE_LAT_US, c[2] = SE_THR_US, c[3] = SE_SERIAL_LAT_US, c[4] = SE_SETUP_US;
+  c[5] = SE_MARGIN;
+}
+
+int dkg_seat_eval_shape(size_t n, size_t t, size_t waves, uint32_t x_max, int chunk, uint32_t* L, uint32_t* G,
+                        uint32_t* stages, uint64_t* scratch_bytes) {
+  if (!L || !G || !stages || !scratch_bytes || n == 0 || waves == 0 || x_max == 0 || (size_t)x_max > n || chunk < 0 ||
+      t >= 0xffffffffu || waves > 0xffffffffu)
+    return DKG_E_ARG;
+  const size_t N = t + 1;
+  // Q and its ping-pong partner, [40][G][64 waves] words each; none for the serial walk
+  auto scratch = [&](size_t g) { return g > 1 ? (uint64_t)2 * 160 * g * 64 * waves : (uint64_t)0; };
+  if (chunk > 0) {
+    const size_t l = std::min((size_t)chunk, N), g = (N + l - 1) / l;
+    dkg_receiver_plan p;
+    // k_seat_chunks runs the chunks along grid.y; 65535 of them fold in 16 stages, so the second test never fires
+    if (g > 65535 || !fill_plan(N, x_max, l, &p)) return DKG_E_ARG;
+    *L = (uint32_t)l, *G = (uint32_t)g, *stages = p.stages, *scratch_bytes = scratch(g);
+    return DKG_OK;
+  }
+  uint8_t xb[32];
+  u32_bytes(xb, x_max);
+  const double cx = chain_ops(xb) + 1, lanes = 64.0 * (double)waves;
+  const long serial_chain = (long)(N - 1) * (long)cx;
+  double best_us = SE_LAUNCH_US + SE_SERIAL_LAT_US * (double)serial_chain + SE_THR_US * lanes * (double)serial_chain;
+  size_t best_l = N, best_g = 1;
+  uint32_t best_s = 0;
+  for (size_t l = 2; l < N && l <= 64; l *= 2) {
+    dkg_receiver_plan p;
+    size_t g = (N + l - 1) / l;
+    if (g > 65535 || scratch(g) > SE_SCRATCH_MAX || !fill_plan(N, x_max, l, &p)) continue;
+    long chain = (long)(l - 1) * (long)cx;
+    double us = SE_SETUP_US + SE_LAUNCH_US + SE_LAT_US * (double)chain + SE_THR_US * lanes * (double)(N - g) * cx;
+    for (uint32_t s = 0; s < p.stages; s++) {
+      const double cy = chain_ops(p.mult[s]) + 1;
+      const size_t gout = (g + 1) / 2;
+      chain += (long)cy;
+      us += SE_LAUNCH_US + SE_LAT_US * cy + SE_THR_US * lanes * (double)(g - gout) * cy;
+      g = gout;
+    }
+    if (chain > serial_chain) continue;  // as dkg_receiver_plan_for: a longer chain and more work never pays
+    us /= SE_MARGIN;  // best_us is the serial estimate, or a chunked one already divided
+    if (us < best_us) best_us = us, best_l = l, best_g = (N + l - 1) / l, best_s = p.stages;
+  }
+  *L = (uint32_t)best_l, *G = (uint32_t)best_g, *stages = best_s, *scratch_bytes = scratch(best_g);
   return DKG_OK;
 }
 

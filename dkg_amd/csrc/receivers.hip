@@ -10,7 +10,8 @@
 // come from the host as signed digits (dkg_receiver_plan_for).  Every addition is the complete
 // formula, so identity rows, equal operands and torsion representatives need no redo.
 // k_pair_eval gives one wave to one (row, index) pair; k_seat_horner walks the seats (ceremony, party) of
-// one operator serially, seats of equal x side by side in a wave (dkg_seat_pack).
+// one operator serially, seats of equal x side by side in a wave (dkg_seat_pack); k_seat_chunks and
+// k_seat_fold are stages 1 and 2 on that placement, for the seats of large committees.
 // Built twice like kernels.hip (dkg_amd/Makefile): namespace dkgk, and dkgk_ilp with DKG_FE_ILP.
 #ifdef DKG_FE_ILP
 #define dkgk dkgk_ilp
@@ -239,6 +240,80 @@ __global__ __launch_bounds__(64, 3) void k_seat_horner(size_t n, size_t N, size_
   if (live) pt_store_aos(R, (size_t)seat * n + d, acc);
 }
 
+// k_seat_horner cut into G = ceil(N / L) chunks that are walked side by side, for the seats of large
+// committees whose serial walk leaves the device empty: grid (waves, G), block (v, u) has k_seat_horner's
+// lane map and walks coefficients [uL, min(uL + L, N)) of its column from the top down (the last chunk
+// may be short; L = 1 has no step).  The partial goes to Q [40][G][64 waves], lanes minor: lane
+// v 64 + threadIdx.x of chunk u, dead lanes (which walk column 0) included, so that k_seat_fold reads
+// only what was written.  The exactness note of k_recv_chunks holds unchanged: every addition is
+// complete, and a multiplier may be any representative mod l since the operands lie in 2E.
+__global__ __launch_bounds__(64, 3) void k_seat_chunks(size_t n, size_t N, size_t cols, uint32_t wshift, size_t L,
+                                                       const uint32_t* __restrict__ wdesc,
+                                                       const uint32_t* __restrict__ wseat,
+                                                       const uint32_t* __restrict__ scol,
+                                                       const uint32_t* __restrict__ C, uint32_t* __restrict__ Q) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* q = qs + threadIdx.x;
+  const size_t v = blockIdx.x, u = blockIdx.y, G = gridDim.y, lanes = (size_t)gridDim.x * 64;
+  const uint32_t x = wdesc[2 * v], tile = wdesc[2 * v + 1];
+  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
+  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
+  const size_t d = (size_t)tile * 64 + i;
+  const bool live = seat != 0xffffffffu && d < n;
+  size_t col = 0;
+  if (live) col = (size_t)scol[seat] * n + d;
+  uint32_t pos, neg;
+  const int len = small_recode(x, pos, neg);
+  const size_t lo = u * L, hi = lo + L < N ? lo + L : N;
+  const size_t S = N * cols;
+  ge_p3 acc, c;
+  pt_load(acc, C, S, (hi - 1) * cols + col);
+#pragma unroll 1
+  for (size_t k = hi - 1; k-- > lo;) {
+    recv_mul_small(acc, pos, neg, len, q);
+    pt_load(c, C, S, k * cols + col);
+    add_point_lds(acc, c, q);
+  }
+  pt_store(Q, G * lanes, u * lanes + v * 64 + threadIdx.x, acc);
+}
+
+// One fold stage of the seats' partials, arity 2: grid (waves, Gout = ceil(Gin / 2)),
+// out[v'] = y in[2 v' + 1] + in[2 v'], or in[2 v'] alone where the upper partial does not exist (odd
+// Gin).  y = x^(L 2^stage) mod l is uniform over the wave but differs from wave to wave: wave v reads
+// the 17-word record (recv_mul_long's format) digits[xslot[v] * dstride ..] of its x at this stage; at
+// x = 1 the chain is empty.  in [40][Gin][64 waves], out [40][Gout][64 waves]; the last stage (Gout == 1)
+// stores the live lanes to R [seat n + d][40] point-major instead, dead lanes nothing.
+__global__ __launch_bounds__(64, 3) void k_seat_fold(size_t n, uint32_t wshift, size_t Gin,
+                                                     const uint32_t* __restrict__ wdesc,
+                                                     const uint32_t* __restrict__ wseat,
+                                                     const uint32_t* __restrict__ xslot,
+                                                     const uint32_t* __restrict__ digits, size_t dstride,
+                                                     const uint32_t* __restrict__ in, uint32_t* __restrict__ out,
+                                                     uint32_t* __restrict__ R) {
+  __shared__ uint32_t qs[PT_WORDS * 64];
+  uint32_t* q = qs + threadIdx.x;
+  const size_t v = blockIdx.x, w = blockIdx.y, Gout = gridDim.y, lanes = (size_t)gridDim.x * 64;
+  const size_t lane = v * 64 + threadIdx.x, S = Gin * lanes;
+  ge_p3 acc, c;
+  if (2 * w + 1 < Gin) {
+    pt_load(acc, in, S, (2 * w + 1) * lanes + lane);
+    recv_mul_long(acc, digits + (size_t)xslot[v] * dstride, q);
+    pt_load(c, in, S, 2 * w * lanes + lane);
+    add_point_lds(acc, c, q);
+  } else {
+    pt_load(acc, in, S, 2 * w * lanes + lane);
+  }
+  if (Gout != 1) {
+    pt_store(out, Gout * lanes, w * lanes + lane, acc);
+    return;
+  }
+  const uint32_t tile = wdesc[2 * v + 1];
+  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
+  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
+  const size_t d = (size_t)tile * 64 + i;
+  if (seat != 0xffffffffu && d < n) pt_store_aos(R, (size_t)seat * n + d, acc);
+}
+
 // sok[p n + i] = dok[scol[p] n + i] (and extra[p n + i], may be null): dealer i's data decodes for seat p
 __global__ __launch_bounds__(256) void k_seat_ok(size_t S, size_t n, const uint32_t* __restrict__ scol,
                                                  const uint8_t* __restrict__ dok, const uint8_t* __restrict__ extra,
@@ -336,6 +411,27 @@ void seat_horner(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, 
   if (!waves || !n || !N || (1u << wshift) != width || width > 64 || cols < n) return;
   hipLaunchKernelGGL(k_seat_horner, dim3((unsigned)waves), dim3(64), 0, stream, n, N, cols, wshift, wdesc, wseat, scol,
                      C, R);
+}
+
+void seat_chunks(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, size_t L, const uint32_t* wdesc,
+                 const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* Q, hipStream_t stream) {
+  uint32_t wshift = 0;
+  while ((1u << wshift) < width) wshift++;
+  if (!waves || !n || !N || !L || (1u << wshift) != width || width > 64 || cols < n) return;
+  const size_t G = (N + L - 1) / L;
+  if (G > 65535) return;  // grid.y
+  hipLaunchKernelGGL(k_seat_chunks, dim3((unsigned)waves, (unsigned)G), dim3(64), 0, stream, n, N, cols, wshift, L,
+                     wdesc, wseat, scol, C, Q);
+}
+
+void seat_fold(size_t waves, size_t n, uint32_t width, size_t Gin, const uint32_t* wdesc, const uint32_t* wseat,
+               const uint32_t* xslot, const uint32_t* digits, size_t dstride, const uint32_t* in, uint32_t* out,
+               uint32_t* R, hipStream_t stream) {
+  uint32_t wshift = 0;
+  while ((1u << wshift) < width) wshift++;
+  if (!waves || !n || Gin < 2 || Gin > 65535 || (1u << wshift) != width || width > 64) return;
+  hipLaunchKernelGGL(k_seat_fold, dim3((unsigned)waves, (unsigned)((Gin + 1) / 2)), dim3(64), 0, stream, n, wshift,
+                     Gin, wdesc, wseat, xslot, digits, dstride, in, out, R);
 }
 
 void seat_ok(size_t S, size_t n, const uint32_t* scol, const uint8_t* dok, const uint8_t* extra, uint8_t* sok,

@@ -42,7 +42,8 @@ struct dkg_ctx {
   hipEvent_t pev[5] = {};               // phase profiling inside verify_device (nsub == 1)
   hipEvent_t hev[9] = {};               // full mode: encrypt / decrypt kernels (nsub == 1)
   hipEvent_t bpev[3] = {};              // batches by proven complaints: around the two complaint stages
-  hipEvent_t rpev[7] = {};              // one party's checks (recv.*): decrypt, decode, chunks, fold, check, prove
+  hipEvent_t rpev[8] = {};              // one party's checks (recv.*): decrypt, decode, chunks, fold, check, prove;
+                                        // [7]: the seats' chunk walk done, its folds begin
   int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
   int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
   std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
@@ -69,6 +70,9 @@ struct dkg_ctx {
   int seat_deal = 0;                    // K = pk r of dkg_party_round1_seats: 0 automatic (DKG_SEAT_DEAL_AUTO), 1
                                         // radix-16 combs per key slot, 2 the joint chain (seat_deal.hip)
   int last_seat_deal = 0;               // the route the last such call ran (0: none yet)
+  int seat_eval = 0, seat_eval_chunk = 0;  // the seats' evaluation: 0 dkg_seat_eval_shape's rule, 1 k_seat_horner,
+                                           // 2 chunked with this chunk (0: the rule's)
+  int last_seat_eval = 0, last_seat_eval_chunk = 0;  // the route and L the last seats call ran (0: none yet)
   uint8_t fb_base[32] = {0};            // dkg_fixed_base_batch: the caller base whose comb sits in fb_tabw
   bool fb_valid = false;
   int comb_build = 0;                   // radix-2^BITS comb builder: 0 automatic (comb_build_auto), 1 one
@@ -4482,6 +4486,17 @@ int dkg_ctx_set_seat_deal(dkg_ctx* ctx, int mode) {
 }
 int dkg_ctx_last_seat_deal(const dkg_ctx* ctx) { return ctx ? ctx->last_seat_deal : 0; }
 
+int dkg_ctx_set_seat_eval(dkg_ctx* ctx, int mode, int chunk) {
+  if (!ctx || mode < 0 || mode > 2 || chunk < 0 || (mode != 2 && chunk != 0)) return DKG_E_ARG;
+  ctx->seat_eval = mode;
+  ctx->seat_eval_chunk = chunk;
+  return DKG_OK;
+}
+int dkg_ctx_last_seat_eval(const dkg_ctx* ctx, int* chunk) {
+  if (chunk) *chunk = ctx ? ctx->last_seat_eval_chunk : 0;
+  return ctx ? ctx->last_seat_eval : 0;
+}
+
 int dkg_ctx_set_comb_build(dkg_ctx* ctx, int mode) {
   if (!ctx || mode < 0 || mode > 2) return DKG_E_ARG;
   ctx->comb_build = mode;
@@ -5441,11 +5456,17 @@ struct SeatEval {
   uint8_t* sok = nullptr;      // [S][n] dealer i's data decodes for seat p
   uint32_t* sx = nullptr;      // [S] device: the seats' 1-based indices
   uint32_t* scer = nullptr;    // [S] device: the seats' ceremonies
+  std::vector<uint32_t> xslot, dig;  // chunked route: per-wave slot and the [distinct x][stage][17] digit records
+  bool folded = false;         // rpev[7] separates the chunk walk from the folds
 };
+
+constexpr size_t SEAT_DIG_WORDS = 17;               // per (distinct x, stage): 8 + 8 digit words, length
+constexpr uint64_t SEAT_SCRATCH_MAX = (uint64_t)1 << 30;  // Q and its ping-pong partner
 
 // Decode the distinct ceremonies the seats name (C [B * n][N][32]) and evaluate dealer i of seat p's
 // ceremony at js[p] + 1 by dkg_seat_pack's waves.  extra (device [S][n], may be null) is ANDed into sok.
-// Marks rpev[1] (start), [2] (decoded), [3] (evaluated).
+// The route is ctx->seat_eval's: k_seat_horner, or k_seat_chunks and k_seat_fold in dkg_seat_eval_shape's
+// shape.  Marks rpev[1] (start), [2] (decoded), [7] (chunks walked, when folded) and [3] (evaluated).
 int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer, const uint32_t* js,
                const uint8_t* C, const uint8_t* extra, SeatEval& ev) {
   if (B > 0xffffffffu / n) return DKG_E_ARG;  // dealer rows are 32-bit
@@ -5453,6 +5474,41 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
   if (rc) return rc;
   const dkgh::SeatPlan& pl = ev.plan;
   const size_t N = t + 1, Bd = pl.cers.size(), D = Bd * n, cols = pad64(D);
+  // the route, before anything is uploaded: a forced shape may be refused
+  uint32_t L = (uint32_t)std::min<size_t>(N, 0x7fffffffu), G = 1, stages = 0;
+  uint64_t scratch = 0;
+  if (ctx->seat_eval != 1 && pl.waves) {
+    const uint32_t x_max = *std::max_element(pl.seat_x.begin(), pl.seat_x.end());
+    const int rs = dkg_seat_eval_shape(n, t, pl.waves, x_max, ctx->seat_eval_chunk, &L, &G, &stages, &scratch);
+    if (rs) {
+      ctx->err = "seats: dkg_seat_eval_shape refuses chunk " + std::to_string(ctx->seat_eval_chunk);
+      return rs;
+    }
+    if (scratch > SEAT_SCRATCH_MAX) {
+      ctx->err = "seats: the forced chunk " + std::to_string(L) + " needs " + std::to_string(scratch) +
+                 " bytes of scratch, more than " + std::to_string(SEAT_SCRATCH_MAX);
+      return DKG_E_ARG;
+    }
+  }
+  if (G > 1) {  // one digit record per (distinct x, stage); the waves name their x's records
+    std::vector<uint32_t> wx(pl.waves), xs;
+    for (size_t v = 0; v < pl.waves; v++) wx[v] = pl.wave_desc[2 * v];
+    dkgh::distinct_places(pl.waves, wx.data(), xs, ev.xslot);
+    ev.dig.assign(xs.size() * stages * SEAT_DIG_WORDS, 0);
+    for (size_t k = 0; k < xs.size(); k++) {
+      dkg_receiver_plan p;
+      if (dkg_receiver_plan_for(n, t, xs[k], (int)L, &p) != DKG_OK || p.stages != stages) {
+        ctx->err = "seats: no fold plan for index " + std::to_string(xs[k]);
+        return DKG_E_ARG;
+      }
+      for (uint32_t s = 0; s < stages; s++) {
+        uint32_t* d = &ev.dig[(k * stages + s) * SEAT_DIG_WORDS];
+        d[16] = (uint32_t)dkgh::naf256(p.mult[s], d, d + 8, nullptr);
+      }
+    }
+  }
+  ctx->last_seat_eval = G > 1 ? 2 : 1;
+  ctx->last_seat_eval_chunk = (int)L;
   ev.rows.resize(D);
   for (size_t c = 0; c < Bd; c++)
     for (size_t i = 0; i < n; i++) ev.rows[c * n + i] = (uint32_t)(pl.cers[c] * n + i);
@@ -5487,7 +5543,29 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
   dkgk::seat_ok(S, n, dscol, dok, extra, ev.sok, st);
   recv_mark(ctx, 2);
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_SEAT_ILP);
-  (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, Cpm, ev.R, st);
+  if (G == 1) {
+    (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, Cpm, ev.R, st);
+  } else {
+    uint32_t* dxslot = buf<uint32_t>(ctx, "st_xslot", 4 * ev.xslot.size());
+    uint32_t* ddig = buf<uint32_t>(ctx, "st_dig", 4 * ev.dig.size());
+    h2d(ctx, dxslot, ev.xslot.data(), 4 * ev.xslot.size());
+    h2d(ctx, ddig, ev.dig.data(), 4 * ev.dig.size());
+    uint32_t* q0 = buf<uint32_t>(ctx, "st_q", scratch);  // 2 x [40][G][64 waves] words
+    uint32_t* Q[2] = {q0, q0 + scratch / 8};
+    (ilp ? dkgk_ilp::seat_chunks : dkgk::seat_chunks)(pl.waves, n, N, cols, pl.width, L, dwdesc, dwseat, dscol, Cpm, Q[0], st);
+    recv_mark(ctx, 7);
+    ev.folded = true;
+    size_t Gin = G;
+    for (uint32_t s = 0; s < stages; s++) {
+      (ilp ? dkgk_ilp::seat_fold : dkgk::seat_fold)(pl.waves, n, pl.width, Gin, dwdesc, dwseat, dxslot, ddig + s * SEAT_DIG_WORDS,
+                                                    stages * SEAT_DIG_WORDS, Q[s & 1], Q[(s + 1) & 1], ev.R, st);
+      Gin = (Gin + 1) / 2;
+    }
+    if (Gin != 1) {
+      ctx->err = "seats: the fold does not end in one value";
+      return DKG_E_ARG;
+    }
+  }
   check_launch(ctx);
   recv_mark(ctx, 3);
   return DKG_OK;
@@ -5523,6 +5601,7 @@ int dkg_commitment_eval_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t
     seat_phase(ctx, "decrypt", -1, 0);
     seat_phase(ctx, "decode", 1, 2);
     seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
     seat_phase(ctx, "check", -1, 0);
     seat_phase(ctx, "prove", -1, 0);
     return DKG_OK;
@@ -5555,6 +5634,7 @@ int dkg_verify_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, int round, size
     seat_phase(ctx, "decrypt", -1, 0);
     seat_phase(ctx, "decode", 1, 2);
     seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
     seat_phase(ctx, "check", 3, 4);
     seat_phase(ctx, "prove", -1, 0);
     return DKG_OK;
@@ -5609,6 +5689,7 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     seat_phase(ctx, "decrypt", 0, 1);
     seat_phase(ctx, "decode", 1, 2);
     seat_phase(ctx, "eval", 2, 3);
+    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
     seat_phase(ctx, "check", 3, 4);
     seat_phase(ctx, "prove", -1, 0);
     std::vector<size_t> rej;  // (seat, dealer) pairs p * n + i

@@ -384,6 +384,44 @@ int dkg_party_round2_seats(dkg_ctx *ctx, size_t B, size_t n, size_t t, size_t S,
                            const uint32_t *js, const uint8_t *E, const uint8_t *e1, const uint8_t *ct,
                            const uint8_t *sk, const uint8_t *w, uint8_t *s_out, uint8_t *sp_out, uint8_t *dec,
                            int32_t *complaints, uint8_t *r2_error, uint8_t *proofs);
+/* ---- hosted seats of large committees: chunked evaluation (receivers.hip k_seat_chunks, k_seat_fold;
+ * DESIGN.md section 4) ----
+ * k_seat_horner walks the t + 1 coefficients of a seat's polynomials as one dependent chain (the
+ * shared-scalar case of vartime_multiscalar_multiplication, committee.rs:287-296 and :532-539).  A few
+ * seats of a large committee leave the device empty behind that chain, so the three calls above may
+ * instead cut every polynomial into G = ceil((t+1) / L) chunks that dkg_seat_pack's waves walk side by
+ * side (grid waves x G) and fold the partials in `stages` = ceil(log2 G) launches of arity 2 with the
+ * multipliers of dkg_receiver_plan_for(n, t, x, L), one digit record per (distinct x, stage).  The
+ * placement, the decode and everything after the evaluation are unchanged, and so is the exactness note
+ * of the chunked plan above: a multiplier may be any representative mod l.
+ *
+ * The shape for `waves` waves of dkg_seat_pack whose largest index is x_max (1-based).  chunk >= 1
+ * forced: L = min(chunk, t+1), G, stages as dkg_receiver_plan_for's; chunk 0 automatic: the cheapest, by
+ * the fitted rule of dkg_receiver_plan_cost_us with 64 * waves lanes and the chain taken at x_max, of the
+ * serial walk (L = t+1, G = 1, stages = 0) and L = 2, 4, .., 64 < t+1 whose chain is no longer than the
+ * serial one and whose scratch is at most 1 GiB.  *scratch_bytes = 2 * 160 * G * 64 * waves (the partials
+ * and their ping-pong partner), 0 for G = 1.  Host only, no GPU, a pure function.  DKG_E_ARG for n == 0,
+ * waves == 0, x_max == 0 or > n, chunk < 0, a NULL output, or a forced chunk with G > 65535 (the launch
+ * grid; more than 16 stages cannot occur below that). */
+int dkg_seat_eval_shape(size_t n, size_t t, size_t waves, uint32_t x_max, int chunk, uint32_t *L, uint32_t *G,
+                        uint32_t *stages, uint64_t *scratch_bytes);
+/* The rule's fitted constants (profiles/seat_chunks_time.json), c = {per launch us, per dependent point
+ * operation of the chunked kernels us, per lane and operation us, per dependent operation of
+ * k_seat_horner us, setup of a chunked call us, margin}: a chunked shape is chosen only where its
+ * estimate is below margin x the serial walk's (the estimates miss the record by up to a quarter). */
+void dkg_seat_eval_constants(double c[6]);
+/* The evaluation of the three seats calls: 1 = the serial walk (k_seat_horner); 2 = chunked with
+ * dkg_seat_eval_shape(.., chunk) -- a shape that resolves to G = 1 runs the serial kernel and reports 1,
+ * one above 1 GiB of scratch is DKG_E_ARG at the call, dkg_ctx_last_error naming the size; 0 (default) =
+ * automatic, the rule with chunk 0.  chunk is read in mode 2 only and must be 0 otherwise.  Outputs never
+ * depend on mode or chunk.  dkg_ctx_set_field_mode selects the kernel copy of either route;
+ * dkg_ctx_set_receiver_chunk does not apply to seats.  A chunked call on one stream also records
+ * "seats.fold", the fold stages alone (inside "seats.eval"); -1 otherwise.  DKG_E_ARG for any other
+ * mode, chunk < 0, or chunk != 0 outside mode 2. */
+int dkg_ctx_set_seat_eval(dkg_ctx *ctx, int mode, int chunk);
+/* The route (1 or 2) the last seats call ran and, in *chunk (may be NULL), its L (t + 1 for the serial
+ * walk); 0 and 0 before the first. */
+int dkg_ctx_last_seat_eval(const dkg_ctx *ctx, int *chunk);
 
 /* ---- hosted seats deal round 1 (seat_deal.hip) ----
  * Phases<Initialise>::init (committee.rs:124-216) for every seat of an operator in one call: seat p, party
