@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "seat_map.h"
+
 namespace dkgh {
 
 void blake2b(uint8_t* out, size_t outlen, const uint8_t* in, size_t inlen);
@@ -48,7 +50,7 @@ void distinct_places(size_t count, const uint32_t* v, std::vector<uint32_t>& dis
 // evaluates at x = wave_desc[2v] the dealers wave_desc[2v + 1] * 64 + i, i < width, of the seats
 // wave_seat[v * per_wave + slot] (SEAT_NONE: an empty slot); seat p's commitments are ceremony slot
 // seat_col[p] among the distinct ceremonies `cers` (order of first appearance), the only ones decoded.
-constexpr uint32_t SEAT_NONE = 0xffffffffu;
+using ::SEAT_NONE;  // seat_map.h
 struct SeatPlan {
   uint32_t width = 0, per_wave = 0, tiles = 0, waves = 0;
   std::vector<uint32_t> cers, seat_col, seat_x, wave_desc, wave_seat;

@@ -18,6 +18,7 @@
 #endif
 #include "kernels.h"
 #include "points.h"
+#include "seat_map.h"
 
 namespace dkgk {
 
@@ -86,6 +87,21 @@ DKG_DEV void recv_store(bool last, uint32_t* __restrict__ out, size_t ostride, s
   else if (live) pt_store_aos(R, ridx, acc);
 }
 
+// acc = sum over k in [lo, hi) of x^(k - lo) C[k] for one column of a position-major table, from the top
+// down: coefficient k of the column is element k * kstride + col at word stride S; (pos, neg, len) is
+// small_recode(x), q the lane's LDS slot.  hi - lo - 1 steps; a chunk of one coefficient has none.
+DKG_DEV void chunk_walk(ge_p3& acc, const uint32_t* __restrict__ C, size_t S, size_t kstride, size_t col, size_t lo,
+                        size_t hi, uint32_t pos, uint32_t neg, int len, uint32_t* q) {
+  ge_p3 c;
+  pt_load(acc, C, S, (hi - 1) * kstride + col);
+#pragma unroll 1
+  for (size_t k = hi - 1; k-- > lo;) {
+    recv_mul_small(acc, pos, neg, len, q);
+    pt_load(c, C, S, k * kstride + col);
+    add_point_lds(acc, c, q);
+  }
+}
+
 }  // namespace
 
 // Stage 1.  C position-major [40][N][npad]; xs[m] = receiver index (1-based) of slot m0 + blockIdx.z.
@@ -101,22 +117,16 @@ __global__ __launch_bounds__(64, 3) void k_recv_chunks(size_t ndealers, size_t n
   const uint32_t x = xs[m0 + m];
   uint32_t pos, neg;
   const int len = small_recode(x, pos, neg);
-  const size_t lo = u * L, hi = lo + L < N ? lo + L : N;
-  const size_t S = N * npad;
-  ge_p3 acc, c;
-  pt_load(acc, C, S, (hi - 1) * npad + d);
-#pragma unroll 1
-  for (size_t k = hi - 1; k-- > lo;) {
-    recv_mul_small(acc, pos, neg, len, q);
-    pt_load(c, C, S, k * npad + d);
-    add_point_lds(acc, c, q);
-  }
+  const ChunkSpan ch = chunk_span(u, L, N);
+  ge_p3 acc;
+  chunk_walk(acc, C, N * npad, npad, d, ch.lo, ch.hi, pos, neg, len, q);
   recv_store(G == 1, Q, (size_t)gridDim.z * G * npad, (m * G + u) * npad + d, R, (m0 + m) * ndealers + d,
              d < ndealers, acc);
 }
 
 // Stage 2, one fold stage: out[v] = sum_{i < r} y^i in[v r + i] over the partials that exist
-// (Gin need not be a multiple of r).  dg: the stage's digits of slot m0 + blockIdx.z (17 words, stride dstride).
+// (Gin need not be a multiple of r).  dg: the stage's digits of slot m0 + blockIdx.z (FOLD_DIG_WORDS words,
+// stride dstride).
 __global__ __launch_bounds__(64, 3) void k_recv_fold(size_t ndealers, size_t npad, size_t Gin, size_t r,
                                                      const uint32_t* __restrict__ in,
                                                      const uint32_t* __restrict__ digits, size_t dstride, size_t m0,
@@ -144,7 +154,7 @@ __global__ __launch_bounds__(64, 3) void k_recv_fold(size_t ndealers, size_t npa
 // the wave, and the lanes hold G <= 64 chunks of L coefficients of that one polynomial (G = ceil(N / L),
 // S = ceil(log2 G): dkg_pair_eval_shape).  Item b: c = list[b] (b itself with a null list), row
 // crow[c] - 1 of the decoded commitments Eext (element row * N + k, as k_cmp_horner reads them), index
-// x = xs[c], digit records digits[slot[b]][S][17] of the multipliers y_s = x^(L 2^s).
+// x = xs[c], digit records digits[slot[b]][S][FOLD_DIG_WORDS] of the multipliers y_s = x^(L 2^s).
 //   stage 1  lane u walks coefficients [uL, min(uL + L, N)) by Horner in x: L - 1 steps in every lane; a
 //            position past the row's end, and every position of a lane >= G, is the identity
 //   fold s   V_u = y_s V_u + V_(u - 2^s) in the lanes whose bit s is set: recv_mul_long leaves cached(V_u)
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(64, 3) void k_pair_eval(const uint32_t* __restrict_
   }
 #pragma unroll 1
   for (uint32_t s = 0; s < S; s++) {
-    const uint32_t* dg = digits + ((size_t)slot[b] * S + s) * 17;
+    const uint32_t* dg = digits + fold_record(slot[b], S, s);
     {  // recv_mul_long, whose first step is skipped by the empty chain (y_s = 1 at x = 1): the column
        // is written either way, since the partner reads it
       ge_cached cc;
@@ -206,10 +216,9 @@ __global__ __launch_bounds__(64, 3) void k_pair_eval(const uint32_t* __restrict_
 // P_i(x) for the SEATS (ceremony, party) of one operator, one 64-lane workgroup per wave of dkg_seat_pack's
 // placement.  Every polynomial of a seat is evaluated at the seat's x = j + 1, and the host packs only
 // seats of equal x into one wave, so the multiplier is wave-uniform as in k_recv_chunks: the serial walk
-// acc = x acc + C[k] over the N coefficients, no fold.  Wave v: x = wdesc[2v], dealer tile wdesc[2v + 1];
-// lane l = slot W + i (W = 1 << wshift) is dealer d = tile 64 + i of seat wseat[v (64 / W) + slot], whose
-// commitments are columns scol[seat] n + d of the position-major table C [40][N][cols] over the decoded
-// ceremonies.  A lane with d >= n or in an empty slot (SEAT_NONE) walks column 0 and stores nothing.
+// acc = x acc + C[k] over the N coefficients, no fold.  Wave v evaluates at x = wdesc[2v]; seat_map.h has
+// the lane map (seat_lane) and the lane's column of the position-major table C [40][N][cols] over the
+// decoded ceremonies (seat_column).  A dead lane walks column 0 and stores nothing.
 // R point-major [seat n + d][40].
 __global__ __launch_bounds__(64, 3) void k_seat_horner(size_t n, size_t N, size_t cols, uint32_t wshift,
                                                        const uint32_t* __restrict__ wdesc,
@@ -219,25 +228,13 @@ __global__ __launch_bounds__(64, 3) void k_seat_horner(size_t n, size_t N, size_
   __shared__ uint32_t qs[PT_WORDS * 64];
   uint32_t* q = qs + threadIdx.x;
   const size_t v = blockIdx.x;
-  const uint32_t x = wdesc[2 * v], tile = wdesc[2 * v + 1];
-  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
-  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
-  const size_t d = (size_t)tile * 64 + i;
-  const bool live = seat != 0xffffffffu && d < n;
-  size_t col = 0;
-  if (live) col = (size_t)scol[seat] * n + d;
+  const SeatLane m = seat_lane(n, wshift, v, threadIdx.x, wdesc, wseat);
+  const size_t col = seat_column(m, n, scol);
   uint32_t pos, neg;
-  const int len = small_recode(x, pos, neg);
-  const size_t S = N * cols;
-  ge_p3 acc, c;
-  pt_load(acc, C, S, (N - 1) * cols + col);
-#pragma unroll 1
-  for (size_t k = N - 1; k-- > 0;) {
-    recv_mul_small(acc, pos, neg, len, q);
-    pt_load(c, C, S, k * cols + col);
-    add_point_lds(acc, c, q);
-  }
-  if (live) pt_store_aos(R, (size_t)seat * n + d, acc);
+  const int len = small_recode(wdesc[2 * v], pos, neg);
+  ge_p3 acc;
+  chunk_walk(acc, C, N * cols, cols, col, 0, N, pos, neg, len, q);
+  if (m.live) pt_store_aos(R, seat_result(m, n), acc);
 }
 
 // k_seat_horner cut into G = ceil(N / L) chunks that are walked side by side, for the seats of large
@@ -255,33 +252,21 @@ __global__ __launch_bounds__(64, 3) void k_seat_chunks(size_t n, size_t N, size_
   __shared__ uint32_t qs[PT_WORDS * 64];
   uint32_t* q = qs + threadIdx.x;
   const size_t v = blockIdx.x, u = blockIdx.y, G = gridDim.y, lanes = (size_t)gridDim.x * 64;
-  const uint32_t x = wdesc[2 * v], tile = wdesc[2 * v + 1];
-  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
-  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
-  const size_t d = (size_t)tile * 64 + i;
-  const bool live = seat != 0xffffffffu && d < n;
-  size_t col = 0;
-  if (live) col = (size_t)scol[seat] * n + d;
+  const SeatLane m = seat_lane(n, wshift, v, threadIdx.x, wdesc, wseat);
+  const size_t col = seat_column(m, n, scol);
   uint32_t pos, neg;
-  const int len = small_recode(x, pos, neg);
-  const size_t lo = u * L, hi = lo + L < N ? lo + L : N;
-  const size_t S = N * cols;
-  ge_p3 acc, c;
-  pt_load(acc, C, S, (hi - 1) * cols + col);
-#pragma unroll 1
-  for (size_t k = hi - 1; k-- > lo;) {
-    recv_mul_small(acc, pos, neg, len, q);
-    pt_load(c, C, S, k * cols + col);
-    add_point_lds(acc, c, q);
-  }
-  pt_store(Q, G * lanes, u * lanes + v * 64 + threadIdx.x, acc);
+  const int len = small_recode(wdesc[2 * v], pos, neg);
+  const ChunkSpan ch = chunk_span(u, L, N);
+  ge_p3 acc;
+  chunk_walk(acc, C, N * cols, cols, col, ch.lo, ch.hi, pos, neg, len, q);
+  pt_store(Q, G * lanes, seat_partial(lanes, u, seat_wave_lane(v, threadIdx.x)), acc);
 }
 
 // One fold stage of the seats' partials, arity 2: grid (waves, Gout = ceil(Gin / 2)),
 // out[v'] = y in[2 v' + 1] + in[2 v'], or in[2 v'] alone where the upper partial does not exist (odd
 // Gin).  y = x^(L 2^stage) mod l is uniform over the wave but differs from wave to wave: wave v reads
-// the 17-word record (recv_mul_long's format) digits[xslot[v] * dstride ..] of its x at this stage; at
-// x = 1 the chain is empty.  in [40][Gin][64 waves], out [40][Gout][64 waves]; the last stage (Gout == 1)
+// the record (recv_mul_long's format, FOLD_DIG_WORDS words) digits[xslot[v] * dstride ..] of its x at this
+// stage; at x = 1 the chain is empty.  in [40][Gin][64 waves], out [40][Gout][64 waves]; the last stage (Gout == 1)
 // stores the live lanes to R [seat n + d][40] point-major instead, dead lanes nothing.
 __global__ __launch_bounds__(64, 3) void k_seat_fold(size_t n, uint32_t wshift, size_t Gin,
                                                      const uint32_t* __restrict__ wdesc,
@@ -293,25 +278,22 @@ __global__ __launch_bounds__(64, 3) void k_seat_fold(size_t n, uint32_t wshift, 
   __shared__ uint32_t qs[PT_WORDS * 64];
   uint32_t* q = qs + threadIdx.x;
   const size_t v = blockIdx.x, w = blockIdx.y, Gout = gridDim.y, lanes = (size_t)gridDim.x * 64;
-  const size_t lane = v * 64 + threadIdx.x, S = Gin * lanes;
+  const size_t lane = seat_wave_lane(v, threadIdx.x), S = Gin * lanes;
   ge_p3 acc, c;
   if (2 * w + 1 < Gin) {
-    pt_load(acc, in, S, (2 * w + 1) * lanes + lane);
+    pt_load(acc, in, S, seat_partial(lanes, 2 * w + 1, lane));
     recv_mul_long(acc, digits + (size_t)xslot[v] * dstride, q);
-    pt_load(c, in, S, 2 * w * lanes + lane);
+    pt_load(c, in, S, seat_partial(lanes, 2 * w, lane));
     add_point_lds(acc, c, q);
   } else {
-    pt_load(acc, in, S, 2 * w * lanes + lane);
+    pt_load(acc, in, S, seat_partial(lanes, 2 * w, lane));
   }
   if (Gout != 1) {
-    pt_store(out, Gout * lanes, w * lanes + lane, acc);
+    pt_store(out, Gout * lanes, seat_partial(lanes, w, lane), acc);
     return;
   }
-  const uint32_t tile = wdesc[2 * v + 1];
-  const uint32_t slot = threadIdx.x >> wshift, i = threadIdx.x & ((1u << wshift) - 1u);
-  const uint32_t seat = wseat[(v << (6 - wshift)) + slot];
-  const size_t d = (size_t)tile * 64 + i;
-  if (seat != 0xffffffffu && d < n) pt_store_aos(R, (size_t)seat * n + d, acc);
+  const SeatLane m = seat_lane(n, wshift, v, threadIdx.x, wdesc, wseat);
+  if (m.live) pt_store_aos(R, seat_result(m, n), acc);
 }
 
 // sok[p n + i] = dok[scol[p] n + i] (and extra[p n + i], may be null): dealer i's data decodes for seat p
@@ -406,32 +388,29 @@ void pair_eval(size_t cnt, const uint32_t* list, const uint32_t* xs, const uint3
 
 void seat_horner(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, const uint32_t* wdesc,
                  const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* R, hipStream_t stream) {
-  uint32_t wshift = 0;
-  while ((1u << wshift) < width) wshift++;
-  if (!waves || !n || !N || (1u << wshift) != width || width > 64 || cols < n) return;
-  hipLaunchKernelGGL(k_seat_horner, dim3((unsigned)waves), dim3(64), 0, stream, n, N, cols, wshift, wdesc, wseat, scol,
-                     C, R);
+  const int wshift = seat_wshift(width);
+  if (!waves || !n || !N || wshift < 0 || cols < n) return;
+  hipLaunchKernelGGL(k_seat_horner, dim3((unsigned)waves), dim3(64), 0, stream, n, N, cols, (uint32_t)wshift,
+                     wdesc, wseat, scol, C, R);
 }
 
 void seat_chunks(size_t waves, size_t n, size_t N, size_t cols, uint32_t width, size_t L, const uint32_t* wdesc,
                  const uint32_t* wseat, const uint32_t* scol, const uint32_t* C, uint32_t* Q, hipStream_t stream) {
-  uint32_t wshift = 0;
-  while ((1u << wshift) < width) wshift++;
-  if (!waves || !n || !N || !L || (1u << wshift) != width || width > 64 || cols < n) return;
+  const int wshift = seat_wshift(width);
+  if (!waves || !n || !N || !L || wshift < 0 || cols < n) return;
   const size_t G = (N + L - 1) / L;
   if (G > 65535) return;  // grid.y
-  hipLaunchKernelGGL(k_seat_chunks, dim3((unsigned)waves, (unsigned)G), dim3(64), 0, stream, n, N, cols, wshift, L,
-                     wdesc, wseat, scol, C, Q);
+  hipLaunchKernelGGL(k_seat_chunks, dim3((unsigned)waves, (unsigned)G), dim3(64), 0, stream, n, N, cols,
+                     (uint32_t)wshift, L, wdesc, wseat, scol, C, Q);
 }
 
 void seat_fold(size_t waves, size_t n, uint32_t width, size_t Gin, const uint32_t* wdesc, const uint32_t* wseat,
                const uint32_t* xslot, const uint32_t* digits, size_t dstride, const uint32_t* in, uint32_t* out,
                uint32_t* R, hipStream_t stream) {
-  uint32_t wshift = 0;
-  while ((1u << wshift) < width) wshift++;
-  if (!waves || !n || Gin < 2 || Gin > 65535 || (1u << wshift) != width || width > 64) return;
-  hipLaunchKernelGGL(k_seat_fold, dim3((unsigned)waves, (unsigned)((Gin + 1) / 2)), dim3(64), 0, stream, n, wshift,
-                     Gin, wdesc, wseat, xslot, digits, dstride, in, out, R);
+  const int wshift = seat_wshift(width);
+  if (!waves || !n || Gin < 2 || Gin > 65535 || wshift < 0) return;
+  hipLaunchKernelGGL(k_seat_fold, dim3((unsigned)waves, (unsigned)((Gin + 1) / 2)), dim3(64), 0, stream, n,
+                     (uint32_t)wshift, Gin, wdesc, wseat, xslot, digits, dstride, in, out, R);
 }
 
 void seat_ok(size_t S, size_t n, const uint32_t* scol, const uint8_t* dok, const uint8_t* extra, uint8_t* sok,

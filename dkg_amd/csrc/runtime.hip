@@ -42,12 +42,12 @@ struct dkg_ctx {
   hipEvent_t pev[5] = {};               // phase profiling inside verify_device (nsub == 1)
   hipEvent_t hev[9] = {};               // full mode: encrypt / decrypt kernels (nsub == 1)
   hipEvent_t bpev[3] = {};              // batches by proven complaints: around the two complaint stages
-  hipEvent_t rpev[8] = {};              // one party's checks (recv.*): decrypt, decode, chunks, fold, check, prove;
-                                        // [7]: the seats' chunk walk done, its folds begin
+  hipEvent_t rpev[8] = {};              // the marks of a one-party, pairs or seats call (recv.*, pairs.*, seats.*),
+                                        // one per RecvMark, the same names in every family
   int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
   int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
   std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
-  std::map<std::array<size_t, 3>, std::vector<uint32_t>> pair_digits;  // k_pair_eval's [S][17] records by (t, x, L)
+  std::map<std::array<size_t, 3>, std::vector<uint32_t>> pair_digits;  // k_pair_eval's fold_records by (t, x, L)
   int hy_timed = 0;                     // hev[] hold the phases of the last serialised encrypt (1)
                                         // and / or decrypt (2) since the last collect_hybrid_phases
   static constexpr int MAX_SUB = 8;
@@ -316,6 +316,13 @@ uint32_t* upload_scalars(dkg_ctx* ctx, const char* name, const uint8_t* host, si
 }
 
 // Upload an optional byte mask: null (absent) stays null.
+// host words to a named device buffer; the vector is the caller's to keep until it has synchronised
+uint32_t* upload_words(dkg_ctx* ctx, const char* name, const std::vector<uint32_t>& host) {
+  uint32_t* d = buf<uint32_t>(ctx, name, 4 * host.size());
+  h2d(ctx, d, host.data(), 4 * host.size());
+  return d;
+}
+
 const uint8_t* upload_mask(dkg_ctx* ctx, const char* name, const uint8_t* host, size_t bytes) {
   if (!host) return nullptr;
   uint8_t* d = buf<uint8_t>(ctx, name, bytes);
@@ -2210,12 +2217,21 @@ bool complaint_tables_pay(size_t n, size_t N, size_t count) {
 #define DKG_PAIR_ILP 1
 #endif
 
+// The fold multipliers of a plan as the digit records recv_mul_long reads (receivers.hip): the NAF of
+// mult[s] in out[fold_record(0, stages, s) ..], stages * FOLD_DIG_WORDS words in all.
+void fold_records(const dkg_receiver_plan& p, uint32_t* out) {
+  for (uint32_t s = 0; s < p.stages; s++) {
+    uint32_t* d = out + fold_record(0, p.stages, s);
+    d[16] = (uint32_t)dkgh::naf256(p.mult[s], d, d + 8, nullptr);
+  }
+}
+
 // One wave per (row, index) item (receivers.hip k_pair_eval) in the shape of dkg_pair_eval_shape under
 // ctx->receiver_chunk.  Item b < cnt: c = dlist[b] (b itself with a null dlist), row dcrow[c] - 1 of Cext
 // (element row * N + k, stride), index dxs[c] = hx[b] (1-based; hx on the host, per ITEM).  The fold's
-// multipliers are dkg_receiver_plan_for's for the forced chunk L, as signed digits, one [S][17] record
-// per DISTINCT index of the call (cached on the ctx).  R[c][40].  The staging vectors `slot` and `dig`
-// are the caller's to keep until it has synchronised.
+// multipliers are dkg_receiver_plan_for's for the forced chunk L, as signed digits (fold_records), one
+// [S][FOLD_DIG_WORDS] record per DISTINCT index of the call (cached on the ctx).  R[c][40].  The staging
+// vectors `slot` and `dig` are the caller's to keep until it has synchronised.
 struct PairStage {
   std::vector<uint32_t> xs, slot, dig;
 };
@@ -2231,7 +2247,8 @@ void pair_eval_launch(dkg_ctx* ctx, size_t t, size_t cnt, const uint32_t* dlist,
   }
   ctx->last_receiver_chunk = (int)L;
   dkgh::distinct_places(cnt, hx, ps.xs, ps.slot);
-  ps.dig.assign(std::max<size_t>(1, ps.xs.size() * S * 17), 0);
+  const size_t rec_words = fold_record(1, S, 0);
+  ps.dig.assign(std::max<size_t>(1, ps.xs.size() * rec_words), 0);
   for (size_t m = 0; m < ps.xs.size() && S; m++) {
     const uint32_t x = ps.xs[m];
     const std::array<size_t, 3> key = {t, x, L};
@@ -2242,18 +2259,15 @@ void pair_eval_launch(dkg_ctx* ctx, size_t t, size_t cnt, const uint32_t* dlist,
         ctx->err = "pair evaluation: no plan for the index";
         throw Fail{DKG_E_ARG};
       }
-      std::vector<uint32_t> rec(S * 17, 0);
-      for (uint32_t k = 0; k < S; k++)
-        rec[k * 17 + 16] = (uint32_t)dkgh::naf256(p.mult[k], &rec[k * 17], &rec[k * 17 + 8], nullptr);
+      std::vector<uint32_t> rec(rec_words, 0);
+      fold_records(p, rec.data());
       if (ctx->pair_digits.size() >= 65536) ctx->pair_digits.clear();
       it = ctx->pair_digits.emplace(key, std::move(rec)).first;
     }
-    memcpy(&ps.dig[m * S * 17], it->second.data(), 4 * S * 17);
+    memcpy(&ps.dig[m * rec_words], it->second.data(), 4 * rec_words);
   }
-  uint32_t* dslot = buf<uint32_t>(ctx, "pe_slot", 4 * cnt);
-  uint32_t* ddig = buf<uint32_t>(ctx, "pe_dig", 4 * ps.dig.size());
-  h2d(ctx, dslot, ps.slot.data(), 4 * cnt);
-  h2d(ctx, ddig, ps.dig.data(), 4 * ps.dig.size());
+  uint32_t* dslot = upload_words(ctx, "pe_slot", ps.slot);
+  uint32_t* ddig = upload_words(ctx, "pe_dig", ps.dig);
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_PAIR_ILP);
   (ilp ? dkgk_ilp::pair_eval : dkgk::pair_eval)(cnt, dlist, dxs, dcrow, dslot, Cext, stride, N, L, G, S, ddig, R,
                                                 ctx->stream);
@@ -5069,8 +5083,6 @@ int dkg_ctx_last_receiver_chunk(const dkg_ctx* ctx) { return ctx ? ctx->last_rec
 
 namespace {
 
-constexpr size_t RECV_DIG_WORDS = 20;                      // per (index, stage): 8 + 8 digit words, length
-constexpr size_t RECV_DIG_STRIDE = 16 * RECV_DIG_WORDS;    // per index
 constexpr size_t RECV_SLAB_BYTES = (size_t)256 << 20;      // chunk partials held at a time
 
 // Field multiplication of the evaluation's launches when dkg_ctx_set_field_mode leaves the choice
@@ -5079,13 +5091,19 @@ constexpr size_t RECV_SLAB_BYTES = (size_t)256 << 20;      // chunk partials hel
 #define DKG_RECV_ILP 1
 #endif
 
+// The marks of a one-party, pairs or seats call, one event of ctx->rpev[] each, in the order a call passes them:
+// the decryption begins (round 2), the call proper begins, the commitments are decoded, the chunk walk is done and
+// the folds begin (where one launch sequence covers the call), evaluated, decided, around the proofs (round 2).
+enum RecvMark { RM_DECRYPT, RM_START, RM_DECODED, RM_SPLIT, RM_EVALUATED, RM_CHECKED, RM_PROVE, RM_PROVED, RM_COUNT };
+static_assert(RM_COUNT == sizeof(dkg_ctx::rpev) / sizeof(hipEvent_t), "one event per mark");
+
 void recv_mark(dkg_ctx* ctx, int k) {
   if (ctx->nsub == 1) HCK(hipEventRecord(ctx->rpev[k], ctx->stream));
 }
 
-// After a sync: recv.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); others erased.
-void recv_phase(dkg_ctx* ctx, const char* name, int a, int b) {
-  const std::string key = std::string("recv.") + name;
+// After a sync: <tag>.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); a < 0: not run, erased
+void call_phase(dkg_ctx* ctx, const char* tag, const char* name, int a, int b) {
+  const std::string key = std::string(tag) + "." + name;
   ctx->phase_ms.erase(key);
   if (ctx->nsub != 1 || a < 0) return;
   float ms = 0;
@@ -5093,20 +5111,63 @@ void recv_phase(dkg_ctx* ctx, const char* name, int a, int b) {
   ctx->phase_ms[key] = ms;
 }
 
+// After a call's sync: every phase of family `tag` from the stages that ran, the others erased.  "recv" times the
+// chunk walk as `chunks` (up to RM_SPLIT where that was marked), "seats" the whole evaluation as `eval`, both the
+// folds after RM_SPLIT as `fold`; "pairs" has decode and eval only.  `prove` is erased here, set by round2_tail.
+enum { RAN_DECRYPT = 1, RAN_SPLIT = 2, RAN_CHECK = 4 };
+void call_phases(dkg_ctx* ctx, const char* tag, unsigned ran) {
+  const bool recv = !strcmp(tag, "recv"), split = (ran & RAN_SPLIT) != 0;
+  call_phase(ctx, tag, "decode", RM_START, RM_DECODED);
+  call_phase(ctx, tag, recv ? "chunks" : "eval", RM_DECODED, recv && split ? RM_SPLIT : RM_EVALUATED);
+  if (!strcmp(tag, "pairs")) return;
+  call_phase(ctx, tag, "decrypt", (ran & RAN_DECRYPT) ? RM_DECRYPT : -1, RM_START);
+  call_phase(ctx, tag, "fold", split ? RM_SPLIT : -1, RM_EVALUATED);
+  call_phase(ctx, tag, "check", (ran & RAN_CHECK) ? RM_EVALUATED : -1, RM_CHECKED);
+  call_phase(ctx, tag, "prove", -1, 0);
+}
+
+// Compressed rows Cc [..][N][32] on the device, decoded: the `rows` rows that dlist (device, may be null:
+// the first `rows`) names, in that order.  Cext [rows * N] points at stride rows * N, pok per point, rowok
+// per row; Cpm the position-major table [40][N][pad64(rows)] when asked for.
+struct Decoded {
+  uint32_t* Cext = nullptr;
+  uint8_t *pok = nullptr, *rowok = nullptr;
+  uint32_t* Cpm = nullptr;
+};
+void decode_stage(dkg_ctx* ctx, const uint32_t* Cc, const uint32_t* dlist, size_t rows, size_t N, bool pm,
+                  Decoded& d) {
+  hipStream_t st = ctx->stream;
+  if (dlist) {
+    uint32_t* gc = buf<uint32_t>(ctx, "dc_rows", 32 * rows * N);
+    dkgk::gather_rows(rows, N, dlist, Cc, nullptr, gc, st);
+    Cc = gc;
+  }
+  d.Cext = buf<uint32_t>(ctx, "Cext", PTB * rows * N);
+  d.pok = buf<uint8_t>(ctx, "pok", rows * N);
+  d.rowok = buf<uint8_t>(ctx, "dok", rows);
+  dkgk::decode_points(Cc, rows * N, d.Cext, rows * N, d.pok, st);
+  dkgk::dealer_ok(rows, N, d.pok, d.rowok, st);
+  if (pm) {
+    d.Cpm = buf<uint32_t>(ctx, "Cpm", PTB * N * pad64(rows));
+    dkgk::to_position_major(rows, N, pad64(rows), d.Cext, d.Cpm, st);
+  }
+}
+
 struct RecvEval {
   uint32_t* R = nullptr;    // [M * D][40] point-major, slot m's values at m * D + i
   uint8_t* dok = nullptr;   // [D] rows that decode
   uint32_t* xs = nullptr;   // [M] device: the 1-based indices (null: not uploaded)
   bool want_xs = true;      // in: the caller reads xs (recv_decide)
-  bool split_timed = false; // rpev[3] separates the chunk walk from the fold (one slab, one plan)
+  unsigned ran = 0;         // RAN_SPLIT: RM_SPLIT separates the chunk walk from the fold (one slab, one plan)
 };
 
 // Decode C [D][N][32] and evaluate every row at the M indices js[m] + 1 by the plans of
-// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks rpev[1] (start), [2] (decoded),
-// [3] (chunks, when split_timed) and [4] (evaluated).
+// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks RM_START, RM_DECODED, RM_SPLIT (then
+// ev.ran says so) and RM_EVALUATED.
 int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, size_t nplan, const uint8_t* C,
               RecvEval& ev) {
   const size_t N = t + 1, npad = pad64(D);
+  const size_t dig_stride = fold_record(1, 16, 0);  // per index: a plan has 16 stages at most
   std::vector<dkg_receiver_plan> plans(M);
   std::vector<uint32_t> hx(M), dig;
   int last = 0;
@@ -5140,36 +5201,23 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     hx[m] = js[m] + 1;
     const int rc = plan_of(hx[m], chunk, plans[m]);
     if (rc) return rc;
-    if (plans[m].stages && dig.empty()) dig.assign(M * RECV_DIG_STRIDE, 0);
-    for (uint32_t s = 0; s < plans[m].stages; s++) {
-      uint32_t* d = &dig[m * RECV_DIG_STRIDE + s * RECV_DIG_WORDS];
-      d[16] = (uint32_t)dkgh::naf256(plans[m].mult[s], d, d + 8, nullptr);
-    }
+    if (plans[m].stages && dig.empty()) dig.assign(M * dig_stride, 0);
+    if (plans[m].stages) fold_records(plans[m], &dig[m * dig_stride]);
     any_stage |= plans[m].stages != 0;
     last = std::max(last, (int)std::min<uint32_t>(plans[m].chunk, 0x7fffffffu));
   }
   ctx->last_receiver_chunk = last;
-  recv_mark(ctx, 1);
+  recv_mark(ctx, RM_START);
   uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
   h2d(ctx, Cc, C, 32 * D * N);
-  uint32_t* Cext = buf<uint32_t>(ctx, "Cext", PTB * D * N);
-  uint8_t* pok = buf<uint8_t>(ctx, "pok", D * N);
-  ev.dok = buf<uint8_t>(ctx, "dok", D);
-  uint32_t* Cpm = buf<uint32_t>(ctx, "Cpm", PTB * N * npad);
-  dkgk::decode_points(Cc, D * N, Cext, D * N, pok, ctx->stream);
-  dkgk::dealer_ok(D, N, pok, ev.dok, ctx->stream);
-  dkgk::to_position_major(D, N, npad, Cext, Cpm, ctx->stream);
+  Decoded dc;
+  decode_stage(ctx, Cc, nullptr, D, N, true, dc);
+  ev.dok = dc.rowok;
   uint32_t* ddig = nullptr;
-  if (any_stage || ev.want_xs) {  // the serial walk of one index reads neither
-    ev.xs = buf<uint32_t>(ctx, "rv_xs", 4 * M);
-    h2d(ctx, ev.xs, hx.data(), 4 * M);
-  }
-  if (any_stage) {
-    ddig = buf<uint32_t>(ctx, "rv_dig", 4 * dig.size());
-    h2d(ctx, ddig, dig.data(), 4 * dig.size());
-  }
+  if (any_stage || ev.want_xs) ev.xs = upload_words(ctx, "rv_xs", hx);  // the serial walk of one index reads neither
+  if (any_stage) ddig = upload_words(ctx, "rv_dig", dig);
   ev.R = buf<uint32_t>(ctx, "rv_R", PTB * M * D);
-  recv_mark(ctx, 2);
+  recv_mark(ctx, RM_DECODED);
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_RECV_ILP);
   auto chunks = ilp ? dkgk_ilp::recv_chunks : dkgk::recv_chunks;
   auto fold = ilp ? dkgk_ilp::recv_fold : dkgk::recv_fold;
@@ -5177,7 +5225,7 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
   for (size_t m0 = 0; m0 < M;) {
     const dkg_receiver_plan& p = plans[m0];
     if (p.stages == 0) {  // the serial walk: k_horner, as dkg_verify_receiver runs it
-      dkgk::horner(D, npad, N, Cpm, hx[m0], 1, ev.R + m0 * D * PT_WORDS_H, ctx->stream);
+      dkgk::horner(D, npad, N, dc.Cpm, hx[m0], 1, ev.R + m0 * D * PT_WORDS_H, ctx->stream);
       m0++, launches++;
       continue;
     }
@@ -5191,15 +5239,15 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     uint32_t* Q[2] = {buf<uint32_t>(ctx, "rv_q0", PTB * Ms * G * npad), buf<uint32_t>(ctx, "rv_q1", PTB * Ms * G1 * npad)};
     for (size_t b = 0; b < run; b += Ms) {
       const size_t ms = std::min(Ms, run - b);
-      chunks(D, npad, N, L, Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
+      chunks(D, npad, N, L, dc.Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
       if (launches == 0 && run == M && ms == run) {
-        recv_mark(ctx, 3);
-        ev.split_timed = true;
+        recv_mark(ctx, RM_SPLIT);
+        ev.ran = RAN_SPLIT;
       }
       size_t Gin = G;
       for (uint32_t s = 0; s < p.stages; s++) {
-        fold(D, npad, Gin, p.arity[s], Q[s & 1], ddig + s * RECV_DIG_WORDS, RECV_DIG_STRIDE, m0 + b, ms, Q[(s + 1) & 1],
-             ev.R, ctx->stream);
+        fold(D, npad, Gin, p.arity[s], Q[s & 1], ddig + fold_record(0, p.stages, s), dig_stride, m0 + b, ms,
+             Q[(s + 1) & 1], ev.R, ctx->stream);
         Gin = (Gin + p.arity[s] - 1) / p.arity[s];
       }
       if (Gin != 1) {
@@ -5211,14 +5259,8 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     m0 += run;
   }
   check_launch(ctx);
-  recv_mark(ctx, 4);
+  recv_mark(ctx, RM_EVALUATED);
   return DKG_OK;
-}
-
-void recv_eval_phases(dkg_ctx* ctx, const RecvEval& ev) {
-  recv_phase(ctx, "decode", 1, 2);
-  recv_phase(ctx, "chunks", 2, ev.split_timed ? 3 : 4);  // several slabs or plans: the whole evaluation
-  recv_phase(ctx, "fold", ev.split_timed ? 3 : -1, 4);
 }
 
 // decisions [M][n] of the evaluated slots against the share columns (device, [M][n][8])
@@ -5234,7 +5276,46 @@ void recv_check(dkg_ctx* ctx, size_t n, int round, size_t M, size_t j0, const Re
   }
   if (M > 1 || qualified) dkgk::recv_decide(M, n, round, ev.xs, ev.dok, qualified, dec, ctx->stream);
   check_launch(ctx);
-  recv_mark(ctx, 5);
+  recv_mark(ctx, RM_CHECKED);
+}
+
+// The end of a round-2 call over S seats (dkg_party_round2: S = 1) once its decisions dec [S][n] are on the host:
+// complaints[p] and r2_error[p] per seat (either may be null) and, with w, the proofs [S][n][192] of the rejected
+// dealers -- all seats in one run, zero elsewhere, <tag>.prove its time.  sk [S][32]; e1, ct, w [S][n][64].
+int round2_tail(dkg_ctx* ctx, const char* tag, size_t n, size_t t, size_t S, const uint8_t* dec, const uint8_t* sk,
+                const uint8_t* e1, const uint8_t* ct, const uint8_t* w, int32_t* complaints, uint8_t* r2_error,
+                uint8_t* proofs) {
+  std::vector<size_t> rej;  // (seat, dealer) pairs p * n + i
+  for (size_t p = 0; p < S; p++) {
+    size_t cnt = 0;
+    for (size_t i = 0; i < n; i++)
+      if (dec[p * n + i] == DKG_REJECT) rej.push_back(p * n + i), cnt++;
+    if (complaints) complaints[p] = (int32_t)cnt;
+    if (r2_error) r2_error[p] = cnt > t ? 1 : 0;  // committee.rs:340-347
+  }
+  if (!w) return DKG_OK;
+  memset(proofs, 0, 192 * S * n);
+  if (rej.empty()) return DKG_OK;
+  // ProofOfMisbehaviour::generate per rejected dealer (:309-322)
+  const size_t Cn = rej.size();
+  std::vector<uint8_t> ksk(32 * Cn), kenc(128 * Cn), kw(64 * Cn), kp(192 * Cn);
+  for (size_t c = 0; c < Cn; c++) {
+    const size_t e = rej[c];
+    memcpy(&ksk[32 * c], sk + 32 * (e / n), 32);
+    memcpy(&kenc[128 * c], e1 + 64 * e, 32);             // e1 of the randomness
+    memcpy(&kenc[128 * c + 32], ct + 64 * e, 32);
+    memcpy(&kenc[128 * c + 64], e1 + 64 * e + 32, 32);   // e1 of the share
+    memcpy(&kenc[128 * c + 96], ct + 64 * e + 32, 32);
+    memcpy(&kw[64 * c], w + 64 * e, 64);
+  }
+  recv_mark(ctx, RM_PROVE);
+  const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
+  if (rp) return rp;
+  recv_mark(ctx, RM_PROVED);
+  sync(ctx);
+  call_phase(ctx, tag, "prove", RM_PROVE, RM_PROVED);
+  for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
+  return DKG_OK;
 }
 
 void recv_reset_last(dkg_ctx* ctx) {
@@ -5263,10 +5344,7 @@ int dkg_commitment_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32
     d2h(ctx, P, Pc, 32 * M * D);
     if (ok) d2h(ctx, ok, ev.dok, D);
     sync(ctx);
-    recv_eval_phases(ctx, ev);
-    recv_phase(ctx, "check", -1, 0);
-    recv_phase(ctx, "decrypt", -1, 0);
-    recv_phase(ctx, "prove", -1, 0);
+    call_phases(ctx, "recv", ev.ran);
     return DKG_OK;
   });
 }
@@ -5287,44 +5365,29 @@ int dkg_commitment_eval_pairs(dkg_ctx* ctx, size_t D, size_t t, size_t count, co
     dkgh::distinct_places(count, rows, drows, crow);
     for (size_t p = 0; p < count; p++) crow[p] += 1, hx[p] = js[p] + 1;  // 1-based, as k_cmp_horner's lists
     const size_t Rn = drows.size();
-    recv_mark(ctx, 1);
+    recv_mark(ctx, RM_START);
     // the distinct rows gathered and decoded, as the batch complaint stage does it
     uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
     h2d(ctx, Cc, C, 32 * D * N);
-    uint32_t* dlist = buf<uint32_t>(ctx, "pe_rows", 4 * Rn);
-    uint32_t* dcrow = buf<uint32_t>(ctx, "pe_crow", 4 * count);
-    uint32_t* dxs = buf<uint32_t>(ctx, "pe_xs", 4 * count);
-    h2d(ctx, dlist, drows.data(), 4 * Rn);
-    h2d(ctx, dcrow, crow.data(), 4 * count);
-    h2d(ctx, dxs, hx.data(), 4 * count);
-    uint32_t* rc = buf<uint32_t>(ctx, "pe_rc", 32 * Rn * N);
-    uint32_t* rext = buf<uint32_t>(ctx, "pe_ext", PTB * Rn * N);
-    uint8_t* pok = buf<uint8_t>(ctx, "pe_pok", Rn * N);
-    uint8_t* rowok = buf<uint8_t>(ctx, "pe_rowok", Rn);
+    uint32_t* dlist = upload_words(ctx, "pe_rows", drows);
+    uint32_t* dcrow = upload_words(ctx, "pe_crow", crow);
+    uint32_t* dxs = upload_words(ctx, "pe_xs", hx);
+    Decoded dc;
+    decode_stage(ctx, Cc, dlist, Rn, N, false, dc);
     uint8_t* iok = buf<uint8_t>(ctx, "pe_ok", count);
-    dkgk::gather_rows(Rn, N, dlist, Cc, nullptr, rc, st);
-    dkgk::decode_points(rc, Rn * N, rext, Rn * N, pok, st);
-    dkgk::dealer_ok(Rn, N, pok, rowok, st);
-    dkgk::pair_ok(count, dcrow, rowok, iok, st);
-    recv_mark(ctx, 2);
+    dkgk::pair_ok(count, dcrow, dc.rowok, iok, st);
+    recv_mark(ctx, RM_DECODED);
     uint32_t* R = buf<uint32_t>(ctx, "pe_R", PTB * count);
     PairStage ps;
-    pair_eval_launch(ctx, t, count, nullptr, hx.data(), dxs, dcrow, rext, Rn * N, R, ps);
-    recv_mark(ctx, 4);
+    pair_eval_launch(ctx, t, count, nullptr, hx.data(), dxs, dcrow, dc.Cext, Rn * N, R, ps);
+    recv_mark(ctx, RM_EVALUATED);
     uint32_t* Pc = buf<uint32_t>(ctx, "pe_P", 32 * count);
     dkgk::recv_encode(1, count, R, iok, Pc, st);
     check_launch(ctx);
     d2h(ctx, P, Pc, 32 * count);
     if (ok) d2h(ctx, ok, iok, count);
     sync(ctx);  // the staging vectors live until here
-    for (const char* k : {"pairs.decode", "pairs.eval"}) ctx->phase_ms.erase(k);
-    if (ctx->nsub == 1) {
-      float ms = 0;
-      HCK(hipEventElapsedTime(&ms, ctx->rpev[1], ctx->rpev[2]));
-      ctx->phase_ms["pairs.decode"] = ms;
-      HCK(hipEventElapsedTime(&ms, ctx->rpev[2], ctx->rpev[4]));
-      ctx->phase_ms["pairs.eval"] = ms;
-    }
+    call_phases(ctx, "pairs", 0);
     return DKG_OK;
   });
 }
@@ -5354,10 +5417,7 @@ int dkg_verify_receivers(dkg_ctx* ctx, size_t n, size_t t, int round, size_t M, 
     recv_check(ctx, n, round, M, js[0], ev, ds, dsp, dq, dec);
     d2h(ctx, decision, dec, M * n);
     sync(ctx);
-    recv_eval_phases(ctx, ev);
-    recv_phase(ctx, "check", 4, 5);
-    recv_phase(ctx, "decrypt", -1, 0);
-    recv_phase(ctx, "prove", -1, 0);
+    call_phases(ctx, "recv", ev.ran | RAN_CHECK);
     return DKG_OK;
   });
 }
@@ -5371,7 +5431,7 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
     if (j >= n || (w && !proofs)) return DKG_E_ARG;
     recv_reset_last(ctx);
     // committee.rs:282-286: the pairs addressed to j, decrypted with sk_j (one recipient)
-    recv_mark(ctx, 0);
+    recv_mark(ctx, RM_DECRYPT);
     uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, 1);
     uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 64 * n);
     uint32_t* dct = buf<uint32_t>(ctx, "pr_ct", 64 * n);
@@ -5394,39 +5454,8 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
     if (s_out) d2h(ctx, s_out, ds, 32 * n);
     if (sp_out) d2h(ctx, sp_out, dsp, 32 * n);
     sync(ctx);
-    recv_phase(ctx, "decrypt", 0, 1);
-    recv_eval_phases(ctx, ev);
-    recv_phase(ctx, "check", 4, 5);
-    recv_phase(ctx, "prove", -1, 0);
-    std::vector<size_t> rej;
-    for (size_t i = 0; i < n; i++)
-      if (dec[i] == DKG_REJECT) rej.push_back(i);
-    if (complaints) *complaints = (int32_t)rej.size();
-    if (r2_error) *r2_error = rej.size() > t ? 1 : 0;  // :340-347
-    if (w) {
-      memset(proofs, 0, 192 * n);
-      if (!rej.empty()) {  // ProofOfMisbehaviour::generate per rejected dealer (:309-322)
-        const size_t Cn = rej.size();
-        std::vector<uint8_t> ksk(32 * Cn), kenc(128 * Cn), kw(64 * Cn), kp(192 * Cn);
-        for (size_t c = 0; c < Cn; c++) {
-          const size_t i = rej[c];
-          memcpy(&ksk[32 * c], sk, 32);
-          memcpy(&kenc[128 * c], e1 + 64 * i, 32);             // e1 of the randomness
-          memcpy(&kenc[128 * c + 32], ct + 64 * i, 32);
-          memcpy(&kenc[128 * c + 64], e1 + 64 * i + 32, 32);   // e1 of the share
-          memcpy(&kenc[128 * c + 96], ct + 64 * i + 32, 32);
-          memcpy(&kw[64 * c], w + 64 * i, 64);
-        }
-        recv_mark(ctx, 5);
-        const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
-        if (rp) return rp;
-        recv_mark(ctx, 6);
-        sync(ctx);
-        recv_phase(ctx, "prove", 5, 6);
-        for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
-      }
-    }
-    return DKG_OK;
+    call_phases(ctx, "recv", ev.ran | RAN_DECRYPT | RAN_CHECK);
+    return round2_tail(ctx, "recv", n, t, 1, dec, sk, e1, ct, w, complaints, r2_error, proofs);
   });
 }
 
@@ -5439,16 +5468,6 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
 
 namespace {
 
-// After a sync: seats.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); a < 0: not run
-void seat_phase(dkg_ctx* ctx, const char* name, int a, int b) {
-  const std::string key = std::string("seats.") + name;
-  ctx->phase_ms.erase(key);
-  if (ctx->nsub != 1 || a < 0) return;
-  float ms = 0;
-  HCK(hipEventElapsedTime(&ms, ctx->rpev[a], ctx->rpev[b]));
-  ctx->phase_ms[key] = ms;
-}
-
 struct SeatEval {
   dkgh::SeatPlan plan;         // host staging of the descriptors: lives until the caller has synchronised
   std::vector<uint32_t> rows;  // dealer rows of the distinct ceremonies
@@ -5456,17 +5475,16 @@ struct SeatEval {
   uint8_t* sok = nullptr;      // [S][n] dealer i's data decodes for seat p
   uint32_t* sx = nullptr;      // [S] device: the seats' 1-based indices
   uint32_t* scer = nullptr;    // [S] device: the seats' ceremonies
-  std::vector<uint32_t> xslot, dig;  // chunked route: per-wave slot and the [distinct x][stage][17] digit records
-  bool folded = false;         // rpev[7] separates the chunk walk from the folds
+  std::vector<uint32_t> xslot, dig;  // chunked route: per-wave slot and the fold_records per distinct x
+  unsigned ran = 0;            // RAN_SPLIT: RM_SPLIT separates the chunk walk from the folds
 };
 
-constexpr size_t SEAT_DIG_WORDS = 17;               // per (distinct x, stage): 8 + 8 digit words, length
 constexpr uint64_t SEAT_SCRATCH_MAX = (uint64_t)1 << 30;  // Q and its ping-pong partner
 
 // Decode the distinct ceremonies the seats name (C [B * n][N][32]) and evaluate dealer i of seat p's
 // ceremony at js[p] + 1 by dkg_seat_pack's waves.  extra (device [S][n], may be null) is ANDed into sok.
 // The route is ctx->seat_eval's: k_seat_horner, or k_seat_chunks and k_seat_fold in dkg_seat_eval_shape's
-// shape.  Marks rpev[1] (start), [2] (decoded), [7] (chunks walked, when folded) and [3] (evaluated).
+// shape.  Marks RM_START, RM_DECODED, RM_SPLIT (chunks walked, when folded) and RM_EVALUATED.
 int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer, const uint32_t* js,
                const uint8_t* C, const uint8_t* extra, SeatEval& ev) {
   if (B > 0xffffffffu / n) return DKG_E_ARG;  // dealer rows are 32-bit
@@ -5494,17 +5512,14 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
     std::vector<uint32_t> wx(pl.waves), xs;
     for (size_t v = 0; v < pl.waves; v++) wx[v] = pl.wave_desc[2 * v];
     dkgh::distinct_places(pl.waves, wx.data(), xs, ev.xslot);
-    ev.dig.assign(xs.size() * stages * SEAT_DIG_WORDS, 0);
+    ev.dig.assign(fold_record(xs.size(), stages, 0), 0);
     for (size_t k = 0; k < xs.size(); k++) {
       dkg_receiver_plan p;
       if (dkg_receiver_plan_for(n, t, xs[k], (int)L, &p) != DKG_OK || p.stages != stages) {
         ctx->err = "seats: no fold plan for index " + std::to_string(xs[k]);
         return DKG_E_ARG;
       }
-      for (uint32_t s = 0; s < stages; s++) {
-        uint32_t* d = &ev.dig[(k * stages + s) * SEAT_DIG_WORDS];
-        d[16] = (uint32_t)dkgh::naf256(p.mult[s], d, d + 8, nullptr);
-      }
+      fold_records(p, &ev.dig[fold_record(k, stages, 0)]);
     }
   }
   ctx->last_seat_eval = G > 1 ? 2 : 1;
@@ -5513,52 +5528,41 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
   for (size_t c = 0; c < Bd; c++)
     for (size_t i = 0; i < n; i++) ev.rows[c * n + i] = (uint32_t)(pl.cers[c] * n + i);
   hipStream_t st = ctx->stream;
-  recv_mark(ctx, 1);
+  recv_mark(ctx, RM_START);
   uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * B * n * N);
   h2d(ctx, Cc, C, 32 * B * n * N);
-  uint32_t* drows = buf<uint32_t>(ctx, "st_rows", 4 * D);
-  uint32_t* dscol = buf<uint32_t>(ctx, "st_scol", 4 * S);
-  uint32_t* dwdesc = buf<uint32_t>(ctx, "st_wdesc", 4 * pl.wave_desc.size());
-  uint32_t* dwseat = buf<uint32_t>(ctx, "st_wseat", 4 * pl.wave_seat.size());
-  ev.sx = buf<uint32_t>(ctx, "st_sx", 4 * S);
+  uint32_t* drows = upload_words(ctx, "st_rows", ev.rows);
+  uint32_t* dscol = upload_words(ctx, "st_scol", pl.seat_col);
+  uint32_t* dwdesc = upload_words(ctx, "st_wdesc", pl.wave_desc);
+  uint32_t* dwseat = upload_words(ctx, "st_wseat", pl.wave_seat);
+  ev.sx = upload_words(ctx, "st_sx", pl.seat_x);
   ev.scer = buf<uint32_t>(ctx, "st_scer", 4 * S);
-  h2d(ctx, drows, ev.rows.data(), 4 * D);
-  h2d(ctx, dscol, pl.seat_col.data(), 4 * S);
-  h2d(ctx, dwdesc, pl.wave_desc.data(), 4 * pl.wave_desc.size());
-  h2d(ctx, dwseat, pl.wave_seat.data(), 4 * pl.wave_seat.size());
-  h2d(ctx, ev.sx, pl.seat_x.data(), 4 * S);
   h2d(ctx, ev.scer, cer, 4 * S);
   // only the ceremonies named are gathered and decoded, as the pair evaluation does with its rows
-  uint32_t* gc = buf<uint32_t>(ctx, "st_rc", 32 * D * N);
-  uint32_t* Cext = buf<uint32_t>(ctx, "Cext", PTB * D * N);
-  uint8_t* pok = buf<uint8_t>(ctx, "pok", D * N);
-  uint8_t* dok = buf<uint8_t>(ctx, "dok", D);
-  uint32_t* Cpm = buf<uint32_t>(ctx, "Cpm", PTB * N * cols);
+  Decoded dc;
+  decode_stage(ctx, Cc, drows, D, N, true, dc);
   ev.sok = buf<uint8_t>(ctx, "st_sok", S * n);
   ev.R = buf<uint32_t>(ctx, "rv_R", PTB * S * n);
-  dkgk::gather_rows(D, N, drows, Cc, nullptr, gc, st);
-  dkgk::decode_points(gc, D * N, Cext, D * N, pok, st);
-  dkgk::dealer_ok(D, N, pok, dok, st);
-  dkgk::to_position_major(D, N, cols, Cext, Cpm, st);
-  dkgk::seat_ok(S, n, dscol, dok, extra, ev.sok, st);
-  recv_mark(ctx, 2);
+  dkgk::seat_ok(S, n, dscol, dc.rowok, extra, ev.sok, st);
+  recv_mark(ctx, RM_DECODED);
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_SEAT_ILP);
   if (G == 1) {
-    (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, Cpm, ev.R, st);
+    (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, dc.Cpm,
+                                                      ev.R, st);
   } else {
-    uint32_t* dxslot = buf<uint32_t>(ctx, "st_xslot", 4 * ev.xslot.size());
-    uint32_t* ddig = buf<uint32_t>(ctx, "st_dig", 4 * ev.dig.size());
-    h2d(ctx, dxslot, ev.xslot.data(), 4 * ev.xslot.size());
-    h2d(ctx, ddig, ev.dig.data(), 4 * ev.dig.size());
+    uint32_t* dxslot = upload_words(ctx, "st_xslot", ev.xslot);
+    uint32_t* ddig = upload_words(ctx, "st_dig", ev.dig);
     uint32_t* q0 = buf<uint32_t>(ctx, "st_q", scratch);  // 2 x [40][G][64 waves] words
     uint32_t* Q[2] = {q0, q0 + scratch / 8};
-    (ilp ? dkgk_ilp::seat_chunks : dkgk::seat_chunks)(pl.waves, n, N, cols, pl.width, L, dwdesc, dwseat, dscol, Cpm, Q[0], st);
-    recv_mark(ctx, 7);
-    ev.folded = true;
+    (ilp ? dkgk_ilp::seat_chunks : dkgk::seat_chunks)(pl.waves, n, N, cols, pl.width, L, dwdesc, dwseat, dscol, dc.Cpm,
+                                                      Q[0], st);
+    recv_mark(ctx, RM_SPLIT);
+    ev.ran = RAN_SPLIT;
     size_t Gin = G;
     for (uint32_t s = 0; s < stages; s++) {
-      (ilp ? dkgk_ilp::seat_fold : dkgk::seat_fold)(pl.waves, n, pl.width, Gin, dwdesc, dwseat, dxslot, ddig + s * SEAT_DIG_WORDS,
-                                                    stages * SEAT_DIG_WORDS, Q[s & 1], Q[(s + 1) & 1], ev.R, st);
+      (ilp ? dkgk_ilp::seat_fold : dkgk::seat_fold)(pl.waves, n, pl.width, Gin, dwdesc, dwseat, dxslot,
+                                                    ddig + fold_record(0, stages, s), fold_record(1, stages, 0),
+                                                    Q[s & 1], Q[(s + 1) & 1], ev.R, st);
       Gin = (Gin + 1) / 2;
     }
     if (Gin != 1) {
@@ -5567,18 +5571,18 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
     }
   }
   check_launch(ctx);
-  recv_mark(ctx, 3);
+  recv_mark(ctx, RM_EVALUATED);
   return DKG_OK;
 }
 
-// decisions [S][n] of the evaluated seats against their share columns (device, [S][n][8]); marks rpev[4]
+// decisions [S][n] of the evaluated seats against their share columns (device, [S][n][8]); marks RM_CHECKED
 void seats_check(dkg_ctx* ctx, size_t n, int round, size_t S, const SeatEval& ev, const uint32_t* ds,
                  const uint32_t* dsp, const uint8_t* qualified, uint8_t* dec) {
   // pair p * n + i as "dealer" of one receiver, as recv_check; recv_base = n keeps check's self test off
   dkgk::check(S * n, 1, 0, n, n, round, ds, dsp, ev.R, ctx->tab_gw, ctx->tab_hw, ev.sok, dec, ctx->stream);
   dkgk::seat_decide(S, n, round, ev.sx, ev.scer, ev.sok, qualified, dec, ctx->stream);
   check_launch(ctx);
-  recv_mark(ctx, 4);
+  recv_mark(ctx, RM_CHECKED);
 }
 
 }  // namespace
@@ -5598,12 +5602,7 @@ int dkg_commitment_eval_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t
     d2h(ctx, P, Pc, 32 * S * n);
     if (ok) d2h(ctx, ok, ev.sok, S * n);
     sync(ctx);
-    seat_phase(ctx, "decrypt", -1, 0);
-    seat_phase(ctx, "decode", 1, 2);
-    seat_phase(ctx, "eval", 2, 3);
-    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
-    seat_phase(ctx, "check", -1, 0);
-    seat_phase(ctx, "prove", -1, 0);
+    call_phases(ctx, "seats", ev.ran);
     return DKG_OK;
   });
 }
@@ -5631,12 +5630,7 @@ int dkg_verify_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, int round, size
     seats_check(ctx, n, round, S, ev, ds, dsp, dq, dec);
     d2h(ctx, decision, dec, S * n);
     sync(ctx);
-    seat_phase(ctx, "decrypt", -1, 0);
-    seat_phase(ctx, "decode", 1, 2);
-    seat_phase(ctx, "eval", 2, 3);
-    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
-    seat_phase(ctx, "check", 3, 4);
-    seat_phase(ctx, "prove", -1, 0);
+    call_phases(ctx, "seats", ev.ran | RAN_CHECK);
     return DKG_OK;
   });
 }
@@ -5656,7 +5650,7 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     hipStream_t st = ctx->stream;
     // committee.rs:282-286 for every seat: the n pairs addressed to seat p, decrypted with sk_p -- one wave
     // per (seat key, w, 64 dealers), the scalar wave-uniform (k_bdec_mul_w4's chain, seat-addressed)
-    recv_mark(ctx, 0);
+    recv_mark(ctx, RM_DECRYPT);
     const size_t items = 2 * S * n;
     uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, S);
     uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 32 * items);
@@ -5686,44 +5680,8 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     if (s_out) d2h(ctx, s_out, ds, 32 * S * n);
     if (sp_out) d2h(ctx, sp_out, dsp, 32 * S * n);
     sync(ctx);
-    seat_phase(ctx, "decrypt", 0, 1);
-    seat_phase(ctx, "decode", 1, 2);
-    seat_phase(ctx, "eval", 2, 3);
-    seat_phase(ctx, "fold", ev.folded ? 7 : -1, 3);
-    seat_phase(ctx, "check", 3, 4);
-    seat_phase(ctx, "prove", -1, 0);
-    std::vector<size_t> rej;  // (seat, dealer) pairs p * n + i
-    for (size_t p = 0; p < S; p++) {
-      size_t cnt = 0;
-      for (size_t i = 0; i < n; i++)
-        if (dec[p * n + i] == DKG_REJECT) rej.push_back(p * n + i), cnt++;
-      if (complaints) complaints[p] = (int32_t)cnt;
-      if (r2_error) r2_error[p] = cnt > t ? 1 : 0;  // :340-347
-    }
-    if (w) {
-      memset(proofs, 0, 192 * S * n);
-      if (!rej.empty()) {  // ProofOfMisbehaviour::generate per rejected dealer (:309-322), all seats in one run
-        const size_t Cn = rej.size();
-        std::vector<uint8_t> ksk(32 * Cn), kenc(128 * Cn), kw(64 * Cn), kp(192 * Cn);
-        for (size_t c = 0; c < Cn; c++) {
-          const size_t e = rej[c];
-          memcpy(&ksk[32 * c], sk + 32 * (e / n), 32);
-          memcpy(&kenc[128 * c], e1 + 64 * e, 32);             // e1 of the randomness
-          memcpy(&kenc[128 * c + 32], ct + 64 * e, 32);
-          memcpy(&kenc[128 * c + 64], e1 + 64 * e + 32, 32);   // e1 of the share
-          memcpy(&kenc[128 * c + 96], ct + 64 * e + 32, 32);
-          memcpy(&kw[64 * c], w + 64 * e, 64);
-        }
-        recv_mark(ctx, 5);
-        const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
-        if (rp) return rp;
-        recv_mark(ctx, 6);
-        sync(ctx);
-        seat_phase(ctx, "prove", 5, 6);
-        for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
-      }
-    }
-    return DKG_OK;
+    call_phases(ctx, "seats", ev.ran | RAN_DECRYPT | RAN_CHECK);
+    return round2_tail(ctx, "seats", n, t, S, dec, sk, e1, ct, w, complaints, r2_error, proofs);
   });
 }
 
@@ -6054,6 +6012,7 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
                        const uint8_t* r2_error, const uint8_t* r4_error, const uint8_t* A0, const uint8_t* s,
                        size_t D5, const uint32_t* d_ceremony, const uint32_t* d_sender, const uint32_t* d_dealer,
                        const uint8_t* d_share, uint8_t* mpk, int32_t* status, int32_t* recovery_index) {
+  enum { FIN_START, FIN_LAGRANGE, FIN_MPK };  // this call's marks: the first three events of rpev[]
   return guarded(ctx, [&] {
     if (!S) return DKG_OK;
     if (!B || !n || !cer || !js || !qualified || !reconstruct || !A0 || !s || !mpk || !status) return DKG_E_ARG;
@@ -6170,9 +6129,9 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
     const uint32_t* ds = upload_scalars(ctx, "sf.s", s, S * n);
     const uint32_t* dy = upload_scalars(ctx, "sf.dy", hy.data(), hy.size() / 32);
     uint32_t* sigma = buf<uint32_t>(ctx, "sf.sigma", 32 * S);
-    recv_mark(ctx, 0);
+    recv_mark(ctx, FIN_START);
     dkgk::seat_lagrange(S, n, dslot, dsx, dskip, drptr, drdeal, ddptr, ddx, dy, ds, longest + 1, sigma, st);
-    recv_mark(ctx, 1);
+    recv_mark(ctx, FIN_LAGRANGE);
     // ---- mpk_p = sum of the A_i0 it adds + g sigma_p (:789-795): only the named ceremonies' rows
     std::vector<uint8_t> ha0(32 * D);
     for (size_t c = 0; c < Bd; c++) memcpy(&ha0[32 * c * n], A0 + 32 * (size_t)cers[c] * n, 32 * n);
@@ -6196,14 +6155,14 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
     dkgk::fixed_base(S, sigma, ctx->tab_gw, ge, st);
     dkgk::add_points(S, ge, Hs, S, ge, st);
     dkgk::encode_points(ge, S, S, oc, st);
-    recv_mark(ctx, 2);
+    recv_mark(ctx, FIN_MPK);
     check_launch(ctx);
     std::vector<uint8_t> okh(D), outh(32 * S);
     d2h(ctx, okh.data(), a0ok, D);
     d2h(ctx, outh.data(), oc, 32 * S);
     sync(ctx);
-    seat_phase(ctx, "lagrange", 0, 1);
-    seat_phase(ctx, "mpk", 1, 2);
+    call_phase(ctx, "seats", "lagrange", FIN_START, FIN_LAGRANGE);
+    call_phase(ctx, "seats", "mpk", FIN_LAGRANGE, FIN_MPK);
     memset(mpk, 0, 32 * S);
     for (size_t p = 0; p < S; p++) {
       int32_t index = -1;

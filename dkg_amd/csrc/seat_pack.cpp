@@ -93,13 +93,14 @@ int seat_plan(size_t B, size_t n, size_t S, const uint32_t* cer, const uint32_t*
   out.seat_x.resize(S);
   out.wave_desc.assign(2 * (size_t)out.waves, 0);
   out.wave_seat.assign((size_t)out.waves * out.per_wave, SEAT_NONE);
+  const uint32_t wshift = (uint32_t)seat_wshift(out.width);  // dkg_seat_pack's widths are valid
   for (size_t p = 0; p < S; p++) {
     out.seat_x[p] = js[p] + 1;
     for (uint32_t tile = 0; tile < out.tiles; tile++) {
       const size_t wv = (size_t)wave_of[p] + tile;
       out.wave_desc[2 * wv] = js[p] + 1;
       out.wave_desc[2 * wv + 1] = tile;
-      out.wave_seat[wv * out.per_wave + slot_of[p]] = (uint32_t)p;
+      out.wave_seat[seat_cell(wshift, wv, slot_of[p] << wshift)] = (uint32_t)p;  // where the slot's lanes read
     }
   }
   out.live_lanes = S * n;

@@ -303,6 +303,62 @@ def test_party_round2_proofs(be, golden):
     assert bytes(v for k, v in enumerate(r["dec"]) if k != i) == bytes(v for k, v in enumerate(base["dec"]) if k != i)
 
 
+# ---------------------------------------------------------------- phase records
+def test_phase_records(golden):
+    """recv.* and pairs.* of every one-party call on one stream: which phases a call records and which read
+    -1; with the default two streams every key reads -1, the records of earlier calls included."""
+    c = golden("full_n10_t4.json")
+    n, t = c["n"], c["t"]
+    E, sk = H(c["E"]), H(c["member_sk"])
+    s, sp = columns(H(c["s"]), n, [1, 3]), columns(H(c["s_prime"]), n, [1, 3])
+    j, i = 1, 4
+    e1c, ctc = party_column(c, n, j)
+    bad = bytearray(ctc)
+    bad[64 * i + 32] ^= 1  # dealer i's share to j, corrupted in transit
+    w = bytes(range(64)) * n
+    recv, pairs = ("decrypt", "decode", "chunks", "fold", "check", "prove"), ("decode", "eval")
+
+    def calls(b, want_recv, want_pairs):
+        """every call; want_*(ran): the phase times expected, ran = the keys the call records"""
+        b.set_receiver_chunk(2)
+        b.commitment_eval(n, t, [1], E)
+        want_recv({"decode", "chunks", "fold"})
+        b.set_receiver_chunk(t + 1)  # one chunk: the serial walk
+        b.commitment_eval(n, t, [1], E)
+        want_recv({"decode", "chunks"})
+        b.set_receiver_chunk(0)
+        b.verify_receivers(n, t, 2, [1, 3], E, s, sp)
+        ph = b.phase_times("recv")
+        want_recv({"decode", "chunks", "check"} | ({"fold"} if ph["fold"] >= 0 else set()))
+        r = b.party_round2(n, t, j, E, e1c, bytes(bad), sk[32 * j:32 * j + 32], w)
+        assert r["dec"][i] == REJECT and r["complaints"] == 1
+        ph = b.phase_times("recv")
+        want_recv({"decrypt", "decode", "chunks", "check", "prove"} | ({"fold"} if ph["fold"] >= 0 else set()))
+        r = b.party_round2(n, t, j, E, e1c, ctc, sk[32 * j:32 * j + 32], w)
+        assert r["complaints"] == 0
+        ph = b.phase_times("recv")
+        want_recv({"decrypt", "decode", "chunks", "check"} | ({"fold"} if ph["fold"] >= 0 else set()))
+        b.commitment_eval_pairs(n, t, [0, 2, 2], [1, 1, 5], E)
+        want_pairs({"decode", "eval"})
+
+    b = dkg_amd.Backend(0)
+    try:
+        b.env_init(t, n, CK)
+
+        def expect(tag, names, recorded):
+            def want(ran):
+                ph = b.phase_times(tag)
+                for k in names:
+                    assert ph[k] >= 0 if recorded and k in ran else ph[k] == -1, (k, ph)
+            return want
+        b.set_streams(1)
+        calls(b, expect("recv", recv, True), expect("pairs", pairs, True))
+        b.set_streams(2)  # the default
+        calls(b, expect("recv", recv, False), expect("pairs", pairs, False))
+    finally:
+        b.close()
+
+
 # ---------------------------------------------------------------- argument errors
 def test_argument_errors(golden):
     c = golden("ceremony_n10_t4.json")

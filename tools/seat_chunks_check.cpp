@@ -1,8 +1,9 @@
 // Stand-alone host check of the seats' chunked evaluation (receivers.hip k_seat_chunks / k_seat_fold):
-// the chunk and fold index arithmetic replayed lane by lane, from dkgh::seat_plan's descriptors and
-// dkg_seat_eval_shape, exactly as the runtime (seats_eval) launches it.  Every Q read must be in bounds and
-// written earlier in the same call, every xslot in range, and every live (seat, dealer) must get exactly
-// one R store, dead lanes none.  Meant to be built with -fsanitize=address,undefined and run on the CPU:
+// the chunk and fold index arithmetic of seat_map.h -- the functions the kernels themselves run -- walked lane
+// by lane, from dkgh::seat_plan's descriptors and dkg_seat_eval_shape, as the runtime (seats_eval) launches
+// it.  Every Q read must be in bounds and written earlier in the same call, every xslot in range, and every
+// live (seat, dealer) must get exactly one R store, dead lanes none.  Meant to be built with
+// -fsanitize=address,undefined and run on the CPU:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //       tools/seat_chunks_check.cpp dkg_amd/csrc/seat_pack.cpp dkg_amd/csrc/receiver_plan.cpp \
 //       dkg_amd/csrc/host_crypto.cpp -o seat_chunks_check
@@ -37,8 +38,8 @@ static int run(size_t B, size_t n, size_t t, const std::vector<uint32_t>& cer, c
   dkgh::SeatPlan pl;
   CHECK(dkgh::seat_plan(B, n, S, cer.data(), js.data(), pl) == DKG_OK);
   const size_t waves = pl.waves, lanes = 64 * waves, W = pl.width;
-  uint32_t wshift = 0;
-  while ((1u << wshift) < W) wshift++;
+  CHECK(seat_wshift((uint32_t)W) >= 0);  // the launchers' validity test
+  const uint32_t wshift = (uint32_t)seat_wshift((uint32_t)W);
   const uint32_t x_max = *std::max_element(pl.seat_x.begin(), pl.seat_x.end());
   uint32_t L = 0, G = 0, stages = 0;
   uint64_t scratch = 0;
@@ -51,7 +52,7 @@ static int run(size_t B, size_t n, size_t t, const std::vector<uint32_t>& cer, c
   std::vector<uint32_t> wx(waves), xs, xslot;
   for (size_t v = 0; v < waves; v++) wx[v] = pl.wave_desc[2 * v];
   dkgh::distinct_places(waves, wx.data(), xs, xslot);
-  const size_t dig_words = xs.size() * stages * 17;
+  const size_t dig_words = fold_record(xs.size(), stages, 0);
   for (size_t k = 0; k < xs.size(); k++) {
     dkg_receiver_plan p;
     CHECK(dkg_receiver_plan_for(n, t, xs[k], (int)L, &p) == DKG_OK && p.stages == stages);
@@ -71,22 +72,13 @@ static int run(size_t B, size_t n, size_t t, const std::vector<uint32_t>& cer, c
   for (size_t v = 0; v < waves; v++)
     for (size_t u = 0; u < G; u++)
       for (uint32_t l = 0; l < 64; l++) {
-        const uint32_t tile = pl.wave_desc[2 * v + 1];
-        const uint32_t slot = l >> wshift, i = l & (uint32_t)(W - 1);
-        const size_t cell = (v << (6 - wshift)) + slot;
-        CHECK(cell < pl.wave_seat.size());
-        const uint32_t seat = pl.wave_seat[cell];
-        const size_t d = (size_t)tile * 64 + i;
-        const bool live = seat != dkgh::SEAT_NONE && d < n;
-        size_t col = 0;
-        if (live) {
-          CHECK(seat < S);
-          col = (size_t)pl.seat_col[seat] * n + d;
-        }
-        CHECK(col < cols);
-        const size_t lo = u * L, hi = lo + L < N ? lo + L : N;
-        CHECK(lo < hi && hi <= N);  // C reads (hi - 1) * cols + col .. lo * cols + col of N * cols
-        const size_t e = u * lanes + v * 64 + l;
+        CHECK(seat_cell(wshift, v, l) < pl.wave_seat.size());
+        const SeatLane m = seat_lane(n, wshift, v, l, pl.wave_desc.data(), pl.wave_seat.data());
+        if (m.live) CHECK(m.seat < S);
+        CHECK(seat_column(m, n, pl.seat_col.data()) < cols);
+        const ChunkSpan ch = chunk_span(u, L, N);
+        CHECK(ch.lo < ch.hi && ch.hi <= N);  // C reads (hi - 1) * cols + col .. lo * cols + col of N * cols
+        const size_t e = seat_partial(lanes, u, seat_wave_lane(v, l));
         CHECK(in_bounds((size_t)G * lanes, e));
         CHECK(stamp[0][e] == 0);  // written once
         stamp[0][e] = launch;
@@ -101,28 +93,26 @@ static int run(size_t B, size_t n, size_t t, const std::vector<uint32_t>& cer, c
     std::vector<uint32_t>& in = stamp[s & 1];
     std::vector<uint32_t>& out = stamp[(s + 1) & 1];
     for (size_t v = 0; v < waves; v++) {
-      const size_t rec = (size_t)s * 17 + (size_t)xslot[v] * stages * 17;  // ddig + s * 17, stride stages * 17
-      CHECK(rec + 17 <= dig_words);
+      // seats_eval passes ddig + fold_record(0, stages, s) and the stride fold_record(1, stages, 0)
+      const size_t rec = fold_record(0, stages, s) + (size_t)xslot[v] * fold_record(1, stages, 0);
+      CHECK(rec + FOLD_DIG_WORDS <= dig_words);
       for (size_t w = 0; w < Gout; w++)
         for (uint32_t l = 0; l < 64; l++) {
-          const size_t lane = v * 64 + l;
-          const size_t e0 = 2 * w * lanes + lane, e1 = (2 * w + 1) * lanes + lane;
+          const size_t lane = seat_wave_lane(v, l);
+          const size_t e0 = seat_partial(lanes, 2 * w, lane), e1 = seat_partial(lanes, 2 * w + 1, lane);
           CHECK(in_bounds(Gin * lanes, e0) && in[e0] == launch - 1);  // what the launch before wrote
           if (2 * w + 1 < Gin) CHECK(in_bounds(Gin * lanes, e1) && in[e1] == launch - 1);
           if (Gout != 1) {
-            const size_t e = w * lanes + lane;
+            const size_t e = seat_partial(lanes, w, lane);
             CHECK(in_bounds(Gout * lanes, e));
             CHECK(out[e] != launch);  // once per launch
             out[e] = launch;
             continue;
           }
-          const uint32_t tile = pl.wave_desc[2 * v + 1];
-          const uint32_t slot = l >> wshift, i = l & (uint32_t)(W - 1);
-          const uint32_t seat = pl.wave_seat[(v << (6 - wshift)) + slot];
-          const size_t d = (size_t)tile * 64 + i;
-          if (seat == dkgh::SEAT_NONE || d >= n) continue;  // dead: nothing stored
-          CHECK(seat < S && d < n && !stored[(size_t)seat * n + d]);
-          stored[(size_t)seat * n + d] = 1;
+          const SeatLane m = seat_lane(n, wshift, v, l, pl.wave_desc.data(), pl.wave_seat.data());
+          if (!m.live) continue;  // dead: nothing stored
+          CHECK(m.seat < S && m.d < n && !stored[seat_result(m, n)]);
+          stored[seat_result(m, n)] = 1;
         }
     }
     Gin = Gout;

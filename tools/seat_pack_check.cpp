@@ -1,6 +1,7 @@
 // Stand-alone host check of the seats calls' plain C++: dkg_seat_pack and the descriptor builder
-// (dkgh::seat_plan: distinct ceremonies, per-wave and per-seat records), replayed lane by lane as
-// k_seat_horner reads them.  Meant to be built with -fsanitize=address,undefined and run on the CPU:
+// (dkgh::seat_plan: distinct ceremonies, per-wave and per-seat records), read lane by lane through
+// seat_map.h, the lane map k_seat_horner itself runs.  Meant to be built with -fsanitize=address,undefined
+// and run on the CPU:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude \
 //       tools/seat_pack_check.cpp dkg_amd/csrc/seat_pack.cpp dkg_amd/csrc/receiver_plan.cpp \
 //       dkg_amd/csrc/host_crypto.cpp -o seat_pack_check
@@ -27,7 +28,7 @@ static uint32_t rnd() {
   return seed >> 8;
 }
 
-// one seat list through dkg_seat_pack and seat_plan; the kernel's reads replayed with bounds
+// one seat list through dkg_seat_pack and seat_plan; the kernel's reads (seat_map.h) with bounds
 static int run(size_t B, size_t n, const std::vector<uint32_t>& cer, const std::vector<uint32_t>& js) {
   const size_t S = js.size();
   uint32_t W = 0, per = 0, tiles = 0, waves = 0;
@@ -53,26 +54,22 @@ static int run(size_t B, size_t n, const std::vector<uint32_t>& cer, const std::
   // the kernel's view: wave v, lane l -> (seat, dealer) or dead; every pair exactly once
   const size_t cols = (pl.cers.size() * n + 63) / 64 * 64;
   std::vector<uint8_t> seen(S * n, 0);
-  uint32_t wshift = 0;
-  while ((1u << wshift) < W) wshift++;
+  const uint32_t wshift = (uint32_t)seat_wshift(W);  // W is a valid width: checked above
   for (size_t v = 0; v < waves; v++) {
     const uint32_t x = pl.wave_desc[2 * v], tile = pl.wave_desc[2 * v + 1];
     CHECK(x >= 1 && x <= n && tile < tiles);
     CHECK(v == 0 || pl.wave_desc[2 * (v - 1)] <= x);  // groups in ascending x
     bool any = false;
     for (uint32_t l = 0; l < 64; l++) {
-      const uint32_t slot = l >> wshift, i = l & (W - 1);
-      const size_t cell = (v << (6 - wshift)) + slot;
-      CHECK(cell < pl.wave_seat.size());
-      const uint32_t seat = pl.wave_seat[cell];
-      const size_t d = (size_t)tile * 64 + i;
-      if (seat == dkgh::SEAT_NONE || d >= n) continue;
+      CHECK(seat_cell(wshift, v, l) < pl.wave_seat.size());
+      const SeatLane m = seat_lane(n, wshift, v, l, pl.wave_desc.data(), pl.wave_seat.data());
+      if (!m.live) continue;
+      const uint32_t seat = m.seat;
       CHECK(seat < S && js[seat] + 1 == x);
-      CHECK(wave_of[seat] + tile == v && slot_of[seat] == slot);
-      const size_t col = (size_t)pl.seat_col[seat] * n + d;
-      CHECK(col < cols);
-      CHECK(!seen[(size_t)seat * n + d]);
-      seen[(size_t)seat * n + d] = 1;
+      CHECK(wave_of[seat] + tile == v && slot_of[seat] == m.slot);
+      CHECK(seat_column(m, n, pl.seat_col.data()) < cols);
+      CHECK(!seen[seat_result(m, n)]);
+      seen[seat_result(m, n)] = 1;
       any = true;
     }
     CHECK(any);  // no wave without a live lane
