@@ -8,6 +8,7 @@
 #include <cstring>
 #include <algorithm>
 #include <array>
+#include <iterator>
 #include <map>
 #include <memory>
 #include <optional>
@@ -39,17 +40,19 @@ struct dkg_ctx {
   bool have_h = false;
   size_t threshold = 0, nr_members = 0;
   hipEvent_t ev[8] = {};
-  hipEvent_t pev[5] = {};               // phase profiling inside verify_device (nsub == 1)
-  hipEvent_t hev[9] = {};               // full mode: encrypt / decrypt kernels (nsub == 1)
-  hipEvent_t bpev[3] = {};              // batches by proven complaints: around the two complaint stages
-  hipEvent_t rpev[8] = {};              // the marks of a one-party, pairs or seats call (recv.*, pairs.*, seats.*),
-                                        // one per RecvMark, the same names in every family
+  // The phase recorder behind dkg_ctx_phase_ms: every family's device-time marks of the current call in record
+  // order, mark k on phase_pool[k] (grow-only).  phase_mark adds one, phase_collect turns a tag's marks into
+  // "<tag>.<name>" entries after the sync; guarded() clears the list, so a call's uncollected marks end with it.
+  struct PhaseMark {
+    const char* tag;                    // the family (a literal); null once collected
+    int phase;                          // the phase whose segment the mark closes; < 0: a start mark
+  };
+  std::vector<hipEvent_t> phase_pool;
+  std::vector<PhaseMark> phase_marks;
   int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
   int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
   std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
   std::map<std::array<size_t, 3>, std::vector<uint32_t>> pair_digits;  // k_pair_eval's fold_records by (t, x, L)
-  int hy_timed = 0;                     // hev[] hold the phases of the last serialised encrypt (1)
-                                        // and / or decrypt (2) since the last collect_hybrid_phases
   static constexpr int MAX_SUB = 8;
   int nsub = 2;                         // dealer-chunk streams of verify_device
   hipStream_t sub[MAX_SUB] = {};
@@ -151,13 +154,8 @@ struct dkg_ctx {
   const uint32_t* shard_s = nullptr;
   size_t shard_n = 0, shard_d0 = 0, shard_D = 0;
   // full mode of the batches (dkg_ceremony_batch_full_device and its primitives): ceremonies per
-  // chunk of the hybrid stage (0: automatic, bfull_chunk_size), and the phase marks of the last call --
-  // (phase, event) in stream order, a segment between two marks belonging to the later one's phase
-  // (-1: a start mark); events come from a grow-only pool
+  // chunk of the hybrid stage (0: automatic, bfull_chunk_size)
   size_t bfull_chunk = 0;
-  std::vector<hipEvent_t> bf_pool;
-  std::vector<std::pair<int, hipEvent_t>> bf_marks;
-  std::string timed_tag;                // set while pev[] hold a serialised verify_device's phases
   std::map<std::string, double> phase_ms;  // last value per "r<round>.<phase>"
 };
 
@@ -251,6 +249,7 @@ int guarded(dkg_ctx* ctx, F&& f) {
   if (!ctx) return DKG_E_ARG;
   try {
     HCK(hipSetDevice(ctx->device));
+    ctx->phase_marks.clear();  // no entry point runs inside another's guarded()
     int rc = f();
     return rc;
   } catch (const Fail& x) {
@@ -347,17 +346,73 @@ bool binom_nt(size_t r, size_t columns) {
   return 2.0 * (double)(r + 1) * (double)columns * 160.0 > lim;
 }
 
-// After a sync: record the device time of binomial / stepping / check of the last verify_device
-// when it ran serialised and timed (names "<tag>.binomial" etc.; tag r2, r4 or r24 = fused).
-void collect_phases(dkg_ctx* ctx) {
-  if (ctx->timed_tag.empty()) return;
-  const char* names[4] = {"binomial", "stepping", "combine", "check"};
-  for (int i = 0; i < 4; i++) {
-    float ms = 0;
-    HCK(hipEventElapsedTime(&ms, ctx->pev[i], ctx->pev[i + 1]));
-    ctx->phase_ms[ctx->timed_tag + "." + names[i]] = ms;
+// ---- the phase recorder (dkg_ctx_phase_ms): each family marks its stages with phase_mark lines and names them in
+// one table of rows for phase_collect.
+// The next pooled event, recorded on `st` as family `tag`'s mark closing `phase` (< 0: a start mark).  The pool
+// covers the families with a fixed number of marks from dkg_ctx_create on; only the chunked loops grow it.
+constexpr size_t PHASE_POOL_MIN = 32;
+void phase_mark(dkg_ctx* ctx, hipStream_t st, const char* tag, int phase) {
+  const size_t k = ctx->phase_marks.size();
+  if (k == ctx->phase_pool.size()) {
+    hipEvent_t e;
+    HCK(hipEventCreate(&e));
+    ctx->phase_pool.push_back(e);
   }
-  ctx->timed_tag.clear();
+  HCK(hipEventRecord(ctx->phase_pool[k], st));
+  ctx->phase_marks.push_back({tag, phase});
+}
+// ... on ctx->stream, for the families that are timed only when everything runs on that one stream
+void phase_mark_serial(dkg_ctx* ctx, const char* tag, int phase) {
+  if (ctx->nsub == 1) phase_mark(ctx, ctx->stream, tag, phase);
+}
+
+struct PhaseRow {
+  const char* name;
+  unsigned phases;  // the phase ids (bit 1 << id) whose segments the row sums
+};
+// After a sync: the segment between two consecutive marks of `tag` belongs to the later mark's phase (a start
+// mark owns none, and marks of another tag in between cut nothing: party_round2's decrypt spans decrypt_device's
+// full.* marks).  "<tag>.<name>" of every row becomes the sum of its phases' segments, over all chunks of a
+// chunked loop; a row none of whose phases closed a segment did not run and is erased (reads -1).  Consumes the
+// tag's marks and touches no other name.
+void phase_collect(dkg_ctx* ctx, const char* tag, const PhaseRow* rows, size_t count) {
+  double ms[32] = {};
+  unsigned seen = 0;
+  hipEvent_t prev = nullptr;
+  for (size_t k = 0; k < ctx->phase_marks.size(); k++) {
+    dkg_ctx::PhaseMark& m = ctx->phase_marks[k];
+    if (!m.tag || strcmp(m.tag, tag)) continue;
+    if (m.phase >= 0 && prev) {
+      float v = 0;
+      HCK(hipEventElapsedTime(&v, prev, ctx->phase_pool[k]));
+      ms[m.phase] += v;
+      seen |= 1u << m.phase;
+    }
+    prev = ctx->phase_pool[k];
+    m.tag = nullptr;
+  }
+  for (size_t i = 0; i < count; i++) {
+    const std::string name = std::string(tag) + "." + rows[i].name;
+    double sum = 0;
+    for (int p = 0; p < 32; p++)
+      if (rows[i].phases >> p & 1) sum += ms[p];
+    if (seen & rows[i].phases) ctx->phase_ms[name] = sum;
+    else ctx->phase_ms.erase(name);
+  }
+}
+
+// verify_device's phases under its tag r2, r4 or r24 (= fused), after the sync of a call that ran it timed; a
+// verification that was not timed leaves the entries of an earlier one.
+enum { VP_BINOMIAL, VP_STEPPING, VP_COMBINE, VP_CHECK };
+const PhaseRow VERIFY_PHASES[] = {{"binomial", 1u << VP_BINOMIAL}, {"stepping", 1u << VP_STEPPING},
+                                  {"combine", 1u << VP_COMBINE}, {"check", 1u << VP_CHECK}};
+void collect_verify_phases(dkg_ctx* ctx) {
+  for (const char* tag : {"r2", "r4", "r24"})
+    for (const dkg_ctx::PhaseMark& m : ctx->phase_marks)
+      if (m.tag && !strcmp(m.tag, tag)) {
+        phase_collect(ctx, tag, VERIFY_PHASES, std::size(VERIFY_PHASES));
+        break;
+      }
 }
 
 // One block of rows to verify: `D` dealers [dealer_base, dealer_base + D) against receivers
@@ -916,7 +971,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
       dkgk::commit_position_major(d1 - d0, N, ctx->r1_a + d0 * N * 8, ctx->r1_b + d0 * N * 8, ctx->tab_gw,
                                   ctx->tab_hw, Cpm + c0, W, L, npad, ctx->r1_A0 + d0, D, st);
     }
-    if (tm) HCK(hipEventRecord(ctx->pev[0], st));
+    if (tm) phase_mark(ctx, st, tag, -1);
     const uint32_t* e;
     if (per_wave) {
       e = dkgk::binomial_wave(w, W, L, Cpm + c0, e0 + c0, st, U, npad, Lr,
@@ -948,7 +1003,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
       if (bflags && DKG_BINOM_STEP_DED == 2)
         dkgk::binomial_wave_redo(w, W, L, Cpm + c0, bin, st, U, npad, Lr, bflags, c0, D, (unsigned)gw);
     }
-    if (tm) HCK(hipEventRecord(ctx->pev[1], st));
+    if (tm) phase_mark(ctx, st, tag, VP_BINOMIAL);
     if (!per_wave || !DKG_BINOM_WAVE_COLMAJOR)  // timed with the stepping
       dkgk::to_column_major(w, W, L, e, eT + c0 * L, U, npad, st);
     uint32_t* fl = sflags ? sflags + dkgk::stepping_flag_words(c0, U) : nullptr;
@@ -958,7 +1013,7 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
               sb ? sb + c0 * n * 40 : nullptr, st, U, npad, Lr, whole, fl, c0, D, (unsigned)gw,
               Rz ? Rz + c0 * n * 10 : nullptr, tail_a, tail_b, r_scaled))
       throw Fail{DKG_E_ARG};  // stepping flag words: an internal layout error, never silently dropped
-    if (tm) HCK(hipEventRecord(ctx->pev[2], st));
+    if (tm) phase_mark(ctx, st, tag, VP_STEPPING);
     if (jsf) {
       dkgk::affine_pairs(w, npad, U, n, R + c0 * n * PT_WORDS_H, Aff + c0 * n * AFFP_WORDS_H, st, 0, 0, r_scaled);
       dkgk::combine_short_jsf(w, npad, U, n, sdig, stop, sev, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
@@ -968,14 +1023,12 @@ void verify_device(dkg_ctx* ctx, size_t n, size_t t, const VerifySeg* segs, int 
       dkgk::combine_short_aff(w, npad, U, n, sdig, stop, Aff + c0 * n * AFFP_WORDS_H, R + c0 * n * PT_WORDS_H, st);
     } else if (short_mult) dkgk::combine_short(w, npad, U, n, sdig, stop, R + c0 * n * PT_WORDS_H, st);
     else dkgk::combine(w, npad, U, n, ydig, ytop, R + c0 * n * PT_WORDS_H, st);
-    if (tm) HCK(hipEventRecord(ctx->pev[3], st));
+    if (tm) phase_mark(ctx, st, tag, VP_COMBINE);
     checks(g0 * 64, std::min(D, g1 * 64), st);
-    if (tm) HCK(hipEventRecord(ctx->pev[4], st));
+    if (tm) phase_mark(ctx, st, tag, VP_CHECK);
   };
-  ctx->timed_tag.clear();
   if (nsub <= 1) {
     chunk(0, groups, home, timed);
-    if (timed) ctx->timed_tag = tag;
   } else {
     HCK(hipEventRecord(ctx->fork, home));
     size_t g0 = 0;
@@ -1006,7 +1059,7 @@ void verify_one(dkg_ctx* ctx, size_t n, size_t t, int round, size_t D, size_t de
 // DKG_MISSING); a_ok (may be null): 0 = its phase-3 commitments are missing (round 4: accusation)
 // (full mode), folded into the round-2 decisions like an undecodable commitment.
 // host_between = false (fused rounds only): `between` only queues device work, so it follows the
-// checks on the stream without a host round trip; the caller syncs and calls collect_phases.
+// checks on the stream without a host round trip; the caller syncs and calls collect_verify_phases.
 template <typename F>
 void verify_rounds_group(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dealer_base, const uint32_t* Ecomp,
                          const uint32_t* Acomp, const uint32_t* s, const uint32_t* sp, uint8_t* dec2, uint8_t* dec4,
@@ -1018,7 +1071,7 @@ void verify_rounds_group(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t deal
     if (after2) HCK(hipEventRecord(after2, ctx->stream));
     if (host_between) {
       sync(ctx);
-      collect_phases(ctx);
+      collect_verify_phases(ctx);
     }
     between();
   } else {
@@ -1026,11 +1079,11 @@ void verify_rounds_group(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t deal
     verify_device(ctx, n, t, &g2, 1, true, "r2");
     if (after2) HCK(hipEventRecord(after2, ctx->stream));
     sync(ctx);
-    collect_phases(ctx);
+    collect_verify_phases(ctx);
     between();
     verify_one(ctx, n, t, 4, D, dealer_base, Acomp, s, nullptr, dec4, true, a_ok);
     sync(ctx);
-    collect_phases(ctx);
+    collect_verify_phases(ctx);
   }
 }
 
@@ -1076,6 +1129,10 @@ const uint32_t* vinv_table(dkg_ctx* ctx, size_t N) {
   return dev;
 }
 
+enum { IP_INTERPOLATE, IP_COEF_CHECK, IP_DECIDE, IP_FALLBACK };
+const PhaseRow INTERP_PHASES[] = {{"interpolate", 1u << IP_INTERPOLATE}, {"coef_check", 1u << IP_COEF_CHECK},
+                                  {"decide", 1u << IP_DECIDE}, {"fallback", 1u << IP_FALLBACK}};
+
 template <typename F>
 void verify_rounds_interp(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dealer_base, const uint32_t* Ecomp,
                           const uint32_t* Acomp, const uint32_t* s, const uint32_t* sp, uint8_t* dec2, uint8_t* dec4,
@@ -1083,7 +1140,7 @@ void verify_rounds_interp(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dea
   const size_t N = t + 1;
   hipStream_t st = ctx->stream;
   if (D) {
-    HCK(hipEventRecord(ctx->pev[0], st));
+    phase_mark(ctx, st, "interp", -1);
     // the commitments as group elements [D][N]
     const uint32_t *Ee, *Ae;
     size_t cs;
@@ -1113,7 +1170,7 @@ void verify_rounds_interp(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dea
     uint32_t* Fa = buf<uint32_t>(ctx, "i.F", 32 * D * N);
     uint32_t* Fb = buf<uint32_t>(ctx, "i.Fp", 32 * D * N);
     dkgk::interp(D, N, n, WT, s, sp, Fa, Fb, st);  // F, F' through receivers 1..t+1
-    HCK(hipEventRecord(ctx->pev[1], st));
+    phase_mark(ctx, st, "interp", IP_INTERPOLATE);
     uint8_t* okE = buf<uint8_t>(ctx, "i.okE", D * N);
     uint8_t* okA = buf<uint8_t>(ctx, "i.okA", D * N);
     dkgk::coef_check(D, N, Fa, Fb, Ee, Ae, cs, ctx->tab_gw, ctx->tab_hw, okE, okA, st);
@@ -1121,10 +1178,10 @@ void verify_rounds_interp(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dea
     uint8_t* cA = buf<uint8_t>(ctx, "i.cA", D);
     dkgk::dealer_ok(D, N, okE, cE, st);
     dkgk::dealer_ok(D, N, okA, cA, st);
-    HCK(hipEventRecord(ctx->pev[2], st));
+    phase_mark(ctx, st, "interp", IP_COEF_CHECK);
     dkgk::interp_decide(D, n, N, dealer_base, n, s, sp, Fa, Fb, dokE, dokA, cE, cA, ctx->tab_gw, ctx->tab_hw, dec2,
                         dec4, st);
-    HCK(hipEventRecord(ctx->pev[3], st));
+    phase_mark(ctx, st, "interp", IP_DECIDE);
     check_launch(ctx);
     // rows whose commitments are not g F + h F' (case B): difference tables, every P_i(j) in the group
     std::vector<uint8_t> h_dE(D), h_dA(D), h_cE(D), h_cA(D);
@@ -1194,19 +1251,12 @@ void verify_rounds_interp(dkg_ctx* ctx, size_t n, size_t t, size_t D, size_t dea
       }
       check_launch(ctx);
     }
-    HCK(hipEventRecord(ctx->pev[4], st));
+    phase_mark(ctx, st, "interp", IP_FALLBACK);  // spans the host round trip after the decisions
     ctx->fallback_rows = rows.size();
   }
   if (after2) HCK(hipEventRecord(after2, st));
   sync(ctx);
-  if (D) {
-    const char* names[4] = {"interpolate", "coef_check", "decide", "fallback"};
-    for (int i = 0; i < 4; i++) {
-      float ms = 0;
-      HCK(hipEventElapsedTime(&ms, ctx->pev[i], ctx->pev[i + 1]));
-      ctx->phase_ms[std::string("interp.") + names[i]] = ms;
-    }
-  }
+  if (D) phase_collect(ctx, "interp", INTERP_PHASES, std::size(INTERP_PHASES));
   between();
 }
 
@@ -1493,7 +1543,7 @@ RoundsResult receivers_rounds_once(dkg_ctx* ctx, size_t n, size_t t, const uint3
   }
   binom_mark_copy(ctx);
   sync(ctx);
-  collect_phases(ctx);
+  collect_verify_phases(ctx);
   std::vector<uint8_t> qualified(h, h + n), r2err(n), recon(h + n, h + 2 * n), r4e(h + 2 * n, h + 3 * n);
   std::vector<int32_t> complaints(n);
   memcpy(complaints.data(), h + 3 * n, 4 * n);
@@ -1805,7 +1855,7 @@ void batch_receivers(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint32_t*
   sync(ctx);
   for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); k++)
     if (staged[k]) memcpy(outs[k].host, staged[k], outs[k].bytes);
-  collect_phases(ctx);
+  collect_verify_phases(ctx);
   round2_host(V, t, qualified.data(), complaints.data(), r2err.data());
   recon = h_rej4;
   round4_host(V, qualified.data(), recon.data());
@@ -1899,6 +1949,14 @@ void batch_times(dkg_ctx* ctx, dkg_batch_out* out, bool round1) {
 // ctx->key_comb forces a kind; at 0 the kind is 1 unless the caller lets the cost rule choose
 // (choose: the sharded full calls, where a key serves 2 D items and a cold 2^10 build outweighs them).
 // Returns the keys' decode mask [n] of the kind used (device).
+// full.*: the kernels' device times of a ceremony's serialised encrypt + decrypt, collected after its sync by
+// every full-mode ceremony, so that a phase it did not time (chunk streams, or a verify-only ceremony without
+// encryption) reads -1.
+enum { FP_ENC_MUL, FP_ENC_ENCODE, FP_ENC_SYM, FP_DEC_DECODE, FP_DEC_MUL, FP_DEC_ENCODE, FP_DEC_SYM };
+const PhaseRow FULL_PHASES[] = {{"enc_mul", 1u << FP_ENC_MUL},       {"enc_encode", 1u << FP_ENC_ENCODE},
+                                {"enc_sym", 1u << FP_ENC_SYM},       {"dec_decode", 1u << FP_DEC_DECODE},
+                                {"dec_mul", 1u << FP_DEC_MUL},       {"dec_encode", 1u << FP_DEC_ENCODE},
+                                {"dec_sym", 1u << FP_DEC_SYM}};
 const uint8_t* encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* pkc, const uint32_t* s,
                               const uint32_t* sp, const uint32_t* r, uint32_t* e1, uint32_t* ct,
                               hipStream_t st = nullptr, const uint8_t* pk_host = nullptr, bool choose = false) {
@@ -1928,20 +1986,19 @@ const uint8_t* encrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* 
   uint32_t* Kc = buf<uint32_t>(ctx, "hy.Kc", 32 * items);
   // phase events (serialised runs, nsub == 1): the bench's per-kernel roofline of full mode
   const bool tm = ctx->nsub == 1;
-  if (tm) HCK(hipEventRecord(ctx->hev[0], st));
+  if (tm) phase_mark(ctx, st, "full", -1);
   if (kind == 1) {
     dkgk::enc_mul(D, n, r, ctx->tab_gw, tabs, R, K, st);
   } else {
     dkgk::fixed_base(items, r, ctx->tab_gw, R, st);         // e1 = G::generator() * r  (elgamal.rs:141)
     dkgk::benc_mul(n, n, D, r, tabs, K, items, st);         // key = pk * r  (elgamal.rs:138-140)
   }
-  if (tm) HCK(hipEventRecord(ctx->hev[1], st));
+  if (tm) phase_mark(ctx, st, "full", FP_ENC_MUL);
   dkgk::encode_points(R, items, items, e1, st);
   dkgk::encode_points(K, items, items, Kc, st);
-  if (tm) HCK(hipEventRecord(ctx->hev[2], st));
+  if (tm) phase_mark(ctx, st, "full", FP_ENC_ENCODE);
   dkgk::sym_xor(D, n, Kc, false, ct, const_cast<uint32_t*>(s), const_cast<uint32_t*>(sp), st);
-  if (tm) HCK(hipEventRecord(ctx->hev[3], st));
-  if (tm) ctx->hy_timed |= 1;
+  if (tm) phase_mark(ctx, st, "full", FP_ENC_SYM);
   check_launch(ctx);
   return pk_ok;
 }
@@ -1956,38 +2013,18 @@ void decrypt_device(dkg_ctx* ctx, size_t D, size_t n, const uint32_t* sk, const 
   uint32_t* K = buf<uint32_t>(ctx, "hy.K", PTB * items);
   uint32_t* Kc = buf<uint32_t>(ctx, "hy.Kc", 32 * items);
   const bool tm = ctx->nsub == 1;
-  if (tm) HCK(hipEventRecord(ctx->hev[4], st));
+  if (tm) phase_mark(ctx, st, "full", -1);
   dkgk::decode_points(e1, items, R, items, item_ok, st);
-  if (tm) HCK(hipEventRecord(ctx->hev[5], st));
+  if (tm) phase_mark(ctx, st, "full", FP_DEC_DECODE);
   const size_t tw = dkgk::dec_mul_table_words(D, n);
   dkgk::dec_mul(D, n, sk, R, K, st, tw ? buf<uint32_t>(ctx, "hy.dec_tab", 4 * tw) : nullptr);
-  if (tm) HCK(hipEventRecord(ctx->hev[6], st));
+  if (tm) phase_mark(ctx, st, "full", FP_DEC_MUL);
   dkgk::encode_points(K, items, items, Kc, st);
-  if (tm) HCK(hipEventRecord(ctx->hev[7], st));
+  if (tm) phase_mark(ctx, st, "full", FP_DEC_ENCODE);
   dkgk::sym_xor(D, n, Kc, true, const_cast<uint32_t*>(ct), s, sp, st);
-  if (tm) HCK(hipEventRecord(ctx->hev[8], st));
-  if (tm) ctx->hy_timed |= 2;
+  if (tm) phase_mark(ctx, st, "full", FP_DEC_SYM);
   if (dealer_ok_out) dkgk::dealer_ok(D, 2 * n, item_ok, dealer_ok_out, st);
   check_launch(ctx);
-}
-
-// After a sync: the full-mode kernels' device times of the last serialised encrypt + decrypt
-// (dkg_ctx_phase_ms "full.enc_mul", "full.enc_encode", "full.enc_sym", "full.dec_decode",
-// "full.dec_mul", "full.dec_encode", "full.dec_sym").
-// Every full.* entry of an earlier ceremony is dropped first: a phase this ceremony did not time
-// (chunk streams, or a verify-only ceremony without encryption) reads -1.
-void collect_hybrid_phases(dkg_ctx* ctx) {
-  const char* names[8] = {"enc_mul", "enc_encode", "enc_sym", "", "dec_decode", "dec_mul", "dec_encode", "dec_sym"};
-  for (const char* nm : names)
-    if (nm[0]) ctx->phase_ms.erase(std::string("full.") + nm);
-  const int timed = ctx->hy_timed;
-  ctx->hy_timed = 0;
-  for (int i = 0; i < 8; i++) {
-    if (!names[i][0] || !(timed & (i < 4 ? 1 : 2))) continue;
-    float ms = 0;
-    HCK(hipEventElapsedTime(&ms, ctx->hev[i], ctx->hev[i + 1]));
-    ctx->phase_ms[std::string("full.") + names[i]] = ms;
-  }
 }
 
 // ---- full mode for batches (hybrid_batch.hip): ceremony c's recipients own keys c*n .. c*n + n-1.
@@ -1999,8 +2036,12 @@ enum {
   BF_ENC_DECODE, BF_ENC_TAB, BF_ENC_E1, BF_ENC_MUL, BF_ENC_ENCODE, BF_ENC_SYM,
   BF_DEC_DECODE, BF_DEC_MUL, BF_DEC_ENCODE, BF_DEC_SYM, BF_PHASES
 };
-const char* const BF_NAMES[BF_PHASES] = {"enc_decode", "enc_tab", "enc_e1", "enc_mul", "enc_encode", "enc_sym",
-                                         "dec_decode", "dec_mul", "dec_encode", "dec_sym"};
+// bfull.*: the summed device times of a call's hybrid kernels over all chunks; a phase it did not run reads -1
+const PhaseRow BF_ROWS[BF_PHASES] = {
+    {"enc_decode", 1u << BF_ENC_DECODE}, {"enc_tab", 1u << BF_ENC_TAB},       {"enc_e1", 1u << BF_ENC_E1},
+    {"enc_mul", 1u << BF_ENC_MUL},       {"enc_encode", 1u << BF_ENC_ENCODE}, {"enc_sym", 1u << BF_ENC_SYM},
+    {"dec_decode", 1u << BF_DEC_DECODE}, {"dec_mul", 1u << BF_DEC_MUL},       {"dec_encode", 1u << BF_DEC_ENCODE},
+    {"dec_sym", 1u << BF_DEC_SYM}};
 
 size_t bfull_chunk_size(const dkg_ctx* ctx, size_t B, size_t n) {
   const size_t items = 2 * n * n;
@@ -2009,39 +2050,6 @@ size_t bfull_chunk_size(const dkg_ctx* ctx, size_t B, size_t n) {
   const size_t fit = std::min(BFULL_SCRATCH_BYTES / per, dkgk::bdec_launch_waves() / (2 * n * ((n + 63) / 64)));
   const size_t c = ctx->bfull_chunk ? ctx->bfull_chunk : std::max<size_t>(1, fit);
   return std::min(c, B);
-}
-
-void bf_reset(dkg_ctx* ctx) { ctx->bf_marks.clear(); }
-void bf_mark(dkg_ctx* ctx, hipStream_t st, int phase) {
-  const size_t k = ctx->bf_marks.size();
-  if (k == ctx->bf_pool.size()) {
-    hipEvent_t e;
-    HCK(hipEventCreate(&e));
-    ctx->bf_pool.push_back(e);
-  }
-  HCK(hipEventRecord(ctx->bf_pool[k], st));
-  ctx->bf_marks.emplace_back(phase, ctx->bf_pool[k]);
-}
-// After a sync: the summed device times of the last call's hybrid kernels over all chunks
-// (dkg_ctx_phase_ms "bfull.enc_decode", ".enc_tab", ".enc_e1", ".enc_mul", ".enc_encode", ".enc_sym",
-// ".dec_decode", ".dec_mul", ".dec_encode", ".dec_sym"); a phase the call did not run reads -1.
-void collect_bfull_phases(dkg_ctx* ctx) {
-  double ms[BF_PHASES] = {};
-  bool seen[BF_PHASES] = {};
-  for (size_t k = 1; k < ctx->bf_marks.size(); k++) {
-    const int ph = ctx->bf_marks[k].first;
-    if (ph < 0) continue;
-    float v = 0;
-    HCK(hipEventElapsedTime(&v, ctx->bf_marks[k - 1].second, ctx->bf_marks[k].second));
-    ms[ph] += v;
-    seen[ph] = true;
-  }
-  for (int i = 0; i < BF_PHASES; i++) {
-    const std::string name = std::string("bfull.") + BF_NAMES[i];
-    if (seen[i]) ctx->phase_ms[name] = ms[i];
-    else ctx->phase_ms.erase(name);
-  }
-  ctx->bf_marks.clear();
 }
 
 // Dealers' side: pkc [B*n][8] key encodings, s / sp [B*n][n][8], r [B*n][n][2][8] -> e1, ct
@@ -2056,24 +2064,24 @@ void encrypt_batch_device(dkg_ctx* ctx, size_t B, size_t n, const uint32_t* pkc,
   uint32_t* R = buf<uint32_t>(ctx, "bf.R", PTB * mi);
   uint32_t* K = buf<uint32_t>(ctx, "bf.K", PTB * mi);
   uint32_t* Kc = buf<uint32_t>(ctx, "bf.Kc", 32 * mi);
-  bf_mark(ctx, st, -1);
+  phase_mark(ctx, st, "bfull", -1);
   for (size_t c0 = 0; c0 < B; c0 += chunk) {
     const size_t Bc = std::min(chunk, B - c0), keys = Bc * n, items = 2 * keys * n;
     const size_t k0 = c0 * n, p0 = k0 * n, i0 = 2 * p0;  // first key / (dealer, recipient) pair / item
     dkgk::decode_points(pkc + 8 * k0, keys, pk_ext, keys, pk_ok + k0, st);
-    bf_mark(ctx, st, BF_ENC_DECODE);
+    phase_mark(ctx, st, "bfull", BF_ENC_DECODE);
     dkgk::benc_tab(keys, pk_ext, keys, tab, st);
-    bf_mark(ctx, st, BF_ENC_TAB);
+    phase_mark(ctx, st, "bfull", BF_ENC_TAB);
     dkgk::fixed_base(items, r + 8 * i0, ctx->tab_gw, R, st);  // e1 = G::generator() * r  (elgamal.rs:141)
-    bf_mark(ctx, st, BF_ENC_E1);
+    phase_mark(ctx, st, "bfull", BF_ENC_E1);
     dkgk::benc_mul(keys, n, n, r + 8 * i0, tab, K, items, st);   // key = pk * r  (elgamal.rs:138-140)
-    bf_mark(ctx, st, BF_ENC_MUL);
+    phase_mark(ctx, st, "bfull", BF_ENC_MUL);
     dkgk::encode_points(R, items, items, e1 + 8 * i0, st);
     dkgk::encode_points(K, items, items, Kc, st);
-    bf_mark(ctx, st, BF_ENC_ENCODE);
+    phase_mark(ctx, st, "bfull", BF_ENC_ENCODE);
     dkgk::sym_xor(keys, n, Kc, false, ct + 8 * i0, const_cast<uint32_t*>(s) + 8 * p0,
                   const_cast<uint32_t*>(sp) + 8 * p0, st);
-    bf_mark(ctx, st, BF_ENC_SYM);
+    phase_mark(ctx, st, "bfull", BF_ENC_SYM);
   }
   check_launch(ctx);
 }
@@ -2088,18 +2096,18 @@ void decrypt_batch_device(dkg_ctx* ctx, size_t B, size_t n, const uint32_t* sk, 
   uint32_t* K = buf<uint32_t>(ctx, "bf.K", PTB * mi);
   uint32_t* Kc = buf<uint32_t>(ctx, "bf.Kc", 32 * mi);
   uint32_t* T = buf<uint32_t>(ctx, "bf.dec_tab", 4 * dkgk::bdec_mul_table_words(mk, n));
-  bf_mark(ctx, st, -1);
+  phase_mark(ctx, st, "bfull", -1);
   for (size_t c0 = 0; c0 < B; c0 += chunk) {
     const size_t Bc = std::min(chunk, B - c0), keys = Bc * n, items = 2 * keys * n;
     const size_t k0 = c0 * n, p0 = k0 * n, i0 = 2 * p0;
     dkgk::decode_points(e1 + 8 * i0, items, R, items, item_ok + i0, st);
-    bf_mark(ctx, st, BF_DEC_DECODE);
+    phase_mark(ctx, st, "bfull", BF_DEC_DECODE);
     dkgk::bdec_mul(keys, n, sk + 8 * k0, R, K, items, T, st);  // committee.rs:282-286
-    bf_mark(ctx, st, BF_DEC_MUL);
+    phase_mark(ctx, st, "bfull", BF_DEC_MUL);
     dkgk::encode_points(K, items, items, Kc, st);
-    bf_mark(ctx, st, BF_DEC_ENCODE);
+    phase_mark(ctx, st, "bfull", BF_DEC_ENCODE);
     dkgk::sym_xor(keys, n, Kc, true, const_cast<uint32_t*>(ct) + 8 * i0, s + 8 * p0, sp + 8 * p0, st);
-    bf_mark(ctx, st, BF_DEC_SYM);
+    phase_mark(ctx, st, "bfull", BF_DEC_SYM);
   }
   if (dealer_ok_out) dkgk::dealer_ok(B * n, 2 * n, item_ok, dealer_ok_out, st);
   check_launch(ctx);
@@ -2706,6 +2714,8 @@ void complaints2_rows(dkg_ctx* ctx, size_t n, size_t t, size_t C2, size_t R2, co
 // only (dev.e1, dev.ct).  Always the per-complaint Horner walk (k_cmp_horner): ctx->complaint_eval
 // does not apply.  Leaves the masks and the device verdicts in bp; the index arrays go through one
 // pinned staging buffer.
+enum { BP_C4, BP_C2 };
+const PhaseRow BPROVEN_PHASES[] = {{"c4", 1u << BP_C4}, {"c2", 1u << BP_C2}};
 void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDevice& dev, const BatchComplaints2* c2,
                       const BatchComplaints4& c4, BatchProven& bp) {
   const size_t N = t + 1, V = B * n, C2 = c2 ? c2->C : 0, C4 = c4.C;
@@ -2736,7 +2746,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
   const uint32_t* seq = dix + at;  // list and ridx of the Horner walks: item k is element k of Rh
   for (size_t k = 0; k < iota; k++) hix[at + k] = (uint32_t)k;
   h2d(ctx, dix, hix, 4 * words);
-  HCK(hipEventRecord(ctx->bpev[0], st));
+  phase_mark(ctx, st, "bproven", -1);
   // ---- round 4 (k_c3_*): the E and A rows of the accused dealers, gathered and decoded once
   uint8_t* proven4 = buf<uint8_t>(ctx, "bp.proven4", V);
   int32_t* dver4 = buf<int32_t>(ctx, "bp.verdict4", 4 * C4);
@@ -2748,7 +2758,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
     complaints4_rows(ctx, n, t, C4, R4, rc, x4, crow4, drow4, seq, c4.share, c4.randomness, nullptr, dev.fetched3,
                      dver4);
   }
-  HCK(hipEventRecord(ctx->bpev[1], st));
+  phase_mark(ctx, st, "bproven", BP_C4);
   // ---- round 2 (k_cv_*): the E rows of the accused dealers, the ciphertext pairs from the batch's own
   uint8_t *cmask = nullptr, *pair = nullptr;
   int32_t* dver2 = nullptr;
@@ -2770,7 +2780,7 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
   }
   // ---- the verdicts as the rounds' masks
   dkgk::proven_masks(C2, n, drow2, x2, dver2, C4, drow4, dver4, cmask, pair, proven4, st);
-  HCK(hipEventRecord(ctx->bpev[2], st));
+  if (c2) phase_mark(ctx, st, "bproven", BP_C2);  // without a round-2 stage bproven.c2 reads -1
   check_launch(ctx);
   bp.a_ok = dev.fetched3;
   bp.cmask = cmask;
@@ -2788,14 +2798,9 @@ void batch_complaints(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchDev
 // After the batch's sync: the stages' device times, and per ceremony what proven_outcome does for one --
 // the verdicts against dealers that round 2 disqualified become IGNORED, the finalising parties' common
 // outcome, and a zeroed mpk where they panic.
-void batch_proven_outcome(dkg_ctx* ctx, size_t B, size_t n, size_t t, bool have_c2, const BatchComplaints4& c4,
+void batch_proven_outcome(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchComplaints4& c4,
                           const BatchProven& bp, dkg_batch_out* out) {
-  float ms = 0;
-  HCK(hipEventElapsedTime(&ms, ctx->bpev[0], ctx->bpev[1]));
-  ctx->phase_ms["bproven.c4"] = ms;
-  HCK(hipEventElapsedTime(&ms, ctx->bpev[1], ctx->bpev[2]));
-  if (have_c2) ctx->phase_ms["bproven.c2"] = ms;
-  else ctx->phase_ms.erase("bproven.c2");
+  phase_collect(ctx, "bproven", BPROVEN_PHASES, std::size(BPROVEN_PHASES));
   for (size_t c = 0; c < c4.C; c++)
     if (!bp.qualified[(size_t)c4.ceremony[c] * n + c4.accused[c] - 1]) c4.verdict[c] = DKG_COMPLAINT_IGNORED;
   for (size_t g = 0; g < B; g++) {
@@ -2905,7 +2910,7 @@ int verify_ceremony(dkg_ctx* ctx, size_t n, size_t t, const CeremonyInput& in, d
   }
   const RoundsResult r = receivers_rounds(ctx, n, t, cm.E, cm.A, ds, dsp, out, true, m);  // waits for the shares
   if (full) {
-    collect_hybrid_phases(ctx);  // decryption phases only (no encryption here: full.enc_* read -1)
+    phase_collect(ctx, "full", FULL_PHASES, std::size(FULL_PHASES));  // no encryption here: full.enc_* read -1
     if (out->s) d2h(ctx, out->s, ds, 32 * n * n);
     if (out->s_prime) d2h(ctx, out->s_prime, dsp, 32 * n * n);
     sync(ctx);
@@ -2965,14 +2970,13 @@ int verify_batch(dkg_ctx* ctx, size_t B, size_t n, size_t t, const BatchInput& i
     uint32_t* rsp = buf<uint32_t>(ctx, "bfm_sp", 32 * V * n);
     uint8_t* iok = buf<uint8_t>(ctx, "bfm_iok", items);
     uint8_t* eok = buf<uint8_t>(ctx, "bfm_eok", V);
-    bf_reset(ctx);
     decrypt_batch_device(ctx, B, n, d.sk, d.e1, d.ct, rs, rsp, iok, eok);
     d.s = rs, d.s_prime = rsp;
     e_ok = eok;  // the decode mask of the dealer's ciphertexts
   }
   batch_receivers(ctx, B, n, t, d.E, d.A, d.s, d.s_prime, out, e_ok, in.c4 ? &bp : nullptr);
-  if (full) collect_bfull_phases(ctx);
-  if (in.c4) batch_proven_outcome(ctx, B, n, t, in.c2 != nullptr, *in.c4, bp, out);
+  if (full) phase_collect(ctx, "bfull", BF_ROWS, BF_PHASES);
+  if (in.c4) batch_proven_outcome(ctx, B, n, t, *in.c4, bp, out);
   if (full) {
     if (in.s_out) d2h(ctx, in.s_out, d.s, 32 * V * n);
     if (in.s_prime_out) d2h(ctx, in.s_prime_out, d.s_prime, 32 * V * n);
@@ -3062,10 +3066,8 @@ int dkg_ctx_create(int device, dkg_ctx** out) {
     HCK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     HCK(hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, greatest));
     for (auto& e : ctx->ev) HCK(hipEventCreate(&e));
-    for (auto& e : ctx->pev) HCK(hipEventCreate(&e));
-    for (auto& e : ctx->hev) HCK(hipEventCreate(&e));
-    for (auto& e : ctx->bpev) HCK(hipEventCreate(&e));
-    for (auto& e : ctx->rpev) HCK(hipEventCreate(&e));
+    ctx->phase_pool.resize(PHASE_POOL_MIN);
+    for (auto& e : ctx->phase_pool) HCK(hipEventCreate(&e));
     for (auto& e : ctx->cb_ev) HCK(hipEventCreate(&e));
     for (auto& st : ctx->sub) HCK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest));
     HCK(hipStreamCreateWithPriority(&ctx->side, hipStreamNonBlocking, least));
@@ -3108,19 +3110,11 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   if (ctx->tab_hw) (void)hipFree(ctx->tab_hw);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->pev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->hev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->bpev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->rpev)
+  for (auto& e : ctx->phase_pool)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->cb_ev)
     if (e) (void)hipEventDestroy(e);
   for (auto& e : ctx->join)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->bf_pool)
     if (e) (void)hipEventDestroy(e);
   if (ctx->fork) (void)hipEventDestroy(ctx->fork);
   for (auto& st : ctx->sub)
@@ -3130,6 +3124,7 @@ void dkg_ctx_destroy(dkg_ctx* ctx) {
   if (ctx->side_fork) (void)hipEventDestroy(ctx->side_fork);
   if (ctx->shares_done) (void)hipEventDestroy(ctx->shares_done);
   if (ctx->pub_done) (void)hipEventDestroy(ctx->pub_done);
+  if (ctx->terms_done) (void)hipEventDestroy(ctx->terms_done);
   delete ctx;
 }
 
@@ -4081,8 +4076,8 @@ int shard_ceremony(dkg_ctx* ctx, size_t n, size_t t, size_t d0, size_t d1, const
     binom_mark_copy(ctx);
     sync(ctx);
   });
-  collect_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
-  if (full) collect_hybrid_phases(ctx);
+  collect_verify_phases(ctx);  // the checks' serialised phases (shard_rows queues no host round trip)
+  if (full) phase_collect(ctx, "full", FULL_PHASES, std::size(FULL_PHASES));
   if (sp) shard_proven_verdicts(*sp);
   if (in.ms_total) *in.ms_total = ev_ms(ctx, 0, 1);
   return DKG_OK;
@@ -4995,7 +4990,7 @@ int dkg_ceremony_run_full_device(dkg_ctx* ctx, size_t n, size_t t, const void* d
     RoundMasks m;
     m.e_ok = eok;
     receivers_rounds(ctx, n, t, cm.E, cm.A, rs, rsp, out, false, m);
-    collect_hybrid_phases(ctx);
+    phase_collect(ctx, "full", FULL_PHASES, std::size(FULL_PHASES));
     ceremony_times(ctx, out, true);
     return DKG_OK;
   });
@@ -5091,40 +5086,18 @@ constexpr size_t RECV_SLAB_BYTES = (size_t)256 << 20;      // chunk partials hel
 #define DKG_RECV_ILP 1
 #endif
 
-// The marks of a one-party, pairs or seats call, one event of ctx->rpev[] each, in the order a call passes them:
-// the decryption begins (round 2), the call proper begins, the commitments are decoded, the chunk walk is done and
-// the folds begin (where one launch sequence covers the call), evaluated, decided, around the proofs (round 2).
-enum RecvMark { RM_DECRYPT, RM_START, RM_DECODED, RM_SPLIT, RM_EVALUATED, RM_CHECKED, RM_PROVE, RM_PROVED, RM_COUNT };
-static_assert(RM_COUNT == sizeof(dkg_ctx::rpev) / sizeof(hipEvent_t), "one event per mark");
-
-void recv_mark(dkg_ctx* ctx, int k) {
-  if (ctx->nsub == 1) HCK(hipEventRecord(ctx->rpev[k], ctx->stream));
-}
-
-// After a sync: <tag>.<name> = rpev[a] .. rpev[b] of a serialised call (nsub == 1); a < 0: not run, erased
-void call_phase(dkg_ctx* ctx, const char* tag, const char* name, int a, int b) {
-  const std::string key = std::string(tag) + "." + name;
-  ctx->phase_ms.erase(key);
-  if (ctx->nsub != 1 || a < 0) return;
-  float ms = 0;
-  HCK(hipEventElapsedTime(&ms, ctx->rpev[a], ctx->rpev[b]));
-  ctx->phase_ms[key] = ms;
-}
-
-// After a call's sync: every phase of family `tag` from the stages that ran, the others erased.  "recv" times the
-// chunk walk as `chunks` (up to RM_SPLIT where that was marked), "seats" the whole evaluation as `eval`, both the
-// folds after RM_SPLIT as `fold`; "pairs" has decode and eval only.  `prove` is erased here, set by round2_tail.
-enum { RAN_DECRYPT = 1, RAN_SPLIT = 2, RAN_CHECK = 4 };
-void call_phases(dkg_ctx* ctx, const char* tag, unsigned ran) {
-  const bool recv = !strcmp(tag, "recv"), split = (ran & RAN_SPLIT) != 0;
-  call_phase(ctx, tag, "decode", RM_START, RM_DECODED);
-  call_phase(ctx, tag, recv ? "chunks" : "eval", RM_DECODED, recv && split ? RM_SPLIT : RM_EVALUATED);
-  if (!strcmp(tag, "pairs")) return;
-  call_phase(ctx, tag, "decrypt", (ran & RAN_DECRYPT) ? RM_DECRYPT : -1, RM_START);
-  call_phase(ctx, tag, "fold", split ? RM_SPLIT : -1, RM_EVALUATED);
-  call_phase(ctx, tag, "check", (ran & RAN_CHECK) ? RM_EVALUATED : -1, RM_CHECKED);
-  call_phase(ctx, tag, "prove", -1, 0);
-}
+// The phases of a one-party, pairs or seats call (recv.*, pairs.*, seats.*), in the order a call passes them: the
+// decryption (round 2; its closing mark opens a call that has none), the commitments decoded, the chunk walk done
+// (the whole evaluation where no one launch sequence covers the call), folded, decided, the proofs (round 2).
+// "recv" names the walk `chunks`, "seats" walk and folds together `eval`; `prove` is round2_tail's own collect.
+enum { CP_DECRYPT, CP_DECODE, CP_WALK, CP_FOLD, CP_CHECK, CP_PROVE };
+const PhaseRow RECV_PHASES[] = {{"decrypt", 1u << CP_DECRYPT}, {"decode", 1u << CP_DECODE}, {"chunks", 1u << CP_WALK},
+                                {"fold", 1u << CP_FOLD},       {"check", 1u << CP_CHECK},   {"prove", 1u << CP_PROVE}};
+const PhaseRow SEATS_PHASES[] = {{"decrypt", 1u << CP_DECRYPT}, {"decode", 1u << CP_DECODE},
+                                 {"eval", 1u << CP_WALK | 1u << CP_FOLD}, {"fold", 1u << CP_FOLD},
+                                 {"check", 1u << CP_CHECK},     {"prove", 1u << CP_PROVE}};
+const PhaseRow PAIRS_PHASES[] = {{"decode", 1u << CP_DECODE}, {"eval", 1u << CP_WALK}};
+const PhaseRow PROVE_PHASES[] = {{"prove", 1u << CP_PROVE}};
 
 // Compressed rows Cc [..][N][32] on the device, decoded: the `rows` rows that dlist (device, may be null:
 // the first `rows`) names, in that order.  Cext [rows * N] points at stride rows * N, pok per point, rowok
@@ -5158,12 +5131,11 @@ struct RecvEval {
   uint8_t* dok = nullptr;   // [D] rows that decode
   uint32_t* xs = nullptr;   // [M] device: the 1-based indices (null: not uploaded)
   bool want_xs = true;      // in: the caller reads xs (recv_decide)
-  unsigned ran = 0;         // RAN_SPLIT: RM_SPLIT separates the chunk walk from the fold (one slab, one plan)
 };
 
 // Decode C [D][N][32] and evaluate every row at the M indices js[m] + 1 by the plans of
-// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks RM_START, RM_DECODED, RM_SPLIT (then
-// ev.ran says so) and RM_EVALUATED.
+// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks recv.decode, .chunks and, where one slab of one
+// plan covers the call so that one mark separates the chunk walk from the folds, .fold.
 int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, size_t nplan, const uint8_t* C,
               RecvEval& ev) {
   const size_t N = t + 1, npad = pad64(D);
@@ -5207,7 +5179,7 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     last = std::max(last, (int)std::min<uint32_t>(plans[m].chunk, 0x7fffffffu));
   }
   ctx->last_receiver_chunk = last;
-  recv_mark(ctx, RM_START);
+  phase_mark_serial(ctx, "recv", CP_DECRYPT);
   uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
   h2d(ctx, Cc, C, 32 * D * N);
   Decoded dc;
@@ -5217,7 +5189,8 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
   if (any_stage || ev.want_xs) ev.xs = upload_words(ctx, "rv_xs", hx);  // the serial walk of one index reads neither
   if (any_stage) ddig = upload_words(ctx, "rv_dig", dig);
   ev.R = buf<uint32_t>(ctx, "rv_R", PTB * M * D);
-  recv_mark(ctx, RM_DECODED);
+  phase_mark_serial(ctx, "recv", CP_DECODE);
+  bool split = false;
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_RECV_ILP);
   auto chunks = ilp ? dkgk_ilp::recv_chunks : dkgk::recv_chunks;
   auto fold = ilp ? dkgk_ilp::recv_fold : dkgk::recv_fold;
@@ -5241,8 +5214,8 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
       const size_t ms = std::min(Ms, run - b);
       chunks(D, npad, N, L, dc.Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
       if (launches == 0 && run == M && ms == run) {
-        recv_mark(ctx, RM_SPLIT);
-        ev.ran = RAN_SPLIT;
+        phase_mark_serial(ctx, "recv", CP_WALK);
+        split = true;
       }
       size_t Gin = G;
       for (uint32_t s = 0; s < p.stages; s++) {
@@ -5259,7 +5232,7 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     m0 += run;
   }
   check_launch(ctx);
-  recv_mark(ctx, RM_EVALUATED);
+  phase_mark_serial(ctx, "recv", split ? CP_FOLD : CP_WALK);
   return DKG_OK;
 }
 
@@ -5276,7 +5249,7 @@ void recv_check(dkg_ctx* ctx, size_t n, int round, size_t M, size_t j0, const Re
   }
   if (M > 1 || qualified) dkgk::recv_decide(M, n, round, ev.xs, ev.dok, qualified, dec, ctx->stream);
   check_launch(ctx);
-  recv_mark(ctx, RM_CHECKED);
+  phase_mark_serial(ctx, "recv", CP_CHECK);
 }
 
 // The end of a round-2 call over S seats (dkg_party_round2: S = 1) once its decisions dec [S][n] are on the host:
@@ -5308,12 +5281,12 @@ int round2_tail(dkg_ctx* ctx, const char* tag, size_t n, size_t t, size_t S, con
     memcpy(&kenc[128 * c + 96], ct + 64 * e + 32, 32);
     memcpy(&kw[64 * c], w + 64 * e, 64);
   }
-  recv_mark(ctx, RM_PROVE);
+  phase_mark_serial(ctx, tag, -1);
   const int rp = complaints_prove_run(ctx, Cn, ksk.data(), kenc.data(), kw.data(), kp.data());
   if (rp) return rp;
-  recv_mark(ctx, RM_PROVED);
+  phase_mark_serial(ctx, tag, CP_PROVE);
   sync(ctx);
-  call_phase(ctx, tag, "prove", RM_PROVE, RM_PROVED);
+  phase_collect(ctx, tag, PROVE_PHASES, std::size(PROVE_PHASES));
   for (size_t c = 0; c < Cn; c++) memcpy(proofs + 192 * rej[c], &kp[192 * c], 192);
   return DKG_OK;
 }
@@ -5344,7 +5317,7 @@ int dkg_commitment_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32
     d2h(ctx, P, Pc, 32 * M * D);
     if (ok) d2h(ctx, ok, ev.dok, D);
     sync(ctx);
-    call_phases(ctx, "recv", ev.ran);
+    phase_collect(ctx, "recv", RECV_PHASES, std::size(RECV_PHASES));
     return DKG_OK;
   });
 }
@@ -5365,7 +5338,7 @@ int dkg_commitment_eval_pairs(dkg_ctx* ctx, size_t D, size_t t, size_t count, co
     dkgh::distinct_places(count, rows, drows, crow);
     for (size_t p = 0; p < count; p++) crow[p] += 1, hx[p] = js[p] + 1;  // 1-based, as k_cmp_horner's lists
     const size_t Rn = drows.size();
-    recv_mark(ctx, RM_START);
+    phase_mark_serial(ctx, "pairs", -1);
     // the distinct rows gathered and decoded, as the batch complaint stage does it
     uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
     h2d(ctx, Cc, C, 32 * D * N);
@@ -5376,18 +5349,18 @@ int dkg_commitment_eval_pairs(dkg_ctx* ctx, size_t D, size_t t, size_t count, co
     decode_stage(ctx, Cc, dlist, Rn, N, false, dc);
     uint8_t* iok = buf<uint8_t>(ctx, "pe_ok", count);
     dkgk::pair_ok(count, dcrow, dc.rowok, iok, st);
-    recv_mark(ctx, RM_DECODED);
+    phase_mark_serial(ctx, "pairs", CP_DECODE);
     uint32_t* R = buf<uint32_t>(ctx, "pe_R", PTB * count);
     PairStage ps;
     pair_eval_launch(ctx, t, count, nullptr, hx.data(), dxs, dcrow, dc.Cext, Rn * N, R, ps);
-    recv_mark(ctx, RM_EVALUATED);
+    phase_mark_serial(ctx, "pairs", CP_WALK);
     uint32_t* Pc = buf<uint32_t>(ctx, "pe_P", 32 * count);
     dkgk::recv_encode(1, count, R, iok, Pc, st);
     check_launch(ctx);
     d2h(ctx, P, Pc, 32 * count);
     if (ok) d2h(ctx, ok, iok, count);
     sync(ctx);  // the staging vectors live until here
-    call_phases(ctx, "pairs", 0);
+    phase_collect(ctx, "pairs", PAIRS_PHASES, std::size(PAIRS_PHASES));
     return DKG_OK;
   });
 }
@@ -5417,7 +5390,7 @@ int dkg_verify_receivers(dkg_ctx* ctx, size_t n, size_t t, int round, size_t M, 
     recv_check(ctx, n, round, M, js[0], ev, ds, dsp, dq, dec);
     d2h(ctx, decision, dec, M * n);
     sync(ctx);
-    call_phases(ctx, "recv", ev.ran | RAN_CHECK);
+    phase_collect(ctx, "recv", RECV_PHASES, std::size(RECV_PHASES));
     return DKG_OK;
   });
 }
@@ -5431,7 +5404,7 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
     if (j >= n || (w && !proofs)) return DKG_E_ARG;
     recv_reset_last(ctx);
     // committee.rs:282-286: the pairs addressed to j, decrypted with sk_j (one recipient)
-    recv_mark(ctx, RM_DECRYPT);
+    phase_mark_serial(ctx, "recv", -1);
     uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, 1);
     uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 64 * n);
     uint32_t* dct = buf<uint32_t>(ctx, "pr_ct", 64 * n);
@@ -5454,7 +5427,7 @@ int dkg_party_round2(dkg_ctx* ctx, size_t n, size_t t, size_t j, const uint8_t* 
     if (s_out) d2h(ctx, s_out, ds, 32 * n);
     if (sp_out) d2h(ctx, sp_out, dsp, 32 * n);
     sync(ctx);
-    call_phases(ctx, "recv", ev.ran | RAN_DECRYPT | RAN_CHECK);
+    phase_collect(ctx, "recv", RECV_PHASES, std::size(RECV_PHASES));
     return round2_tail(ctx, "recv", n, t, 1, dec, sk, e1, ct, w, complaints, r2_error, proofs);
   });
 }
@@ -5476,7 +5449,6 @@ struct SeatEval {
   uint32_t* sx = nullptr;      // [S] device: the seats' 1-based indices
   uint32_t* scer = nullptr;    // [S] device: the seats' ceremonies
   std::vector<uint32_t> xslot, dig;  // chunked route: per-wave slot and the fold_records per distinct x
-  unsigned ran = 0;            // RAN_SPLIT: RM_SPLIT separates the chunk walk from the folds
 };
 
 constexpr uint64_t SEAT_SCRATCH_MAX = (uint64_t)1 << 30;  // Q and its ping-pong partner
@@ -5484,7 +5456,7 @@ constexpr uint64_t SEAT_SCRATCH_MAX = (uint64_t)1 << 30;  // Q and its ping-pong
 // Decode the distinct ceremonies the seats name (C [B * n][N][32]) and evaluate dealer i of seat p's
 // ceremony at js[p] + 1 by dkg_seat_pack's waves.  extra (device [S][n], may be null) is ANDed into sok.
 // The route is ctx->seat_eval's: k_seat_horner, or k_seat_chunks and k_seat_fold in dkg_seat_eval_shape's
-// shape.  Marks RM_START, RM_DECODED, RM_SPLIT (chunks walked, when folded) and RM_EVALUATED.
+// shape.  Marks seats.decode and the evaluation: the chunk walk and, when folded, the folds.
 int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint32_t* cer, const uint32_t* js,
                const uint8_t* C, const uint8_t* extra, SeatEval& ev) {
   if (B > 0xffffffffu / n) return DKG_E_ARG;  // dealer rows are 32-bit
@@ -5528,7 +5500,7 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
   for (size_t c = 0; c < Bd; c++)
     for (size_t i = 0; i < n; i++) ev.rows[c * n + i] = (uint32_t)(pl.cers[c] * n + i);
   hipStream_t st = ctx->stream;
-  recv_mark(ctx, RM_START);
+  phase_mark_serial(ctx, "seats", CP_DECRYPT);
   uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * B * n * N);
   h2d(ctx, Cc, C, 32 * B * n * N);
   uint32_t* drows = upload_words(ctx, "st_rows", ev.rows);
@@ -5544,7 +5516,7 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
   ev.sok = buf<uint8_t>(ctx, "st_sok", S * n);
   ev.R = buf<uint32_t>(ctx, "rv_R", PTB * S * n);
   dkgk::seat_ok(S, n, dscol, dc.rowok, extra, ev.sok, st);
-  recv_mark(ctx, RM_DECODED);
+  phase_mark_serial(ctx, "seats", CP_DECODE);
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_SEAT_ILP);
   if (G == 1) {
     (ilp ? dkgk_ilp::seat_horner : dkgk::seat_horner)(pl.waves, n, N, cols, pl.width, dwdesc, dwseat, dscol, dc.Cpm,
@@ -5556,8 +5528,7 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
     uint32_t* Q[2] = {q0, q0 + scratch / 8};
     (ilp ? dkgk_ilp::seat_chunks : dkgk::seat_chunks)(pl.waves, n, N, cols, pl.width, L, dwdesc, dwseat, dscol, dc.Cpm,
                                                       Q[0], st);
-    recv_mark(ctx, RM_SPLIT);
-    ev.ran = RAN_SPLIT;
+    phase_mark_serial(ctx, "seats", CP_WALK);
     size_t Gin = G;
     for (uint32_t s = 0; s < stages; s++) {
       (ilp ? dkgk_ilp::seat_fold : dkgk::seat_fold)(pl.waves, n, pl.width, Gin, dwdesc, dwseat, dxslot,
@@ -5571,18 +5542,18 @@ int seats_eval(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, const uint3
     }
   }
   check_launch(ctx);
-  recv_mark(ctx, RM_EVALUATED);
+  phase_mark_serial(ctx, "seats", G == 1 ? CP_WALK : CP_FOLD);
   return DKG_OK;
 }
 
-// decisions [S][n] of the evaluated seats against their share columns (device, [S][n][8]); marks RM_CHECKED
+// decisions [S][n] of the evaluated seats against their share columns (device, [S][n][8]); marks seats.check
 void seats_check(dkg_ctx* ctx, size_t n, int round, size_t S, const SeatEval& ev, const uint32_t* ds,
                  const uint32_t* dsp, const uint8_t* qualified, uint8_t* dec) {
   // pair p * n + i as "dealer" of one receiver, as recv_check; recv_base = n keeps check's self test off
   dkgk::check(S * n, 1, 0, n, n, round, ds, dsp, ev.R, ctx->tab_gw, ctx->tab_hw, ev.sok, dec, ctx->stream);
   dkgk::seat_decide(S, n, round, ev.sx, ev.scer, ev.sok, qualified, dec, ctx->stream);
   check_launch(ctx);
-  recv_mark(ctx, RM_CHECKED);
+  phase_mark_serial(ctx, "seats", CP_CHECK);
 }
 
 }  // namespace
@@ -5602,7 +5573,7 @@ int dkg_commitment_eval_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t
     d2h(ctx, P, Pc, 32 * S * n);
     if (ok) d2h(ctx, ok, ev.sok, S * n);
     sync(ctx);
-    call_phases(ctx, "seats", ev.ran);
+    phase_collect(ctx, "seats", SEATS_PHASES, std::size(SEATS_PHASES));
     return DKG_OK;
   });
 }
@@ -5630,7 +5601,7 @@ int dkg_verify_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, int round, size
     seats_check(ctx, n, round, S, ev, ds, dsp, dq, dec);
     d2h(ctx, decision, dec, S * n);
     sync(ctx);
-    call_phases(ctx, "seats", ev.ran | RAN_CHECK);
+    phase_collect(ctx, "seats", SEATS_PHASES, std::size(SEATS_PHASES));
     return DKG_OK;
   });
 }
@@ -5650,7 +5621,7 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     hipStream_t st = ctx->stream;
     // committee.rs:282-286 for every seat: the n pairs addressed to seat p, decrypted with sk_p -- one wave
     // per (seat key, w, 64 dealers), the scalar wave-uniform (k_bdec_mul_w4's chain, seat-addressed)
-    recv_mark(ctx, RM_DECRYPT);
+    phase_mark_serial(ctx, "seats", -1);
     const size_t items = 2 * S * n;
     uint32_t* dsk = upload_scalars(ctx, "pr_sk", sk, S);
     uint32_t* de1 = buf<uint32_t>(ctx, "pr_e1", 32 * items);
@@ -5680,7 +5651,7 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     if (s_out) d2h(ctx, s_out, ds, 32 * S * n);
     if (sp_out) d2h(ctx, sp_out, dsp, 32 * S * n);
     sync(ctx);
-    call_phases(ctx, "seats", ev.ran | RAN_DECRYPT | RAN_CHECK);
+    phase_collect(ctx, "seats", SEATS_PHASES, std::size(SEATS_PHASES));
     return round2_tail(ctx, "seats", n, t, S, dec, sk, e1, ct, w, complaints, r2_error, proofs);
   });
 }
@@ -5695,28 +5666,12 @@ int dkg_party_round2_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
 namespace {
 
 enum { SD_COMMIT, SD_E1, SD_MUL, SD_ENCODE, SD_SYM, SD_PHASES };
-const char* const SD_NAMES[SD_PHASES] = {"commit", "deal_e1", "deal_mul", "deal_encode", "deal_sym"};
-
-// After a sync: seats.<SD_NAMES> = the summed device times of the call's marks over all chunks (bf_mark's
-// segments); a phase without a mark reads -1.
-void collect_seat_deal_phases(dkg_ctx* ctx) {
-  double ms[SD_PHASES] = {};
-  bool seen[SD_PHASES] = {};
-  for (size_t k = 1; k < ctx->bf_marks.size(); k++) {
-    const int ph = ctx->bf_marks[k].first;
-    if (ph < 0) continue;
-    float v = 0;
-    HCK(hipEventElapsedTime(&v, ctx->bf_marks[k - 1].second, ctx->bf_marks[k].second));
-    ms[ph] += v;
-    seen[ph] = true;
-  }
-  for (int i = 0; i < SD_PHASES; i++) {
-    const std::string name = std::string("seats.") + SD_NAMES[i];
-    if (seen[i]) ctx->phase_ms[name] = ms[i];
-    else ctx->phase_ms.erase(name);
-  }
-  ctx->bf_marks.clear();
-}
+// seats.commit and .deal_*: the call's device times, the hybrid kernels' summed over all chunks of seats
+const PhaseRow SD_ROWS[SD_PHASES] = {{"commit", 1u << SD_COMMIT},
+                                     {"deal_e1", 1u << SD_E1},
+                                     {"deal_mul", 1u << SD_MUL},
+                                     {"deal_encode", 1u << SD_ENCODE},
+                                     {"deal_sym", 1u << SD_SYM}};
 
 // Seats per chunk of the hybrid stage: the extended-form R and K, the K encodings and, on the comb route,
 // the per-slot key copies, their gather index and their radix-16 combs within BFULL_SCRATCH_BYTES;
@@ -5777,10 +5732,7 @@ int dkg_party_round1_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     uint32_t* de1 = buf<uint32_t>(ctx, "sd_e1", 64 * S * n);
     uint32_t* dct = buf<uint32_t>(ctx, "sd_ct", 64 * S * n);
     dkgk::decode_points(dpk, Ck, pk_ext, Ck, pk_ok, st);
-    bf_reset(ctx);
-    auto mark = [&](int phase) {  // phase times are recorded on one stream only, as the seats calls do
-      if (ctx->nsub == 1) bf_mark(ctx, st, phase);
-    };
+    auto mark = [&](int phase) { phase_mark_serial(ctx, "seats", phase); };
     mark(-1);
     round1_device(ctx, S, n, t, da, db, Ec, Ac, ds, dsp);  // committee.rs:141-167 with D = S dealers
     mark(SD_COMMIT);
@@ -5828,7 +5780,7 @@ int dkg_party_round1_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S,
     if (s_out) d2h(ctx, s_out, ds, 32 * S * n);
     if (sp_out) d2h(ctx, sp_out, dsp, 32 * S * n);
     sync(ctx);
-    collect_seat_deal_phases(ctx);
+    phase_collect(ctx, "seats", SD_ROWS, SD_PHASES);
     for (size_t k = 0; k < Ck; k++)
       if (!okh[k]) {
         ctx->err = "party_round1_seats: the key of recipient " + std::to_string(k % n) + " of ceremony " +
@@ -6012,7 +5964,8 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
                        const uint8_t* r2_error, const uint8_t* r4_error, const uint8_t* A0, const uint8_t* s,
                        size_t D5, const uint32_t* d_ceremony, const uint32_t* d_sender, const uint32_t* d_dealer,
                        const uint8_t* d_share, uint8_t* mpk, int32_t* status, int32_t* recovery_index) {
-  enum { FIN_START, FIN_LAGRANGE, FIN_MPK };  // this call's marks: the first three events of rpev[]
+  enum { SF_LAGRANGE, SF_MPK };
+  static const PhaseRow SF_ROWS[] = {{"lagrange", 1u << SF_LAGRANGE}, {"mpk", 1u << SF_MPK}};
   return guarded(ctx, [&] {
     if (!S) return DKG_OK;
     if (!B || !n || !cer || !js || !qualified || !reconstruct || !A0 || !s || !mpk || !status) return DKG_E_ARG;
@@ -6129,9 +6082,9 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
     const uint32_t* ds = upload_scalars(ctx, "sf.s", s, S * n);
     const uint32_t* dy = upload_scalars(ctx, "sf.dy", hy.data(), hy.size() / 32);
     uint32_t* sigma = buf<uint32_t>(ctx, "sf.sigma", 32 * S);
-    recv_mark(ctx, FIN_START);
+    phase_mark_serial(ctx, "seats", -1);
     dkgk::seat_lagrange(S, n, dslot, dsx, dskip, drptr, drdeal, ddptr, ddx, dy, ds, longest + 1, sigma, st);
-    recv_mark(ctx, FIN_LAGRANGE);
+    phase_mark_serial(ctx, "seats", SF_LAGRANGE);
     // ---- mpk_p = sum of the A_i0 it adds + g sigma_p (:789-795): only the named ceremonies' rows
     std::vector<uint8_t> ha0(32 * D);
     for (size_t c = 0; c < Bd; c++) memcpy(&ha0[32 * c * n], A0 + 32 * (size_t)cers[c] * n, 32 * n);
@@ -6155,14 +6108,13 @@ int dkg_finalise_seats(dkg_ctx* ctx, size_t B, size_t n, size_t t, size_t S, con
     dkgk::fixed_base(S, sigma, ctx->tab_gw, ge, st);
     dkgk::add_points(S, ge, Hs, S, ge, st);
     dkgk::encode_points(ge, S, S, oc, st);
-    recv_mark(ctx, FIN_MPK);
+    phase_mark_serial(ctx, "seats", SF_MPK);
     check_launch(ctx);
     std::vector<uint8_t> okh(D), outh(32 * S);
     d2h(ctx, okh.data(), a0ok, D);
     d2h(ctx, outh.data(), oc, 32 * S);
     sync(ctx);
-    call_phase(ctx, "seats", "lagrange", FIN_START, FIN_LAGRANGE);
-    call_phase(ctx, "seats", "mpk", FIN_LAGRANGE, FIN_MPK);
+    phase_collect(ctx, "seats", SF_ROWS, std::size(SF_ROWS));
     memset(mpk, 0, 32 * S);
     for (size_t p = 0; p < S; p++) {
       int32_t index = -1;
@@ -6345,13 +6297,12 @@ int dkg_encrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* pk
     uint32_t* dct = buf<uint32_t>(ctx, "bx_ct", 32 * items);
     uint8_t* pok = buf<uint8_t>(ctx, "bx_pkok", V);
     uint8_t* ok = hbuf<uint8_t>(ctx, "hb.bf_pkok", V);
-    bf_reset(ctx);
     encrypt_batch_device(ctx, B, n, dpk, ds, dsp, dr, de1, dct, pok);
     d2h(ctx, ok, pok, V);
     d2h(ctx, e1, de1, 32 * items);
     d2h(ctx, ct, dct, 32 * items);
     sync(ctx);
-    collect_bfull_phases(ctx);
+    phase_collect(ctx, "bfull", BF_ROWS, BF_PHASES);
     return batch_keys_status(ctx, ok, V);
   });
 }
@@ -6370,13 +6321,12 @@ int dkg_decrypt_shares_batch(dkg_ctx* ctx, size_t B, size_t n, const uint8_t* sk
     uint32_t* ds = buf<uint32_t>(ctx, "bx_s", 32 * V * n);
     uint32_t* dsp = buf<uint32_t>(ctx, "bx_sp", 32 * V * n);
     uint8_t* iok = buf<uint8_t>(ctx, "bx_ok", items);
-    bf_reset(ctx);
     decrypt_batch_device(ctx, B, n, dsk, de1, dct, ds, dsp, iok, nullptr);
     d2h(ctx, s, ds, 32 * V * n);
     d2h(ctx, s_prime, dsp, 32 * V * n);
     if (ok) d2h(ctx, ok, iok, items);
     sync(ctx);
-    collect_bfull_phases(ctx);
+    phase_collect(ctx, "bfull", BF_ROWS, BF_PHASES);
     return DKG_OK;
   });
 }
@@ -6410,14 +6360,13 @@ int dkg_ceremony_batch_full_device(dkg_ctx* ctx, size_t B, size_t n, size_t t, c
     uint8_t* ok = hbuf<uint8_t>(ctx, "hb.bf_pkok", V);  // pinned: the copy below must not stall the queue
     BatchRound1 r1(ctx, V, n, t, (const uint32_t*)d_a, (const uint32_t*)d_b, ds, dsp);
     wait_shares(ctx, ctx->stream);  // the encryption reads the shares the side stream evaluates
-    bf_reset(ctx);
     encrypt_batch_device(ctx, B, n, dpk, ds, dsp, (const uint32_t*)d_r, e1, ct, pok);  // committee.rs:169-172
     d2h(ctx, ok, pok, V);
     HCK(hipEventRecord(ctx->ev[1], ctx->stream));
     decrypt_batch_device(ctx, B, n, dsk, e1, ct, rs, rsp, iok, eok);                    // committee.rs:282-286
     std::unique_ptr<ExtScope> ext(r1.deferred() ? nullptr : new ExtScope(ctx, V, N));
     batch_receivers(ctx, B, n, t, Ec, Ac, rs, rsp, out, eok);
-    collect_bfull_phases(ctx);
+    phase_collect(ctx, "bfull", BF_ROWS, BF_PHASES);
     batch_times(ctx, out, true);
     return batch_keys_status(ctx, ok, V);
   });
