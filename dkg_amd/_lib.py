@@ -23,6 +23,8 @@ COMPLAINT_IGNORED, COMPLAINT_NO_PHASE3 = 4, 5
 # a sharded proven call's verdict for a complaint against another rank's dealer: below every real code, so
 # that the element-wise maximum over the ranks' arrays is the ceremony's verdict list
 COMPLAINT_NOT_OWNED = -2
+# dkg_public_shares / dkg_public_share_status
+DKG_PS_OK, DKG_PS_NO_COMMITMENT, DKG_PS_NO_DISCLOSURE = 0, 1, 2
 
 _lib = None
 
@@ -187,6 +189,11 @@ def lib():
         L.dkg_seat_eval_constants.restype = None
         L.dkg_ctx_set_seat_eval.argtypes = [p, ctypes.c_int, ctypes.c_int]
         L.dkg_ctx_last_seat_eval.argtypes = [p, ctypes.POINTER(ctypes.c_int)]
+    if hasattr(L, "dkg_public_shares"):  # absent from an older library loaded through DKG_AMD_LIB
+        L.dkg_commitment_sum.argtypes = [p, sz, sz, sz, u8p, u8p, p, p]
+        L.dkg_public_shares.argtypes = [p, sz, sz, sz, u8p, u8p, u8p, u8p, sz, p, sz, p, p, p, u8p, p, p, p, p]
+        L.dkg_public_share_status.argtypes = [sz, u8p, u8p, u8p, ctypes.c_uint32, sz, p, p, p]
+        L.dkg_ctx_set_public_share_slab.argtypes = [p, sz]
     L.dkg_ceremony_run.argtypes = [p, sz, sz, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
     L.dkg_ceremony_verify_fetched.argtypes = [p, sz, sz, u8p, u8p, u8p, u8p, u8p, u8p, ctypes.POINTER(CeremonyOut)]
@@ -338,4 +345,5 @@ EXPORTED = [
     "dkg_seat_finalise_status",
     "dkg_party_round1_seats", "dkg_ctx_set_seat_deal", "dkg_ctx_last_seat_deal", "dkg_seat_enc_digits",
     "dkg_seat_eval_shape", "dkg_seat_eval_constants", "dkg_ctx_set_seat_eval", "dkg_ctx_last_seat_eval",
+    "dkg_commitment_sum", "dkg_public_shares", "dkg_public_share_status", "dkg_ctx_set_public_share_slab",
 ]

@@ -123,6 +123,16 @@ class PartyFinalise:
     recovery_index: List[int]
 
 
+@dataclass
+class PublicShares:
+    """dkg_public_shares: V [B][M][32] (32 zero bytes unless status is DKG_PS_OK), status and which per
+    (ceremony, index) as dkg_public_share_status gives them, S [B][t+1][32] the summed commitments or None."""
+    V: bytes
+    status: List[int]
+    which: List[int]
+    S: Optional[bytes]
+
+
 class Backend:
     """One GPU (one process per GPU).  Owns a dkg_ctx."""
 
@@ -303,7 +313,7 @@ class Backend:
         """Device ms of binomial / stepping / combine / check in the last ceremony's checks: tag "r24" (rounds
         2 and 4 fused, the default schedule), "r2" or "r4" (protocol order), "full" (the hybrid
         encryption / decryption kernels of the last full-mode ceremony), "recv" (the last one-party call:
-        commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs), "seats" (the last
+        commitment_eval, verify_receivers, party_round2), "pairs" (the last commitment_eval_pairs), "pubshares" (the last commitment_sum / public_shares), "seats" (the last
         commitment_eval_seats, verify_seats, party_round2_seats; lagrange / mpk: the last finalise_seats; commit /
         deal_*: the last party_round1_seats).  Only recorded with set_streams(1); -1 otherwise."""
         L = _lib.lib()
@@ -312,6 +322,7 @@ class Backend:
         names = (("interpolate", "coef_check", "decide", "fallback") if tag == "interp"
                  else ("decrypt", "decode", "chunks", "fold", "check", "prove") if tag == "recv"
                  else ("decode", "eval") if tag == "pairs"
+                 else ("decode", "sum", "eval", "disclosed") if tag == "pubshares"
                  else ("decrypt", "decode", "eval", "fold", "check", "prove", "lagrange", "mpk", "commit", "deal_e1", "deal_mul",
                        "deal_encode", "deal_sym") if tag == "seats"
                  else ("enc_mul", "enc_encode", "enc_sym", "dec_decode", "dec_mul", "dec_encode", "dec_sym")
@@ -599,6 +610,53 @@ class Backend:
             mask(r4_error), A0, s_cols, D5, arr(dc), arr(dsnd), arr(dd), dsh if D5 else None, mpk, st, ri))
         m = mpk.raw
         return PartyFinalise([m[32 * p:32 * p + 32] for p in range(S)], list(st)[:S], list(ri)[:S])
+
+    # ---- public shares of every party from the broadcast commitments (k_commit_colsum)
+    def commitment_sum(self, B: int, n: int, t: int, A: bytes, mask=None):
+        """(S, ok) of dkg_commitment_sum: S[c][k] = the sum over the dealers i with mask[c][i] (None: all) of
+        A_{c,i}[k] as B*(t+1) encodings, A [B*n][t+1][32]; ok [B] = 0 (and row c zero) where a masked row does not
+        decode."""
+        N = t + 1
+        S = ctypes.create_string_buffer(max(32 * B * N, 1))
+        ok = ctypes.create_string_buffer(max(B, 1))
+        _check(self._ctx, _lib.lib().dkg_commitment_sum(self._ctx, B, n, t, A,
+                                                         None if mask is None else bytes(bytearray(mask)), S, ok))
+        return S.raw[: 32 * B * N], ok.raw[:B]
+
+    def public_shares(self, B: int, n: int, t: int, A: bytes, qualified, js: Sequence[int], reconstruct=None,
+                      disclosures=(), fetched3=None, want_sum: bool = False) -> "PublicShares":
+        """The public shares g s_j of the parties js (0-based; one list for all B ceremonies) from public data
+        (dkg_public_shares): A [B*n][t+1][32] the round-3 vectors, qualified / reconstruct [B][n] (reconstruct
+        None = none), fetched3 [B*n] (None = all present); disclosures: the phase-5 shares in the two forms
+        finalise_seats takes.  PublicShares: V [B][M][32], status and which [B*M], S [B][t+1][32] with want_sum."""
+        M = len(js)
+        if isinstance(disclosures, tuple) and len(disclosures) == 4 and isinstance(disclosures[3], (bytes, bytearray)):
+            dc, dsnd, dd, dsh = disclosures
+            dsh = bytes(dsh)
+        else:
+            disclosures = list(disclosures)
+            dc, dsnd, dd = ([d[k] for d in disclosures] for k in range(3))
+            dsh = b"".join(d[3] for d in disclosures)
+        D5 = len(dc)
+        if len(dsnd) != D5 or len(dd) != D5 or len(dsh) != 32 * D5:
+            raise ValueError("the disclosure arrays differ in length")
+        mask = lambda x: None if x is None else bytes(bytearray(x))  # noqa: E731
+        arr = lambda v: _carray(ctypes.c_uint32, D5, v) if D5 else None  # noqa: E731
+        N = t + 1
+        V = ctypes.create_string_buffer(max(32 * B * M, 1))
+        st = _carray(ctypes.c_int32, B * M)
+        wh = _carray(ctypes.c_int32, B * M)
+        S = ctypes.create_string_buffer(max(32 * B * N, 1)) if want_sum else None
+        _check(self._ctx, _lib.lib().dkg_public_shares(
+            self._ctx, B, n, t, A, mask(qualified), mask(reconstruct), mask(fetched3), M,
+            _carray(ctypes.c_uint32, M, js), D5, arr(dc), arr(dsnd), arr(dd), dsh if D5 else None, V, st, wh, S))
+        return PublicShares(V.raw[: 32 * B * M], list(st)[: B * M], list(wh)[: B * M],
+                            S.raw[: 32 * B * N] if S is not None else None)
+
+    def set_public_share_slab(self, rows: int = 0):
+        """Rows of A that commitment_sum / public_shares decode at a time: 0 (default) automatic.  Outputs do
+        not depend on it."""
+        _check(self._ctx, _lib.lib().dkg_ctx_set_public_share_slab(self._ctx, rows))
 
     # ---- whole ceremony
     def _ceremony_out(self, n, t, big):
@@ -1356,6 +1414,25 @@ def seat_finalise_status(n: int, t: int, p: int, qualified, reconstruct, points:
     if rc < 0:
         raise _lib.DkgError(rc, "seat_finalise_status")
     return rc, idx.value
+
+
+def public_share_status(n: int, qualified, reconstruct, j: int, disclosures=(), a_present=None):
+    """dkg_public_share_status (host only): (status, which) of the public share of party j (0-based) of one
+    ceremony: qualified, reconstruct [n] (reconstruct None = none); disclosures: the (sender, dealer) pairs, 1-based,
+    of the phase-5 shares at hand; a_present [n] (None = all): dealer i's round-3 vector was fetched and decodes.
+    DKG_PS_NO_COMMITMENT first (which = the lowest used dealer that is absent), then DKG_PS_NO_DISCLOSURE (the lowest
+    reconstructed dealer j did not disclose), else DKG_PS_OK and -1: what public_shares reports per (ceremony, j)."""
+    mask = lambda x: None if x is None else bytes(bytearray(x))  # noqa: E731
+    disclosures = list(disclosures)
+    D5 = len(disclosures)
+    which = ctypes.c_int32(-1)
+    rc = _lib.lib().dkg_public_share_status(
+        n, mask(qualified), mask(reconstruct), mask(a_present), j, D5,
+        _carray(ctypes.c_uint32, D5, [d[0] for d in disclosures]) if D5 else None,
+        _carray(ctypes.c_uint32, D5, [d[1] for d in disclosures]) if D5 else None, ctypes.byref(which))
+    if rc < 0:
+        raise _lib.DkgError(rc, "public_share_status")
+    return rc, which.value
 
 
 def seat_disclosures(qualified, reconstruct, s_col: bytes, t: Optional[int] = None):

@@ -481,4 +481,14 @@ void seat_decide(size_t S, size_t n, int round, const uint32_t* sx, const uint32
 // ok[p] = rowok[crow[p] - 1], p < cnt
 void pair_ok(size_t cnt, const uint32_t* crow, const uint8_t* rowok, uint8_t* ok, hipStream_t stream);
 
+// ---- public shares from the broadcast commitments (pubshares.hip; one build, namespace dkgk only)
+// Sacc [40][N][bpad] += the column sums of the slab's used rows: the slab holds global rows [r0, r0 + rows)
+// decoded position-major, C [40][N][spad] with rowok [rows]; use [B n] over the global rows (null: all
+// used): 0 not used, 1 used, 2 used but absent.  ok[c] = 0 where a used row of ceremony c is absent or does
+// not decode.  Nothing is launched for spad < rows or a ceremony past bpad.
+void commit_colsum(size_t n, size_t N, size_t r0, size_t rows, size_t spad, const uint32_t* C, const uint8_t* rowok,
+                   const uint8_t* use, size_t bpad, uint32_t* Sacc, uint8_t* ok, hipStream_t stream);
+// V [B][M][8] = encodings of R[m B + c] (point-major) + G[c M + m] (SoA at stride B M; null: nothing added)
+void pubshare_out(size_t B, size_t M, const uint32_t* R, const uint32_t* G, uint32_t* V, hipStream_t stream);
+
 }  // namespace dkgk

@@ -59,6 +59,12 @@ DKG_DEV uint32_t pt_word(const ge_p3& p, int w) {
   return f.v[w % 10];
 }
 
+// p, or the identity (0, 1, 1, 0) where !keep
+DKG_DEV void pt_or_identity(ge_p3& p, bool keep) {
+#pragma unroll
+  for (int w = 0; w < PT_WORDS; w++) pt_word(p, w) = keep ? pt_word(p, w) : ((w == 10 || w == 20) ? 1u : 0u);
+}
+
 // Signed-digit recoding of a small positive multiplier m for the binomial's chains (mul_small_*):
 // the NAF, except that a leading 1 0 -1 (2^k - 2^(k-2)) becomes 1 1 (2^(k-1) + 2^(k-2)): one
 // doubling fewer for the same additions.  That is the cheapest signed-binary chain of every m < 256

@@ -74,12 +74,6 @@ DKG_DEV void recv_mul_long(ge_p3& y, const uint32_t* __restrict__ dg, uint32_t* 
   recv_chain_long(y, dg, len, q);
 }
 
-// p, or the identity (0, 1, 1, 0) where !keep
-DKG_DEV void pt_or_identity(ge_p3& p, bool keep) {
-#pragma unroll
-  for (int w = 0; w < PT_WORDS; w++) pt_word(p, w) = keep ? pt_word(p, w) : ((w == 10 || w == 20) ? 1u : 0u);
-}
-
 // final values: point-major R[m * ndealers + d] (what check and k_recv_encode read)
 DKG_DEV void recv_store(bool last, uint32_t* __restrict__ out, size_t ostride, size_t oidx, uint32_t* __restrict__ R,
                         size_t ridx, bool live, const ge_p3& acc) {

@@ -51,6 +51,7 @@ struct dkg_ctx {
   std::vector<PhaseMark> phase_marks;
   int receiver_chunk = 0;               // chunk length of the one-party evaluation (0: dkg_receiver_plan_for's rule)
   int last_receiver_chunk = 0;          // the chunk the last such call ran (the largest over its indices)
+  size_t ps_slab = 0;                   // rows decoded at a time by dkg_commitment_sum / dkg_public_shares (0: automatic)
   std::map<std::array<size_t, 4>, dkg_receiver_plan> recv_plans;  // dkg_receiver_plan_for by (n, t, x, chunk)
   std::map<std::array<size_t, 3>, std::vector<uint32_t>> pair_digits;  // k_pair_eval's fold_records by (t, x, L)
   static constexpr int MAX_SUB = 8;
@@ -5131,17 +5132,24 @@ struct RecvEval {
   uint8_t* dok = nullptr;   // [D] rows that decode
   uint32_t* xs = nullptr;   // [M] device: the 1-based indices (null: not uploaded)
   bool want_xs = true;      // in: the caller reads xs (recv_decide)
+  // the plans of the M indices and their host staging (recv_plans): lives with the caller until it has synchronised
+  std::vector<dkg_receiver_plan> plans;
+  std::vector<uint32_t> hx, dig;
+  bool any_stage = false;
 };
 
-// Decode C [D][N][32] and evaluate every row at the M indices js[m] + 1 by the plans of
-// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks recv.decode, .chunks and, where one slab of one
-// plan covers the call so that one mark separates the chunk walk from the folds, .fold.
-int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, size_t nplan, const uint8_t* C,
-              RecvEval& ev) {
-  const size_t N = t + 1, npad = pad64(D);
-  const size_t dig_stride = fold_record(1, 16, 0);  // per index: a plan has 16 stages at most
-  std::vector<dkg_receiver_plan> plans(M);
-  std::vector<uint32_t> hx(M), dig;
+const size_t RECV_DIG_STRIDE = fold_record(1, 16, 0);  // per index: a plan has 16 stages at most
+
+// The plans of dkg_receiver_plan_for for the M indices js[m] + 1 (nplan = the n its cost rule sees), their 1-based
+// indices and fold records: host only.
+int recv_plans(dkg_ctx* ctx, size_t t, size_t M, const uint32_t* js, size_t nplan, RecvEval& ev) {
+  const size_t N = t + 1;
+  const size_t dig_stride = RECV_DIG_STRIDE;
+  std::vector<dkg_receiver_plan>& plans = ev.plans;
+  std::vector<uint32_t>&hx = ev.hx, &dig = ev.dig;
+  plans.assign(M, dkg_receiver_plan());
+  hx.assign(M, 0);
+  dig.clear();
   int last = 0;
   bool any_stage = false;
   auto plan_of = [&](uint32_t x, int chunk, dkg_receiver_plan& out) {
@@ -5179,17 +5187,27 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     last = std::max(last, (int)std::min<uint32_t>(plans[m].chunk, 0x7fffffffu));
   }
   ctx->last_receiver_chunk = last;
-  phase_mark_serial(ctx, "recv", CP_DECRYPT);
-  uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
-  h2d(ctx, Cc, C, 32 * D * N);
-  Decoded dc;
-  decode_stage(ctx, Cc, nullptr, D, N, true, dc);
-  ev.dok = dc.rowok;
+  ev.any_stage = any_stage;
+  return DKG_OK;
+}
+
+// The evaluation half: every row of a prepared position-major table Cpm [40][N][pad64(D)] (padding columns valid
+// points), rowok [D], at the M indices by ev's plans (recv_plans).  Marks, under `tag`, CP_DECODE (which closes the
+// caller's preparation), CP_WALK and, where one slab of one plan covers the call so that one mark separates the
+// chunk walk from the folds, CP_FOLD.
+int recv_eval_table(dkg_ctx* ctx, const char* tag, size_t D, size_t t, size_t M, const uint32_t* Cpm, uint8_t* rowok,
+                    RecvEval& ev) {
+  const size_t N = t + 1, npad = pad64(D);
+  const size_t dig_stride = RECV_DIG_STRIDE;
+  const std::vector<dkg_receiver_plan>& plans = ev.plans;
+  const std::vector<uint32_t>&hx = ev.hx, &dig = ev.dig;
+  const bool any_stage = ev.any_stage;
+  ev.dok = rowok;
   uint32_t* ddig = nullptr;
   if (any_stage || ev.want_xs) ev.xs = upload_words(ctx, "rv_xs", hx);  // the serial walk of one index reads neither
   if (any_stage) ddig = upload_words(ctx, "rv_dig", dig);
   ev.R = buf<uint32_t>(ctx, "rv_R", PTB * M * D);
-  phase_mark_serial(ctx, "recv", CP_DECODE);
+  phase_mark_serial(ctx, tag, CP_DECODE);
   bool split = false;
   const bool ilp = ctx->fe_mode == 2 || (ctx->fe_mode == 0 && DKG_RECV_ILP);
   auto chunks = ilp ? dkgk_ilp::recv_chunks : dkgk::recv_chunks;
@@ -5198,7 +5216,7 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
   for (size_t m0 = 0; m0 < M;) {
     const dkg_receiver_plan& p = plans[m0];
     if (p.stages == 0) {  // the serial walk: k_horner, as dkg_verify_receiver runs it
-      dkgk::horner(D, npad, N, dc.Cpm, hx[m0], 1, ev.R + m0 * D * PT_WORDS_H, ctx->stream);
+      dkgk::horner(D, npad, N, Cpm, hx[m0], 1, ev.R + m0 * D * PT_WORDS_H, ctx->stream);
       m0++, launches++;
       continue;
     }
@@ -5212,9 +5230,9 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     uint32_t* Q[2] = {buf<uint32_t>(ctx, "rv_q0", PTB * Ms * G * npad), buf<uint32_t>(ctx, "rv_q1", PTB * Ms * G1 * npad)};
     for (size_t b = 0; b < run; b += Ms) {
       const size_t ms = std::min(Ms, run - b);
-      chunks(D, npad, N, L, dc.Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
+      chunks(D, npad, N, L, Cpm, ev.xs, m0 + b, ms, Q[0], ev.R, ctx->stream);
       if (launches == 0 && run == M && ms == run) {
-        phase_mark_serial(ctx, "recv", CP_WALK);
+        phase_mark_serial(ctx, tag, CP_WALK);
         split = true;
       }
       size_t Gin = G;
@@ -5232,8 +5250,24 @@ int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, si
     m0 += run;
   }
   check_launch(ctx);
-  phase_mark_serial(ctx, "recv", split ? CP_FOLD : CP_WALK);
+  phase_mark_serial(ctx, tag, split ? CP_FOLD : CP_WALK);
   return DKG_OK;
+}
+
+// Decode C [D][N][32] and evaluate every row at the M indices js[m] + 1 by the plans of
+// dkg_receiver_plan_for (nplan = the n its cost rule sees).  Marks recv.decode, .chunks and, where one slab of one
+// plan covers the call so that one mark separates the chunk walk from the folds, .fold.
+int recv_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32_t* js, size_t nplan, const uint8_t* C,
+              RecvEval& ev) {
+  const size_t N = t + 1;
+  const int rc = recv_plans(ctx, t, M, js, nplan, ev);
+  if (rc) return rc;
+  phase_mark_serial(ctx, "recv", CP_DECRYPT);
+  uint32_t* Cc = buf<uint32_t>(ctx, "vr_C", 32 * D * N);
+  h2d(ctx, Cc, C, 32 * D * N);
+  Decoded dc;
+  decode_stage(ctx, Cc, nullptr, D, N, true, dc);
+  return recv_eval_table(ctx, "recv", D, t, M, dc.Cpm, dc.rowok, ev);
 }
 
 // decisions [M][n] of the evaluated slots against the share columns (device, [M][n][8])
@@ -5318,6 +5352,225 @@ int dkg_commitment_eval(dkg_ctx* ctx, size_t D, size_t t, size_t M, const uint32
     if (ok) d2h(ctx, ok, ev.dok, D);
     sync(ctx);
     phase_collect(ctx, "recv", RECV_PHASES, std::size(RECV_PHASES));
+    return DKG_OK;
+  });
+}
+
+// ---- public shares from the broadcast commitments (pubshares.hip)
+int dkg_ctx_set_public_share_slab(dkg_ctx* ctx, size_t rows) {
+  if (!ctx || rows > ((size_t)1 << 30)) return DKG_E_ARG;
+  ctx->ps_slab = rows;
+  return DKG_OK;
+}
+
+namespace {
+
+// the phases of a public-shares call: the evaluator's ids (recv_eval_table marks them) and two of its own
+enum { PS_SUM = 6, PS_DISCLOSED = 7 };
+const PhaseRow PS_PHASES[] = {{"decode", 1u << CP_DECODE}, {"sum", 1u << PS_SUM},
+                              {"eval", 1u << CP_WALK | 1u << CP_FOLD}, {"disclosed", 1u << PS_DISCLOSED}};
+
+struct CommitSum {
+  uint32_t* Sacc = nullptr;  // [40][N][bpad] position-major over the ceremonies, padding columns the identity
+  uint8_t* ok = nullptr;     // [B] device: no used row of the ceremony is absent or undecodable
+  size_t bpad = 0;
+};
+
+// S_c[k] = the sum over the used dealers i of A_{c,i}[k], for B ceremonies (A [B * n][N][32], host): the rows are
+// uploaded and decoded in slabs (ctx->ps_slab, or as many as RECV_SLAB_BYTES of decoded points hold) and summed
+// column by column into cs.Sacc (k_commit_colsum); a slab may cut through a ceremony.  use [B * n] (host, may be
+// null: all used): commit_colsum's codes.  hrowok (host [B * n], may be null) receives "the row decodes" after the
+// caller's sync.  Marks pubshares' decode and sum per slab.
+void commit_sum_run(dkg_ctx* ctx, size_t B, size_t n, size_t N, const uint8_t* A, const uint8_t* use, uint8_t* hrowok,
+                    CommitSum& cs) {
+  hipStream_t st = ctx->stream;
+  const size_t total = B * n;
+  cs.bpad = pad64(B);
+  cs.Sacc = buf<uint32_t>(ctx, "ps_S", PTB * N * cs.bpad);
+  cs.ok = buf<uint8_t>(ctx, "ps_ok", B);
+  dkgk::fill_identity(N * cs.bpad, cs.Sacc, st);
+  HCK(hipMemsetAsync(cs.ok, 1, B, st));
+  const uint8_t* duse = upload_mask(ctx, "ps_use", use, total);
+  const size_t slab =
+      std::min(total, ctx->ps_slab ? ctx->ps_slab : std::max<size_t>(1, RECV_SLAB_BYTES / (2 * PTB * N)));
+  uint32_t* Cc = buf<uint32_t>(ctx, "ps_C", 32 * slab * N);
+  phase_mark_serial(ctx, "pubshares", -1);
+  for (size_t r0 = 0; r0 < total; r0 += slab) {
+    const size_t rows = std::min(slab, total - r0);
+    h2d(ctx, Cc, A + 32 * N * r0, 32 * N * rows);
+    Decoded dc;
+    decode_stage(ctx, Cc, nullptr, rows, N, true, dc);
+    phase_mark_serial(ctx, "pubshares", CP_DECODE);
+    dkgk::commit_colsum(n, N, r0, rows, pad64(rows), dc.Cpm, dc.rowok, duse, cs.bpad, cs.Sacc, cs.ok, st);
+    if (hrowok) d2h(ctx, hrowok + r0, dc.rowok, rows);
+    phase_mark_serial(ctx, "pubshares", PS_SUM);
+  }
+  check_launch(ctx);
+}
+
+// The encodings of cs.Sacc, queued: staging [N][bpad][32] (host) is read by commit_sum_store after the sync
+void commit_sum_fetch(dkg_ctx* ctx, size_t N, const CommitSum& cs, std::vector<uint8_t>& staging) {
+  const size_t count = N * cs.bpad;
+  uint32_t* Sc = buf<uint32_t>(ctx, "ps_Sc", 32 * count);
+  dkgk::encode_points(cs.Sacc, count, count, Sc, ctx->stream);
+  check_launch(ctx);
+  staging.resize(32 * count);
+  d2h(ctx, staging.data(), Sc, 32 * count);
+}
+// S [B][N][32] from the staging; row c zero where hok[c] == 0
+void commit_sum_store(size_t B, size_t N, size_t bpad, const std::vector<uint8_t>& staging, const uint8_t* hok,
+                      uint8_t* S) {
+  for (size_t c = 0; c < B; c++)
+    for (size_t k = 0; k < N; k++) {
+      if (hok[c]) memcpy(S + 32 * (c * N + k), &staging[32 * (k * bpad + c)], 32);
+      else memset(S + 32 * (c * N + k), 0, 32);
+    }
+}
+
+}  // namespace
+
+int dkg_commitment_sum(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* A, const uint8_t* mask, uint8_t* S,
+                       uint8_t* ok) {
+  return guarded(ctx, [&] {
+    if (!B) return DKG_OK;
+    if (!n || !A || !S || B > 0xffffffffu / n) return DKG_E_ARG;
+    recv_reset_last(ctx);
+    const size_t N = t + 1;
+    std::vector<uint8_t> use;
+    if (mask) {
+      use.resize(B * n);
+      for (size_t e = 0; e < B * n; e++) use[e] = mask[e] ? 1 : 0;
+    }
+    CommitSum cs;
+    commit_sum_run(ctx, B, n, N, A, mask ? use.data() : nullptr, nullptr, cs);
+    std::vector<uint8_t> staging, hok(B);
+    commit_sum_fetch(ctx, N, cs, staging);
+    d2h(ctx, hok.data(), cs.ok, B);
+    sync(ctx);
+    phase_collect(ctx, "pubshares", PS_PHASES, std::size(PS_PHASES));
+    commit_sum_store(B, N, cs.bpad, staging, hok.data(), S);
+    if (ok) memcpy(ok, hok.data(), B);
+    return DKG_OK;
+  });
+}
+
+int dkg_public_shares(dkg_ctx* ctx, size_t B, size_t n, size_t t, const uint8_t* A, const uint8_t* qualified,
+                      const uint8_t* reconstruct, const uint8_t* fetched3, size_t M, const uint32_t* js, size_t D5,
+                      const uint32_t* d_ceremony, const uint32_t* d_sender, const uint32_t* d_dealer,
+                      const uint8_t* d_share, uint8_t* V, int32_t* status, int32_t* which, uint8_t* S) {
+  return guarded(ctx, [&] {
+    if (!B || !M) return DKG_OK;
+    if (!n || !A || !qualified || !js || !V || !status) return DKG_E_ARG;
+    if (D5 && (!d_ceremony || !d_sender || !d_dealer || !d_share)) return DKG_E_ARG;
+    // party indices are multipliers below 2^24 on the device; rows and list places are 32-bit
+    if (n >= ((size_t)1 << 24) || B > 0xffffffffu / n || M >= 0xffffffffu || D5 >= 0xffffffffu) return DKG_E_ARG;
+    for (size_t m = 0; m < M; m++)
+      if (js[m] >= n) return DKG_E_ARG;
+    for (size_t d = 0; d < D5; d++)
+      if (d_ceremony[d] >= B || d_sender[d] < 1 || d_sender[d] > n || d_dealer[d] < 1 || d_dealer[d] > n)
+        return DKG_E_ARG;
+    const size_t N = t + 1, total = B * n;
+    // the dealers the sum uses, and per ceremony how many are reconstructed
+    std::vector<uint8_t> use(total);
+    std::vector<uint32_t> nrec(B, 0);
+    for (size_t c = 0; c < B; c++)
+      for (size_t i = 0; i < n; i++) {
+        const size_t e = c * n + i;
+        const bool r = reconstruct && reconstruct[e];
+        if (r && !qualified[e]) {
+          ctx->err = "public_shares: only qualified members should be reconstructed (committee.rs:746-747 panics)";
+          return DKG_E_ARG;
+        }
+        nrec[c] += r;
+        use[e] = qualified[e] && !r ? (fetched3 && !fetched3[e] ? 2 : 1) : 0;
+      }
+    // the disclosed shares of the reconstructed dealers, summed per (ceremony, distinct index)
+    std::vector<uint32_t> dj, place;
+    dkgh::distinct_places(M, js, dj, place);
+    const size_t Md = dj.size();
+    constexpr uint32_t NONE = 0xffffffffu;
+    std::vector<uint32_t> jslot(n, NONE);
+    for (size_t k = 0; k < Md; k++) jslot[dj[k]] = (uint32_t)k;
+    auto key = [&](size_t c, uint32_t sender0, uint32_t dealer0) { return ((uint64_t)c * n + sender0) * n + dealer0; };
+    std::unordered_set<uint64_t> seen;
+    seen.reserve(2 * D5);
+    std::vector<dkgh::Zl> sums;
+    std::vector<uint32_t> cnt;
+    size_t kept = 0;
+    for (size_t d = 0; d < D5; d++) {
+      const size_t c = d_ceremony[d];
+      const uint32_t q = d_sender[d] - 1, i = d_dealer[d] - 1;
+      if (!seen.insert(key(c, q, i)).second) {
+        ctx->err = "public_shares: a (ceremony, sender, dealer) disclosure is listed twice";
+        return DKG_E_ARG;
+      }
+      if (!(reconstruct && reconstruct[c * n + i]) || jslot[q] == NONE) continue;
+      if (sums.empty()) {
+        sums.assign(B * Md, dkgh::zl_from_u64(0));
+        cnt.assign(B * Md, 0);
+      }
+      const size_t at = c * Md + jslot[q];
+      sums[at] = dkgh::zl_add(sums[at], dkgh::zl_from_bits(d_share + 32 * d));
+      cnt[at]++;
+      kept++;
+    }
+    recv_reset_last(ctx);
+    hipStream_t st = ctx->stream;
+    RecvEval ev;
+    ev.want_xs = false;
+    const int rp = recv_plans(ctx, t, M, js, B, ev);  // the cost rule sees the evaluator's rows: B ceremonies
+    if (rp) return rp;
+    // ---- S_c, then sum_k (j+1)^k S_c[k] with the ceremonies as the evaluator's rows
+    std::vector<uint8_t> hrowok(total), hok(B), staging;
+    CommitSum cs;
+    commit_sum_run(ctx, B, n, N, A, use.data(), hrowok.data(), cs);
+    const int re = recv_eval_table(ctx, "pubshares", B, t, M, cs.Sacc, cs.ok, ev);
+    if (re) return re;
+    // ---- g times the disclosed shares
+    uint32_t* G = nullptr;
+    std::vector<uint8_t> hsc;
+    if (kept) {
+      hsc.assign(32 * B * M, 0);
+      for (size_t c = 0; c < B; c++)
+        for (size_t m = 0; m < M; m++) dkgh::zl_to_bytes(&hsc[32 * (c * M + m)], sums[c * Md + place[m]]);
+      uint32_t* dsc = buf<uint32_t>(ctx, "ps_sc", 32 * B * M);
+      h2d(ctx, dsc, hsc.data(), 32 * B * M);
+      G = buf<uint32_t>(ctx, "ps_G", PTB * B * M);
+      dkgk::fixed_base(B * M, dsc, ctx->tab_gw, G, st);
+      check_launch(ctx);
+      phase_mark_serial(ctx, "pubshares", PS_DISCLOSED);
+    }
+    uint32_t* Vd = buf<uint32_t>(ctx, "ps_V", 32 * B * M);
+    dkgk::pubshare_out(B, M, ev.R, G, Vd, st);
+    check_launch(ctx);
+    d2h(ctx, V, Vd, 32 * B * M);
+    d2h(ctx, hok.data(), cs.ok, B);
+    if (S) commit_sum_fetch(ctx, N, cs, staging);
+    sync(ctx);
+    phase_collect(ctx, "pubshares", PS_PHASES, std::size(PS_PHASES));
+    if (S) commit_sum_store(B, N, cs.bpad, staging, hok.data(), S);
+    // ---- dkg_public_share_status per (ceremony, index)
+    for (size_t c = 0; c < B; c++) {
+      int32_t absent = -1;  // the lowest used dealer without a usable row
+      for (size_t i = 0; i < n && absent < 0; i++)
+        if (use[c * n + i] == 2 || (use[c * n + i] == 1 && !hrowok[c * n + i])) absent = (int32_t)i;
+      for (size_t m = 0; m < M; m++) {
+        int32_t stt = DKG_PS_OK, w = -1;
+        if (absent >= 0) {
+          stt = DKG_PS_NO_COMMITMENT, w = absent;
+        } else if (nrec[c] && (cnt.empty() || cnt[c * Md + place[m]] < nrec[c])) {
+          stt = DKG_PS_NO_DISCLOSURE;
+          for (size_t i = 0; i < n; i++)
+            if (reconstruct[c * n + i] && !seen.count(key(c, js[m], (uint32_t)i))) {
+              w = (int32_t)i;
+              break;
+            }
+        }
+        status[c * M + m] = stt;
+        if (which) which[c * M + m] = w;
+        if (stt != DKG_PS_OK) memset(V + 32 * (c * M + m), 0, 32);
+      }
+    }
     return DKG_OK;
   });
 }

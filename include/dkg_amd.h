@@ -546,6 +546,66 @@ int dkg_seat_finalise_status(size_t n, size_t t, size_t p, const uint8_t *qualif
                              const uint8_t *a_present, const uint32_t *points, int r2_error, int r4_error,
                              int32_t *recovery_index);
 
+/* ---- public shares of every party from the broadcast commitments (pubshares.hip) ----
+ * The verification keys g s_j of a finished ceremony from PUBLIC data alone.  s_j is the sum over the final
+ * dealers of s_ij (committee.rs:453-461), and round 4 accepted g s_ij = sum_k (j+1)^k A_i[k] for every dealer
+ * that stays (:532-539), so with S[k] = the sum over those dealers of A_i[k]
+ *   public_share[j] = sum_k (j+1)^k S[k]  +  g (the sum over the reconstructed dealers i of s_ij).
+ * A reconstructed dealer's A_i is missing or proven inconsistent; its term is the share party j itself
+ * disclosed in phase 5 (BroadcastPhase5, committee.rs:660-669), which is public: no interpolation.
+ * The value equals g final_share_j (what the drivers and dkg_party_round3_seats compute from the secret share,
+ * :462-467) for a party whose checks accepted every dealer used.  The master public key stays with the
+ * finalise calls: S[0] lacks the reconstructed dealers' secrets (:784-789).
+ * Rows as in the batch and seats calls: A [B*n][t+1][32], row c * n + i = dealer i of ceremony c. */
+#define DKG_PS_OK 0
+#define DKG_PS_NO_COMMITMENT 1 /* a dealer the sum uses was not fetched or does not decode */
+#define DKG_PS_NO_DISCLOSURE 2 /* index j disclosed no share of some reconstructed dealer */
+/* S[c][k] = the sum over the dealers i with mask[c][i] of A_{c,i}[k], compressed: the aggregated committed
+ * polynomial of MembersFetchedState3's vectors (committee.rs:520-559 reads them one dealer at a time).  mask
+ * [B][n] (NULL = all dealers); S [B][t+1][32]; ok[c] (may be NULL) = 0, and row c of S zero bytes, where a masked
+ * row does not decode -- a row outside the mask is never interpreted.  An empty mask gives the identity in every
+ * coefficient: 32 zero bytes with ok = 1.  B == 0 returns DKG_OK and touches nothing; DKG_E_ARG for n == 0, a
+ * NULL A or S, or more than 2^32 - 1 rows.  One 64-lane workgroup per column (c, k) adds the dealers with the
+ * complete formula (k_commit_colsum); the rows are uploaded and decoded in slabs (below).  Phase times (one
+ * stream): "pubshares.decode", "pubshares.sum".  Needs no dkg_env_init. */
+int dkg_commitment_sum(dkg_ctx *ctx, size_t B, size_t n, size_t t, const uint8_t *A, const uint8_t *mask, uint8_t *S,
+                       uint8_t *ok);
+/* V[c][m] = the public share of party js[m] of ceremony c, [B][M][32] (the layout of the batch drivers'
+ * public_share): sum_k (js[m]+1)^k S_c[k] + g (the sum over the dealers i reconstructed in c of
+ * d_share(c, js[m]+1, i+1)).  Dealer i of ceremony c enters S_c iff qualified[c][i] && !reconstruct[c][i]
+ * (:733-739); qualified [B][n]; reconstruct [B][n] (NULL = none; reconstruct without qualified is DKG_E_ARG,
+ * :746-747 panics); fetched3 [B*n] (NULL = all present).  js [M]: 0-based, below n (DKG_E_ARG otherwise), any
+ * order, repeats allowed, one list for all ceremonies.  The D5 disclosures are dkg_finalise_seats' flat form
+ * (sender, dealer 1-based; shares read reduced mod l); a duplicate (ceremony, sender, dealer) or an index out of
+ * range is DKG_E_ARG; entries of dealers that are not reconstructed, or of senders not in js, are ignored.
+ * status [B][M] and which [B][M] (may be NULL) are exactly dkg_public_share_status's for the ceremony's slices,
+ * a_present = fetched and decodes.  V is 32 zero bytes unless the status is DKG_PS_OK -- the identity encodes as
+ * zero bytes too, so read the status.  S (may be NULL) = dkg_commitment_sum's output for the call's mask.
+ * B == 0 or M == 0 returns DKG_OK and touches nothing.  S_c is evaluated by dkg_commitment_eval's evaluator
+ * with the B ceremonies as its rows and js as its indices: dkg_ctx_set_receiver_chunk and
+ * dkg_ctx_set_field_mode apply as they do there; outputs do not depend on them.  g's comb is built in
+ * dkg_ctx_create: needs no dkg_env_init.  Phase times (one stream): "pubshares.decode", "pubshares.sum",
+ * "pubshares.eval", "pubshares.disclosed" (-1 when no disclosure is used).  Host pointers, one device. */
+int dkg_public_shares(dkg_ctx *ctx, size_t B, size_t n, size_t t, const uint8_t *A, const uint8_t *qualified,
+                      const uint8_t *reconstruct, const uint8_t *fetched3, size_t M, const uint32_t *js, size_t D5,
+                      const uint32_t *d_ceremony, const uint32_t *d_sender, const uint32_t *d_dealer,
+                      const uint8_t *d_share, uint8_t *V, int32_t *status, int32_t *which, uint8_t *S);
+/* The status of dkg_public_shares for ONE ceremony and one 0-based index j, a pure host function (no GPU, no
+ * context): qualified [n]; reconstruct [n] (NULL = none); a_present [n] (NULL = all): dealer i's round-3 vector
+ * was fetched and decodes (committee.rs:527-530 stores nothing otherwise); the D5 disclosures (sender, dealer)
+ * of that ceremony, 1-based.  DKG_PS_NO_COMMITMENT wins, *which (may be NULL) the lowest 0-based dealer that
+ * is used (qualified, not reconstructed) but absent; otherwise DKG_PS_NO_DISCLOSURE with the lowest
+ * reconstructed dealer i without an entry (j + 1, i + 1) (:660-669); otherwise DKG_PS_OK and -1.  DKG_E_ARG
+ * for n == 0, j >= n, a NULL qualified (or a NULL list with D5 > 0), reconstruct without qualified, an index
+ * outside 1..n, or a duplicate pair. */
+int dkg_public_share_status(size_t n, const uint8_t *qualified, const uint8_t *reconstruct, const uint8_t *a_present,
+                            uint32_t j, size_t D5, const uint32_t *d_sender, const uint32_t *d_dealer,
+                            int32_t *which);
+/* Rows of A that dkg_commitment_sum / dkg_public_shares upload and decode at a time: 0 (default) = automatic,
+ * as many as 256 MiB of decoded points hold; >= 1 forced (a slab may cut through a ceremony).  Outputs do not
+ * depend on it.  DKG_E_ARG for more than 2^30 rows. */
+int dkg_ctx_set_public_share_slab(dkg_ctx *ctx, size_t rows);
+
 /* ---- whole ceremony (rounds 1-5, every party played in one process as the reference tests do,
  * committee.rs:1518-1656) in plaintext-share mode. ---- */
 typedef struct {
